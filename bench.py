@@ -12,6 +12,11 @@ slices stay in HBM (the PCIe-inclusive rate is reported separately in DESIGN.md)
 Contract: python bench.py --gpus N --steps K --warmup W  (N>1 under torch.distributed.run,
 one rank per GPU, one independent connection per GPU: weak scaling, no collective
 on the data path).  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set up, W warm-up steps, ONE timed region of exactly K steps,
+the line.  --full adds everything else the line has carried: three timed regions (median), verification of the
+delivered bytes, per-kernel times and the roofline, the comparison legs, the RTT legs, the fan-out, the CPU and
+TCP baselines.  --dump-outputs DIR writes what the last timed step delivered (see dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -213,6 +218,32 @@ def err_text(e):
     tb = traceback.extract_tb(e.__traceback__)
     where = "%s:%d" % (os.path.basename(tb[-1].filename), tb[-1].lineno) if tb else "?"
     return ("%s at %s: %s" % (type(e).__name__, where, e))[:240]
+
+
+def dump_outputs(out_dir, g, dst, dst_cap, slices, n_sample=1 << 21, seed=0):
+    """What a reader of the connection receives from the last timed step: the delivered slices, in order, and their bytes.
+    The byte stream (the slices concatenated, ~1 GiB at the default size) is too big to write whole, so every slice's
+    byte sum covers all of it and a fixed, seeded sample of n_sample stream positions gives the bytes themselves.  Where
+    the receiver placed a slice in its arena is not part of it.  ~26 MB at the default size."""
+    import numpy as np
+    arena = np.empty(dst_cap, dtype=np.uint8)
+    g._lib.check(g.load().grdma_copy_to_host(arena.ctypes.data, dst.ptr, dst_cap))
+    offs = np.array([o for o, _ in slices], dtype=np.int64)
+    lens = np.array([n for _, n in slices], dtype=np.int64)
+    stream = np.concatenate([arena[o:o + n] for o, n in slices]) if slices else np.zeros(0, np.uint8)
+    del arena
+    assert offs.size == 0 or int((offs + lens).max()) <= dst_cap
+    sums = np.zeros(lens.size, dtype=np.float64)
+    nz = lens > 0
+    if nz.any():  # (uint32 holds any slice below 16 MiB exactly and sums twice as fast)
+        acc = np.uint32 if int(lens.max()) < (1 << 24) else np.uint64
+        sums[nz] = np.add.reduceat(stream, (np.cumsum(lens) - lens)[nz], dtype=acc)
+    pos = np.sort(np.random.default_rng(seed).integers(0, max(1, stream.size), n_sample)) if stream.size else np.zeros(0, np.int64)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "delivered_slice_lengths.npy"), lens.astype(np.float64))
+    np.save(os.path.join(out_dir, "delivered_slice_byte_sums.npy"), sums)
+    np.save(os.path.join(out_dir, "delivered_stream_sample_positions.npy"), pos.astype(np.float64))
+    np.save(os.path.join(out_dir, "delivered_stream_sample_bytes.npy"), stream[pos].astype(np.float32))
 
 
 def measured_copy_ceiling(torch, dev, nbytes=256 * MIB, reps=20):
@@ -515,8 +546,14 @@ def main():
                     help="how the timed step is launched: the round-by-round kernels of a HIP graph (the persistent link "
                          "engine, k_link -- a third of this rate in rounds 2 - 4 -- was retired in round 5)")
     ap.add_argument("--no-tcp-baseline", action="store_true", help="skip the loop-back TCP baselines")
-    ap.add_argument("--reps", type=int, default=3,
-                    help="timed regions of --steps steps each; the median is reported (reference protocol: 3 repetitions)")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="timed regions of --steps steps each; the median is reported (reference protocol: 3 repetitions, "
+                         "the default with --full; 1 otherwise)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: three timed regions, verification, per-kernel times and the "
+                         "roofline, the comparison legs, RTT, fan-out, CPU and TCP baselines (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the headline delivered as DIR/<name>.npy (rank 0)")
     ap.add_argument("--rtt-iters", type=int, default=200000,
                     help="64 B round trips (>= 10 s of them on this part; the reference runs >= 10 s or 1 M RPCs behind "
                          "10 000 warm-up calls, examples/cpp/micro-bench/mb_client.cc:41-44)")
@@ -530,6 +567,13 @@ def main():
     ap.add_argument("--h2-only", action="store_true", help="(internal) run only the with-h2 legs")
     ap.add_argument("--h2-bulk-pairs-only", action="store_true", help="(internal) run only the 32-frames-per-bulk-step h2 leg")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 3 if args.full else 1
+    if not args.full:
+        # a plain run: the headline alone, timed once, neither verified nor instrumented
+        args.no_extra_legs = args.no_small_ring = args.no_rtt = args.no_fanout = True
+        args.no_cpu_baseline = args.no_tcp_baseline = args.no_verify = True
+        args.conns = 1
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         # Multi-GPU runs measure the headline (and the fan-out leg) only: the comparison legs are
         # single-GPU questions, and a leg that failed on one rank alone would leave the others waiting
@@ -601,9 +645,10 @@ def main():
 
     def measure(ring_kb, steps, warmup, verify, instrument, n_links=1, msgs_per_link=None, payload=None,
                 pipeline=False, max_sge=None, wire_flags=None, wls=None, reps=1, sends=None, promise=False,
-                reindex=False, bidi=False, fused_wire=None):
+                reindex=False, bidi=False, fused_wire=None, dump=None):
         """n_links connections with rings of ring_kb KiB: calibrate the number of rounds, capture the graph, time
-        `steps` replays.  Then verify, optionally instrument."""
+        `steps` replays.  Then dump what the first link's last timed step delivered (dump = a directory), verify,
+        optionally instrument."""
         ring = ring_kb * 1024
         max_sge = max_sge or args.max_sge
         if sends is None:
@@ -682,6 +727,8 @@ def main():
                "wire_groups": wire_groups,
                "user_bytes": sum(w.user_bytes for w in wls), "N": total_n,
                "E": sum(w.E for w in wls)}
+        if dump and rank == 0:  # (before the verification pass replays the step)
+            dump_outputs(dump, g, keep[0][2], keep[0][3], job.delivered_slices(0))
         if verify:  # correctness of what the timed region produced (untimed)
             r = job.run(gs.RUN_GRAPH)
             assert r.done and r.bytes_delivered == total_n and r.bytes_sent == total_n
@@ -859,15 +906,16 @@ def main():
     head = None
     if args.pipeline:
         try:
-            head = measure(args.ring_kb, args.steps, args.warmup, not args.no_verify, True, pipeline=True, reps=args.reps,
-                           promise=args.promise, wls=[wl])
+            head = measure(args.ring_kb, args.steps, args.warmup, not args.no_verify, args.full, pipeline=True, reps=args.reps,
+                           promise=args.promise, wls=[wl], dump=args.dump_outputs)
         except Exception as e:  # keep the line: fall back to the plain schedule and say so
             schedule = "sequential (pipelined run failed: %s)" % str(e)[:120]
     seq = None
     if head is None or not args.no_extra_legs:
         seq = measure(args.ring_kb, args.steps if head is None else max(2, args.steps // 2),
-                      args.warmup if head is None else 1, not args.no_verify, head is None, pipeline=False,
-                      reps=args.reps if head is None else 1, wls=[wl] if head is None else None)
+                      args.warmup if head is None else 1, not args.no_verify, head is None and args.full, pipeline=False,
+                      reps=args.reps if head is None else 1, wls=[wl] if head is None else None,
+                      dump=args.dump_outputs if head is None else None)
     if head is None:
         head, seq = seq, None
     graph_head = head
@@ -880,111 +928,113 @@ def main():
         small = measure(4096, max(2, args.steps // 2), 1, not args.no_verify, False, pipeline=True, sends=1, promise=True)
         small_seq = measure(4096, max(2, args.steps // 2), 1, False, False)
 
-    # algorithmic bytes per step per kernel class:
-    alg = {"gather": 2 * wl.N,          # K1: N read + N written (tags E-N by tx_plan)
-           "wire": 2 * wl.E,            # loop-back stand-in for the NIC: E read + E written
-           "rx_apply": 3 * wl.N}        # K4: N read + N written + N cleared (tags by rx_plan)
-    dom = max((k for k in classes if k in alg), key=lambda k: classes[k]["ms"])
-    per_launch = alg[dom] / classes[dom]["launches"]
-    achieved = per_launch / (classes[dom]["us_per_launch"] * 1e-6) / 1e9
-    kname = "k_rx_apply" if dom == "rx_apply" else "k_copy"
-    traffic = None
-    pmc, pmc_d, pmc_stale = pmc_summary_for(args.ring_kb)
-    # (the summary's figure is per FULL-SIZE launch -- two Sends of 4095 slices scattered, two gathered: the same launch
-    #  whatever the number of messages per step)
-    pmc_usable = pmc_d is not None and args.wire == "staged" and args.max_sge == 4095 and args.sends == 2 and args.payload == MIB
-    if pmc_usable:
-        try:
-            k = pmc_d["kernels"][kname]
-            # one FULL launch against the algorithmic bytes of one full launch (the plain mean also counts the
-            # short last round of a step and the warm-ups)
-            traffic = k.get("hbm_traffic_bytes_full_size_launch", k["hbm_traffic_bytes"])
-        except Exception:
-            traffic = None
-    roofline = {"bound": "hbm", "kernel": "%s (%s)" % (kname, dom),
-                "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
-                "traffic_source": (os.path.relpath(pmc, ROOT) + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
-                                   "command, committed, collected from these sources: sources_sha16 %s; NOT re-measured "
-                                   "in this run)" % sources_sha16()) if traffic is not None
-                else ("none: " + (pmc_stale or "not the profiled configuration")),
-                "bytes_per_launch": int(per_launch),
-                "us_per_launch": round(classes[dom]["us_per_launch"], 2)}
-    # The default schedule runs the scatter of round t and the gather of round t + 1 as ONE launch (k_rx_apply_gather):
-    # that launch is the dominant HBM kernel of the timed region.  Its algorithmic bytes: 3 x the payload of the
-    # rounds it scatters (read + written + cleared) + 2 x the payload of the rounds it gathers (read + written); the
-    # rounds are the slice list in chunks of max_sge slices (no Send is cut by credit at this ring size).
-    sched = head.get("schedule_classes") or {}
-    if "scatter_gather" in sched and args.schedule != "engine":
-        sge = min(args.max_sge, 4095) * head.get("sends", 1)  # (slices per round)
-        chunks = [sum(wl.lens[i:i + sge]) for i in range(0, len(wl.lens), sge)]
-        sg = sched["scatter_gather"]
-        if len(chunks) == rounds and sg["launches"] == rounds - 1:
-            fused_bytes = 3 * sum(chunks[:-1]) + 2 * sum(chunks[1:])
-        else:
-            fused_bytes = 5 * wl.N * sg["launches"] / max(1, rounds)
-        per_launch_sg = fused_bytes / sg["launches"]
-        ach = per_launch_sg / (sg["us_per_launch"] * 1e-6) / 1e9
-        traffic_sg = None
+    roofline = None
+    if classes:  # (per-kernel times: --full)
+        # algorithmic bytes per step per kernel class:
+        alg = {"gather": 2 * wl.N,          # K1: N read + N written (tags E-N by tx_plan)
+               "wire": 2 * wl.E,            # loop-back stand-in for the NIC: E read + E written
+               "rx_apply": 3 * wl.N}        # K4: N read + N written + N cleared (tags by rx_plan)
+        dom = max((k for k in classes if k in alg), key=lambda k: classes[k]["ms"])
+        per_launch = alg[dom] / classes[dom]["launches"]
+        achieved = per_launch / (classes[dom]["us_per_launch"] * 1e-6) / 1e9
+        kname = "k_rx_apply" if dom == "rx_apply" else "k_copy"
+        traffic = None
+        pmc, pmc_d, pmc_stale = pmc_summary_for(args.ring_kb)
+        # (the summary's figure is per FULL-SIZE launch -- two Sends of 4095 slices scattered, two gathered: the same launch
+        #  whatever the number of messages per step)
+        pmc_usable = pmc_d is not None and args.wire == "staged" and args.max_sge == 4095 and args.sends == 2 and args.payload == MIB
         if pmc_usable:
             try:
-                k = pmc_d["kernels"]["k_rx_apply_gather"]
-                traffic_sg = k.get("hbm_traffic_bytes_full_size_launch")
+                k = pmc_d["kernels"][kname]
+                # one FULL launch against the algorithmic bytes of one full launch (the plain mean also counts the
+                # short last round of a step and the warm-ups)
+                traffic = k.get("hbm_traffic_bytes_full_size_launch", k["hbm_traffic_bytes"])
             except Exception:
-                traffic_sg = None
-        alone = {"kernel": roofline["kernel"], "achieved": roofline["achieved"], "frac": roofline["frac"],
-                 "bytes_per_launch": roofline["bytes_per_launch"], "us_per_launch": roofline["us_per_launch"],
-                 "traffic": roofline["traffic"],
-                 "note": "the scatter as a launch of its own (in-order instrumented pass; what rounds 1 and 2 reported)"}
-        roofline = {"bound": "hbm",
-                    "kernel": "k_rx_apply_gather (scatter of round t + gather of round t + 1: one launch of the timed schedule)",
-                    "achieved": round(ach, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                    "frac": round(ach / HBM_PEAK_GBPS, 4), "traffic": traffic_sg,
-                    "traffic_source": (os.path.relpath(pmc, ROOT) + " (hbm_traffic_bytes_full_size_launch: rocprofv3 --pmc "
-                                       "FETCH_SIZE / WRITE_SIZE passes of this command, mean over the full-size launches "
-                                       "-- %d B algorithmic for one of those; committed, collected from these sources: "
-                                       "sources_sha16 %s; NOT re-measured in this run)"
-                                       % (5 * max(chunks), sources_sha16())) if traffic_sg is not None
+                traffic = None
+        roofline = {"bound": "hbm", "kernel": "%s (%s)" % (kname, dom),
+                    "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
+                    "traffic_source": (os.path.relpath(pmc, ROOT) + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
+                                       "command, committed, collected from these sources: sources_sha16 %s; NOT re-measured "
+                                       "in this run)" % sources_sha16()) if traffic is not None
                     else ("none: " + (pmc_stale or "not the profiled configuration")),
-                    "bytes_per_launch": int(per_launch_sg), "us_per_launch": round(sg["us_per_launch"], 2),
-                    "launches_per_step": sg["launches"],
-                    "measured": "HIP events around every launch of the timed schedule, enqueued in the graph's order on "
-                                "one stream (GRDMA_RUN_INSTRUMENTED_SCHEDULE); mean over the %d fused launches of a step, "
-                                "the last of which gathers the short last round" % sg["launches"],
-                    "scatter_alone": alone}
-        tot_s = sum(v["ms"] for v in sched.values())
-        roofline["schedule_kernels"] = {k: {"launches": v["launches"], "us_per_launch": round(v["us_per_launch"], 2),
-                                            "share_of_kernel_time": round(v["ms"] / tot_s, 3)} for k, v in sched.items()}
-    # what the roofline of the dominant HBM kernel does not show: the kernel that takes the most TIME (a planner is
-    # latency-bound and moves next to nothing), and the step as a whole against the HBM peak
-    tot_ms = sum(v["ms"] for v in classes.values())
-    top = max(classes, key=lambda k: classes[k]["ms"])
-    step_bytes = 2 * wl.N + 3 * wl.E  # K1 (N read + E written) + K4 (E read + N written + E cleared); the wire is the NIC's
-    step_s = elapsed / args.steps
-    roofline["dominant_by_time"] = {
-        "kernel": top, "us_per_launch": round(classes[top]["us_per_launch"], 2),
-        "share_of_kernel_time": round(classes[top]["ms"] / tot_ms, 3),
-        "planner_share_of_kernel_time": round(sum(classes[k]["ms"] for k in ("tx_plan", "rx_plan") if k in classes) / tot_ms, 3),
-        "note": "per-class HIP-event time of the instrumented in-order pass (a class = the launches between two events)"}
-    if roofline.get("schedule_kernels"):
-        # the same question for the schedule that was timed: its launches are the planner pair (drain plan of round t +
-        # send plan of round t + 1), the fused scatter + gather and the wire
-        sk = roofline["schedule_kernels"]
-        top_s = max(sk, key=lambda k: sk[k]["share_of_kernel_time"])
-        roofline["dominant_by_time_in_order_pass"] = roofline["dominant_by_time"]
+                    "bytes_per_launch": int(per_launch),
+                    "us_per_launch": round(classes[dom]["us_per_launch"], 2)}
+        # The default schedule runs the scatter of round t and the gather of round t + 1 as ONE launch (k_rx_apply_gather):
+        # that launch is the dominant HBM kernel of the timed region.  Its algorithmic bytes: 3 x the payload of the
+        # rounds it scatters (read + written + cleared) + 2 x the payload of the rounds it gathers (read + written); the
+        # rounds are the slice list in chunks of max_sge slices (no Send is cut by credit at this ring size).
+        sched = head.get("schedule_classes") or {}
+        if "scatter_gather" in sched and args.schedule != "engine":
+            sge = min(args.max_sge, 4095) * head.get("sends", 1)  # (slices per round)
+            chunks = [sum(wl.lens[i:i + sge]) for i in range(0, len(wl.lens), sge)]
+            sg = sched["scatter_gather"]
+            if len(chunks) == rounds and sg["launches"] == rounds - 1:
+                fused_bytes = 3 * sum(chunks[:-1]) + 2 * sum(chunks[1:])
+            else:
+                fused_bytes = 5 * wl.N * sg["launches"] / max(1, rounds)
+            per_launch_sg = fused_bytes / sg["launches"]
+            ach = per_launch_sg / (sg["us_per_launch"] * 1e-6) / 1e9
+            traffic_sg = None
+            if pmc_usable:
+                try:
+                    k = pmc_d["kernels"]["k_rx_apply_gather"]
+                    traffic_sg = k.get("hbm_traffic_bytes_full_size_launch")
+                except Exception:
+                    traffic_sg = None
+            alone = {"kernel": roofline["kernel"], "achieved": roofline["achieved"], "frac": roofline["frac"],
+                     "bytes_per_launch": roofline["bytes_per_launch"], "us_per_launch": roofline["us_per_launch"],
+                     "traffic": roofline["traffic"],
+                     "note": "the scatter as a launch of its own (in-order instrumented pass; what rounds 1 and 2 reported)"}
+            roofline = {"bound": "hbm",
+                        "kernel": "k_rx_apply_gather (scatter of round t + gather of round t + 1: one launch of the timed schedule)",
+                        "achieved": round(ach, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                        "frac": round(ach / HBM_PEAK_GBPS, 4), "traffic": traffic_sg,
+                        "traffic_source": (os.path.relpath(pmc, ROOT) + " (hbm_traffic_bytes_full_size_launch: rocprofv3 --pmc "
+                                           "FETCH_SIZE / WRITE_SIZE passes of this command, mean over the full-size launches "
+                                           "-- %d B algorithmic for one of those; committed, collected from these sources: "
+                                           "sources_sha16 %s; NOT re-measured in this run)"
+                                           % (5 * max(chunks), sources_sha16())) if traffic_sg is not None
+                        else ("none: " + (pmc_stale or "not the profiled configuration")),
+                        "bytes_per_launch": int(per_launch_sg), "us_per_launch": round(sg["us_per_launch"], 2),
+                        "launches_per_step": sg["launches"],
+                        "measured": "HIP events around every launch of the timed schedule, enqueued in the graph's order on "
+                                    "one stream (GRDMA_RUN_INSTRUMENTED_SCHEDULE); mean over the %d fused launches of a step, "
+                                    "the last of which gathers the short last round" % sg["launches"],
+                        "scatter_alone": alone}
+            tot_s = sum(v["ms"] for v in sched.values())
+            roofline["schedule_kernels"] = {k: {"launches": v["launches"], "us_per_launch": round(v["us_per_launch"], 2),
+                                                "share_of_kernel_time": round(v["ms"] / tot_s, 3)} for k, v in sched.items()}
+        # what the roofline of the dominant HBM kernel does not show: the kernel that takes the most TIME (a planner is
+        # latency-bound and moves next to nothing), and the step as a whole against the HBM peak
+        tot_ms = sum(v["ms"] for v in classes.values())
+        top = max(classes, key=lambda k: classes[k]["ms"])
+        step_bytes = 2 * wl.N + 3 * wl.E  # K1 (N read + E written) + K4 (E read + N written + E cleared); the wire is the NIC's
+        step_s = elapsed / args.steps
         roofline["dominant_by_time"] = {
-            "kernel": top_s + {"plan_pair": " (k_plan_pair_mw)", "scatter_gather": " (k_rx_apply_gather)"}.get(top_s, ""),
-            "us_per_launch": sk[top_s]["us_per_launch"], "share_of_kernel_time": sk[top_s]["share_of_kernel_time"],
-            "planner_share_of_kernel_time": round(sum(sk[k]["share_of_kernel_time"] for k in ("tx_plan", "plan_pair", "rx_plan")
-                                                      if k in sk), 3),
-            "note": "per-launch HIP-event time of the timed schedule's launches (GRDMA_RUN_INSTRUMENTED_SCHEDULE)"}
-    roofline["step_level"] = {"bytes": int(step_bytes), "achieved": round(step_bytes / step_s / 1e9, 1), "unit": "GB/s",
-                              "frac": round(step_bytes / step_s / 1e9 / HBM_PEAK_GBPS, 4),
-                              "frac_with_wire": round((step_bytes + 2 * wl.E) / step_s / 1e9 / HBM_PEAK_GBPS, 4)}
-    try:
-        roofline["measured_ceiling"] = None if EMULATED else measured_copy_ceiling(torch, device)
-    except Exception as e:
-        roofline["measured_ceiling"] = {"error": str(e)[:120]}
+            "kernel": top, "us_per_launch": round(classes[top]["us_per_launch"], 2),
+            "share_of_kernel_time": round(classes[top]["ms"] / tot_ms, 3),
+            "planner_share_of_kernel_time": round(sum(classes[k]["ms"] for k in ("tx_plan", "rx_plan") if k in classes) / tot_ms, 3),
+            "note": "per-class HIP-event time of the instrumented in-order pass (a class = the launches between two events)"}
+        if roofline.get("schedule_kernels"):
+            # the same question for the schedule that was timed: its launches are the planner pair (drain plan of round t +
+            # send plan of round t + 1), the fused scatter + gather and the wire
+            sk = roofline["schedule_kernels"]
+            top_s = max(sk, key=lambda k: sk[k]["share_of_kernel_time"])
+            roofline["dominant_by_time_in_order_pass"] = roofline["dominant_by_time"]
+            roofline["dominant_by_time"] = {
+                "kernel": top_s + {"plan_pair": " (k_plan_pair_mw)", "scatter_gather": " (k_rx_apply_gather)"}.get(top_s, ""),
+                "us_per_launch": sk[top_s]["us_per_launch"], "share_of_kernel_time": sk[top_s]["share_of_kernel_time"],
+                "planner_share_of_kernel_time": round(sum(sk[k]["share_of_kernel_time"] for k in ("tx_plan", "plan_pair", "rx_plan")
+                                                          if k in sk), 3),
+                "note": "per-launch HIP-event time of the timed schedule's launches (GRDMA_RUN_INSTRUMENTED_SCHEDULE)"}
+        roofline["step_level"] = {"bytes": int(step_bytes), "achieved": round(step_bytes / step_s / 1e9, 1), "unit": "GB/s",
+                                  "frac": round(step_bytes / step_s / 1e9 / HBM_PEAK_GBPS, 4),
+                                  "frac_with_wire": round((step_bytes + 2 * wl.E) / step_s / 1e9 / HBM_PEAK_GBPS, 4)}
+        try:
+            roofline["measured_ceiling"] = None if EMULATED else measured_copy_ceiling(torch, device)
+        except Exception as e:
+            roofline["measured_ceiling"] = {"error": str(e)[:120]}
 
     total_user = wl.user_bytes * args.steps * world
     value = total_user / elapsed / (1 << 30)
@@ -1032,7 +1082,7 @@ def main():
                    "stages": "gather+encode, wire, ready-detect, decode+scatter+zero, credit"},
         "roofline": roofline,
         "kernels": {k: {"launches": v["launches"], "us_per_launch": round(v["us_per_launch"], 2)}
-                    for k, v in classes.items()},
+                    for k, v in classes.items()} if classes else None,
         "endpoint_bytes_per_step": wl.N, "ring_bytes_per_step": wl.E, "verified": verified,
     }
     # ---- single-stream fan-out (BASELINE.json configs[4]): the one collective of the path ---

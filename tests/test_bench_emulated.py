@@ -1,5 +1,6 @@
 """bench.py --gpus 2, launched the way the driver launches it -- `python -m torch.distributed.run --nnodes=1
---nproc-per-node 2 --master-addr 127.0.0.1 --master-port P bench.py --gpus 2 --steps K --warmup W` -- and run END TO END on
+--nproc-per-node 2 --master-addr 127.0.0.1 --master-port P bench.py --gpus 2 --steps K --warmup W`, with --full for every
+leg -- and run END TO END on
 the CPU: GRDMA_BENCH_EMULATED=1 puts the product sources compiled over the wave emulator (oracle/_build/libgrdma_emu.so)
 in the library's place, CPU tensors and gloo in place of HBM tensors and RCCL.  No second GPU has been available to any
 round (SCALE_r0*.json: skipped), so this is where the N > 1 path of the script executes: one process per rank, every
@@ -41,7 +42,8 @@ def emu_env(built):
 
 def test_bench_two_ranks_as_the_driver_launches_it(emu_env):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"] + SMALL
+           "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           "--full"] + SMALL
     p = subprocess.run(cmd, cwd=ROOT, env=emu_env, capture_output=True, text=True, timeout=1200)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

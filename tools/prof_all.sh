@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 out=$R/gpurun_out/profiles_new
 rm -rf $out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --no-cpu-baseline --no-tcp-baseline --no-small-ring --no-rtt --no-extra-legs --conns 1"
+B="python $R/bench.py --full --no-cpu-baseline --no-tcp-baseline --no-small-ring --no-rtt --no-extra-legs --conns 1"
 stats() { tag=$1; shift
   rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$tag -o bench -- $B "$@" > $out/stats_$tag.stdout 2>&1
   f=$(find $out/stats_$tag -name '*kernel_stats.csv' | head -1)
@@ -18,6 +18,6 @@ for ctr in FETCH_SIZE WRITE_SIZE "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ
   d=$out/pmc/$(echo $ctr | cut -d' ' -f1)
   rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $d -o pmc -- $B --no-verify --steps 4 --warmup 1 > $d.stdout 2>&1
 done
-python $R/tools/pmc_summary.py $out/pmc $out/pmc_ring256m_summary.json "rocprofv3 --pmc <CTRS> --kernel-trace --output-format csv -- python bench.py --no-cpu-baseline --no-tcp-baseline --no-verify --no-small-ring --no-rtt --no-extra-legs --conns 1 --steps 4 --warmup 1 (one counter family per pass; tools/prof_all.sh)"
+python $R/tools/pmc_summary.py $out/pmc $out/pmc_ring256m_summary.json "rocprofv3 --pmc <CTRS> --kernel-trace --output-format csv -- python bench.py --full --no-cpu-baseline --no-tcp-baseline --no-verify --no-small-ring --no-rtt --no-extra-legs --conns 1 --steps 4 --warmup 1 (one counter family per pass; tools/prof_all.sh)"
 rm -rf $out/stats_ring256m $out/stats_ring4m $out/pmc $out/*.stdout
 ls -la $out

@@ -10,7 +10,7 @@ rc=$?
 tail -3 $out/pytest.log
 echo "pytest rc=$rc"
 [ $rc -ne 0 ] && exit $rc
-timeout 100 python bench.py > $out/bench.log 2> $out/bench.err < /dev/null
+timeout 100 python bench.py --full > $out/bench.log 2> $out/bench.err < /dev/null
 echo "bench rc=$?"
 grep -o '"value": [0-9.]*\|"rx_plan": {[^}]*}\|"value_ring4096_sge30": [0-9.]*\|"value_mixed_sizes": [0-9.]*\|"rtt_p50_us": [0-9.]*' $out/bench.log | head -5
 timeout 30 python tools/plan_phases.py > $out/phases.log 2>&1 < /dev/null

@@ -13,7 +13,7 @@ export GRAFT_REPO_ROOT=$R
 timeout 900 bash tools/prof_all.sh < /dev/null 2>&1 | grep -A6 "== ring"
 cp $R/gpurun_out/profiles_new/pmc_ring256m_summary.json $R/profiles/${RND}_pmc_ring256m_summary.json 2>/dev/null
 mkdir -p $out/profiles_new; cp -r $R/gpurun_out/profiles_new/* $out/profiles_new/ 2>/dev/null
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err < /dev/null
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err < /dev/null
 echo "bench rc=$?"; python - <<PY
 import json
 try:
