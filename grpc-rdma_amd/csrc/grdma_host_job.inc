@@ -50,29 +50,20 @@ struct grdma_stream_job {
   uint64_t hooks_gen = 0, exec_hooks_gen = 0;
   uint64_t exec_rounds = 0;
   int exec_pipeline = -1;
-  int exec_fastkey = -1;              // rx_fast | tx_fast << 1 | deep << 2 the graph was built for
+  int exec_fastkey = -1;              // job_fastkey of the job the graph was built for (planner kernels, Sends per plan, modes)
   int runs = 0;
   int rx_miss = 0, tx_miss = 0;       // consecutive runs whose drains / Sends of link 0 mostly went to the general planner
   uint64_t seen[4] = {0, 0, 0, 0};    // the result blocks' taken / declined counters at the end of the last run
   int pipeline = 0;                   // 1: overlap the send plan / gather / scatter of
                                       // neighbouring rounds on side streams
-  int deep = 1;                       // pipelined graph: 1 = the limit-driven schedule (job_build_graph),
-                                      // 0 = the schedule of rounds 1-2 (GRDMA_JOB_SCHEDULE=pair)
   hipStream_t s_wire = nullptr, s_rxplan = nullptr, s_apply = nullptr;
-  // reserved-CU schedule (job_enqueue_masked): the two planners on streams whose CU mask is a few CUs of
-  // their own, the copy kernels on streams masked to the rest, so a one-workgroup planner never waits for a
-  // machine-filling copy kernel to retire
   int tx_fast = 1;                    // Sends of one-Send rounds are priced from an index of the slice buffer: k_tx_index at
                                       // the start of a step, k_tx_fast per Send, the general planner behind it for the rest
+                                      // (0: the general planner alone -- grdma_stream_job_run, after repeated declines)
   grdma_txf_ctl* d_txf = nullptr;     // [n]
-  int pair_job = 1;                   // pipelined graph: drain of round t and Send of round t + 1 in one launch (k_plan_pair_mw)
   int fuse_wire = 1;                  // paired schedule, few links with small rings: the wire of round t inside the planner
                                       // pair's launch (k_plan_pair_mw's wire workgroups) -- two launches per round;
-                                      // GRDMA_JOB_FUSE_WIRE=0: a k_copy launch of its own, as for every other job
-  int fuse_ag = 1;                    // paired schedule: the scatter of round t and the gather of round t + 1 in one launch
-                                      // (k_rx_apply_gather); GRDMA_JOB_FUSE_AG=0: two launches
-  int rx_multi = 1;                   // paired schedule: the drain plan laid out by several workgroups (k_plan_pair_mw,
-                                      // csrc/grdma_rx_multi.h); GRDMA_RX_MULTI=0: the limit-driven schedule with the one-workgroup planners
+                                      // grdma_stream_job_set_fused_wire(j, 0): a k_copy launch of its own, as for every other job
   // The index of the slice table (k_tx_index) is a function of the table alone, and the job owns the table: built by
   // the first run, kept for the later ones -- unless something may rewrite the table between steps (kernel nodes hung
   // in front of the job, or a caller that asked where the table lives: the HTTP/2 pipe does both).
@@ -85,9 +76,7 @@ struct grdma_stream_job {
                                       // planners of grdma_tx_multi.h / grdma_rx_multi.h: 16 workgroups per Send's worth of records)
   int rx_fast = 1;                    // drains of one-Send rounds go through k_rx_fast first (grdma_rx_fast.hip), the
                                       // general planner behind it only does what that kernel declined
-  int cumask_bits = 0;                // planner CUs (low bits of the mask); 0 = off
-  hipStream_t m_txplan = nullptr, m_rxplan = nullptr, m_copy = nullptr, m_apply = nullptr;
-  std::vector<hipEvent_t> mev;
+                                      // (0: the general planner alone -- grdma_stream_job_run, after repeated declines)
   std::vector<hipEvent_t> pev;        // dependency events of the pipelined schedule
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::vector<hipEvent_t> kev;
@@ -95,9 +84,6 @@ struct grdma_stream_job {
   hipStream_t stream = nullptr;
   bool direct = false;
   uint64_t max_ring = 0;
-  static constexpr uint32_t burst = 1;   // (the burst schedule of round 3 -- several Sends per round, each with plans and a
-                                         //  staging buffer of its own -- gave way to grdma_stream_job_set_sends in round 4
-                                         //  and was removed in round 5; what is left of it is this constant)
 };
 
 namespace {
@@ -105,17 +91,37 @@ namespace {
 inline int job_opset(uint64_t round) { return round == 0 ? 0 : ((round & 1) ? 1 : 2); }
 inline bool job_index_needed(const grdma_stream_job* j) { return !j->index_valid || !j->pre_hooks.empty() || j->sges_exposed; }
 inline int job_fastkey(const grdma_stream_job* j) {
-  return (j->rx_fast ? 1 : 0) | (j->tx_fast ? 2 : 0) | (j->deep ? 4 : 0) | (j->pair_job ? 8 : 0) |
-         (j->fuse_ag ? 32 : 0) | (j->rx_multi ? 64 : 0) | (j->fuse_wire ? 128 : 0) | ((int)(j->sends & 7) << 8) | (job_index_needed(j) ? (1 << 12) : 0) | (j->promise ? (1 << 13) : 0) | ((int)j->sends << 16);
+  return (j->rx_fast ? 1 : 0) | (j->tx_fast ? 2 : 0) | (j->fuse_wire ? 128 : 0) | ((int)(j->sends & 7) << 8) |
+         (job_index_needed(j) ? (1 << 12) : 0) | (j->promise ? (1 << 13) : 0) | ((int)j->sends << 16);
 }
 inline bool job_exec_stale(const grdma_stream_job* j) {
   return !j->exec || j->exec_rounds != j->rounds || j->exec_pipeline != j->pipeline || j->exec_fastkey != job_fastkey(j) ||
          j->exec_hooks_gen != j->hooks_gen;
 }
+// copy-kernel workgroups per link for `bytes` (gather and wire: half a ring, scatter: a ring), the grid of all links kept
+// around 2048 workgroups in total
+inline uint32_t job_copy_blocks(const grdma_stream_job* j, uint64_t bytes) {
+  const uint32_t grid_cap = copy_blocks_for(~0ull >> 8);
+  return std::max<uint32_t>(1, std::min<uint32_t>(copy_blocks_for(bytes), grid_cap / (uint32_t)j->links.size() + 1));
+}
+// The parameters of a job kernel launched by address (hipLaunchKernel, a graph's kernel node): three pointers, the
+// planner pair's 4-byte workgroup split and its wire plans, padded to GRDMA_JOB_HOOK_ARGS entries -- the runtime reads as
+// many as the kernel has, a kernel with fewer ignores the rest.  `v` points into the object: keep it alive for the call.
+struct job_kargs {
+  const void* p[3];
+  uint32_t split;
+  const void* wire;
+  void* v[GRDMA_JOB_HOOK_ARGS];
+  job_kargs(const void* a0, const void* a1, const void* a2, uint32_t a3 = 0, const void* a4 = nullptr)
+      : p{a0, a1, a2}, split(a3), wire(a4) {
+    static uint64_t none = 0;
+    for (void*& x : v) x = &none;
+    v[0] = &p[0]; v[1] = &p[1]; v[2] = &p[2]; v[3] = &split; v[4] = &wire;
+  }
+  job_kargs(const job_kargs&) = delete;
+  job_kargs& operator=(const job_kargs&) = delete;
+};
 
-// the send plan of round t: priced from the index of the slice buffer (built in front of the first round of a
-// step), the general planner in the same launch for what that declines
-inline bool job_tx_fast(const grdma_stream_job* j) { return j->tx_fast && j->burst == 1; }
 // planner workgroups of a round: sixteen per Send's worth of records
 // (up to two Sends: priced one after the other, each may carry 4095 records.  More: folded into one cut of the index,
 //  a round carries at most sends x max_sge records -- 256 of them per workgroup)
@@ -125,8 +131,6 @@ inline uint32_t job_groups(const grdma_stream_job* j, uint32_t per_send) {
   // slices -- 32 connections x 64 KiB messages -- is planned by 3 + 3 workgroups instead of 16 + 16: a launch of 192
   // planner workgroups for 32 links where there were 1024, every one of them resident at once.  A drain that finds more
   // records than its workgroups cover declines, and the general planner walks it: slower, never wrong.
-  // (GRDMA_JOB_GROUPS_BY_COUNT=0: the fixed sizes of rounds 4-5)
-  static const bool by_count = !(getenv("GRDMA_JOB_GROUPS_BY_COUNT") && atoi(getenv("GRDMA_JOB_GROUPS_BY_COUNT")) == 0);
   uint64_t slices = 1;
   for (const grdma_job_link& l : j->links) slices = std::max<uint64_t>(slices, l.count);
   const bool seq_sends = j->sends <= grdma_tx_multi_seq_sends();
@@ -139,38 +143,33 @@ inline uint32_t job_groups(const grdma_stream_job* j, uint32_t per_send) {
     for (const grdma_job_link& l : j->links) most = std::max<uint64_t>(most, (uint64_t)j->sends * l.tx->max_sge);
     g = std::min<uint64_t>(2 * per_send, (most + 255) / 256);
   }
-  if (by_count) g = std::min<uint64_t>(g, by_table);
-  return (uint32_t)std::max<uint64_t>(1, g);
+  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(g, by_table));
 }
 inline uint32_t job_rx_groups(const grdma_stream_job* j) { return job_groups(j, grdma_rx_multi_groups()); }
-// (promised credit: every planner workgroup of the launch must be resident at once -- one per CU -- or a Send's
-//  workgroups could wait for a drain whose workgroups have no CU yet)
-inline bool job_promise(const grdma_stream_job* j);
 inline uint32_t job_tx_groups(const grdma_stream_job* j) { return job_groups(j, grdma_tx_multi_groups()); }
-inline bool job_mw(const grdma_stream_job* j) { return j->rx_multi && j->pipeline && j->pair_job && j->rx_fast && j->burst == 1 && j->tx_fast; }
+inline bool job_mw(const grdma_stream_job* j) { return j->pipeline && j->rx_fast && j->tx_fast; }
 // the sequential schedule (five launches per round, strictly in order) with the small planner workgroups: what carries
 // several Sends per plan when the job is not pipelined -- a ring every round fills sees its credit at once here, a round
 // late on the paired schedule
-inline bool job_mw_seq(const grdma_stream_job* j) { return j->sends > 1 && j->rx_multi && !j->pipeline && j->rx_fast && j->burst == 1 && j->tx_fast; }
+inline bool job_mw_seq(const grdma_stream_job* j) { return j->sends > 1 && !j->pipeline && j->rx_fast && j->tx_fast; }
 hipError_t job_launch_pair_mw(const grdma_rx_op* rxops, const grdma_tx_op* txops, const grdma_txf_ctl* ctls, uint32_t n, uint32_t g_rx,
                               uint32_t g_tx, hipStream_t s) {
-  // (an array of GRDMA_JOB_HOOK_ARGS entries, as for every kernel launched by address: the runtime reads as many as the kernel has)
-  static uint64_t none = 0;
-  void* args[GRDMA_JOB_HOOK_ARGS];
-  for (uint32_t a = 0; a < GRDMA_JOB_HOOK_ARGS; a++) args[a] = &none;
-  args[0] = (void*)&rxops; args[1] = (void*)&txops; args[2] = (void*)&ctls; args[3] = (void*)&g_rx;
-  return hipLaunchKernel(grdma_kernel_fn_plan_pair_mw(), dim3(n, g_rx + g_tx), dim3(grdma_kernel_threads(0)), args, 0, s);
+  job_kargs a(rxops, txops, ctls, g_rx);
+  return hipLaunchKernel(grdma_kernel_fn_plan_pair_mw(), dim3(n, g_rx + g_tx), dim3(grdma_kernel_threads(0)), a.v, 0, s);
 }
+// Promised credit (k_plan_pair_mw): the Send's workgroups of the planner pair's launch wait for the drain plan of the same
+// launch.  The invariant that keeps this wait, and every other wait between the workgroups of a job's launch, from
+// deadlocking (stated here once): workgroups are dispatched in index order, x (the link) fastest, then y; a workgroup
+// waits only on workgroups with a LOWER blockIdx (wire, then drain, then Send workgroups; a committer is the last of its
+// group); and every wait is bounded -- one that runs out is given up (the promise: csrc/grdma_devfn.h, the wire:
+// csrc/grdma_rx_multi.h).  So whatever a workgroup waits for has a CU or is done before it gets one, and no planner
+// workgroup needs to be resident beside the others.  Through the first half of round 6 the mode also required that
+// (links x (G + H) <= CUs); GRDMA_JOB_PROMISE_RESIDENT=1 restores the condition -- the fallback should a runtime ever
+// dispatch out of order.  64 links of BASELINE configs[3] at 3 + 3 workgroups are 384: the steady state of that leg is
+// 373 -> 440 GiB/s without it.
 inline bool job_promise(const grdma_stream_job* j) {
   // (staged wire only: with a direct wire the gather of round t + 1 writes the ring in the launch of round t's scatter)
   if (!j->promise || !job_mw(j) || j->direct) return false;
-  // Through the first half of round 6 the mode also required every planner workgroup of the launch to have a CU at once
-  // (links x (G + H) <= CUs), for fear of a Send workgroup spinning on a CU that a drain workgroup needs.  It cannot:
-  // workgroups are dispatched in index order, x (the link) fastest, then y -- every drain workgroup of EVERY link
-  // (y < G) has a CU or is done before the first Send workgroup (y >= G) gets one, and a drain workgroup waits for
-  // nothing that comes behind it.  (And the wait is bounded: a promise that does not come is given up, csrc/grdma_devfn.h.)
-  // 64 links of BASELINE configs[3] at 3 + 3 workgroups are 384: the steady state of that leg is 373 -> 440 GiB/s with it.
-  // GRDMA_JOB_PROMISE_RESIDENT=1 restores the condition.
   static const bool resident_only = getenv("GRDMA_JOB_PROMISE_RESIDENT") && atoi(getenv("GRDMA_JOB_PROMISE_RESIDENT")) != 0;
   if (!resident_only) return true;
   static const int cus = [] {
@@ -182,10 +181,11 @@ inline bool job_promise(const grdma_stream_job* j) {
 }
 // Wire workgroups of the planner pair's launch (0: the wire is a k_copy launch of its own).  The planner kernel runs one
 // workgroup per CU (its LDS), a wave of it moves one tile at a time: only a round of a few MiB is moved as fast by W of
-// them as by k_copy's grid, and the drain's workgroups WAIT for the wire's inside the launch -- so every workgroup of
-// the launch must have a CU at once.  One per four 8 KiB tiles of half a ring, at least 8, at most 64.
+// them as by k_copy's grid, and the drain's workgroups WAIT for the wire's inside the launch -- so, for speed, every
+// workgroup of the launch must have a CU at once (what makes the wait safe is job_promise's invariant).  One per four
+// 8 KiB tiles of half a ring, at least 8, at most 64.
 inline uint32_t job_wire_groups(const grdma_stream_job* j) {
-  if (!j->fuse_wire || !job_mw(j) || j->direct || !j->fuse_ag || j->max_ring > (16ull << 20)) return 0;
+  if (!j->fuse_wire || !job_mw(j) || j->direct || j->max_ring > (16ull << 20)) return 0;
   const uint32_t w = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(8, (j->max_ring / 2 / 8192 + 3) / 4));
 #ifdef GRDMA_WAVE_EMU
   return w;  // (the emulator runs the workgroups of a launch one after the other, in index order: the wire's first)
@@ -206,8 +206,10 @@ inline uint32_t job_index_blocks(const grdma_stream_job* j) {  // k_tx_index: 10
   for (const grdma_job_link& l : j->links) most = std::max<uint64_t>(most, l.count);
   return (uint32_t)((most + 1023) / 1024);
 }
+// the send plan of round t: priced from the index of the slice buffer (built in front of the first round of a step), the
+// general planner in the same launch for what that declines
 hipError_t job_launch_tx_plan(grdma_stream_job* j, int k, uint64_t t, uint32_t n, hipStream_t s) {
-  if (!job_tx_fast(j)) return grdma_launch_tx_plan(j->d_txop + k * n, n, s);
+  if (!j->tx_fast) return grdma_launch_tx_plan(j->d_txop + k * n, n, s);
   hipError_t e = hipSuccess;
   if (t == 0 && job_index_needed(j)) e = grdma_launch_tx_index(j->d_txf, n, job_index_blocks(j), s);
   if (e != hipSuccess) return e;
@@ -219,18 +221,13 @@ hipError_t job_launch_tx_plan(grdma_stream_job* j, int k, uint64_t t, uint32_t n
 // the receive plan of a round: k_rx_plan_job = the straight-line steady-state body, then the general planner for what it declines
 hipError_t job_launch_rx_plan(grdma_stream_job* j, const grdma_rx_op* ops, uint32_t n, hipStream_t s) {
   if (j->sends > 1 && (job_mw(j) || job_mw_seq(j))) return job_launch_pair_mw(ops, nullptr, j->d_txf, n, job_rx_groups(j), 0, s);
-  if (j->rx_fast && j->burst == 1) return grdma_launch_rx_plan_job(ops, n, s);
+  if (j->rx_fast) return grdma_launch_rx_plan_job(ops, n, s);
   return grdma_launch_rx_plan(ops, n, s);
 }
 
 int job_enqueue(grdma_stream_job* j, hipStream_t s, bool instrument) {
   const uint32_t n = (uint32_t)j->links.size();
-  const uint32_t tx_blocks = copy_blocks_for(j->max_ring / 2);
-  const uint32_t rx_blocks = copy_blocks_for(j->max_ring);
-  // keep the grid around 2048 workgroups in total
-  const uint32_t grid_cap = copy_blocks_for(~0ull >> 8);
-  const uint32_t txb = std::max<uint32_t>(1, std::min<uint32_t>(tx_blocks, grid_cap / n + 1));
-  const uint32_t rxb = std::max<uint32_t>(1, std::min<uint32_t>(rx_blocks, grid_cap / n + 1));
+  const uint32_t txb = job_copy_blocks(j, j->max_ring / 2), rxb = job_copy_blocks(j, j->max_ring);
   size_t e = 0;
   auto mark = [&]() -> int {
     if (!instrument) return 0;
@@ -268,17 +265,13 @@ int job_enqueue(grdma_stream_job* j, hipStream_t s, bool instrument) {
 // work in the same order; what the events add is the time of each launch by itself (classes 5 = k_plan_pair_mw,
 // 6 = k_rx_apply_gather beside the five of the in-order pass).
 bool job_is_paired(const grdma_stream_job* j) {
-  return j->pipeline && j->burst == 1 && j->rx_fast && job_tx_fast(j) && j->pair_job && j->rounds >= 1;
+  return j->pipeline && j->rx_fast && j->tx_fast && j->rounds >= 1;
 }
 int job_enqueue_schedule_instrumented(grdma_stream_job* j, hipStream_t s) {
   if (!job_is_paired(j))
     return fail(GRDMA_ERR_INVALID, "GRDMA_RUN_INSTRUMENTED_SCHEDULE times the paired schedule (pipelined job, steady-state planners)");
   const uint32_t n = (uint32_t)j->links.size();
-  const uint32_t tx_blocks = copy_blocks_for(j->max_ring / 2);
-  const uint32_t rx_blocks = copy_blocks_for(j->max_ring);
-  const uint32_t grid_cap = copy_blocks_for(~0ull >> 8);
-  const uint32_t txb = std::max<uint32_t>(1, std::min<uint32_t>(tx_blocks, grid_cap / n + 1));
-  const uint32_t rxb = std::max<uint32_t>(1, std::min<uint32_t>(rx_blocks, grid_cap / n + 1));
+  const uint32_t txb = job_copy_blocks(j, j->max_ring / 2), rxb = job_copy_blocks(j, j->max_ring);
   const uint32_t ct = grdma_kernel_threads(1);
   const uint64_t R = j->rounds;
   size_t e = 0;
@@ -295,15 +288,8 @@ int job_enqueue_schedule_instrumented(grdma_stream_job* j, hipStream_t s) {
   };
   auto launch = [&](const void* fn, dim3 grid, uint32_t threads, const void* a0, const void* a1, const void* a2,
                     uint32_t a3 = 0, const void* a4 = nullptr) -> hipError_t {
-    static uint64_t none = 0;
-    void* args[GRDMA_JOB_HOOK_ARGS];
-    for (uint32_t a = 0; a < GRDMA_JOB_HOOK_ARGS; a++) args[a] = &none;
-    args[0] = const_cast<void*>(static_cast<const void*>(&a0));
-    args[1] = const_cast<void*>(static_cast<const void*>(&a1));
-    args[2] = const_cast<void*>(static_cast<const void*>(&a2));
-    args[3] = &a3;
-    args[4] = const_cast<void*>(static_cast<const void*>(&a4));
-    return hipLaunchKernel(fn, grid, dim3(threads), args, 0, s);
+    job_kargs a(a0, a1, a2, a3, a4);
+    return hipLaunchKernel(fn, grid, dim3(threads), a.v, 0, s);
   };
   if (int rc = mark(-1)) return rc;
   for (uint64_t t = 0; t < R; t++) {
@@ -311,17 +297,11 @@ int job_enqueue_schedule_instrumented(grdma_stream_job* j, hipStream_t s) {
     const void* rxop = j->d_rxop + k * n;
     const void* gplans = j->d_plans;
     const void* wplans = j->d_plans + n * (1 + (t & 1));
-    if (t == 0) {
-      if (j->rx_multi) {  // (k_tx_index +) the Send priced by k_plan_pair_mw's small workgroups (as the graph does)
-        if (job_index_needed(j)) HIP_TRY(grdma_launch_tx_index(j->d_txf, n, job_index_blocks(j), s));
-        HIP_TRY(launch(grdma_kernel_fn_plan_pair_mw(), dim3(n, job_tx_groups(j)), grdma_kernel_threads(0), nullptr,
-                       j->d_txop + k * n, j->d_txf, 0u));
-      } else {
-        HIP_TRY(job_launch_tx_plan(j, k, 0, n, s));  // k_tx_index + k_tx_plan_job
-      }
+    if (t == 0) {  // (k_tx_index +) the Send priced by k_plan_pair_mw's small workgroups (as the graph does)
+      if (job_index_needed(j)) HIP_TRY(grdma_launch_tx_index(j->d_txf, n, job_index_blocks(j), s));
+      HIP_TRY(launch(grdma_kernel_fn_plan_pair_mw(), dim3(n, job_tx_groups(j)), grdma_kernel_threads(0), nullptr,
+                     j->d_txop + k * n, j->d_txf, 0u));
       if (int rc = mark(0)) return rc;
-    }
-    if (t == 0 || !j->fuse_ag) {
       HIP_TRY(launch(grdma_kernel_fn(1), dim3(txb, n), ct, gplans, nullptr, nullptr));
       if (int rc = mark(1)) return rc;
     }
@@ -335,7 +315,7 @@ int job_enqueue_schedule_instrumented(grdma_stream_job* j, hipStream_t s) {
     HIP_TRY(launch(grdma_kernel_fn_plan_pair_mw(), dim3(n, wg_wire + job_rx_groups(j) + (more ? job_tx_groups(j) : 0)),
                    grdma_kernel_threads(0), rxop, more ? txop_next : nullptr, j->d_txf, job_pair_mode(j), wg_wire ? wplans : nullptr));
     if (int rc = mark(5)) return rc;
-    if (more && j->fuse_ag) {
+    if (more) {
       HIP_TRY(launch(grdma_kernel_fn(8), dim3(std::max(rxb, txb), 2 * n), ct, rxop, gplans, nullptr));
       if (int rc = mark(6)) return rc;
     } else {
@@ -352,24 +332,17 @@ int job_enqueue_schedule_instrumented(grdma_stream_job* j, hipStream_t s) {
 //   plan_t -> gather_t -> wire_t -> rx_plan_t -> rx_apply_t      the data path of one round
 //   wire_{t-2} -> plan_t      two staging buffers (and wire plans) alternate; the one of
 //       this parity comes free when the round before last has left it
-//   rx_plan_{t-1} -> wire_t   the loop-back wire is a parallel copy: it does not deliver
-//       the footer of a record after its payload the way an RC queue pair does, so the
-//       receiver must not be walking the chain while new records land behind it
 //   rx_apply_{t-2} -> rx_plan_t   the scatter plan and result block of that parity are free
 //   rx_apply_{t-2} -> plan_t      the sender sees every credit but (possibly) the last one
 // Everything else overlaps: the send plan and gather of round t+1 run while round t is on
 // the wire and being walked, and the scatter of round t runs under round t+1.  The
 // sender may see the credit of a scatter one round later than in the sequential
 // schedule; with rounds of at most ring/6 that never limits a Send.
-// Round 3 (j->deep, the default): every drain of a job walks only up to the tail its own Send computed
-// (grdma_rx_op::limit_ptr), so the third rule is dropped -- see the graph builder below for the edges.
+// Every drain of a job walks only up to the tail its own Send computed (grdma_rx_op::limit_ptr), so round t + 1 may
+// land in the ring while round t is walked (no rx_plan_{t-1} -> wire_t) -- the graph builder's limit-driven schedule.
 int job_enqueue_pipelined(grdma_stream_job* j, hipStream_t s) {
   const uint32_t n = (uint32_t)j->links.size();
-  const uint32_t tx_blocks = copy_blocks_for(j->max_ring / 2);
-  const uint32_t rx_blocks = copy_blocks_for(j->max_ring);
-  const uint32_t grid_cap = copy_blocks_for(~0ull >> 8);
-  const uint32_t txb = std::max<uint32_t>(1, std::min<uint32_t>(tx_blocks, grid_cap / n + 1));
-  const uint32_t rxb = std::max<uint32_t>(1, std::min<uint32_t>(rx_blocks, grid_cap / n + 1));
+  const uint32_t txb = job_copy_blocks(j, j->max_ring / 2), rxb = job_copy_blocks(j, j->max_ring);
   const uint64_t R = j->rounds;
   if (!j->s_wire) {
     HIP_TRY(hipStreamCreateWithFlags(&j->s_wire, hipStreamNonBlocking));
@@ -394,14 +367,8 @@ int job_enqueue_pipelined(grdma_stream_job* j, hipStream_t s) {
   for (uint64_t t = 0; t < R; t++) {
     const int k = job_opset(t);
     if (j->direct) {
-      // the plan itself writes the tags into the peer ring: no part of round t may start
-      // before the receiver has finished walking round t-1
-      // (limit-driven schedule: the drain walks up to its round's tail, only the credit lag is bounded)
-      if (j->deep) {
-        if (t >= 2) HIP_TRY(hipStreamWaitEvent(s, evA(t - 2), 0));
-      } else if (t >= 1) {
-        HIP_TRY(hipStreamWaitEvent(s, evX(t - 1), 0));
-      }
+      // (the gather writes the peer ring: the drain walks up to its round's tail, only the credit lag is bounded)
+      if (t >= 2) HIP_TRY(hipStreamWaitEvent(s, evA(t - 2), 0));
       HIP_TRY(job_launch_tx_plan(j, k, t, n, s));
       HIP_TRY(grdma_launch_copy(j->d_plans, n, txb, s));
       HIP_TRY(hipEventRecord(evW(t), s));
@@ -414,7 +381,6 @@ int job_enqueue_pipelined(grdma_stream_job* j, hipStream_t s) {
       HIP_TRY(grdma_launch_copy(j->d_plans, n, txb, s));
       HIP_TRY(hipEventRecord(evG(t), s));
       HIP_TRY(hipStreamWaitEvent(sW, evG(t), 0));
-      if (t >= 1 && !j->deep) HIP_TRY(hipStreamWaitEvent(sW, evX(t - 1), 0));
       HIP_TRY(grdma_launch_copy(j->d_plans + n * (1 + (t & 1)), n, txb, sW));
       HIP_TRY(hipEventRecord(evW(t), sW));
     }
@@ -436,97 +402,13 @@ int job_enqueue_pipelined(grdma_stream_job* j, hipStream_t s) {
   return 0;
 }
 
-
-// The limit-driven schedule on streams with CU masks.  A planner is ONE workgroup that needs most of a
-// CU's register file; the copy kernels are grid-strided over every slot of the machine and give none back
-// before they end, so a planner that becomes ready while a copy kernel is resident starts only behind it --
-// on a shared machine the planners serialise with the copies whatever the dependency edges say (measured:
-// the limit-driven graph is SLOWER than the paired one, 1.14 vs 1.04 ms per step).  Here the planners own
-// `cumask_bits` CUs (hipExtStreamCreateWithCUMask) and the copies run on the rest:
-//   m_txplan: P_t   after W_{t-2}, A_{t-2}, G_{t-1}
-//   m_copy:   G_t after P_t, then W_t                       (in stream order; they fill the machine anyway)
-//   m_rxplan: X_t   after W_t, A_{t-2}
-//   m_apply:  A_t   after X_t
-int job_enqueue_masked(grdma_stream_job* j, hipStream_t s) {
-  const uint32_t n = (uint32_t)j->links.size();
-  const uint32_t tx_blocks = copy_blocks_for(j->max_ring / 2);
-  const uint32_t rx_blocks = copy_blocks_for(j->max_ring);
-  const uint32_t grid_cap = copy_blocks_for(~0ull >> 8);
-  const uint32_t txb = std::max<uint32_t>(1, std::min<uint32_t>(tx_blocks, grid_cap / n + 1));
-  const uint32_t rxb = std::max<uint32_t>(1, std::min<uint32_t>(rx_blocks, grid_cap / n + 1));
-  const uint64_t R = j->rounds;
-  if (!j->m_txplan) {
-    int dev = 0, cus = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const int words = (cus + 31) / 32;
-    std::vector<uint32_t> mp(words, 0u), mc(words, 0xFFFFFFFFu);
-    for (int b = 0; b < j->cumask_bits && b < cus; b++) {
-      mp[b / 32] |= 1u << (b % 32);
-      mc[b / 32] &= ~(1u << (b % 32));
-    }
-    HIP_TRY(hipExtStreamCreateWithCUMask(&j->m_txplan, (uint32_t)words, mp.data()));
-    HIP_TRY(hipExtStreamCreateWithCUMask(&j->m_rxplan, (uint32_t)words, mp.data()));
-    HIP_TRY(hipExtStreamCreateWithCUMask(&j->m_copy, (uint32_t)words, mc.data()));
-    HIP_TRY(hipExtStreamCreateWithCUMask(&j->m_apply, (uint32_t)words, mc.data()));
-  }
-  while (j->mev.size() < 5 * R + 1) {
-    hipEvent_t ev;
-    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    j->mev.push_back(ev);
-  }
-  auto evP = [&](uint64_t t) { return j->mev[5 * t]; };
-  auto evG = [&](uint64_t t) { return j->mev[5 * t + 1]; };
-  auto evW = [&](uint64_t t) { return j->mev[5 * t + 2]; };  // round t is in the ring
-  auto evX = [&](uint64_t t) { return j->mev[5 * t + 3]; };
-  auto evA = [&](uint64_t t) { return j->mev[5 * t + 4]; };
-  hipStream_t sP = j->m_txplan, sC = j->m_copy, sX = j->m_rxplan, sA = j->m_apply;
-  hipEvent_t fork = j->mev[5 * R];
-  HIP_TRY(hipEventRecord(fork, s));
-  for (hipStream_t st : {sP, sC, sX, sA}) HIP_TRY(hipStreamWaitEvent(st, fork, 0));
-  for (uint64_t t = 0; t < R; t++) {
-    const int k = job_opset(t);
-    if (t >= 1) HIP_TRY(hipStreamWaitEvent(sP, evG(t - 1), 0));
-    if (t >= 2) {
-      HIP_TRY(hipStreamWaitEvent(sP, evW(t - 2), 0));
-      HIP_TRY(hipStreamWaitEvent(sP, evA(t - 2), 0));
-    }
-    HIP_TRY(job_launch_tx_plan(j, k, t, n, sP));
-    HIP_TRY(hipEventRecord(evP(t), sP));
-    HIP_TRY(hipStreamWaitEvent(sC, evP(t), 0));
-    HIP_TRY(grdma_launch_copy(j->d_plans, n, txb, sC));
-    HIP_TRY(hipEventRecord(evG(t), sC));
-    if (!j->direct) HIP_TRY(grdma_launch_copy(j->d_plans + n * (1 + (t & 1)), n, txb, sC));
-    HIP_TRY(hipEventRecord(evW(t), sC));
-    HIP_TRY(hipStreamWaitEvent(sX, evW(t), 0));
-    if (t >= 2) HIP_TRY(hipStreamWaitEvent(sX, evA(t - 2), 0));
-    HIP_TRY(job_launch_rx_plan(j, j->d_rxop + k * n, n, sX));
-    HIP_TRY(hipEventRecord(evX(t), sX));
-    HIP_TRY(hipStreamWaitEvent(sA, evX(t), 0));
-    HIP_TRY(grdma_launch_rx_apply(j->d_rxop + k * n, n, rxb, sA));
-    HIP_TRY(hipEventRecord(evA(t), sA));
-  }
-  if (R > 0) {
-    HIP_TRY(hipStreamWaitEvent(s, evW(R - 1), 0));
-    HIP_TRY(hipStreamWaitEvent(s, evA(R - 1), 0));
-    HIP_TRY(hipStreamWaitEvent(s, evP(R - 1), 0));
-  }
-  HIP_TRY(grdma_launch_tx_commit(j->d_txconns, nullptr, n, s));
-  return 0;
-}
-
-
 // The job as an explicitly built HIP graph: 5 kernel nodes per round, edges exactly as
 // listed above (pipelined) or a plain chain (sequential).  Built node by node rather
 // than recorded from the streams: the dependency structure is known here, and it keeps
 // the replay independent of how a runtime records cross-stream joins.
 int job_build_graph(grdma_stream_job* j, hipGraph_t* out) {
   const uint32_t n = (uint32_t)j->links.size();
-  const uint32_t tx_blocks = copy_blocks_for(j->max_ring / 2);
-  const uint32_t rx_blocks = copy_blocks_for(j->max_ring);
-  const uint32_t grid_cap = copy_blocks_for(~0ull >> 8);
-  const uint32_t txb = std::max<uint32_t>(1, std::min<uint32_t>(tx_blocks, grid_cap / n + 1));
-  const uint32_t rxb = std::max<uint32_t>(1, std::min<uint32_t>(rx_blocks, grid_cap / n + 1));
+  const uint32_t txb = job_copy_blocks(j, j->max_ring / 2), rxb = job_copy_blocks(j, j->max_ring);
   const uint64_t R = j->rounds;
   hipGraph_t g;
   HIP_TRY(hipGraphCreate(&g, 0));
@@ -554,28 +436,20 @@ int job_build_graph(grdma_stream_job* j, hipGraph_t* out) {
     return after;
   };
   const hipGraphNode_t pre_last = R > 0 ? add_hooks(j->pre_hooks, nullptr) : nullptr;
-  // (every node hands over three pointer-sized parameters; a kernel with fewer ignores the rest)
+  // (every node hands over the parameters of job_kargs; a kernel with fewer ignores the rest)
   auto add3 = [&](hipGraphNode_t* node, const void* fn, dim3 grid, uint32_t threads, const void* arg, const void* arg2,
                   const void* arg3, std::initializer_list<hipGraphNode_t> deps, uint32_t arg4 = 0, const void* arg5 = nullptr) -> hipError_t {
     std::vector<hipGraphNode_t> d;
     for (hipGraphNode_t x : deps)
       if (x && std::find(d.begin(), d.end(), x) == d.end()) d.push_back(x);  // (a node twice is an invalid argument)
     if (d.empty() && pre_last) d.push_back(pre_last);  // a root of the job waits for the stage in front of it
-    // (an array of GRDMA_JOB_HOOK_ARGS entries for every node -- the runtime reads as many as the kernel has)
-    static uint64_t none = 0;
-    void* args[GRDMA_JOB_HOOK_ARGS];
-    for (uint32_t a = 0; a < GRDMA_JOB_HOOK_ARGS; a++) args[a] = &none;
-    args[0] = const_cast<void*>(static_cast<const void*>(&arg));
-    args[1] = const_cast<void*>(static_cast<const void*>(&arg2));
-    args[2] = const_cast<void*>(static_cast<const void*>(&arg3));
-    args[3] = &arg4;  // (a fourth, 4-byte parameter: k_plan_pair_mw's workgroup split)
-    args[4] = const_cast<void*>(static_cast<const void*>(&arg5));  // (k_plan_pair_mw's wire plans)
+    job_kargs a(arg, arg2, arg3, arg4, arg5);
     hipKernelNodeParams np;
     memset(&np, 0, sizeof(np));
     np.func = const_cast<void*>(fn);
     np.gridDim = grid;
     np.blockDim = dim3(threads);
-    np.kernelParams = args;
+    np.kernelParams = a.v;
     return hipGraphAddKernelNode(node, g, d.empty() ? nullptr : d.data(), d.size(), &np);
   };
   auto add2 = [&](hipGraphNode_t* node, const void* fn, dim3 grid, uint32_t threads, const void* arg, const void* arg2,
@@ -586,14 +460,12 @@ int job_build_graph(grdma_stream_job* j, hipGraph_t* out) {
                  std::initializer_list<hipGraphNode_t> deps) -> hipError_t {
     return add2(node, fn, grid, threads, arg, nullptr, deps);
   };
-  const void* f_pair = grdma_kernel_fn_plan_pair();
   const void* f_txp = grdma_kernel_fn(0);
   const void* f_cpy = grdma_kernel_fn(1);
   const void* f_rxp = grdma_kernel_fn_rx_plan();
   const void* f_rxa = grdma_kernel_fn(3);
   const uint32_t pt = grdma_kernel_threads(0), ct = grdma_kernel_threads(1);
-  const bool fast = j->rx_fast && j->burst == 1;
-  const bool tfast = job_tx_fast(j);
+  const bool fast = j->rx_fast, tfast = j->tx_fast;
   const void* f_txi = grdma_kernel_fn_tx_index();
   const void* f_txj = grdma_kernel_fn(6);
   const void* f_rxj = grdma_kernel_fn_rx_plan_job();
@@ -617,7 +489,7 @@ int job_build_graph(grdma_stream_job* j, hipGraph_t* out) {
     dv.resize(4, nullptr);  // (round 0's dependencies: at most four, all null today)
     const hipGraphNode_t d0 = pi ? pi : dv[0], d1 = pi ? nullptr : dv[1], d2 = pi ? nullptr : dv[2], d3 = pi ? nullptr : dv[3];
     // (the first Send of a step priced by the small workgroups of the planner pair too: k_plan_pair_mw with no drain)
-    if ((j->rx_multi && j->pipeline && j->pair_job) || job_mw_seq(j))
+    if (j->pipeline || job_mw_seq(j))
       return add3(&P[t], grdma_kernel_fn_plan_pair_mw(), dim3(n, job_tx_groups(j)), grdma_kernel_threads(0), nullptr, txop,
                   j->d_txf, {d0, d1, d2, d3}, 0u);
     return add2(&P[t], f_txj, dim3(n), grdma_tx_plan_job_threads(), txop, j->d_txf, {d0, d1, d2, d3});
@@ -654,15 +526,15 @@ int job_build_graph(grdma_stream_job* j, hipGraph_t* out) {
       }
       if (e == hipSuccess) e = add_rx(t, rxop, {last});
       if (e == hipSuccess) e = add(&A[t], f_rxa, dim3(rxb, n), ct, rxop, {X[t]});
-    } else if (fast && tfast && j->pair_job) {
+    } else if (fast && tfast) {
       // One launch for the drain of round t and the Send of round t + 1 (k_plan_pair_mw): kernels of different
       // branches of a graph do not overlap on this stack (measured: even planner workgroups small enough to sit
       // beside the copy kernels' run behind them), so the round is a chain -- and this one has four links:
       //   G_t: P_t (= X_{t-1})      W_t: G_t      X_t + P_{t+1}: W_t, A_{t-1}      A_t: X_t
-      // (j->fuse_ag, default: the scatter of round t and the gather of round t + 1 share a launch -- both are ready
-      // behind the planner pair, neither touches the other's bytes: G_{t+1} = A_t, three launches per round)
+      // (the scatter of round t and the gather of round t + 1 share a launch -- both are ready behind the planner pair,
+      // neither touches the other's bytes: G_{t+1} = A_t, three launches per round)
       if (t == 0) e = add_tx(0, txop, {});
-      if (e == hipSuccess && (t == 0 || !j->fuse_ag)) e = add(&G[t], f_cpy, dim3(txb, n), ct, gplans, {P[t], at(A, t, 1)});
+      if (e == hipSuccess && t == 0) e = add(&G[t], f_cpy, dim3(txb, n), ct, gplans, {P[t], at(A, t, 1)});
       // (a direct wire has no wire kernel: the gather writes the records into the peer ring, two launches per round)
       // (few links with small rings: the wire rides in the planner pair's launch -- job_wire_groups, k_plan_pair_mw)
       const uint32_t wg_wire = job_wire_groups(j);
@@ -677,17 +549,17 @@ int job_build_graph(grdma_stream_job* j, hipGraph_t* out) {
         if (more) P[t + 1] = X[t];
       }
       if (e == hipSuccess) {
-        if (more && j->fuse_ag) {
+        if (more) {
           e = add2(&A[t], grdma_kernel_fn(8), dim3(std::max(rxb, txb), 2 * n), ct, rxop, gplans, {X[t]});
           G[t + 1] = A[t];
         } else {
           e = add(&A[t], f_rxa, dim3(rxb, n), ct, rxop, {X[t]});
         }
       }
-    } else if (j->deep || fast || tfast) {
-      // Limit-driven schedule (default): the drain of round t walks exactly up to the tail its Send
-      // computed (grdma_rx_op::limit_ptr), so round t + 1 may land in the ring while round t is being
-      // walked -- the edge rx_plan_{t-1} -> wire_t of the older schedule is gone and both planners
+    } else {
+      // Limit-driven schedule (a pipelined job that grdma_stream_job_run switched off rx_fast or tx_fast after repeated
+      // declines): the drain of round t walks exactly up to the tail its Send computed (grdma_rx_op::limit_ptr), so
+      // round t + 1 may land in the ring while round t is being walked -- no edge rx_plan_{t-1} -> wire_t, both planners
       // leave the wire's path.  What is left of the ordering:
       //   P_t: P_{t-1} (the sender's state), G_{t-1} (one gather plan), W_{t-2} (staging / wire plan of
       //        this parity), A_{t-2} (credit lag of at most one round; implies X_{t-2}: the limit slot)
@@ -705,27 +577,6 @@ int job_build_graph(grdma_stream_job* j, hipGraph_t* out) {
         last = W[t];
       }
       if (e == hipSuccess) e = add_rx(t, rxop, {last, at(X, t, 1), at(A, t, 2)});
-      if (e == hipSuccess) e = add(&A[t], f_rxa, dim3(rxb, n), ct, rxop, {X[t], at(A, t, 1)});
-    } else if (j->direct) {
-      e = add(&P[t], f_txp, dim3(n), pt, txop, {at(G, t, 1), at(X, t, 1)});
-      if (e == hipSuccess) e = add(&G[t], f_cpy, dim3(txb, n), ct, gplans, {P[t]});
-      W[t] = nullptr;
-      if (e == hipSuccess) e = add(&X[t], f_rxp, dim3(n), pt, rxop, {G[t], at(A, t, 2)});
-      if (e == hipSuccess) e = add(&A[t], f_rxa, dim3(rxb, n), ct, rxop, {X[t], at(A, t, 1)});
-    } else {
-      // The send plan of round t + 1 shares a launch with the receive plan of round t
-      // (k_plan_pair): P[t + 1] and X[t] are the same node.  Its dependencies are the union of
-      // both kernels': the wire of round t (which implies gather t and everything of round
-      // t - 1 but its scatter) and the scatter of round t - 1 (the credit the next Send may use).
-      if (t == 0) e = add(&P[0], f_txp, dim3(n), pt, txop, {});
-      if (e == hipSuccess) e = add(&G[t], f_cpy, dim3(txb, n), ct, gplans, {P[t], at(A, t, 2)});
-      if (e == hipSuccess) e = add(&W[t], f_cpy, dim3(txb, n), ct, wplans, {G[t], at(X, t, 1)});
-      if (e == hipSuccess) {
-        const bool more = t + 1 < R;
-        const void* txop_next = j->d_txop + job_opset(t + 1) * n;
-        e = add2(&X[t], f_pair, dim3(n, more ? 2 : 1), pt, rxop, more ? txop_next : nullptr, {W[t], at(A, t, 1)});
-        if (more) P[t + 1] = X[t];
-      }
       if (e == hipSuccess) e = add(&A[t], f_rxa, dim3(rxb, n), ct, rxop, {X[t], at(A, t, 1)});
     }
   }
@@ -759,15 +610,6 @@ grdma_stream_job* grdma_stream_job_create_multi(uint32_t n, grdma_pair* const* t
     return nullptr;
   }
   grdma_stream_job* j = new grdma_stream_job();
-  if (const char* e = getenv("GRDMA_JOB_SCHEDULE")) j->deep = strcmp(e, "pair") == 0 ? 0 : 1;
-  if (const char* e = getenv("GRDMA_JOB_CUMASK")) j->cumask_bits = atoi(e);
-  if (const char* e = getenv("GRDMA_RX_FAST")) j->rx_fast = atoi(e) != 0;
-  if (const char* e = getenv("GRDMA_RX_MULTI")) j->rx_multi = atoi(e) != 0;
-  if (const char* e = getenv("GRDMA_PAIR_JOB")) j->pair_job = atoi(e) != 0;
-  if (!j->rx_multi) j->pair_job = 0;  // (the paired schedule's planner pair IS the many-workgroup launch, k_plan_pair_mw)
-  if (const char* e = getenv("GRDMA_JOB_FUSE_AG")) j->fuse_ag = atoi(e) != 0;
-  if (const char* e = getenv("GRDMA_JOB_FUSE_WIRE")) j->fuse_wire = atoi(e) != 0;
-  if (const char* e = getenv("GRDMA_TX_FAST")) j->tx_fast = atoi(e) != 0;
   j->rounds = max_rounds;
   j->stream = tx[0]->stream;
   j->direct = (tx[0]->flags & GRDMA_WIRE_DIRECT) != 0;
@@ -815,11 +657,9 @@ grdma_stream_job* grdma_stream_job_create_multi(uint32_t n, grdma_pair* const* t
     off += l.count;
     ok = hipMemcpy(l.d_sges, tmp.data(), sizeof(grdma_sge) * l.count, hipMemcpyHostToDevice) == hipSuccess;
   }
-  // (the size tables of the rounds: GRDMA_JOB_SIZE_HINTS=0 leaves them out -- drains without a period then walk)
-  if (ok && !(getenv("GRDMA_JOB_SIZE_HINTS") && atoi(getenv("GRDMA_JOB_SIZE_HINTS")) == 0)) {
-    ok = hipMalloc((void**)&j->d_hints, sizeof(grdma_size_hint) * 3 * n) == hipSuccess &&
-         hipMemset(j->d_hints, 0, sizeof(grdma_size_hint) * 3 * n) == hipSuccess;
-  }
+  // (the size tables of the rounds)
+  ok = ok && hipMalloc((void**)&j->d_hints, sizeof(grdma_size_hint) * 3 * n) == hipSuccess &&
+       hipMemset(j->d_hints, 0, sizeof(grdma_size_hint) * 3 * n) == hipSuccess;
   const size_t sz_tx = sizeof(grdma_tx_op) * 3 * n, sz_rx = sizeof(grdma_rx_op) * 3 * n;
   const size_t sz_txr = sizeof(grdma_tx_result) * n, sz_rxr = sizeof(grdma_rx_result) * 2 * n;
   const size_t sz_pl = sizeof(grdma_plan*) * 3 * n;
@@ -855,7 +695,7 @@ grdma_stream_job* grdma_stream_job_create_multi(uint32_t n, grdma_pair* const* t
       t.result = &j->d_txres[i];
       t.use_cursor = k == 0 ? 2 : 1;
       t.tail_out = &j->d_limits[k * n + i];
-      t.sizes_out = j->d_hints ? &j->d_hints[k * n + i] : nullptr;
+      t.sizes_out = &j->d_hints[k * n + i];
       grdma_rx_op& r = h_rx[k * n + i];
       r.conn = l.rx->d_conn;
       r.plan = odd ? l.d_rxplan2 : l.rx->d_rxplan;
@@ -917,7 +757,7 @@ void grdma_stream_job_destroy(grdma_stream_job* j) {
   if (!j) return;
   if (j->stream) hipStreamSynchronize(j->stream);
   if (j->exec) hipGraphExecDestroy(j->exec);
-  for (hipStream_t st : {j->s_wire, j->s_rxplan, j->s_apply, j->m_txplan, j->m_rxplan, j->m_copy, j->m_apply})
+  for (hipStream_t st : {j->s_wire, j->s_rxplan, j->s_apply})
     if (st) {
       hipStreamSynchronize(st);
       hipStreamDestroy(st);
@@ -931,7 +771,6 @@ void grdma_stream_job_destroy(grdma_stream_job* j) {
   }
   for (hipEvent_t e : j->kev) hipEventDestroy(e);
   for (hipEvent_t e : j->pev) hipEventDestroy(e);
-  for (hipEvent_t e : j->mev) hipEventDestroy(e);
   if (j->ev0) hipEventDestroy(j->ev0);
   if (j->ev1) hipEventDestroy(j->ev1);
   for (auto& l : j->links) {
@@ -1067,10 +906,10 @@ int grdma_stream_job_run(grdma_stream_job* j, int mode, grdma_stream_result* out
     HIP_TRY(hipEventRecord(j->ev0, s));
     if (mode == GRDMA_RUN_INSTRUMENTED_SCHEDULE) {
       if (int rc = job_enqueue_schedule_instrumented(j, s)) return rc;
-    } else if (j->pipeline && j->burst == 1 && mode == GRDMA_RUN_EAGER && !j->promise) {
+    } else if (j->pipeline && mode == GRDMA_RUN_EAGER && !j->promise) {
       // (a promised-credit job's eager pass runs in order instead: the stream pipeline sees its credit a round late,
       //  the graph of such a job does not)
-      if (int rc = (j->cumask_bits > 0 ? job_enqueue_masked(j, s) : job_enqueue_pipelined(j, s))) return rc;
+      if (int rc = job_enqueue_pipelined(j, s)) return rc;
     } else {
       if (int rc = job_enqueue(j, s, mode == GRDMA_RUN_INSTRUMENTED)) return rc;
     }
@@ -1119,11 +958,11 @@ int grdma_stream_job_run(grdma_stream_job* j, int mode, grdma_stream_result* out
   // its record sizes, Sends cut by the staging budget, ... -- goes back to the plain planner kernels.
   j->runs++;
   // (round 0 of this run built the index -- only a schedule that prices its Sends from it launches k_tx_index: a run
-  //  with a burst leaves the index as it was)
-  if (job_tx_fast(j) && j->rounds >= 1) j->index_valid = true;
+  //  on the general send planner leaves the index as it was)
+  if (j->tx_fast && j->rounds >= 1) j->index_valid = true;
   // (not with several Sends per plan: only the small planner workgroups price those, and what they decline is planned
   //  by the general planners inside the same launch, at their full register budget)
-  if (j->burst == 1 && j->sends == 1 && !j->promise && j->rounds >= 2 && (j->rx_fast || job_tx_fast(j))) {
+  if (j->sends == 1 && !j->promise && j->rounds >= 2 && (j->rx_fast || j->tx_fast)) {
     uint64_t cnt[3][2];  // {taken, declined with work waiting} of link 0: drains of both parities, Sends
     uint32_t c32[2][2];  // {pad1 = taken, pad0 = declined}
     static_assert(offsetof(grdma_rx_result, pad0) == offsetof(grdma_rx_result, pad1) + 4, "layout");
@@ -1205,7 +1044,6 @@ extern "C" __attribute__((visibility("hidden"))) int grdma_job_set_hooks(grdma_s
 int grdma_stream_job_launch_streams(grdma_stream_job* j) {
   if (int rc = require_ctx()) return rc;
   if (!j) return fail(GRDMA_ERR_INVALID, "null job");
-  if (j->pipeline && j->cumask_bits > 0 && j->burst == 1) return job_enqueue_masked(j, j->stream);
   return j->pipeline ? job_enqueue_pipelined(j, j->stream) : job_enqueue(j, j->stream, false);
 }
 

@@ -1,21 +1,5 @@
-// Planner kernels of the streaming job: k_plan_pair, k_plan_pair_mw (drain plan of round t + send plan of round t + 1 as many small workgroups), k_rx_plan_mw.
+// Planner kernels of the streaming job: k_plan_pair_mw (drain plan of round t + send plan of round t + 1 as many small workgroups), k_rx_plan_mw.
 // (device code, textually included by grdma_rx_plan.hip inside its unnamed namespace: the plan bodies it calls are there)
-// ----------------------------------------------------------------------------
-// k_plan_pair: the two planners of a pipelined round in ONE launch.  The send plan of round t + 1
-// depends on the gather of round t and on the credit of round t - 1, not on the receive plan of
-// round t; both are single-workgroup, latency-bound kernels, and a queue runs kernels one after
-// the other -- so they share a launch: workgroup (link, 0) walks and plans the drain of round t,
-// workgroup (link, 1) prices the Send of round t + 1 on another CU at the same time.  They touch
-// different connection blocks (the receiving and the sending end).  gridDim.y == 1: the receive
-// plan alone (last round).
-// ----------------------------------------------------------------------------
-__global__ __launch_bounds__(PLAN_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void k_plan_pair(const grdma_rx_op* rxops, const grdma_tx_op* txops) {
-  // (both bodies inline: the out-of-line copies used by the resident engine spill)
-  if (blockIdx.y == 0) rx_plan_body(rxops[blockIdx.x]);
-  else tx_plan_body(txops[blockIdx.x]);
-}
-
 // ----------------------------------------------------------------------------
 // k_plan_pair_mw: the planner pair of a streaming job's round as MANY small workgroups: the drain of round t laid out by
 // G workgroups of four wavefronts (grdma_rx_multi.h: one record per thread, nothing exchanged between the workgroups
@@ -43,7 +27,7 @@ void k_plan_pair_mw(const grdma_rx_op* rxops, const grdma_tx_op* txops, const gr
   // wait for the last wire workgroup before they look at the ring (csrc/grdma_rx_multi.h: wire_arrive / wire_wait).  A
   // round is two launches then, and the drain's first 4-5 us run under the wire's.
   // Dispatch order is blockIdx.y order: wire workgroups first, then the drain's, then the Send's -- who waits comes
-  // after whom it waits for, and the host only asks for all this when every workgroup of the launch has a CU at once.
+  // after whom it waits for, and every wait is bounded (the invariant: grdma_host_job.inc, above job_promise).
   const uint32_t Wn = wplans != nullptr ? (G_mode >> 20) : 0u;
   const uint32_t G = G_mode & 0xFFFFu;
   if (blockIdx.y < Wn) {

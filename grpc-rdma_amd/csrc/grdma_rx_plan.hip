@@ -1697,7 +1697,6 @@ extern "C" __attribute__((visibility("hidden"))) int grdma_tx_fast_sends_pair(ui
   out[1] = v[1];
   return 0;
 }
-extern "C" __attribute__((visibility("hidden"))) const void* grdma_kernel_fn_plan_pair(void) { return reinterpret_cast<const void*>(&k_plan_pair); }
 
 extern "C" __attribute__((visibility("hidden"))) hipError_t grdma_launch_rx_plan(const grdma_rx_op* d_ops, uint32_t nops,
                                            hipStream_t s) {

@@ -499,8 +499,8 @@ int grdma_stream_job_set_promised_credit(grdma_stream_job* j, int on);
 /* Paired schedule, staged wire, a job of few links with rings of at most 16 MiB: the wire of a round rides in the launch
  * of the planner pair (wire workgroups of k_plan_pair_mw; the drain's workgroups wait for them before they look at the
  * ring) instead of a k_copy launch of its own -- two launches per round.  On by default where every workgroup of that
- * launch has a CU at once (GRDMA_JOB_FUSE_WIRE=0 in the environment: off); the getter says how many wire workgroups per
- * link the job's graph carries (0: the wire is a launch of its own). */
+ * launch has a CU at once; this call with on = 0 turns it off.  The getter says how many wire workgroups per link the
+ * job's graph carries (0: the wire is a launch of its own). */
 int grdma_stream_job_set_fused_wire(grdma_stream_job* j, int on);
 uint32_t grdma_stream_job_wire_groups(grdma_stream_job* j);
 /* The job's slice tables are rewritten between steps (every grpc_endpoint_write brings a new slice buffer,
