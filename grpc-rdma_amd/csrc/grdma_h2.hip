@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "grdma_h2_kernels.h"
+#include "grdma_h2_asm.h"
 
 // --------------------------------------------------------------------- host API
 // Everything here runs on one non-blocking stream of its own and waits with
@@ -447,11 +448,17 @@ struct grdma_h2_pipe {
   bool chunked = false;  // the parser has chunk buffers for this pipe's event capacity
   bool fused = false;    // framing and deframing are nodes of the job's graph (one launch per step)
   bool timed = false;    // the last step recorded the per-stage timing events
+  grdma_h2_asm* asm_ = nullptr;  // the message assembler behind the deframer (grdma_h2_pipe_attach_assembler)
+  h2a_call* d_call = nullptr;    // where this pipe's deframer leaves its output, for the assembler
+  grdma_job_hook pre[2], post[2];
+  uint32_t n_pre = 0, n_post = 0;
 };
 
 namespace {
 hipStream_t g_pipe_frame_stream = nullptr, g_pipe_deframe_stream = nullptr;
 }
+static void h2_asm_detach(grdma_h2_pipe* p);
+static void h2_asm_enqueue(grdma_h2_asm* a, const h2a_call* d_call, hipStream_t st);
 
 grdma_h2_pipe* grdma_h2_pipe_create(grdma_stream_job* job, uint32_t link, const grdma_h2_msg* msgs, uint64_t nmsgs,
                                     uint32_t max_frame, grdma_h2_parser* parser, uint64_t delivered_slices,
@@ -540,6 +547,10 @@ grdma_h2_pipe* grdma_h2_pipe_create(grdma_stream_job* job, uint32_t link, const 
                                 ptr(p->d_dres)}};
       n_post = 1;
     }
+    memcpy(p->pre, pre, sizeof(pre));
+    memcpy(p->post, post, sizeof(post));
+    p->n_pre = n_pre;
+    p->n_post = n_post;
     if (grdma_job_set_hooks(job, pre, n_pre, post, n_post) != 0) {
       grdma_h2_pipe_destroy(p);
       return nullptr;
@@ -559,6 +570,8 @@ void grdma_h2_pipe_destroy(grdma_h2_pipe* p) {
   }
   if (p->parser && p->parser->last_deframed == p->deframed) p->parser->last_deframed = nullptr;  // (synchronised above)
   if (p->fused && p->job) grdma_job_set_hooks(p->job, nullptr, 0, nullptr, 0);
+  h2_asm_detach(p);
+  hipFree(p->d_call);
   hipFree(p->d_msgs);
   hipFree(p->d_pos);
   hipFree(p->d_hdr);
@@ -615,6 +628,7 @@ int grdma_h2_pipe_enqueue(grdma_h2_pipe* p, int schedule) {
     return -GRDMA_ERR_HIP;  // (the parser state is handed from one deframing to the next)
   hipEventRecord(p->t_d0, p->deframe_stream);
   h2_enqueue_deframe(p->parser, p->dst, p->d_slices, p->delivered, p->d_ev, p->ev_cap, p->d_dres, p->deframe_stream, p->chunked);
+  if (p->asm_) h2_asm_enqueue(p->asm_, p->d_call, p->deframe_stream);
   hipEventRecord(p->t_d1, p->deframe_stream);
   if (hipEventRecord(p->deframed, p->deframe_stream) != hipSuccess) return -GRDMA_ERR_HIP;
   p->parser->last_stream = p->deframe_stream;
@@ -671,4 +685,258 @@ int grdma_h2_pipe_boundary_stats(grdma_h2_pipe* p, uint64_t out[2]) {
   return 0;
 }
 
+// ---- the message assembler (csrc/grdma_h2_asm.h) -----------------------------------------------------------
+struct grdma_h2_asm {
+  grdma_h2_parser* parser = nullptr;
+  h2a_dev* d = nullptr;
+  h2a_dev h;                       // host copy of the configuration words (pointers, capacities)
+  h2a_call* d_call = nullptr;      // standalone calls
+  uint32_t attached = 0;           // pipes that assemble through it
+  float plan_ms = 0, copy_ms = 0;  // of the last standalone call
+  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+};
+
+static void h2_asm_free_scratch(h2a_dev* h) {
+  hipFree(h->tiles);
+  hipFree(h->keys);
+  hipFree(h->comp);
+  hipFree(h->msgs);
+  hipFree(h->pieces);
+  hipFree(h->dtmp);
+  hipFree(h->desc);
+  h->tiles = nullptr;
+  h->keys = nullptr;
+  h->comp = nullptr;
+  h->msgs = nullptr;
+  h->pieces = nullptr;
+  h->dtmp = nullptr;
+  h->desc = nullptr;
+  h->scratch_ev = h->desc_cap = 0;
+}
+
+// per-call buffers for calls of up to ev_cap events (a resize drains the device: setup, not a hot path)
+static bool h2_asm_prepare(grdma_h2_asm* a, uint64_t ev_cap) {
+  ev_cap = (ev_cap + 63) & ~63ull;  // (the kernels work in wave tiles of 64 events)
+  if (ev_cap <= a->h.scratch_ev) return true;
+  if (hipDeviceSynchronize() != hipSuccess) return false;
+  h2a_dev& h = a->h;
+  h2_asm_free_scratch(&h);
+  const uint64_t tiles = (ev_cap + 63) / 64;
+  const uint64_t dcap = ev_cap + (uint64_t)h.tab_mask + 1;
+  const bool ok = hipMalloc((void**)&h.tiles, sizeof(h2a_tile) * tiles) == hipSuccess &&
+                  hipMalloc((void**)&h.keys, sizeof(h2a_key) * tiles * 64) == hipSuccess &&
+                  hipMalloc((void**)&h.comp, sizeof(uint32_t) * tiles * 64) == hipSuccess &&
+                  hipMalloc((void**)&h.msgs, sizeof(h2a_msg) * ev_cap) == hipSuccess &&
+                  hipMalloc((void**)&h.pieces, sizeof(h2a_piece) * ev_cap) == hipSuccess &&
+                  hipMalloc((void**)&h.dtmp, sizeof(grdma_h2_rx_msg) * ev_cap) == hipSuccess &&
+                  hipMalloc((void**)&h.desc, sizeof(grdma_h2_rx_msg) * dcap) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    h2_asm_free_scratch(&h);
+  } else {
+    h.scratch_ev = ev_cap;
+    h.desc_cap = dcap;
+  }
+  // the configuration words only: the ring and the counters stay where the device has them
+  return hipMemcpy(&a->d->scratch_ev, &h.scratch_ev, offsetof(h2a_dev, vh) - offsetof(h2a_dev, scratch_ev),
+                   hipMemcpyHostToDevice) == hipSuccess && ok;
+}
+
+// the assembly of one call, enqueued on st behind its deframing
+static void h2_asm_enqueue(grdma_h2_asm* a, const h2a_call* d_call, hipStream_t st) {
+  h2a_dev* d = a->d;
+  hipLaunchKernelGGL(k_h2_asm_tiles, dim3(H2A_GRID), dim3(H2A_THREADS), 0, st, d, d_call);
+  hipLaunchKernelGGL(k_h2_asm_carry, dim3(1), dim3(H2A_ONE_THREADS), 0, st, d, d_call);
+  hipLaunchKernelGGL(k_h2_asm_begin, dim3(H2A_GRID), dim3(H2A_THREADS), 0, st, d, d_call);
+  hipLaunchKernelGGL(k_h2_asm_bytes, dim3(H2A_GRID), dim3(H2A_THREADS), 0, st, d, d_call);
+  hipLaunchKernelGGL(k_h2_asm_finish, dim3(1), dim3(H2A_ONE_THREADS), 0, st, d, d_call);
+  hipLaunchKernelGGL(k_h2_asm_copy, dim3(H2A_GRID), dim3(H2A_THREADS), 0, st, d, d_call);
+}
+
+// the same six kernels as post hooks of a fused pipe's graph, behind the deframer's
+static uint32_t h2_asm_hooks(grdma_h2_asm* a, const h2a_call* d_call, grdma_job_hook* out) {
+  const void* fns[6] = {(const void*)k_h2_asm_tiles, (const void*)k_h2_asm_carry, (const void*)k_h2_asm_begin,
+                        (const void*)k_h2_asm_bytes, (const void*)k_h2_asm_finish, (const void*)k_h2_asm_copy};
+  const uint32_t grids[6] = {H2A_GRID, 1, H2A_GRID, H2A_GRID, 1, H2A_GRID};
+  const uint32_t threads[6] = {H2A_THREADS, H2A_ONE_THREADS, H2A_THREADS, H2A_THREADS, H2A_ONE_THREADS, H2A_THREADS};
+  for (int k = 0; k < 6; k++) {
+    memset(&out[k], 0, sizeof(out[k]));
+    out[k].fn = fns[k];
+    out[k].grid = grids[k];
+    out[k].threads = threads[k];
+    out[k].args[0] = (uint64_t)(uintptr_t)a->d;
+    out[k].args[1] = (uint64_t)(uintptr_t)d_call;
+  }
+  return 6;
+}
+
+static void h2_asm_detach(grdma_h2_pipe* p) {
+  if (p->asm_) {
+    p->asm_->attached--;
+    p->asm_ = nullptr;
+  }
+}
+
+grdma_h2_asm* grdma_h2_asm_create(grdma_h2_parser* parser, void* d_arena, uint64_t arena_bytes,
+                                  uint64_t max_message_bytes, uint32_t max_pending) {
+  if (grdma_device_count() <= 0 || !parser || !d_arena || arena_bytes < H2A_GRANULE || max_pending == 0 ||
+      max_pending >= 0x7fffffffu)
+    return nullptr;
+  grdma_h2_asm* a = new grdma_h2_asm();
+  a->parser = parser;
+  memset(&a->h, 0, sizeof(a->h));
+  h2a_dev& h = a->h;
+  h.arena = static_cast<uint8_t*>(d_arena);
+  h.arena_bytes = arena_bytes;
+  h.max_msg = max_message_bytes;
+  h.max_pending = max_pending;
+  h.tab_mask = parser->slots - 1;
+  bool ok = hipMalloc((void**)&a->d, sizeof(h2a_dev)) == hipSuccess &&
+            hipMalloc((void**)&h.tab, sizeof(h2a_carry) * parser->slots) == hipSuccess &&
+            hipMalloc((void**)&h.recs, sizeof(h2a_rec) * max_pending) == hipSuccess &&
+            hipMalloc((void**)&h.fin, sizeof(h2a_key) * H2A_LDS_KEYS) == hipSuccess &&
+            hipMalloc((void**)&a->d_call, sizeof(h2a_call)) == hipSuccess &&
+            hipMemset(h.tab, 0, sizeof(h2a_carry) * parser->slots) == hipSuccess &&
+            hipMemcpy(a->d, &h, sizeof(h), hipMemcpyHostToDevice) == hipSuccess &&
+            hipEventCreate(&a->e0) == hipSuccess && hipEventCreate(&a->e1) == hipSuccess &&
+            hipEventCreate(&a->e2) == hipSuccess;
+  if (!ok) {
+    grdma_h2_asm_destroy(a);
+    return nullptr;
+  }
+  return a;
+}
+
+void grdma_h2_asm_destroy(grdma_h2_asm* a) {
+  if (!a || a->attached) return;  // (a pipe's graph still runs its kernels on it: destroy the pipes first)
+  hipDeviceSynchronize();
+  h2_asm_free_scratch(&a->h);
+  hipFree(a->h.tab);
+  hipFree(a->h.recs);
+  hipFree(a->h.fin);
+  hipFree(a->d);
+  hipFree(a->d_call);
+  for (hipEvent_t e : {a->e0, a->e1, a->e2})
+    if (e) hipEventDestroy(e);
+  delete a;
+}
+
+int64_t grdma_h2_deframe_messages(grdma_h2_parser* p, grdma_h2_asm* a, const void* d_arena,
+                                  const grdma_read_slice* slices, uint64_t n,
+                                  grdma_h2_event* events_out, uint64_t ev_cap,
+                                  grdma_h2_rx_msg* msgs_out, uint64_t msgs_cap, int* h2_error) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!p || !a || a->parser != p || a->attached || !d_arena || (!slices && n) || ev_cap == 0 || (!msgs_out && msgs_cap))
+    return -GRDMA_ERR_INVALID;
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  if (!h2_grow(&p->d_sl, &p->sl_cap, n ? n : 1) || !h2_grow(&p->d_ev, &p->ev_cap, ev_cap) || !h2_asm_prepare(a, ev_cap))
+    return -GRDMA_ERR_HIP;
+  hipStream_t st = hc->stream;
+  const h2a_call call{p->d_ev, p->d_res, p->d_sl, static_cast<const uint8_t*>(d_arena), ev_cap, 0};
+  if (hipMemcpyAsync(a->d_call, &call, sizeof(call), hipMemcpyHostToDevice, st) != hipSuccess ||
+      (n && hipMemcpyAsync(p->d_sl, slices, sizeof(grdma_slice_out) * n, hipMemcpyHostToDevice, st) != hipSuccess))
+    return -GRDMA_ERR_HIP;
+  const bool chunked = n >= H2_CHUNK_MIN_SLICES && h2_chunks_prepare(p, ev_cap, st);
+  h2_enqueue_deframe(p, static_cast<const uint8_t*>(d_arena), p->d_sl, n, p->d_ev, ev_cap, p->d_res, st, chunked);
+  // the assembly: the plan (five kernels), then the copy, timed apart
+  h2a_dev* d = a->d;
+  hipEventRecord(a->e0, st);
+  hipLaunchKernelGGL(k_h2_asm_tiles, dim3(H2A_GRID), dim3(H2A_THREADS), 0, st, d, (const h2a_call*)a->d_call);
+  hipLaunchKernelGGL(k_h2_asm_carry, dim3(1), dim3(H2A_ONE_THREADS), 0, st, d, (const h2a_call*)a->d_call);
+  hipLaunchKernelGGL(k_h2_asm_begin, dim3(H2A_GRID), dim3(H2A_THREADS), 0, st, d, (const h2a_call*)a->d_call);
+  hipLaunchKernelGGL(k_h2_asm_bytes, dim3(H2A_GRID), dim3(H2A_THREADS), 0, st, d, (const h2a_call*)a->d_call);
+  hipLaunchKernelGGL(k_h2_asm_finish, dim3(1), dim3(H2A_ONE_THREADS), 0, st, d, (const h2a_call*)a->d_call);
+  hipEventRecord(a->e1, st);
+  hipLaunchKernelGGL(k_h2_asm_copy, dim3(H2A_GRID), dim3(H2A_THREADS), 0, st, d, (const h2a_call*)a->d_call);
+  hipEventRecord(a->e2, st);
+  grdma_h2_deframe_result h_res;
+  h2a_dev h;
+  if (hipMemcpyAsync(&h_res, p->d_res, sizeof(h_res), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return -GRDMA_ERR_HIP;
+  if (hipEventElapsedTime(&a->plan_ms, a->e0, a->e1) != hipSuccess) a->plan_ms = 0;
+  if (hipEventElapsedTime(&a->copy_ms, a->e1, a->e2) != hipSuccess) a->copy_ms = 0;
+  if (h2_error) *h2_error = (int)h_res.error;
+  const uint64_t m = h_res.nevents < ev_cap ? h_res.nevents : ev_cap;
+  if (events_out && m &&
+      (hipMemcpyAsync(events_out, p->d_ev, sizeof(grdma_h2_event) * m, hipMemcpyDeviceToHost, st) != hipSuccess ||
+       hipStreamSynchronize(st) != hipSuccess))
+    return -GRDMA_ERR_HIP;
+  if (h_res.overflow || h.skip) return -GRDMA_ERR_CAPACITY;
+  if (h.ndesc > msgs_cap || h.ndesc > h.desc_cap) return -GRDMA_ERR_CAPACITY;
+  if (h.ndesc && (hipMemcpyAsync(msgs_out, h.desc, sizeof(grdma_h2_rx_msg) * h.ndesc, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                  hipStreamSynchronize(st) != hipSuccess))
+    return -GRDMA_ERR_HIP;
+  return (int64_t)h.ndesc;
+}
+
+int grdma_h2_asm_release(grdma_h2_asm* a, uint64_t count) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!a || a->attached) return -GRDMA_ERR_INVALID;  // (a pipe step releases everything reported before it itself)
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  // behind the last standalone call (same stream) and the last pipe step of the parser
+  if (a->parser->last_deframed && hipStreamWaitEvent(hc->stream, a->parser->last_deframed, 0) != hipSuccess)
+    return -GRDMA_ERR_HIP;
+  hipLaunchKernelGGL(k_h2_asm_release, dim3(1), dim3(64), 0, hc->stream, a->d, count);
+  return hipGetLastError() == hipSuccess ? 0 : -GRDMA_ERR_HIP;
+}
+
+int grdma_h2_asm_stats(grdma_h2_asm* a, uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!a || !out) return -GRDMA_ERR_INVALID;
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  h2a_dev h;
+  if (a->parser->last_deframed && hipStreamWaitEvent(hc->stream, a->parser->last_deframed, 0) != hipSuccess)
+    return -GRDMA_ERR_HIP;
+  if (hipMemcpyAsync(&h, a->d, sizeof(h), hipMemcpyDeviceToHost, hc->stream) != hipSuccess ||
+      hipStreamSynchronize(hc->stream) != hipSuccess)
+    return -GRDMA_ERR_HIP;
+  out[0] = h.st_reported;
+  out[1] = h.st_ok_bytes;
+  out[2] = h.st_too_large;
+  out[3] = h.st_no_space;
+  out[4] = h.st_trunc;
+  out[5] = h.vh - h.vt;
+  out[6] = (uint64_t)(a->plan_ms * 1e3f);
+  out[7] = (uint64_t)(a->copy_ms * 1e3f);
+  return 0;
+}
+
+int grdma_h2_pipe_attach_assembler(grdma_h2_pipe* p, grdma_h2_asm* a) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!p || !a || a->parser != p->parser || p->asm_) return -GRDMA_ERR_INVALID;
+  if (p->launched && hipStreamSynchronize(p->deframe_stream) != hipSuccess) return -GRDMA_ERR_HIP;
+  if (!h2_asm_prepare(a, p->ev_cap ? p->ev_cap : 1)) return -GRDMA_ERR_HIP;
+  const h2a_call call{p->d_ev, p->d_dres, p->d_slices, p->dst, p->ev_cap, 1};
+  if (!p->d_call && hipMalloc((void**)&p->d_call, sizeof(h2a_call)) != hipSuccess) return -GRDMA_ERR_HIP;
+  if (hipMemcpy(p->d_call, &call, sizeof(call), hipMemcpyHostToDevice) != hipSuccess) return -GRDMA_ERR_HIP;
+  if (p->fused) {
+    grdma_job_hook post[8];
+    memcpy(post, p->post, sizeof(grdma_job_hook) * p->n_post);
+    const uint32_t n_post = p->n_post + h2_asm_hooks(a, p->d_call, post + p->n_post);
+    if (grdma_job_set_hooks(p->job, p->pre, p->n_pre, post, n_post) != 0) return -GRDMA_ERR_HIP;
+  }
+  p->asm_ = a;
+  a->attached++;
+  return 0;
+}
+
+int64_t grdma_h2_pipe_messages(grdma_h2_pipe* p, grdma_h2_rx_msg* out, uint64_t cap) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!p || !p->asm_ || (!out && cap)) return -GRDMA_ERR_INVALID;
+  h2a_dev h;
+  // the step's assembly ends with its deframing event (fused: the job's graph; else the deframe stream)
+  if ((p->launched && hipEventSynchronize(p->deframed) != hipSuccess) || hipStreamSynchronize(p->deframe_stream) != hipSuccess ||
+      hipMemcpy(&h, p->asm_->d, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess)
+    return -GRDMA_ERR_HIP;
+  if (h.skip || h.ndesc > cap || h.ndesc > h.desc_cap) return -GRDMA_ERR_CAPACITY;
+  if (h.ndesc && hipMemcpy(out, h.desc, sizeof(grdma_h2_rx_msg) * h.ndesc, hipMemcpyDeviceToHost) != hipSuccess)
+    return -GRDMA_ERR_HIP;
+  return (int64_t)h.ndesc;
+}
+
 }  // extern "C"
+

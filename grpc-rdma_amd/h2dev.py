@@ -15,6 +15,36 @@ class H2Event(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("kind", "a", "b", "c", "d", "slice")]
 
 
+class H2RxMsg(C.Structure):
+    _fields_ = [("offset", u64), ("length", u64), ("seq", u64), ("stream_id", C.c_uint32), ("status", C.c_uint32),
+                ("flags", C.c_uint32), ("pad", C.c_uint32)]
+
+
+MSG_OK, MSG_TOO_LARGE, MSG_NO_SPACE, MSG_TRUNCATED = 0, 1, 2, 3
+
+
+class Msg(tuple):
+    """One received gRPC message: (offset, length, seq, stream_id, status, flags)."""
+    __slots__ = ()
+    _names = ("offset", "length", "seq", "stream_id", "status", "flags")
+
+    def __new__(cls, offset, length, seq, stream_id, status, flags):
+        return tuple.__new__(cls, (offset, length, seq, stream_id, status, flags))
+
+    def __getattr__(self, k):
+        try:
+            return self[Msg._names.index(k)]
+        except ValueError:
+            raise AttributeError(k)
+
+    def __repr__(self):
+        return "Msg(%s)" % ", ".join("%s=%d" % (k, v) for k, v in zip(Msg._names, self))
+
+
+def _msgs(arr, n):
+    return [Msg(int(m.offset), int(m.length), int(m.seq), int(m.stream_id), int(m.status), int(m.flags)) for m in arr[:n]]
+
+
 _bound = False
 
 
@@ -42,6 +72,20 @@ def _bind():
         lib.grdma_h2_deframe.restype = C.c_int64
         lib.grdma_h2_deframe.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ReadSlice), u64,
                                          C.POINTER(H2Event), u64, C.POINTER(C.c_int)]
+        lib.grdma_h2_asm_create.restype = C.c_void_p
+        lib.grdma_h2_asm_create.argtypes = [C.c_void_p, C.c_void_p, u64, u64, C.c_uint32]
+        lib.grdma_h2_asm_destroy.argtypes = [C.c_void_p]
+        lib.grdma_h2_deframe_messages.restype = C.c_int64
+        lib.grdma_h2_deframe_messages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ReadSlice), u64,
+                                                  C.POINTER(H2Event), u64, C.POINTER(H2RxMsg), u64, C.POINTER(C.c_int)]
+        lib.grdma_h2_asm_release.restype = C.c_int
+        lib.grdma_h2_asm_release.argtypes = [C.c_void_p, u64]
+        lib.grdma_h2_asm_stats.restype = C.c_int
+        lib.grdma_h2_asm_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
+        lib.grdma_h2_pipe_attach_assembler.restype = C.c_int
+        lib.grdma_h2_pipe_attach_assembler.argtypes = [C.c_void_p, C.c_void_p]
+        lib.grdma_h2_pipe_messages.restype = C.c_int64
+        lib.grdma_h2_pipe_messages.argtypes = [C.c_void_p, C.POINTER(H2RxMsg), u64]
         _bound = True
     return lib
 
@@ -129,9 +173,70 @@ class Parser:
         self.last_boundary_steps = int(self.lib.grdma_h2_last_boundary_steps())
         return err.value, [(e.kind, e.a, e.b, e.c, e.d, e.slice) for e in ev[:m]]
 
+    def deframe_messages(self, arena_dev_ptr, slices, assembler, want_events=False, ev_cap=None, msgs_cap=None):
+        """deframe + assemble: -> (h2 error, [Msg...]) or (h2 error, [Msg...], events) with want_events"""
+        n = len(slices)
+        arr = (ReadSlice * max(1, n))()
+        for i, (o, l) in enumerate(slices):
+            arr[i].off, arr[i].len = o, l
+        ev_cap = ev_cap or min(sum(l for _, l in slices) * 2 + 64 if n else 64, 1 << 20)
+        msgs_cap = msgs_cap or ev_cap
+        ev = (H2Event * ev_cap)() if want_events else None
+        out = (H2RxMsg * msgs_cap)()
+        err = C.c_int(0)
+        m = check(self.lib.grdma_h2_deframe_messages(self.h, assembler.h, arena_dev_ptr, arr, n, ev, ev_cap, out, msgs_cap,
+                                                     C.byref(err)))
+        msgs = _msgs(out, m)
+        if not want_events:
+            return err.value, msgs
+        return err.value, msgs, [(e.kind, e.a, e.b, e.c, e.d, e.slice) for e in ev[:ev_cap] if e.kind]
+
     def close(self):
         if self.h:
             self.lib.grdma_h2_parser_destroy(self.h)
+            self.h = None
+
+
+class Assembler:
+    """Received gRPC messages, contiguous in a ring over `arena` (grdma_h2_asm): a DeviceBuffer-like object (.ptr,
+    .nbytes) or a torch uint8 tensor on the device.  max_message_bytes = 0: no limit."""
+
+    def __init__(self, parser, arena, max_message_bytes=4 << 20, max_pending=4096):
+        self.lib = _bind()
+        self.parser = parser  # (kept alive)
+        self.arena = arena
+        if hasattr(arena, "data_ptr"):
+            ptr, size = arena.data_ptr(), arena.numel() * arena.element_size()
+        else:
+            ptr, size = arena.ptr, arena.nbytes
+        self.ptr, self.size = ptr, size
+        self.h = self.lib.grdma_h2_asm_create(parser.h, ptr, size, max_message_bytes, max_pending)
+        if not self.h:
+            raise GrdmaError("h2 assembler creation failed")
+
+    def release(self, n):
+        check(self.lib.grdma_h2_asm_release(self.h, n))
+
+    def stats(self):
+        """dict(reported, ok_bytes, too_large, no_space, truncated, bytes_in_use, plan_us, copy_us)"""
+        out = (u64 * 8)()
+        check(self.lib.grdma_h2_asm_stats(self.h, out))
+        return dict(zip(("reported", "ok_bytes", "too_large", "no_space", "truncated", "bytes_in_use", "plan_us",
+                         "copy_us"), [int(x) for x in out]))
+
+    def view(self, msg):
+        """the bytes of an OK message: a slice of the arena tensor, or bytes read back from the device"""
+        if hasattr(self.arena, "data_ptr"):
+            return self.arena[msg.offset:msg.offset + msg.length]
+        if not msg.length:
+            return b""
+        dst = C.create_string_buffer(msg.length)
+        check(self.lib.grdma_copy_to_host(dst, self.ptr + msg.offset, msg.length))
+        return dst.raw[:msg.length]
+
+    def close(self):
+        if self.h:
+            self.lib.grdma_h2_asm_destroy(self.h)
             self.h = None
 
 
@@ -174,6 +279,17 @@ class Pipe:
         if want_events:
             r["event_list"] = [(e.kind, e.a, e.b, e.c, e.d, e.slice) for e in ev[:min(r["events"], self.events_cap)]]
         return r
+
+    def attach_assembler(self, a):
+        check(self.lib.grdma_h2_pipe_attach_assembler(self.h, a.h))
+        self.assembler = a  # (kept alive)
+
+    def messages(self, cap=None):
+        """the messages of the last synced step"""
+        cap = cap or self.events_cap
+        out = (H2RxMsg * cap)()
+        m = check(self.lib.grdma_h2_pipe_messages(self.h, out, cap))
+        return _msgs(out, m)
 
     def close(self):
         if self.h:

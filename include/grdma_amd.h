@@ -670,6 +670,47 @@ void grdma_h2_pipe_destroy(grdma_h2_pipe* p);
 /* out = {message starts the last synced step parsed with the boundary step, device-clock ticks inside it} */
 int grdma_h2_pipe_boundary_stats(grdma_h2_pipe* p, uint64_t out[2]);
 
+/* ---- Received gRPC messages in device memory (the message assembler, csrc/grdma_h2_asm.h) ----
+ * Behind the deframer of one parser, on the device: every message's payload is copied out of the receive arena into a
+ * ring over d_arena (contiguous, 256-byte granules) and described by one grdma_h2_rx_msg, in the order of the events
+ * that finish the messages (MSG_END, or STREAM_CLOSED / a connection error while the message is partial).  The
+ * surface's receive_message gets its grpc_byte_buffer this way (call.cc receiving_slice_ready /
+ * continue_receiving_slices); max_message_bytes is the message_size filter's limit (0 = none). */
+typedef struct grdma_h2_rx_msg {
+  uint64_t offset;                /* in d_arena (0 unless OK)                                    */
+  uint64_t length;                /* from the 5-byte message header                              */
+  uint64_t seq;                   /* the message's MSG_BEGIN number on this assembler            */
+  uint32_t stream_id, status, flags, pad;  /* flags bit 0: compressed (passed through)           */
+} grdma_h2_rx_msg;
+enum grdma_h2_msg_status {
+  GRDMA_H2_MSG_OK = 0,
+  GRDMA_H2_MSG_TOO_LARGE = 1,     /* length > max_message_bytes: its bytes are dropped           */
+  GRDMA_H2_MSG_NO_SPACE = 2,      /* the ring (or max_pending) was full at its MSG_BEGIN         */
+  GRDMA_H2_MSG_TRUNCATED = 3      /* its stream closed, or the connection failed, mid-message    */
+};
+typedef struct grdma_h2_asm grdma_h2_asm;
+grdma_h2_asm* grdma_h2_asm_create(grdma_h2_parser* parser, void* d_arena, uint64_t arena_bytes,
+                                  uint64_t max_message_bytes, uint32_t max_pending);
+void grdma_h2_asm_destroy(grdma_h2_asm* a);   /* does nothing while a pipe has it attached: destroy the pipes first */
+/* grdma_h2_deframe + the assembler; returns the number of descriptors written to msgs_out.  events_out may be NULL
+ * (no event copy; ev_cap still sizes the device's event list).  -GRDMA_ERR_CAPACITY when events or descriptors
+ * overflow their caps; -GRDMA_ERR_INVALID for bad arguments or an assembler attached to a pipe. */
+int64_t grdma_h2_deframe_messages(grdma_h2_parser* p, grdma_h2_asm* a, const void* d_arena,
+                                  const grdma_read_slice* slices, uint64_t n,
+                                  grdma_h2_event* events_out, uint64_t ev_cap,
+                                  grdma_h2_rx_msg* msgs_out, uint64_t msgs_cap, int* h2_error);
+/* release the oldest `count` reported messages not yet released (ordered on the device after earlier work);
+ * -GRDMA_ERR_INVALID on an assembler attached to a pipe (each pipe step releases everything reported before it) */
+int grdma_h2_asm_release(grdma_h2_asm* a, uint64_t count);
+/* out = {reported, OK bytes, too large, no space, truncated (since creation), bytes in use,
+ *        plan us, copy us (of the last standalone call; 0 in a fused pipe)} */
+int grdma_h2_asm_stats(grdma_h2_asm* a, uint64_t out[8]);
+/* every later step of the pipe assembles its messages (first releasing all reported before); a's parser must be the
+ * pipe's.  Several pipes of one parser share its assembler. */
+int grdma_h2_pipe_attach_assembler(grdma_h2_pipe* p, grdma_h2_asm* a);
+/* the descriptors of the last synced step: their number, or -GRDMA_ERR_CAPACITY if more than cap */
+int64_t grdma_h2_pipe_messages(grdma_h2_pipe* p, grdma_h2_rx_msg* out, uint64_t cap);
+
 /* ---- GRPCProfiler: include/grpcpp/stats_time.h:11-44,111-122, src/core/lib/debug/stats_time.cc ----
  * The reference's scope profiler with its op names in its order: nanoseconds per op per thread slot,
  * opt-in per thread (init(slot) + enable()), the table {Name, Count, Mean, P50, P95, P99, MAX} per slot
