@@ -21,6 +21,7 @@
 //                    common case, because the ring preserves slice boundaries.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -28,6 +29,7 @@
 
 #include "grdma_h2_kernels.h"
 #include "grdma_h2_asm.h"
+#include "grdma_h2_reply.h"
 
 // --------------------------------------------------------------------- host API
 // Everything here runs on one non-blocking stream of its own and waits with
@@ -450,6 +452,7 @@ struct grdma_h2_pipe {
   bool timed = false;    // the last step recorded the per-stage timing events
   grdma_h2_asm* asm_ = nullptr;  // the message assembler behind the deframer (grdma_h2_pipe_attach_assembler)
   h2a_call* d_call = nullptr;    // where this pipe's deframer leaves its output, for the assembler
+  grdma_h2_reply* reply = nullptr;  // a reply pipe (grdma_h2_pipe_create_reply): the framing stage is csrc/grdma_h2_reply.h
   grdma_job_hook pre[2], post[2];
   uint32_t n_pre = 0, n_post = 0;
 };
@@ -459,12 +462,24 @@ hipStream_t g_pipe_frame_stream = nullptr, g_pipe_deframe_stream = nullptr;
 }
 static void h2_asm_detach(grdma_h2_pipe* p);
 static void h2_asm_enqueue(grdma_h2_asm* a, const h2a_call* d_call, hipStream_t st);
+// reply pipes and the pipes they read from (defined with grdma_h2_reply below)
+static bool h2_asm_read_by_reply_pipes(const grdma_h2_asm* a);
+static hipEvent_t h2_asm_last_read(const grdma_h2_asm* a);
+static bool h2_reply_bind_pipe(grdma_h2_reply* r, grdma_h2_pipe* p, uint64_t recorded_wire_bytes);
+static void h2_reply_unbind_pipe(grdma_h2_pipe* p);
+static int h2_reply_wait_source(grdma_h2_pipe* p, hipStream_t st);
+static void h2_reply_enqueue(grdma_h2_reply* r, hipStream_t st);
+static void h2_reply_step_enqueued(grdma_h2_pipe* p, hipEvent_t read_done);
+static uint32_t h2_reply_hooks(grdma_h2_reply* r, grdma_job_hook* out);
+static bool h2_reply_result(grdma_h2_reply* r, grdma_h2_frame_result* fr);
 
-grdma_h2_pipe* grdma_h2_pipe_create(grdma_stream_job* job, uint32_t link, const grdma_h2_msg* msgs, uint64_t nmsgs,
-                                    uint32_t max_frame, grdma_h2_parser* parser, uint64_t delivered_slices,
-                                    uint64_t events_cap) {
-  if (grdma_device_count() <= 0 || !job || !msgs || !nmsgs || !parser || max_frame == 0 || max_frame >= (1u << 24))
-    return nullptr;
+// msgs / nmsgs / max_frame: the host message table of grdma_h2_pipe_create; reply: the framing stage of
+// grdma_h2_pipe_create_reply instead
+static grdma_h2_pipe* h2_pipe_create(grdma_stream_job* job, uint32_t link, const grdma_h2_msg* msgs, uint64_t nmsgs,
+                                     uint32_t max_frame, grdma_h2_parser* parser, uint64_t delivered_slices,
+                                     uint64_t events_cap, grdma_h2_reply* reply, uint64_t recorded_wire_bytes) {
+  if (grdma_device_count() <= 0 || !job || !parser) return nullptr;
+  if (!reply && (!msgs || !nmsgs || max_frame == 0 || max_frame >= (1u << 24))) return nullptr;
   if (!g_pipe_frame_stream &&
       (hipStreamCreateWithFlags(&g_pipe_frame_stream, hipStreamNonBlocking) != hipSuccess ||
        hipStreamCreateWithFlags(&g_pipe_deframe_stream, hipStreamNonBlocking) != hipSuccess))
@@ -492,18 +507,20 @@ grdma_h2_pipe* grdma_h2_pipe_create(grdma_stream_job* job, uint32_t link, const 
   static const bool own_stream = [] { const char* e = getenv("GRDMA_H2_DEFRAME_STREAM"); return e && atoi(e) != 0; }();
   if (ok && !own_stream) p->deframe_stream = p->job_stream;
   p->hdr_cap = 32 * (p->count + 64);
-  ok = ok && hipMalloc((void**)&p->d_msgs, sizeof(grdma_h2_msg_dev) * nmsgs) == hipSuccess &&
+  // (a reply pipe has no message table of its own: the reply's plan builds one per step)
+  ok = ok && (reply || (hipMalloc((void**)&p->d_msgs, sizeof(grdma_h2_msg_dev) * nmsgs) == hipSuccess &&
+                       hipMalloc((void**)&p->d_pos, sizeof(grdma_h2_msg_pos) * nmsgs) == hipSuccess &&
+                       hipMemcpy(p->d_msgs, tmp.data(), sizeof(grdma_h2_msg_dev) * nmsgs, hipMemcpyHostToDevice) == hipSuccess)) &&
        hipMalloc((void**)&p->d_hdr, p->hdr_cap) == hipSuccess &&
-       hipMalloc((void**)&p->d_pos, sizeof(grdma_h2_msg_pos) * nmsgs) == hipSuccess &&
        hipMalloc((void**)&p->d_fres, sizeof(grdma_h2_frame_result)) == hipSuccess &&
        hipMalloc((void**)&p->d_dres, sizeof(grdma_h2_deframe_result)) == hipSuccess &&
        hipMalloc((void**)&p->d_ev, sizeof(grdma_h2_event) * (events_cap ? events_cap : 1)) == hipSuccess &&
-       hipMemcpy(p->d_msgs, tmp.data(), sizeof(grdma_h2_msg_dev) * nmsgs, hipMemcpyHostToDevice) == hipSuccess &&
        hipEventCreateWithFlags(&p->framed, hipEventDisableTiming) == hipSuccess &&
        hipEventCreateWithFlags(&p->job_done, hipEventDisableTiming) == hipSuccess &&
        hipEventCreateWithFlags(&p->deframed, hipEventDisableTiming) == hipSuccess &&
        hipEventCreate(&p->t_f0) == hipSuccess && hipEventCreate(&p->t_f1) == hipSuccess &&
        hipEventCreate(&p->t_d0) == hipSuccess && hipEventCreate(&p->t_d1) == hipSuccess;
+  ok = ok && (!reply || h2_reply_bind_pipe(reply, p, recorded_wire_bytes));
   if (!ok) {
     grdma_h2_pipe_destroy(p);
     return nullptr;
@@ -520,7 +537,9 @@ grdma_h2_pipe* grdma_h2_pipe_create(grdma_stream_job* job, uint32_t link, const 
     memset(post, 0, sizeof(post));
     const uint64_t per = H2_EMIT_THREADS / 64;
     uint32_t n_pre = 2;
-    if (p->nmsgs <= H2_FRAME_ONE_MAX) {
+    if (p->reply) {
+      n_pre = h2_reply_hooks(p->reply, pre);
+    } else if (p->nmsgs <= H2_FRAME_ONE_MAX) {
       pre[0] = grdma_job_hook{(const void*)k_h2_frame_one, (uint32_t)((p->nmsgs + per - 1) / per), H2_EMIT_THREADS,
                               {ptr(p->d_msgs), arg(p->nmsgs), arg(p->max_frame), ptr(p->d_sges), arg(p->count), ptr(p->d_hdr),
                                arg(p->hdr_cap), ptr(p->d_fres)}};
@@ -561,8 +580,22 @@ grdma_h2_pipe* grdma_h2_pipe_create(grdma_stream_job* job, uint32_t link, const 
   return p;
 }
 
+grdma_h2_pipe* grdma_h2_pipe_create(grdma_stream_job* job, uint32_t link, const grdma_h2_msg* msgs, uint64_t nmsgs,
+                                    uint32_t max_frame, grdma_h2_parser* parser, uint64_t delivered_slices,
+                                    uint64_t events_cap) {
+  return h2_pipe_create(job, link, msgs, nmsgs, max_frame, parser, delivered_slices, events_cap, nullptr, 0);
+}
+
+grdma_h2_pipe* grdma_h2_pipe_create_reply(grdma_stream_job* job_back, uint32_t link, grdma_h2_reply* reply,
+                                          grdma_h2_parser* parser_back, uint64_t delivered_slices, uint64_t events_cap,
+                                          uint64_t recorded_wire_bytes) {
+  if (!reply) return nullptr;
+  return h2_pipe_create(job_back, link, nullptr, 0, 0, parser_back, delivered_slices, events_cap, reply, recorded_wire_bytes);
+}
+
 void grdma_h2_pipe_destroy(grdma_h2_pipe* p) {
   if (!p) return;
+  if (h2_asm_read_by_reply_pipes(p->asm_)) return;  // (a reply pipe's job gathers from this pipe's arena: destroy that one first)
   if (p->launched) {
     hipStreamSynchronize(p->frame_stream);
     hipStreamSynchronize(p->job_stream);
@@ -570,6 +603,7 @@ void grdma_h2_pipe_destroy(grdma_h2_pipe* p) {
   }
   if (p->parser && p->parser->last_deframed == p->deframed) p->parser->last_deframed = nullptr;  // (synchronised above)
   if (p->fused && p->job) grdma_job_set_hooks(p->job, nullptr, 0, nullptr, 0);
+  h2_reply_unbind_pipe(p);
   h2_asm_detach(p);
   hipFree(p->d_call);
   hipFree(p->d_msgs);
@@ -596,9 +630,15 @@ int grdma_h2_pipe_enqueue(grdma_h2_pipe* p, int schedule) {
     if (p->parser->last_deframed && p->parser->last_stream != p->job_stream &&
         hipStreamWaitEvent(p->job_stream, p->parser->last_deframed, 0) != hipSuccess)
       return -GRDMA_ERR_HIP;
+    // a reply step reads what the forward step assembled; a forward step's release waits for the reply step that
+    // still gathers from the arena
+    if (p->reply && h2_reply_wait_source(p, p->job_stream) != 0) return -GRDMA_ERR_HIP;
+    if (hipEvent_t rd = h2_asm_last_read(p->asm_))
+      if (hipStreamWaitEvent(p->job_stream, rd, 0) != hipSuccess) return -GRDMA_ERR_HIP;
     const int rc = grdma_stream_job_launch(p->job);
     if (rc < 0) return rc;
     if (hipEventRecord(p->deframed, p->job_stream) != hipSuccess) return -GRDMA_ERR_HIP;
+    if (p->reply) h2_reply_step_enqueued(p, p->deframed);
     p->parser->last_stream = p->job_stream;
     p->parser->last_deframed = p->deframed;
     p->launched = true;
@@ -609,9 +649,13 @@ int grdma_h2_pipe_enqueue(grdma_h2_pipe* p, int schedule) {
   // framing overwrites the slice table the job's previous step read
   if (p->launched && hipStreamWaitEvent(p->frame_stream, p->job_done, 0) != hipSuccess) return -GRDMA_ERR_HIP;
   if (hipMemsetAsync(p->d_fres, 0, sizeof(grdma_h2_frame_result), p->frame_stream) != hipSuccess) return -GRDMA_ERR_HIP;
+  if (p->reply && h2_reply_wait_source(p, p->frame_stream) != 0) return -GRDMA_ERR_HIP;
   hipEventRecord(p->t_f0, p->frame_stream);
-  h2_enqueue_frame(p->d_msgs, p->nmsgs, p->max_frame, p->d_sges, p->count, p->d_hdr, p->hdr_cap, p->d_pos, p->d_fres,
-                   p->frame_stream);
+  if (p->reply)
+    h2_reply_enqueue(p->reply, p->frame_stream);
+  else
+    h2_enqueue_frame(p->d_msgs, p->nmsgs, p->max_frame, p->d_sges, p->count, p->d_hdr, p->hdr_cap, p->d_pos, p->d_fres,
+                     p->frame_stream);
   hipEventRecord(p->t_f1, p->frame_stream);
   if (hipEventRecord(p->framed, p->frame_stream) != hipSuccess) return -GRDMA_ERR_HIP;
   // the job reads the slice table and overwrites what the previous deframing parsed
@@ -621,6 +665,7 @@ int grdma_h2_pipe_enqueue(grdma_h2_pipe* p, int schedule) {
   const int rc = grdma_stream_job_launch(p->job);
   if (rc < 0) return rc;
   if (hipEventRecord(p->job_done, p->job_stream) != hipSuccess) return -GRDMA_ERR_HIP;
+  if (p->reply) h2_reply_step_enqueued(p, p->job_done);
   if (p->deframe_stream != p->job_stream && hipStreamWaitEvent(p->deframe_stream, p->job_done, 0) != hipSuccess)
     return -GRDMA_ERR_HIP;
   if (p->parser->last_deframed && p->parser->last_stream != p->deframe_stream &&
@@ -628,6 +673,8 @@ int grdma_h2_pipe_enqueue(grdma_h2_pipe* p, int schedule) {
     return -GRDMA_ERR_HIP;  // (the parser state is handed from one deframing to the next)
   hipEventRecord(p->t_d0, p->deframe_stream);
   h2_enqueue_deframe(p->parser, p->dst, p->d_slices, p->delivered, p->d_ev, p->ev_cap, p->d_dres, p->deframe_stream, p->chunked);
+  if (hipEvent_t rd = h2_asm_last_read(p->asm_))  // (the release at the start of the assembly, behind the reply's gather)
+    if (hipStreamWaitEvent(p->deframe_stream, rd, 0) != hipSuccess) return -GRDMA_ERR_HIP;
   if (p->asm_) h2_asm_enqueue(p->asm_, p->d_call, p->deframe_stream);
   hipEventRecord(p->t_d1, p->deframe_stream);
   if (hipEventRecord(p->deframed, p->deframe_stream) != hipSuccess) return -GRDMA_ERR_HIP;
@@ -652,6 +699,7 @@ int grdma_h2_pipe_sync(grdma_h2_pipe* p, uint64_t out[14], grdma_h2_event* event
   if (hipMemcpy(&fr, p->d_fres, sizeof(fr), hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(&dr, p->d_dres, sizeof(dr), hipMemcpyDeviceToHost) != hipSuccess)
     return -GRDMA_ERR_HIP;
+  if (p->reply && !h2_reply_result(p->reply, &fr)) return -GRDMA_ERR_HIP;  // (overflow 2: not the recorded shape)
   out[0] = fr.nslices;
   out[1] = fr.overflow;
   out[2] = dr.nevents;
@@ -692,6 +740,9 @@ struct grdma_h2_asm {
   h2a_dev h;                       // host copy of the configuration words (pointers, capacities)
   h2a_call* d_call = nullptr;      // standalone calls
   uint32_t attached = 0;           // pipes that assemble through it
+  uint32_t replies = 0;            // reply framers that read its descriptors (grdma_h2_reply_create)
+  uint32_t reply_pipes = 0;        // ... of which in a pipe: their jobs gather from the arena
+  hipEvent_t last_read = nullptr;  // the gather of the last reply step enqueued: the next release waits for it
   float plan_ms = 0, copy_ms = 0;  // of the last standalone call
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
 };
@@ -808,7 +859,7 @@ grdma_h2_asm* grdma_h2_asm_create(grdma_h2_parser* parser, void* d_arena, uint64
 }
 
 void grdma_h2_asm_destroy(grdma_h2_asm* a) {
-  if (!a || a->attached) return;  // (a pipe's graph still runs its kernels on it: destroy the pipes first)
+  if (!a || a->attached || a->replies) return;  // (a pipe's graph still runs its kernels on it, a reply reads it: destroy those first)
   hipDeviceSynchronize();
   h2_asm_free_scratch(&a->h);
   hipFree(a->h.tab);
@@ -936,6 +987,182 @@ int64_t grdma_h2_pipe_messages(grdma_h2_pipe* p, grdma_h2_rx_msg* out, uint64_t 
   if (h.ndesc && hipMemcpy(out, h.desc, sizeof(grdma_h2_rx_msg) * h.ndesc, hipMemcpyDeviceToHost) != hipSuccess)
     return -GRDMA_ERR_HIP;
   return (int64_t)h.ndesc;
+}
+
+// ---- replies framed from the descriptors (csrc/grdma_h2_reply.h) ---------------------------------------------
+struct grdma_h2_reply {
+  grdma_h2_asm* src = nullptr;
+  h2r_dev* d = nullptr;
+  h2r_dev h;                        // host copy of the configuration words
+  grdma_h2_route* d_routes = nullptr;
+  grdma_h2_pipe* pipe = nullptr;    // the reply pipe that frames through it (at most one: the scratch is one call's)
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+};
+
+static void h2_reply_enqueue(grdma_h2_reply* r, hipStream_t st) {
+  hipLaunchKernelGGL(k_h2_reply_plan, dim3(1), dim3(PLAN_THREADS), 0, st, r->d);
+  hipLaunchKernelGGL(k_h2_reply_emit, dim3(H2R_GRID), dim3(H2_EMIT_THREADS), 0, st, (const h2r_dev*)r->d);
+}
+
+// the same two kernels as pre hooks of the back job's graph: a linear chain in front of its first round
+static uint32_t h2_reply_hooks(grdma_h2_reply* r, grdma_job_hook* out) {
+  memset(out, 0, 2 * sizeof(grdma_job_hook));
+  out[0].fn = (const void*)k_h2_reply_plan;
+  out[0].grid = 1;
+  out[0].threads = PLAN_THREADS;
+  out[1].fn = (const void*)k_h2_reply_emit;
+  out[1].grid = H2R_GRID;
+  out[1].threads = H2_EMIT_THREADS;
+  out[0].args[0] = out[1].args[0] = (uint64_t)(uintptr_t)r->d;
+  return 2;
+}
+
+// where the calls frame to, and (a pipe) the shape they must have: the words of h2r_dev from `out` to the result block
+static bool h2_reply_set_target(grdma_h2_reply* r, grdma_sge* out, uint64_t cap, uint8_t* hdr, uint64_t hdr_cap,
+                                uint64_t check_shape, uint64_t want_slices, uint64_t want_wire, hipStream_t st) {
+  h2r_dev& h = r->h;
+  h.out = out;
+  h.cap = cap;
+  h.hdr = hdr;
+  h.hdr_cap = hdr_cap;
+  h.check_shape = check_shape;
+  h.want_slices = want_slices;
+  h.want_wire = want_wire;
+  const size_t off = offsetof(h2r_dev, out), len = offsetof(h2r_dev, res) - off;
+  uint8_t* dst = reinterpret_cast<uint8_t*>(r->d) + off;
+  const uint8_t* src = reinterpret_cast<const uint8_t*>(&h) + off;
+  return (st ? hipMemcpyAsync(dst, src, len, hipMemcpyHostToDevice, st) : hipMemcpy(dst, src, len, hipMemcpyHostToDevice)) ==
+         hipSuccess;
+}
+
+static bool h2_reply_bind_pipe(grdma_h2_reply* r, grdma_h2_pipe* p, uint64_t recorded_wire_bytes) {
+  if (r->pipe || !r->src->attached) return false;  // (the source of a reply pipe assembles in forward pipes)
+  if (!h2_reply_set_target(r, p->d_sges, p->count, p->d_hdr, p->hdr_cap, 1, p->count, recorded_wire_bytes, nullptr)) return false;
+  r->pipe = p;
+  r->src->reply_pipes++;
+  p->reply = r;
+  p->max_frame = r->h.max_frame;
+  return true;
+}
+
+static void h2_reply_unbind_pipe(grdma_h2_pipe* p) {
+  grdma_h2_reply* r = p->reply;
+  if (!r) return;
+  // (the pipe's streams are synchronised: nothing gathers from the source's arena any more)
+  if (r->src->last_read == p->deframed || r->src->last_read == p->job_done) r->src->last_read = nullptr;
+  r->src->reply_pipes--;
+  r->pipe = nullptr;
+  p->reply = nullptr;
+}
+
+static bool h2_asm_read_by_reply_pipes(const grdma_h2_asm* a) { return a && a->reply_pipes != 0; }
+static hipEvent_t h2_asm_last_read(const grdma_h2_asm* a) { return a ? a->last_read : nullptr; }
+
+// the reply's plan goes behind the assembly of the last forward step enqueued (the forward parser's event)
+static int h2_reply_wait_source(grdma_h2_pipe* p, hipStream_t st) {
+  const grdma_h2_parser* fp = p->reply->src->parser;
+  if (fp->last_deframed && fp->last_stream != st && hipStreamWaitEvent(st, fp->last_deframed, 0) != hipSuccess) return -1;
+  return 0;
+}
+
+static void h2_reply_step_enqueued(grdma_h2_pipe* p, hipEvent_t read_done) { p->reply->src->last_read = read_done; }
+
+static bool h2_reply_result(grdma_h2_reply* r, grdma_h2_frame_result* fr) {
+  uint64_t res[8];
+  if (hipMemcpy(res, reinterpret_cast<uint8_t*>(r->d) + offsetof(h2r_dev, res), sizeof(res), hipMemcpyDeviceToHost) != hipSuccess)
+    return false;
+  fr->nslices = res[H2R_SLICES];
+  fr->hdr_bytes = res[H2R_HDR_BYTES];
+  fr->wire_bytes = res[H2R_WIRE_BYTES];
+  fr->overflow = res[H2R_OVERFLOW];
+  return true;
+}
+
+grdma_h2_reply* grdma_h2_reply_create(grdma_h2_asm* source, const grdma_h2_route* routes, uint32_t n_routes,
+                                      uint32_t max_frame, uint64_t max_messages) {
+  if (grdma_device_count() <= 0 || !source || max_frame == 0 || max_frame >= (1u << 24) || max_messages == 0 ||
+      max_messages >= (1ull << 32) || n_routes > H2R_MAX_ROUTES || (n_routes && !routes))
+    return nullptr;
+  std::vector<grdma_h2_route> tab(routes, routes + n_routes);
+  std::sort(tab.begin(), tab.end(), [](const grdma_h2_route& a, const grdma_h2_route& b) { return a.from_stream < b.from_stream; });
+  for (uint32_t i = 0; i < n_routes; i++)
+    if (tab[i].from_stream == 0 || tab[i].to_stream == 0 || (i && tab[i].from_stream == tab[i - 1].from_stream)) return nullptr;
+  grdma_h2_reply* r = new grdma_h2_reply();
+  r->src = source;
+  source->replies++;
+  memset(&r->h, 0, sizeof(r->h));
+  h2r_dev& h = r->h;
+  h.src = source->d;
+  h.n_routes = n_routes;
+  h.max_frame = max_frame;
+  h.max_messages = max_messages;
+  bool ok = hipMalloc((void**)&r->d, sizeof(h2r_dev)) == hipSuccess &&
+            hipMalloc((void**)&h.msgs, sizeof(grdma_h2_msg_dev) * max_messages) == hipSuccess &&
+            hipMalloc((void**)&h.pos, sizeof(grdma_h2_msg_pos) * max_messages) == hipSuccess &&
+            (!n_routes || (hipMalloc((void**)&r->d_routes, sizeof(grdma_h2_route) * n_routes) == hipSuccess &&
+                           hipMemcpy(r->d_routes, tab.data(), sizeof(grdma_h2_route) * n_routes, hipMemcpyHostToDevice) == hipSuccess));
+  h.routes = r->d_routes;
+  ok = ok && hipMemcpy(r->d, &h, sizeof(h), hipMemcpyHostToDevice) == hipSuccess && hipEventCreate(&r->e0) == hipSuccess &&
+       hipEventCreate(&r->e1) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    grdma_h2_reply_destroy(r);
+    return nullptr;
+  }
+  return r;
+}
+
+void grdma_h2_reply_destroy(grdma_h2_reply* r) {
+  if (!r || r->pipe) return;  // (the pipe's graph still runs the kernels on it: destroy the pipe first)
+  h2_host_ctx* hc = h2_ctx();
+  if (hc) hipStreamSynchronize(hc->stream);  // (standalone calls)
+  r->src->replies--;
+  hipFree(r->h.msgs);
+  hipFree(r->h.pos);
+  hipFree(r->d_routes);
+  hipFree(r->d);
+  for (hipEvent_t e : {r->e0, r->e1})
+    if (e) hipEventDestroy(e);
+  delete r;
+}
+
+int64_t grdma_h2_reply_frame(grdma_h2_reply* r, grdma_slice* d_slices_out, uint64_t slices_cap, void* d_hdr_arena,
+                             uint64_t hdr_cap, uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!r || !d_slices_out || !slices_cap || !d_hdr_arena || !hdr_cap || !out || ((uintptr_t)d_slices_out & 15) ||
+      ((uintptr_t)d_hdr_arena & 15) || r->pipe || r->src->attached)
+    return -GRDMA_ERR_INVALID;
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  // the stream of grdma_h2_deframe_messages: the call is ordered behind the one it reads
+  hipStream_t st = hc->stream;
+  if (!h2_reply_set_target(r, reinterpret_cast<grdma_sge*>(d_slices_out), slices_cap, static_cast<uint8_t*>(d_hdr_arena),
+                           hdr_cap, 0, 0, 0, st))
+    return -GRDMA_ERR_HIP;
+  hipEventRecord(r->e0, st);
+  h2_reply_enqueue(r, st);
+  hipEventRecord(r->e1, st);
+  uint64_t res[8];
+  if (hipMemcpyAsync(res, reinterpret_cast<uint8_t*>(r->d) + offsetof(h2r_dev, res), sizeof(res), hipMemcpyDeviceToHost, st) !=
+          hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return -GRDMA_ERR_HIP;
+  float ms = 0;
+  for (int i = 0; i < 7; i++) out[i] = res[i];
+  out[7] = hipEventElapsedTime(&ms, r->e0, r->e1) == hipSuccess ? (uint64_t)(ms * 1e3f) : 0;
+  if (res[H2R_OVERFLOW]) return -GRDMA_ERR_CAPACITY;
+  return (int64_t)res[H2R_SLICES];
+}
+
+int64_t grdma_h2_pipe_slice_table(grdma_h2_pipe* p, grdma_slice* out, uint64_t cap) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!p || (!out && cap)) return -GRDMA_ERR_INVALID;
+  if (p->count > cap) return -GRDMA_ERR_CAPACITY;
+  static_assert(sizeof(grdma_slice) == sizeof(grdma_sge), "layout");
+  if (hipStreamSynchronize(p->frame_stream) != hipSuccess || hipStreamSynchronize(p->job_stream) != hipSuccess ||
+      (p->count && hipMemcpy(out, p->d_sges, sizeof(grdma_sge) * p->count, hipMemcpyDeviceToHost) != hipSuccess))
+    return -GRDMA_ERR_HIP;
+  return (int64_t)p->count;
 }
 
 }  // extern "C"

@@ -92,8 +92,14 @@ struct frame_walk {
   uint32_t back_inl;  // length of the back slice if it is inlined, else 0
 };
 
+// The bytes to inline travel in two words (byte k of the slice = byte k of lo, then of hi; at most 9): an array indexed
+// by a run-time position would live in scratch memory.
+__device__ __forceinline__ uint8_t inl_byte(uint64_t lo, uint64_t hi, uint32_t k) {
+  return (uint8_t)(k < 8 ? lo >> (8 * k) : hi >> (8 * (k - 8)));
+}
+
 template <bool EMIT>
-__device__ __forceinline__ void add_inlined(frame_walk* w, const uint8_t* bytes, uint32_t n,
+__device__ __forceinline__ void add_inlined(frame_walk* w, uint64_t lo, uint64_t hi, uint32_t n,
                                             bool merge, grdma_sge* out, uint8_t* hdr, uint64_t cap,
                                             uint64_t hdr_cap, uint64_t* overflow) {
   // grpc_slice_buffer_add (merge) / grpc_slice_buffer_add_indexed (no merge)
@@ -105,7 +111,7 @@ __device__ __forceinline__ void add_inlined(frame_walk* w, const uint8_t* bytes,
       // the back slice's bytes end at hdr_off (slots are packed per slice start)
       grdma_sge* back = &out[w->nslices - 1];
       uint8_t* dst = const_cast<uint8_t*>(back->ptr) + back->len;
-      for (uint32_t i = 0; i < cp; i++) dst[i] = bytes[i];
+      for (uint32_t i = 0; i < cp; i++) dst[i] = inl_byte(lo, hi, i);
       back->len += cp;
     }
     w->back_inl += cp;
@@ -120,7 +126,7 @@ __device__ __forceinline__ void add_inlined(frame_walk* w, const uint8_t* bytes,
   }
   if (EMIT) {
     uint8_t* dst = hdr + w->hdr_off;
-    for (uint32_t i = 0; i < rest; i++) dst[i] = bytes[done + i];
+    for (uint32_t i = 0; i < rest; i++) dst[i] = inl_byte(lo, hi, done + i);
     out[w->nslices].ptr = dst;
     out[w->nslices].len = rest;
   }
@@ -150,23 +156,19 @@ template <bool EMIT>
 __device__ void walk_message(const grdma_h2_msg_dev& m, uint32_t max_frame, frame_walk* w,
                              grdma_sge* out, uint8_t* hdr, uint64_t cap, uint64_t hdr_cap,
                              uint64_t* overflow) {
-  uint8_t h5[5];
-  h5[0] = (m.flags & 1) ? 1 : 0;  // chttp2_transport.cc:1504-1509
-  h5[1] = (uint8_t)(m.len >> 24);
-  h5[2] = (uint8_t)(m.len >> 16);
-  h5[3] = (uint8_t)(m.len >> 8);
-  h5[4] = (uint8_t)m.len;
+  // chttp2_transport.cc:1504-1509: compressed flag, then the length big-endian
+  const uint64_t h5 = (uint64_t)((m.flags & 1) ? 1 : 0) | ((m.len >> 24) & 0xFF) << 8 | ((m.len >> 16) & 0xFF) << 16 |
+                      ((m.len >> 8) & 0xFF) << 24 | (m.len & 0xFF) << 32;
   uint64_t h5_left = 5, pay_left = m.len, pay_off = 0;
   uint64_t fcb = 5 + m.len;
   while (fcb > 0) {
     const uint64_t send = fcb < max_frame ? fcb : max_frame;
     const bool last = (m.flags & 2) && send == fcb;
-    uint8_t fh[9];  // frame_data.cc:73-82
-    fh[0] = (uint8_t)(send >> 16); fh[1] = (uint8_t)(send >> 8); fh[2] = (uint8_t)send;
-    fh[3] = 0; fh[4] = last ? 1 : 0;
-    fh[5] = (uint8_t)(m.stream_id >> 24); fh[6] = (uint8_t)(m.stream_id >> 16);
-    fh[7] = (uint8_t)(m.stream_id >> 8); fh[8] = (uint8_t)m.stream_id;
-    add_inlined<EMIT>(w, fh, 9, true, out, hdr, cap, hdr_cap, overflow);
+    // frame_data.cc:73-82: length (3 bytes), type 0, flags, stream id, all big-endian
+    const uint64_t fh = ((send >> 16) & 0xFF) | ((send >> 8) & 0xFF) << 8 | (send & 0xFF) << 16 | (uint64_t)(last ? 1 : 0) << 32 |
+                        (uint64_t)((m.stream_id >> 24) & 0xFF) << 40 | (uint64_t)((m.stream_id >> 16) & 0xFF) << 48 |
+                        (uint64_t)((m.stream_id >> 8) & 0xFF) << 56;
+    add_inlined<EMIT>(w, fh, (uint64_t)(m.stream_id & 0xFF), 9, true, out, hdr, cap, hdr_cap, overflow);
     uint64_t n = send;
     const bool whole = (fcb == n);  // grpc_slice_buffer_move_into: every slice via add()
     if (h5_left > 0) {
@@ -174,7 +176,7 @@ __device__ void walk_message(const grdma_h2_msg_dev& m, uint32_t max_frame, fram
       // n >= slice_len (or the final move_into): merged add; n < slice_len: split,
       // the head goes in un-merged (add_indexed)
       const bool merge = whole || n >= h5_left;
-      add_inlined<EMIT>(w, h5 + (5 - h5_left), (uint32_t)take, merge, out, hdr, cap, hdr_cap, overflow);
+      add_inlined<EMIT>(w, h5 >> (8 * (5 - h5_left)), 0, (uint32_t)take, merge, out, hdr, cap, hdr_cap, overflow);
       h5_left -= take;
       n -= take;
     }

@@ -20,6 +20,10 @@ class H2RxMsg(C.Structure):
                 ("flags", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class H2Route(C.Structure):
+    _fields_ = [("from_stream", C.c_uint32), ("to_stream", C.c_uint32)]
+
+
 MSG_OK, MSG_TOO_LARGE, MSG_NO_SPACE, MSG_TRUNCATED = 0, 1, 2, 3
 
 
@@ -86,6 +90,15 @@ def _bind():
         lib.grdma_h2_pipe_attach_assembler.argtypes = [C.c_void_p, C.c_void_p]
         lib.grdma_h2_pipe_messages.restype = C.c_int64
         lib.grdma_h2_pipe_messages.argtypes = [C.c_void_p, C.POINTER(H2RxMsg), u64]
+        lib.grdma_h2_reply_create.restype = C.c_void_p
+        lib.grdma_h2_reply_create.argtypes = [C.c_void_p, C.POINTER(H2Route), C.c_uint32, C.c_uint32, u64]
+        lib.grdma_h2_reply_destroy.argtypes = [C.c_void_p]
+        lib.grdma_h2_reply_frame.restype = C.c_int64
+        lib.grdma_h2_reply_frame.argtypes = [C.c_void_p, C.c_void_p, u64, C.c_void_p, u64, C.POINTER(u64)]
+        lib.grdma_h2_pipe_create_reply.restype = C.c_void_p
+        lib.grdma_h2_pipe_create_reply.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, u64, u64, u64]
+        lib.grdma_h2_pipe_slice_table.restype = C.c_int64
+        lib.grdma_h2_pipe_slice_table.argtypes = [C.c_void_p, C.POINTER(Slice), u64]
         _bound = True
     return lib
 
@@ -240,19 +253,57 @@ class Assembler:
             self.h = None
 
 
+class Reply:
+    """Replies framed on the device from the descriptors of `assembler`'s last call (grdma_h2_reply): every OK message
+    back on its own stream (routes=None), or the messages of the streams in routes = [(from_stream, to_stream), ...]
+    on their to_stream and the others dropped.  Slices point into the assembler's arena: release behind the send."""
+
+    REPLY_STATS = ("kept", "dropped_status", "unrouted", "slices", "hdr_bytes", "wire_bytes", "overflow", "frame_us")
+
+    def __init__(self, assembler, routes=None, max_frame=16384, max_messages=4096):
+        self.lib = _bind()
+        self.assembler = assembler  # (kept alive)
+        routes = list(routes or [])
+        arr = (H2Route * max(1, len(routes)))()
+        for i, (a, b) in enumerate(routes):
+            arr[i].from_stream, arr[i].to_stream = a, b
+        self.h = self.lib.grdma_h2_reply_create(assembler.h, arr if routes else None, len(routes), max_frame, max_messages)
+        if not self.h:
+            raise GrdmaError("h2 reply creation failed (a duplicate or zero stream id in the routes, more than 4096 of "
+                             "them, max_frame or max_messages out of range)")
+        self.last_stats = None
+
+    def frame(self, slices_ptr, cap, hdr_ptr, hdr_cap):
+        """-> (slice count, dict of REPLY_STATS); raises GrdmaError (capacity) when a cap overflows -- the stats of the
+        failed call stay in .last_stats"""
+        out = (u64 * 8)()
+        n = self.lib.grdma_h2_reply_frame(self.h, slices_ptr, cap, hdr_ptr, hdr_cap, out)
+        self.last_stats = dict(zip(Reply.REPLY_STATS, [int(x) for x in out]))
+        return check(n), self.last_stats
+
+    def close(self):
+        if self.h:
+            self.lib.grdma_h2_reply_destroy(self.h)
+            self.h = None
+
+
 class Pipe:
     """frame -> streaming job -> deframe as one enqueued device pipeline (grdma_h2_pipe).
     msgs: list of (payload device ptr, len, stream_id, flags); the job must have been run once."""
 
-    def __init__(self, job, msgs, parser, delivered_slices, events_cap, link=0, max_frame=16384):
-        self.lib = _bind()
-        lib = self.lib
+    @staticmethod
+    def _bind_pipe(lib):
         lib.grdma_h2_pipe_create.restype = C.c_void_p
         lib.grdma_h2_pipe_create.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(H2Msg), u64, C.c_uint32, C.c_void_p, u64, u64]
         lib.grdma_h2_pipe_enqueue.argtypes = [C.c_void_p, C.c_int]
         lib.grdma_h2_pipe_sync.argtypes = [C.c_void_p, C.POINTER(u64), C.POINTER(H2Event), u64]
         lib.grdma_h2_pipe_destroy.argtypes = [C.c_void_p]
         lib.grdma_h2_pipe_boundary_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
+
+    def __init__(self, job, msgs, parser, delivered_slices, events_cap, link=0, max_frame=16384):
+        self.lib = _bind()
+        lib = self.lib
+        Pipe._bind_pipe(lib)
         arr = (H2Msg * len(msgs))()
         for i, (p, n, sid, fl) in enumerate(msgs):
             arr[i].payload, arr[i].len, arr[i].stream_id, arr[i].flags = p, n, sid, fl
@@ -262,6 +313,30 @@ class Pipe:
         self.h = lib.grdma_h2_pipe_create(job.h, link, arr, len(msgs), max_frame, parser.h, delivered_slices, events_cap)
         if not self.h:
             raise GrdmaError("h2 pipe allocation failed")
+
+    @classmethod
+    def reply(cls, job, reply, parser, delivered_slices, events_cap, recorded_wire_bytes, link=0):
+        """A pipe whose framing stage is `reply` (grdma_h2_pipe_create_reply): a step frames what the last enqueued
+        forward step reported, sends it through `job` and deframes it with `parser`.  recorded_wire_bytes: what the
+        job's recorded run sent.  Close it before the forward pipes and before `reply`."""
+        self = cls.__new__(cls)
+        self.lib = _bind()
+        Pipe._bind_pipe(self.lib)
+        self.events_cap = events_cap
+        self.delivered = delivered_slices
+        self.parser, self.reply_framer = parser, reply  # (kept alive)
+        self.h = self.lib.grdma_h2_pipe_create_reply(job.h, link, reply.h, parser.h, delivered_slices, events_cap,
+                                                     recorded_wire_bytes)
+        if not self.h:
+            raise GrdmaError("h2 reply pipe creation failed")
+        reply.assembler._reply_pipes = getattr(reply.assembler, "_reply_pipes", 0) + 1
+        return self
+
+    def slice_table(self, cap=1 << 16):
+        """the slice table the job sends from, [(ptr, len), ...], once the enqueued steps have ended"""
+        arr = (Slice * cap)()
+        n = check(self.lib.grdma_h2_pipe_slice_table(self.h, arr, cap))
+        return [(int(arr[i].ptr or 0), int(arr[i].len)) for i in range(n)]
 
     def enqueue(self, _unused=False):
         check(self.lib.grdma_h2_pipe_enqueue(self.h, 0))
@@ -293,5 +368,12 @@ class Pipe:
 
     def close(self):
         if self.h:
+            a = getattr(self, "assembler", None)
+            if a is not None and getattr(a, "_reply_pipes", 0):
+                # (grdma_h2_pipe_destroy does nothing then: a reply pipe's job gathers from this pipe's arena)
+                raise GrdmaError("close the reply pipe that reads this pipe's assembler first")
             self.lib.grdma_h2_pipe_destroy(self.h)
             self.h = None
+            rf = getattr(self, "reply_framer", None)
+            if rf is not None:
+                rf.assembler._reply_pipes -= 1

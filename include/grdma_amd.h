@@ -711,6 +711,46 @@ int grdma_h2_pipe_attach_assembler(grdma_h2_pipe* p, grdma_h2_asm* a);
 /* the descriptors of the last synced step: their number, or -GRDMA_ERR_CAPACITY if more than cap */
 int64_t grdma_h2_pipe_messages(grdma_h2_pipe* p, grdma_h2_rx_msg* out, uint64_t cap);
 
+/* ---- Replies framed on the device from received-message descriptors (csrc/grdma_h2_reply.h) ----
+ * What a data plane does with a received message without looking inside it: send it back (echo) or on to another
+ * stream (a proxy).  The descriptors of the source assembler's LAST call are framed where they lie: the wire is what
+ * grdma_h2_frame_messages yields for the kept messages in reported order (compressed flag passed through, never
+ * END_STREAM, open flow-control windows).  Kept: status GRDMA_H2_MSG_OK only (the others own no bytes), and
+ *   - without a route table (routes NULL or n_routes 0): every message, on the stream it came in on;
+ *   - with one (at most 4096 entries, sorted by the library): a message whose stream is a from_stream goes out on
+ *     its to_stream, any other is dropped and counted as unrouted.  A duplicate from_stream or a zero id: NULL.
+ * Payload goes by reference: the slices point into the assembler's arena, so the messages must stay unreleased until
+ * the send that gathers them is done -- grdma_h2_asm_release is the caller's to order behind it. */
+typedef struct grdma_h2_route { uint32_t from_stream, to_stream; } grdma_h2_route;
+typedef struct grdma_h2_reply grdma_h2_reply;   /* route table + scratch for up to max_messages descriptors */
+grdma_h2_reply* grdma_h2_reply_create(grdma_h2_asm* source, const grdma_h2_route* routes, uint32_t n_routes,
+                                      uint32_t max_frame, uint64_t max_messages);
+/* does nothing while a reply pipe frames through it: destroy the pipe first.  Destroy the reply before its source. */
+void grdma_h2_reply_destroy(grdma_h2_reply* r);
+/* Frames what the source assembler's last grdma_h2_deframe_messages reported (ordered behind it on the device);
+ * returns the slice count.  out = {kept, dropped by status, dropped as unrouted, slices, header-arena bytes, wire
+ * bytes, overflow, framing time in microseconds (HIP events)}.  -GRDMA_ERR_CAPACITY when the slices or the header
+ * arena (32 bytes per inlined slice, 16-byte aligned) overflow their caps or the call reported more than max_messages
+ * descriptors: nothing is written then.  -GRDMA_ERR_INVALID for null, zero or misaligned arguments and for a source
+ * attached to a pipe (grdma_h2_pipe_create_reply frames that one). */
+int64_t grdma_h2_reply_frame(grdma_h2_reply* r, grdma_slice* d_slices_out, uint64_t slices_cap,
+                             void* d_hdr_arena, uint64_t hdr_cap, uint64_t out[8]);
+/* A pipe whose framing stage is the reply: a step frames what the LAST ENQUEUED step of the forward pipes (the pipes
+ * `reply`'s source assembler is attached to) reported, sends it through job_back and deframes it with parser_back.
+ * Everything else is grdma_h2_pipe: enqueue, sync, attach_assembler, messages, destroy.  job_back has run once over a
+ * slice list of the lengths the reply will have; recorded_wire_bytes is what that run sent
+ * (grdma_stream_result::bytes_sent).  A step whose reply has another slice count or other wire bytes writes nothing:
+ * the job re-sends its previous table, and grdma_h2_pipe_sync reports frame overflow = 2.  Ordering is by events: the
+ * step waits for the forward step's assembler, and a forward step's release waits for the last reply step that read
+ * the arena.  Destroy the reply pipe before the forward pipes (their destroy does nothing while it exists) and
+ * before `reply`. */
+grdma_h2_pipe* grdma_h2_pipe_create_reply(grdma_stream_job* job_back, uint32_t link, grdma_h2_reply* reply,
+                                          grdma_h2_parser* parser_back, uint64_t delivered_slices, uint64_t events_cap,
+                                          uint64_t recorded_wire_bytes);
+/* the slice table the pipe's job sends from (what the framing stage last wrote), after the enqueued steps have ended:
+ * the number of entries, or -GRDMA_ERR_CAPACITY if more than cap */
+int64_t grdma_h2_pipe_slice_table(grdma_h2_pipe* p, grdma_slice* out, uint64_t cap);
+
 /* ---- GRPCProfiler: include/grpcpp/stats_time.h:11-44,111-122, src/core/lib/debug/stats_time.cc ----
  * The reference's scope profiler with its op names in its order: nanoseconds per op per thread slot,
  * opt-in per thread (init(slot) + enable()), the table {Name, Count, Mean, P50, P95, P99, MAX} per slot
