@@ -55,6 +55,7 @@ struct grdma_h2_parser {
   // the last deframing a pipe enqueued for this parser: the next one is ordered behind it (same stream, or this event)
   hipStream_t last_stream = nullptr;
   hipEvent_t last_deframed = nullptr;
+  uint32_t asm_attached = 0;  // pipes that run an assembler of this parser behind their deframer
 };
 
 // How many chunks a parser created without saying so cuts a long list into: GRDMA_H2_CHUNKS (default and at most 256, 0 or 1 = the
@@ -201,6 +202,7 @@ bool h2_grow(T** buf, uint64_t* cap, uint64_t need) {
 extern "C" {
 
 const char* grdma_last_error(void);
+int grdma_fail_msg(int code, const char* msg);  // (csrc/grdma_pair.hip: sets grdma_last_error, returns -code)
 // duration of the framing / deframing kernel of the last call (HIP events), microseconds
 double grdma_h2_last_kernel_us(void) { return g_h2_last_kernel_us; }
 // message starts the last grdma_h2_deframe call took through the boundary step
@@ -413,6 +415,106 @@ int64_t grdma_h2_deframe(grdma_h2_parser* p, const void* d_arena, const grdma_re
   return h_res.overflow ? -GRDMA_ERR_CAPACITY : (int64_t)m;
 }
 
+// ---- the delivered slices of many transports in one launch (k_h2_deframe_links) ---------------------------------
+// One device block per process holds a call: [table | slice lists | zeroed results] go up in one copy, [results | event
+// segments] come down in one copy, the kernel in between.  Nothing per item returns to the host.  The download moves
+// every item's whole event capacity, not the events produced (their number is only known behind it): callers give
+// tight caps.  The block is process-global and unguarded: one call at a time (as the other grdma_h2_* calls, which share
+// one stream and its timing events).
+namespace {
+struct h2_batch_buf {
+  uint8_t* d = nullptr;
+  uint64_t cap = 0;
+};
+h2_batch_buf g_batch;
+}  // namespace
+
+int grdma_h2_deframe_batch(grdma_h2_deframe_item* items, uint32_t n_items) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!items || n_items == 0 || n_items > GRDMA_H2_BATCH_MAX) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 batch: 1 .. GRDMA_H2_BATCH_MAX items");
+  uint64_t n_sl = 0, n_ev = 0;
+  for (uint32_t i = 0; i < n_items; i++) {
+    const grdma_h2_deframe_item& it = items[i];
+    if (!it.parser || !it.d_arena || (!it.slices && it.n) || (!it.events_out && it.cap))
+      return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 batch: an item without parser, arena, slices or event array");
+    if (it.parser->asm_attached) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 batch: a parser whose assembler is attached to a pipe");
+    for (uint32_t k = 0; k < i; k++)
+      if (items[k].parser == it.parser) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 batch: the same parser twice");
+    n_sl += it.n;
+    n_ev += it.cap;
+  }
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  hipStream_t st = hc->stream;
+  // layout (every part 16-byte aligned): table, slice lists, results, event segments
+  auto up16 = [](uint64_t v) { return (v + 15) & ~15ull; };
+  const uint64_t o_sl = up16(sizeof(grdma_h2_link_deframe) * n_items);
+  const uint64_t o_res = o_sl + sizeof(grdma_slice_out) * n_sl;
+  const uint64_t o_ev = up16(o_res + sizeof(grdma_h2_deframe_result) * n_items);
+  const uint64_t total = o_ev + sizeof(grdma_h2_event) * n_ev + 16;
+  if (total > g_batch.cap) {
+    if (hipStreamSynchronize(st) != hipSuccess) return -GRDMA_ERR_HIP;  // (the previous call's block goes)
+    hipFree(g_batch.d);
+    g_batch.d = nullptr;
+    g_batch.cap = 0;
+    uint64_t want = 1 << 16;
+    while (want < total) want *= 2;
+    if (hipMalloc((void**)&g_batch.d, want) != hipSuccess) return -GRDMA_ERR_HIP;
+    g_batch.cap = want;
+  }
+  uint8_t* const d = g_batch.d;
+  std::vector<uint8_t> up(o_ev, 0), down(total - o_res);  // (the result blocks go up zeroed: a call never reports another's)
+  auto* tab = reinterpret_cast<grdma_h2_link_deframe*>(up.data());
+  auto* sl = reinterpret_cast<grdma_slice_out*>(up.data() + o_sl);
+  static_assert(sizeof(grdma_read_slice) == sizeof(grdma_slice_out), "layout");
+  uint64_t a_sl = 0, a_ev = 0;
+  for (uint32_t i = 0; i < n_items; i++) {
+    const grdma_h2_deframe_item& it = items[i];
+    if (it.n) memcpy(sl + a_sl, it.slices, sizeof(grdma_slice_out) * it.n);
+    tab[i].n_step = nullptr;  // (the caller's list: its length is the count)
+    tab[i].res = reinterpret_cast<grdma_h2_deframe_result*>(d + o_res) + i;
+    tab[i].gp = it.parser->d;
+    tab[i].arena = static_cast<const uint8_t*>(it.d_arena);
+    tab[i].slices = reinterpret_cast<const grdma_slice_out*>(d + o_sl) + a_sl;
+    tab[i].nslices = it.n;
+    tab[i].ev = reinterpret_cast<grdma_h2_event*>(d + o_ev) + a_ev;
+    tab[i].ev_cap = it.cap;
+    a_sl += it.n;
+    a_ev += it.cap;
+  }
+  // behind each parser's previous deframing (a pipe step on another stream)
+  for (uint32_t i = 0; i < n_items; i++) {
+    grdma_h2_parser* p = items[i].parser;
+    if (p->last_deframed && p->last_stream != st && hipStreamWaitEvent(st, p->last_deframed, 0) != hipSuccess) return -GRDMA_ERR_HIP;
+  }
+  if (hipMemcpyAsync(d, up.data(), o_ev, hipMemcpyHostToDevice, st) != hipSuccess) return -GRDMA_ERR_HIP;
+  hipEventRecord(hc->e0, st);
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_h2_deframe_links, dim3(n_items), dim3(H2_DEFRAME_THREADS), 0, st, (const grdma_h2_link_deframe*)d);
+  if (hipGetLastError() != hipSuccess) {
+    hipStreamSynchronize(st);
+    return grdma_fail_msg(GRDMA_ERR_HIP, "h2 batch: the launch of k_h2_deframe_links was rejected");
+  }
+  hipEventRecord(hc->e1, st);
+  if (hipMemcpyAsync(down.data(), d + o_res, total - o_res, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return -GRDMA_ERR_HIP;
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, hc->e0, hc->e1) == hipSuccess) g_h2_last_kernel_us = 1e3 * ms;
+  const auto* res = reinterpret_cast<const grdma_h2_deframe_result*>(down.data());
+  const auto* ev = reinterpret_cast<const grdma_h2_event*>(down.data() + (o_ev - o_res));
+  a_ev = 0;
+  for (uint32_t i = 0; i < n_items; i++) {
+    grdma_h2_deframe_item& it = items[i];
+    const uint64_t m = res[i].nevents < it.cap ? res[i].nevents : it.cap;
+    if (m) memcpy(it.events_out, ev + a_ev, sizeof(grdma_h2_event) * m);
+    it.h2_error = (int)res[i].error;
+    it.n_events = res[i].overflow ? -(int64_t)GRDMA_ERR_CAPACITY : (int64_t)m;
+    a_ev += it.cap;
+  }
+  return 0;
+}
+
 // ---- HTTP/2 inside the device pipeline ------------------------------------------------------
 // frame (k_h2_frame_index + k_h2_frame_emit rebuild the job's slice list from the message table) -> the streaming job
 // -> deframe (the deframer over the slices the job delivered), all enqueued.  By default the two stages are kernel
@@ -421,9 +523,12 @@ int64_t grdma_h2_deframe(grdma_h2_parser* p, const void* d_arena, const grdma_re
 struct grdma_stream_job;
 int grdma_job_link_view(grdma_stream_job* j, uint32_t link, grdma_sge** d_sges, uint64_t* count,
                         grdma_slice_out** d_slices, uint8_t** dst, hipStream_t* stream);
+extern "C" uint32_t grdma_job_link_count(grdma_stream_job* j);
+extern "C" int grdma_job_link_step_slices(grdma_stream_job* j, uint32_t link, const uint64_t** d_count, uint64_t* cap);
 int grdma_stream_job_launch(grdma_stream_job* j);
 extern "C" int grdma_job_set_hooks(grdma_stream_job* j, const grdma_job_hook* pre, uint32_t n_pre, const grdma_job_hook* post,
                                    uint32_t n_post);
+extern "C" int grdma_job_hook_counts(grdma_stream_job* j, uint32_t out[2]);
 
 struct grdma_h2_pipe {
   grdma_stream_job* job = nullptr;
@@ -823,6 +928,7 @@ static uint32_t h2_asm_hooks(grdma_h2_asm* a, const h2a_call* d_call, grdma_job_
 
 static void h2_asm_detach(grdma_h2_pipe* p) {
   if (p->asm_) {
+    p->asm_->parser->asm_attached--;
     p->asm_->attached--;
     p->asm_ = nullptr;
   }
@@ -972,6 +1078,7 @@ int grdma_h2_pipe_attach_assembler(grdma_h2_pipe* p, grdma_h2_asm* a) {
   }
   p->asm_ = a;
   a->attached++;
+  a->parser->asm_attached++;
   return 0;
 }
 
@@ -1163,6 +1270,303 @@ int64_t grdma_h2_pipe_slice_table(grdma_h2_pipe* p, grdma_slice* out, uint64_t c
       (p->count && hipMemcpy(out, p->d_sges, sizeof(grdma_sge) * p->count, hipMemcpyDeviceToHost) != hipSuccess))
     return -GRDMA_ERR_HIP;
   return (int64_t)p->count;
+}
+
+// ---- HTTP/2 on several links of ONE job (the group pipe) -----------------------------------------------------------
+// A job carries one set of hooks (grdma_job_set_hooks assigns): the stages of all listed links are ONE framing kernel
+// over a table of links (k_h2_frame_links) in front of the job and ONE deframing kernel (k_h2_deframe_links) behind
+// it -- one launch per step however many links.  Links that are not listed keep their tables and are carried as before.
+struct h2_group_link {
+  uint32_t link = 0;
+  grdma_h2_parser* parser = nullptr;
+  grdma_sge* d_sges = nullptr;
+  uint64_t count = 0;
+  grdma_slice_out* d_slices = nullptr;
+  uint8_t* dst = nullptr;
+  grdma_h2_msg_dev* d_msgs = nullptr;
+  uint64_t nmsgs = 0;
+  uint8_t* d_hdr = nullptr;
+  uint64_t hdr_cap = 0;
+  grdma_h2_event* d_ev = nullptr;
+  uint64_t ev_cap = 0, delivered = 0;
+};
+struct grdma_h2_group_pipe {
+  grdma_stream_job* job = nullptr;
+  std::vector<h2_group_link> links;
+  hipStream_t job_stream = nullptr, frame_stream = nullptr;
+  grdma_h2_link_frame* d_ftab = nullptr;
+  grdma_h2_link_deframe* d_dtab = nullptr;
+  grdma_h2_frame_result* d_fres = nullptr;    // one per listed link
+  grdma_h2_deframe_result* d_dres = nullptr;  // one per listed link
+  uint32_t frame_grid = 0;
+  hipEvent_t framed = nullptr, job_done = nullptr, deframed = nullptr;
+  hipEvent_t t_f0 = nullptr, t_f1 = nullptr, t_d0 = nullptr, t_d1 = nullptr;
+  bool launched = false, fused = false, timed = false;
+};
+
+static grdma_h2_group_pipe* h2_group_refuse(grdma_h2_group_pipe* p, const char* why) {
+  grdma_h2_group_pipe_destroy(p);
+  grdma_fail_msg(GRDMA_ERR_INVALID, why);
+  return nullptr;
+}
+
+grdma_h2_group_pipe* grdma_h2_group_pipe_create(grdma_stream_job* job, const grdma_h2_link_spec* specs, uint32_t n,
+                                                uint32_t max_frame) {
+  if (grdma_device_count() <= 0) return nullptr;
+  if (!job || !specs || n == 0 || n > GRDMA_H2_BATCH_MAX) return h2_group_refuse(nullptr, "h2 group pipe: a job and 1 .. GRDMA_H2_BATCH_MAX link specs");
+  if (max_frame == 0 || max_frame >= (1u << 24)) return h2_group_refuse(nullptr, "h2 group pipe: max_frame out of range");
+  for (uint32_t i = 0; i < n; i++) {
+    if (!specs[i].msgs || specs[i].nmsgs == 0 || specs[i].nmsgs > H2_FRAME_ONE_MAX)
+      return h2_group_refuse(nullptr, "h2 group pipe: 1 .. 4096 messages per link");
+    if (!specs[i].parser) return h2_group_refuse(nullptr, "h2 group pipe: a link without parser");
+    for (uint32_t k = 0; k < i; k++) {
+      if (specs[k].link == specs[i].link) return h2_group_refuse(nullptr, "h2 group pipe: a link listed twice");
+      if (specs[k].parser == specs[i].parser) return h2_group_refuse(nullptr, "h2 group pipe: a parser listed twice");
+    }
+  }
+  const uint32_t job_links = grdma_job_link_count(job);
+  for (uint32_t i = 0; i < n; i++)
+    if (specs[i].link >= job_links) return h2_group_refuse(nullptr, "h2 group pipe: a link index out of range");
+  for (uint32_t i = 0; i < n; i++)
+    for (uint64_t k = 0; k < specs[i].nmsgs; k++)
+      if (specs[i].msgs[k].len >= (1ull << 32)) return h2_group_refuse(nullptr, "h2 group pipe: a message of 4 GiB or more");
+  uint32_t have[2] = {0, 0};
+  if (grdma_job_hook_counts(job, have) != 0) return nullptr;
+  if (have[0] || have[1]) return h2_group_refuse(nullptr, "h2 group pipe: the job already carries hooks (another pipe's)");
+  if (!g_pipe_frame_stream &&
+      (hipStreamCreateWithFlags(&g_pipe_frame_stream, hipStreamNonBlocking) != hipSuccess ||
+       hipStreamCreateWithFlags(&g_pipe_deframe_stream, hipStreamNonBlocking) != hipSuccess))
+    return nullptr;
+  grdma_h2_group_pipe* p = new grdma_h2_group_pipe();
+  p->job = job;
+  p->frame_stream = g_pipe_frame_stream;
+  p->links.resize(n);
+  std::vector<grdma_h2_link_frame> ftab(n);
+  std::vector<grdma_h2_link_deframe> dtab(n);
+  const uint64_t per = H2_EMIT_THREADS / 64;
+  bool ok = hipMalloc((void**)&p->d_ftab, sizeof(grdma_h2_link_frame) * n) == hipSuccess &&
+            hipMalloc((void**)&p->d_dtab, sizeof(grdma_h2_link_deframe) * n) == hipSuccess &&
+            hipMalloc((void**)&p->d_fres, sizeof(grdma_h2_frame_result) * n) == hipSuccess &&
+            hipMalloc((void**)&p->d_dres, sizeof(grdma_h2_deframe_result) * n) == hipSuccess &&
+            hipMemset(p->d_fres, 0, sizeof(grdma_h2_frame_result) * n) == hipSuccess &&
+            hipMemset(p->d_dres, 0, sizeof(grdma_h2_deframe_result) * n) == hipSuccess;
+  for (uint32_t i = 0; ok && i < n; i++) {
+    h2_group_link& l = p->links[i];
+    const grdma_h2_link_spec& sp = specs[i];
+    const uint64_t* d_step = nullptr;
+    uint64_t slices_cap = 0;
+    if (grdma_job_link_view(job, sp.link, &l.d_sges, &l.count, &l.d_slices, &l.dst, &p->job_stream) != 0 ||
+        grdma_job_link_step_slices(job, sp.link, &d_step, &slices_cap) != 0)
+      return h2_group_refuse(p, "h2 group pipe: a link index out of range");
+    l.link = sp.link;
+    l.parser = sp.parser;
+    l.nmsgs = sp.nmsgs;
+    l.delivered = sp.delivered_slices;
+    l.ev_cap = sp.events_cap;
+    l.hdr_cap = 32 * (l.count + 64);
+    std::vector<grdma_h2_msg_dev> tmp(sp.nmsgs);
+    for (uint64_t k = 0; k < sp.nmsgs; k++) {
+      tmp[k].payload = static_cast<const uint8_t*>(sp.msgs[k].payload);
+      tmp[k].len = sp.msgs[k].len;
+      tmp[k].stream_id = sp.msgs[k].stream_id;
+      tmp[k].flags = sp.msgs[k].flags;
+    }
+    ok = hipMalloc((void**)&l.d_msgs, sizeof(grdma_h2_msg_dev) * sp.nmsgs) == hipSuccess &&
+         hipMemcpy(l.d_msgs, tmp.data(), sizeof(grdma_h2_msg_dev) * sp.nmsgs, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMalloc((void**)&l.d_hdr, l.hdr_cap) == hipSuccess &&
+         hipMalloc((void**)&l.d_ev, sizeof(grdma_h2_event) * (l.ev_cap ? l.ev_cap : 1)) == hipSuccess;
+    grdma_h2_link_frame& f = ftab[i];
+    f.msgs = l.d_msgs;
+    f.nmsgs = l.nmsgs;
+    f.out = l.d_sges;
+    f.cap = l.count;
+    f.hdr = l.d_hdr;
+    f.hdr_cap = l.hdr_cap;
+    f.res = p->d_fres + i;
+    f.max_frame = max_frame;
+    f.wg0 = p->frame_grid;
+    p->frame_grid += (uint32_t)((l.nmsgs + per - 1) / per);
+    // the step's own slice count, as the job's drain leaves it on the device (the recorded run's count is what the
+    // caller expects; a step at another ring phase may deliver a slice more or less), bounded by the table
+    grdma_h2_link_deframe& q = dtab[i];
+    q.res = p->d_dres + i;
+    q.gp = l.parser->d;
+    q.arena = l.dst;
+    q.slices = l.d_slices;
+    q.nslices = slices_cap;
+    q.ev = l.d_ev;
+    q.ev_cap = l.ev_cap;
+    q.n_step = d_step;
+  }
+  ok = ok && hipMemcpy(p->d_ftab, ftab.data(), sizeof(grdma_h2_link_frame) * n, hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy(p->d_dtab, dtab.data(), sizeof(grdma_h2_link_deframe) * n, hipMemcpyHostToDevice) == hipSuccess &&
+       hipEventCreateWithFlags(&p->framed, hipEventDisableTiming) == hipSuccess &&
+       hipEventCreateWithFlags(&p->job_done, hipEventDisableTiming) == hipSuccess &&
+       hipEventCreateWithFlags(&p->deframed, hipEventDisableTiming) == hipSuccess &&
+       hipEventCreate(&p->t_f0) == hipSuccess && hipEventCreate(&p->t_f1) == hipSuccess &&
+       hipEventCreate(&p->t_d0) == hipSuccess && hipEventCreate(&p->t_d1) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    grdma_h2_group_pipe_destroy(p);
+    grdma_fail_msg(GRDMA_ERR_HIP, "h2 group pipe: device allocation failed");
+    return nullptr;
+  }
+  const char* fe = getenv("GRDMA_H2_PIPE_FUSED");
+  if (!fe || atoi(fe) != 0) {
+    grdma_job_hook pre, post;
+    memset(&pre, 0, sizeof(pre));
+    memset(&post, 0, sizeof(post));
+    pre.fn = (const void*)k_h2_frame_links;
+    pre.grid = p->frame_grid;
+    pre.threads = H2_EMIT_THREADS;
+    pre.args[0] = (uint64_t)(uintptr_t)p->d_ftab;
+    pre.args[1] = n;
+    post.fn = (const void*)k_h2_deframe_links;
+    post.grid = n;
+    post.threads = H2_DEFRAME_THREADS;
+    post.args[0] = (uint64_t)(uintptr_t)p->d_dtab;
+    if (grdma_job_set_hooks(job, &pre, 1, &post, 1) != 0) {
+      grdma_h2_group_pipe_destroy(p);
+      return nullptr;
+    }
+    p->fused = true;
+  }
+  return p;
+}
+
+void grdma_h2_group_pipe_destroy(grdma_h2_group_pipe* p) {
+  if (!p) return;
+  if (p->launched) {
+    hipStreamSynchronize(p->frame_stream);
+    hipStreamSynchronize(p->job_stream);
+  }
+  for (h2_group_link& l : p->links) {
+    if (l.parser && l.parser->last_deframed == p->deframed) l.parser->last_deframed = nullptr;  // (synchronised above)
+    hipFree(l.d_msgs);
+    hipFree(l.d_hdr);
+    hipFree(l.d_ev);
+  }
+  if (p->fused && p->job) grdma_job_set_hooks(p->job, nullptr, 0, nullptr, 0);
+  hipFree(p->d_ftab);
+  hipFree(p->d_dtab);
+  hipFree(p->d_fres);
+  hipFree(p->d_dres);
+  for (hipEvent_t e : {p->framed, p->job_done, p->deframed, p->t_f0, p->t_f1, p->t_d0, p->t_d1})
+    if (e) hipEventDestroy(e);
+  delete p;
+}
+
+int grdma_h2_group_pipe_enqueue(grdma_h2_group_pipe* p) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!p) return -GRDMA_ERR_INVALID;
+  const uint32_t n = (uint32_t)p->links.size();
+  // every parser's state is handed over from its previous deframing (a pipe step or a call on another stream)
+  auto wait_parsers = [&]() {
+    for (h2_group_link& l : p->links)
+      if (l.parser->last_deframed && l.parser->last_stream != p->job_stream &&
+          hipStreamWaitEvent(p->job_stream, l.parser->last_deframed, 0) != hipSuccess)
+        return false;
+    return true;
+  };
+  auto done = [&]() {
+    for (h2_group_link& l : p->links) {
+      l.parser->last_stream = p->job_stream;
+      l.parser->last_deframed = p->deframed;
+    }
+    p->launched = true;
+  };
+  if (p->fused) {  // one graph launch: k_h2_frame_links -> the job's rounds -> k_h2_deframe_links
+    if (!wait_parsers()) return -GRDMA_ERR_HIP;
+    const int rc = grdma_stream_job_launch(p->job);
+    if (rc < 0) return rc;
+    if (hipEventRecord(p->deframed, p->job_stream) != hipSuccess) return -GRDMA_ERR_HIP;
+    p->timed = false;
+    done();
+    return 0;
+  }
+  p->timed = true;
+  // framing overwrites the slice tables the job's previous step read
+  if (p->launched && hipStreamWaitEvent(p->frame_stream, p->job_done, 0) != hipSuccess) return -GRDMA_ERR_HIP;
+  if (hipMemsetAsync(p->d_fres, 0, sizeof(grdma_h2_frame_result) * n, p->frame_stream) != hipSuccess) return -GRDMA_ERR_HIP;
+  hipEventRecord(p->t_f0, p->frame_stream);
+  hipLaunchKernelGGL(k_h2_frame_links, dim3(p->frame_grid), dim3(H2_EMIT_THREADS), 0, p->frame_stream,
+                     (const grdma_h2_link_frame*)p->d_ftab, n);
+  hipEventRecord(p->t_f1, p->frame_stream);
+  if (hipEventRecord(p->framed, p->frame_stream) != hipSuccess) return -GRDMA_ERR_HIP;
+  if (hipStreamWaitEvent(p->job_stream, p->framed, 0) != hipSuccess) return -GRDMA_ERR_HIP;
+  const int rc = grdma_stream_job_launch(p->job);
+  if (rc < 0) return rc;
+  if (hipEventRecord(p->job_done, p->job_stream) != hipSuccess) return -GRDMA_ERR_HIP;
+  // the deframing goes behind the job on the job's stream (csrc: why the single pipe does the same by default)
+  if (!wait_parsers()) return -GRDMA_ERR_HIP;
+  hipEventRecord(p->t_d0, p->job_stream);
+  hipLaunchKernelGGL(k_h2_deframe_links, dim3(n), dim3(H2_DEFRAME_THREADS), 0, p->job_stream,
+                     (const grdma_h2_link_deframe*)p->d_dtab);
+  hipEventRecord(p->t_d1, p->job_stream);
+  if (hipEventRecord(p->deframed, p->job_stream) != hipSuccess) return -GRDMA_ERR_HIP;
+  done();
+  return 0;
+}
+
+static int h2_group_wait(grdma_h2_group_pipe* p) {
+  if (hipStreamSynchronize(p->frame_stream) != hipSuccess || hipStreamSynchronize(p->job_stream) != hipSuccess) return -GRDMA_ERR_HIP;
+  return 0;
+}
+
+int grdma_h2_group_pipe_sync(grdma_h2_group_pipe* p, uint64_t* out, uint64_t out_words) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!p || !out || out_words < 14 * p->links.size()) return -GRDMA_ERR_INVALID;
+  if (int rc = h2_group_wait(p)) return rc;
+  const size_t n = p->links.size();
+  std::vector<grdma_h2_frame_result> fr(n);
+  std::vector<grdma_h2_deframe_result> dr(n);
+  if (hipMemcpy(fr.data(), p->d_fres, sizeof(grdma_h2_frame_result) * n, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(dr.data(), p->d_dres, sizeof(grdma_h2_deframe_result) * n, hipMemcpyDeviceToHost) != hipSuccess)
+    return -GRDMA_ERR_HIP;
+  float fms = 0, dms = 0;
+  uint64_t f_us = 0, d_us = 0;
+  if (p->launched && p->timed && hipEventElapsedTime(&fms, p->t_f0, p->t_f1) == hipSuccess) f_us = (uint64_t)(fms * 1e3f);
+  if (p->launched && p->timed && hipEventElapsedTime(&dms, p->t_d0, p->t_d1) == hipSuccess) d_us = (uint64_t)(dms * 1e3f);
+  for (size_t i = 0; i < n; i++) {
+    uint64_t* o = out + 14 * i;
+    o[0] = fr[i].nslices;
+    o[1] = fr[i].overflow;
+    o[2] = dr[i].nevents;
+    o[3] = dr[i].overflow;
+    o[4] = dr[i].slices_done;
+    o[5] = (uint64_t)dr[i].error;
+    o[6] = f_us;  // (the batch's, repeated)
+    o[7] = d_us;
+    o[8] = dr[i].bulk_steps;
+    o[9] = dr[i].bulk_frames;
+    o[10] = dr[i].t_wait;
+    o[11] = dr[i].t_bulk;
+    o[12] = dr[i].t_total;
+    o[13] = dr[i].t_serial;
+  }
+  return 0;
+}
+
+int64_t grdma_h2_group_pipe_events(grdma_h2_group_pipe* p, uint32_t i, grdma_h2_event* out, uint64_t cap) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!p || i >= p->links.size() || (!out && cap)) return -GRDMA_ERR_INVALID;
+  if (int rc = h2_group_wait(p)) return rc;
+  grdma_h2_deframe_result dr;
+  if (hipMemcpy(&dr, p->d_dres + i, sizeof(dr), hipMemcpyDeviceToHost) != hipSuccess) return -GRDMA_ERR_HIP;
+  const uint64_t m = std::min<uint64_t>(dr.nevents, p->links[i].ev_cap);
+  if (m > cap) return -GRDMA_ERR_CAPACITY;
+  if (m && hipMemcpy(out, p->links[i].d_ev, sizeof(grdma_h2_event) * m, hipMemcpyDeviceToHost) != hipSuccess) return -GRDMA_ERR_HIP;
+  return (int64_t)m;
+}
+
+int64_t grdma_h2_group_pipe_slice_table(grdma_h2_group_pipe* p, uint32_t i, grdma_slice* out, uint64_t cap) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!p || i >= p->links.size() || (!out && cap)) return -GRDMA_ERR_INVALID;
+  const h2_group_link& l = p->links[i];
+  if (l.count > cap) return -GRDMA_ERR_CAPACITY;
+  if (int rc = h2_group_wait(p)) return rc;
+  if (l.count && hipMemcpy(out, l.d_sges, sizeof(grdma_sge) * l.count, hipMemcpyDeviceToHost) != hipSuccess) return -GRDMA_ERR_HIP;
+  return (int64_t)l.count;
 }
 
 }  // extern "C"

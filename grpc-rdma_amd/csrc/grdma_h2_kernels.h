@@ -1,5 +1,6 @@
 // Device side of the HTTP/2 DATA framing (K6/K7) and deframing (K8/K9): the structures the kernels keep
-// in HBM and the kernels themselves (k_h2_frame_index, k_h2_frame_emit, k_h2_deframe and the chunked deframer, k_h2_table_ops).  Included by
+// in HBM and the kernels themselves (k_h2_frame_index, k_h2_frame_emit, k_h2_frame_one, k_h2_deframe and the chunked deframer, their
+// many-link forms k_h2_frame_links and k_h2_deframe_links, k_h2_table_ops).  Included by
 // csrc/grdma_h2.hip, which holds the host API, and -- under the wave emulator of tests/cc/wave_emu.h -- by
 // tests/cc/h2_emu_host.cc, which runs k_h2_deframe on the CPU against the oracle.
 #ifndef GRDMA_H2_KERNELS_H
@@ -350,69 +351,43 @@ __global__ __launch_bounds__(H2_EMIT_THREADS) void k_h2_frame_emit(const grdma_h
 __global__ __launch_bounds__(H2_EMIT_THREADS) void k_h2_frame_one(const grdma_h2_msg_dev* msgs, uint64_t nmsgs,
                                                                  uint32_t max_frame, grdma_sge* out, uint64_t cap,
                                                                  uint8_t* hdr, uint64_t hdr_cap, grdma_h2_frame_result* res) {
-  __shared__ uint64_t s_part[H2_EMIT_THREADS / 64][3];
-  __shared__ uint64_t s_mine[H2_EMIT_THREADS / 64][3];
-  __shared__ uint32_t s_mode[H2_EMIT_THREADS / 64];
-  const int lane = threadIdx.x & 63;
-  const uint32_t wave = threadIdx.x >> 6;
-  constexpr uint32_t PER = H2_EMIT_THREADS / 64;
-  const uint64_t i0 = (uint64_t)blockIdx.x * PER;
-  // sizes of the messages in front of this workgroup's, one per thread per pass
-  uint64_t a_sl = 0, a_hdr = 0, a_wire = 0;
-  for (uint64_t j = threadIdx.x; j < i0; j += H2_EMIT_THREADS) {
-    uint64_t n_sl, n_hdr, n_wire;
-    uint32_t mode;
-    h2_msg_size(msgs, j, max_frame, &n_sl, &n_hdr, &n_wire, &mode);
-    a_sl += n_sl;
-    a_hdr += n_hdr;
-    a_wire += n_wire;
+#define H2_FRAME_GROUP blockIdx.x
+#include "grdma_h2_frame_group.inc"
+#undef H2_FRAME_GROUP
+}
+
+// The same for the message tables of L links of one job in ONE launch (the group pipe, csrc/grdma_h2.hip): the grid is
+// the links' shares side by side, link l owning the workgroups [wg0[l], wg0[l + 1]) -- ceil(nmsgs / 4) of them.  A
+// workgroup finds its link by a search over the (tiny) table: the block index is uniform, so the probes are scalar
+// loads and the link's entry ends up in scalar registers, as k_h2_frame_one's parameters do.
+struct grdma_h2_link_frame {
+  const grdma_h2_msg_dev* msgs;
+  uint64_t nmsgs;     // <= H2_FRAME_ONE_MAX
+  grdma_sge* out;     // the link's slice table
+  uint64_t cap;
+  uint8_t* hdr;       // its header arena
+  uint64_t hdr_cap;
+  grdma_h2_frame_result* res;
+  uint32_t max_frame;
+  uint32_t wg0;       // first workgroup of the link (ascending; entry 0: 0)
+};
+__global__ __launch_bounds__(H2_EMIT_THREADS) void k_h2_frame_links(const grdma_h2_link_frame* tab, uint32_t nlinks) {
+  const uint32_t g = blockIdx.x;
+  uint32_t lo = 0, hi = nlinks;  // the last entry with wg0 <= g
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (tab[mid].wg0 <= g) lo = mid; else hi = mid;
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    a_sl += __shfl_xor(a_sl, d, 64);
-    a_hdr += __shfl_xor(a_hdr, d, 64);
-    a_wire += __shfl_xor(a_wire, d, 64);
-  }
-  if (lane == 0) {
-    s_part[wave][0] = a_sl;
-    s_part[wave][1] = a_hdr;
-    s_part[wave][2] = a_wire;
-    // ... and of my own message
-    uint64_t n_sl = 0, n_hdr = 0, n_wire = 0;
-    uint32_t mode = 0;
-    if (i0 + wave < nmsgs) h2_msg_size(msgs, i0 + wave, max_frame, &n_sl, &n_hdr, &n_wire, &mode);
-    s_mine[wave][0] = n_sl;
-    s_mine[wave][1] = n_hdr;
-    s_mine[wave][2] = n_wire;
-    s_mode[wave] = mode;
-  }
-  __syncthreads();
-  uint64_t b_sl = 0, b_hdr = 0, b_wire = 0;
-  for (uint32_t w = 0; w < PER; w++) {
-    b_sl += s_part[w][0];
-    b_hdr += s_part[w][1];
-    b_wire += s_part[w][2];
-  }
-  for (uint32_t w = 0; w < wave; w++) {
-    b_sl += s_mine[w][0];
-    b_hdr += s_mine[w][1];
-    b_wire += s_mine[w][2];
-  }
-  const uint64_t i = i0 + wave;
-  if (i + 1 == nmsgs && lane == 0) {  // the last message's wave knows the totals
-    const uint64_t t_sl = b_sl + s_mine[wave][0], t_hdr = b_hdr + s_mine[wave][1];
-    res->nslices = t_sl;
-    res->hdr_bytes = t_hdr;
-    res->wire_bytes = b_wire + s_mine[wave][2];
-    res->overflow = (t_sl > cap || t_hdr > hdr_cap) ? 1 : 0;
-  }
-  if (i >= nmsgs) return;  // (wave-uniform)
-  grdma_h2_msg_pos q;
-  q.sl = b_sl;
-  q.hdr = b_hdr;
-  q.mode = s_mode[wave];
-  q.pad = 0;
-  h2_emit_message(msgs, i, nmsgs, max_frame, out, cap, hdr, hdr_cap, q, lane);
+  const grdma_h2_link_frame e = tab[lo];
+  const grdma_h2_msg_dev* const msgs = e.msgs;
+  const uint64_t nmsgs = e.nmsgs, cap = e.cap, hdr_cap = e.hdr_cap;
+  const uint32_t max_frame = e.max_frame;
+  grdma_sge* const out = e.out;
+  uint8_t* const hdr = e.hdr;
+  grdma_h2_frame_result* const res = e.res;
+#define H2_FRAME_GROUP (g - e.wg0)
+#include "grdma_h2_frame_group.inc"
+#undef H2_FRAME_GROUP
 }
 
 // ---------------------------------------------------------------- RX deframing
@@ -1145,6 +1120,34 @@ __global__ __launch_bounds__(H2_DEFRAME_THREADS) void k_h2_deframe(grdma_h2_pars
                                                                   grdma_h2_event* ev, uint64_t ev_cap,
                                                                   grdma_h2_deframe_result* res) {
   h2_deframe_body(gp, arena, slices, nslices, ev, ev_cap, res);
+}
+
+// The delivered slices of L transports in ONE launch: workgroup l is k_h2_deframe for entry l of the table (its own
+// parser block, stream map, arena, slice list, event list and result block; nothing is shared between the entries, so
+// an error, an overflow or an empty list of one transport is that workgroup's alone).  The entry is loaded with a
+// uniform index: it sits in scalar registers, as k_h2_deframe's parameters do.  Always the sequential body: the lists
+// of many connections are short and the links supply the parallelism.
+// n_step (may be null): where the producer of the list -- a streaming job's drain -- left the number of slices of THIS
+// step; nslices then only bounds it (the table's capacity).  At small rings a step starts at another ring phase than
+// the recorded run and may deliver a slice more or less (a record cut at the wrap).
+struct grdma_h2_link_deframe {
+  grdma_h2_deframe_result* res;  // (first: in this order the entry costs no more scalar spills than k_h2_deframe's parameters)
+  grdma_h2_parser_dev* gp;
+  const uint8_t* arena;
+  const grdma_slice_out* slices;
+  uint64_t nslices;
+  grdma_h2_event* ev;
+  uint64_t ev_cap;
+  const uint64_t* n_step;
+};
+__global__ __launch_bounds__(H2_DEFRAME_THREADS) void k_h2_deframe_links(const grdma_h2_link_deframe* __restrict__ tab) {
+  const grdma_h2_link_deframe e = tab[blockIdx.x];
+  uint64_t n = e.nslices;
+  if (e.n_step) {
+    const uint64_t now = *e.n_step;
+    n = now < n ? now : n;
+  }
+  h2_deframe_body(e.gp, e.arena, e.slices, n, e.ev, e.ev_cap, e.res);
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -1029,8 +1029,26 @@ extern "C" __attribute__((visibility("hidden"))) int grdma_job_link_view(grdma_s
   return 0;
 }
 
+// How many links the job has, and where a step leaves the number of slices it delivered on one of them: the device
+// word the drain planners keep (grdma_conn::rx_slice_idx of the receiving end) and the capacity of the link's slice
+// table.  Nothing of the job changes (grdma_job_link_view marks the tables as rewritable).
+extern "C" __attribute__((visibility("hidden"))) uint32_t grdma_job_link_count(grdma_stream_job* j) {
+  return j ? (uint32_t)j->links.size() : 0;
+}
+extern "C" __attribute__((visibility("hidden"))) int grdma_job_link_step_slices(grdma_stream_job* j, uint32_t link,
+                                                                                const uint64_t** d_count, uint64_t* cap) {
+  if (!j || link >= j->links.size()) return -1;
+  const grdma_job_link& l = j->links[link];
+  *d_count = reinterpret_cast<const uint64_t*>(reinterpret_cast<const uint8_t*>(l.rx->d_conn) + offsetof(grdma_conn, rx_slice_idx));
+  *cap = l.slices_cap;
+  return 0;
+}
+
 // Kernel nodes in front of and behind the job INSIDE its graph (one launch per step, no graph boundary -- ~15-20 us of
 // idle device each -- between the stages); null / 0 removes them.  The graph is rebuilt at the next launch.
+// Hooks are PER JOB and ASSIGNED, not added: a second caller replaces the first one's kernels, whichever link either
+// of them works on.  A stage that serves several links of one job is one hook over a table of links (the HTTP/2 group
+// pipe); who must not replace somebody else's hooks asks grdma_job_hook_counts first.
 extern "C" __attribute__((visibility("hidden"))) int grdma_job_set_hooks(grdma_stream_job* j, const grdma_job_hook* pre,
                                                                          uint32_t n_pre, const grdma_job_hook* post,
                                                                          uint32_t n_post) {
@@ -1038,6 +1056,15 @@ extern "C" __attribute__((visibility("hidden"))) int grdma_job_set_hooks(grdma_s
   j->pre_hooks.assign(pre, pre + (pre ? n_pre : 0));
   j->post_hooks.assign(post, post + (post ? n_post : 0));
   j->hooks_gen++;
+  return 0;
+}
+
+// out = {pre hooks, post hooks} the job's graph carries.  Not part of include/grdma_amd.h: for the stages that hang
+// hooks into a job (csrc/grdma_h2.hip) and for their tests.
+int grdma_job_hook_counts(grdma_stream_job* j, uint32_t out[2]) {
+  if (!j || !out) return fail(GRDMA_ERR_INVALID, "null job");
+  out[0] = (uint32_t)j->pre_hooks.size();
+  out[1] = (uint32_t)j->post_hooks.size();
   return 0;
 }
 

@@ -199,6 +199,9 @@ uint32_t host_copy_blocks(int dir, uint32_t hbm_blocks) {
 
 }  // namespace
 
+// grdma_last_error for the translation units that do not see fail() (csrc/grdma_h2.hip): returns -code
+extern "C" __attribute__((visibility("hidden"))) int grdma_fail_msg(int code, const char* msg) { return fail(code, "%s", msg); }
+
 // Host control block shared with the device (pinned, device-visible).
 struct grdma_hostblk {
   grdma_tx_op txop;

@@ -24,7 +24,19 @@ class H2Route(C.Structure):
     _fields_ = [("from_stream", C.c_uint32), ("to_stream", C.c_uint32)]
 
 
+class H2DeframeItem(C.Structure):
+    _fields_ = [("parser", C.c_void_p), ("d_arena", C.c_void_p), ("slices", C.POINTER(ReadSlice)), ("n", u64),
+                ("events_out", C.POINTER(H2Event)), ("cap", u64), ("n_events", C.c_int64), ("h2_error", C.c_int)]
+
+
+class H2LinkSpec(C.Structure):
+    _fields_ = [("link", C.c_uint32), ("msgs", C.POINTER(H2Msg)), ("nmsgs", u64), ("parser", C.c_void_p),
+                ("delivered_slices", u64), ("events_cap", u64)]
+
+
 MSG_OK, MSG_TOO_LARGE, MSG_NO_SPACE, MSG_TRUNCATED = 0, 1, 2, 3
+SYNC_KEYS = ("framed", "frame_overflow", "events", "deframe_overflow", "parsed", "h2_error", "frame_us", "deframe_us",
+             "bulk_steps", "bulk_frames", "t_wait", "t_bulk", "t_total", "t_serial")
 
 
 class Msg(tuple):
@@ -99,6 +111,21 @@ def _bind():
         lib.grdma_h2_pipe_create_reply.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, u64, u64, u64]
         lib.grdma_h2_pipe_slice_table.restype = C.c_int64
         lib.grdma_h2_pipe_slice_table.argtypes = [C.c_void_p, C.POINTER(Slice), u64]
+        lib.grdma_h2_deframe_batch.restype = C.c_int
+        lib.grdma_h2_deframe_batch.argtypes = [C.POINTER(H2DeframeItem), C.c_uint32]
+        lib.grdma_h2_group_pipe_create.restype = C.c_void_p
+        lib.grdma_h2_group_pipe_create.argtypes = [C.c_void_p, C.POINTER(H2LinkSpec), C.c_uint32, C.c_uint32]
+        lib.grdma_h2_group_pipe_enqueue.restype = C.c_int
+        lib.grdma_h2_group_pipe_enqueue.argtypes = [C.c_void_p]
+        lib.grdma_h2_group_pipe_sync.restype = C.c_int
+        lib.grdma_h2_group_pipe_sync.argtypes = [C.c_void_p, C.POINTER(u64), u64]
+        lib.grdma_h2_group_pipe_events.restype = C.c_int64
+        lib.grdma_h2_group_pipe_events.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(H2Event), u64]
+        lib.grdma_h2_group_pipe_slice_table.restype = C.c_int64
+        lib.grdma_h2_group_pipe_slice_table.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Slice), u64]
+        lib.grdma_h2_group_pipe_destroy.argtypes = [C.c_void_p]
+        lib.grdma_job_hook_counts.restype = C.c_int   # (not in include/grdma_amd.h: the job's side of the pipes)
+        lib.grdma_job_hook_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         _bound = True
     return lib
 
@@ -210,6 +237,93 @@ class Parser:
             self.h = None
 
 
+def deframe_batch(items, caps=None):
+    """The delivered slices of many transports in ONE launch (grdma_h2_deframe_batch).  items: [(Parser, arena device
+    ptr, [(offset, len), ...]), ...] with distinct parsers; caps: event capacity per item (default: what
+    Parser.deframe takes).  -> [(h2 error, events), ...] per item; every item reports for itself: where the events did
+    not fit the item's capacity, `events` is the integer -GRDMA_ERR_CAPACITY (-5) instead of a list."""
+    lib = _bind()
+    n = len(items)
+    arr = (H2DeframeItem * max(1, n))()
+    keep = []
+    for i, (parser, arena, slices) in enumerate(items):
+        sl = (ReadSlice * max(1, len(slices)))()
+        for k, (o, l) in enumerate(slices):
+            sl[k].off, sl[k].len = o, l
+        cap = (caps[i] if caps is not None else None) or min(sum(l for _, l in slices) * 2 + 64, 1 << 20)
+        ev = (H2Event * cap)()
+        keep.append((sl, ev))
+        arr[i].parser, arr[i].d_arena, arr[i].slices, arr[i].n = parser.h, arena, sl, len(slices)
+        arr[i].events_out, arr[i].cap = ev, cap
+    check(lib.grdma_h2_deframe_batch(arr, n))
+    out = []
+    for i in range(n):
+        m = int(arr[i].n_events)
+        out.append((int(arr[i].h2_error), [(e.kind, e.a, e.b, e.c, e.d, e.slice) for e in keep[i][1][:m]] if m >= 0 else m))
+    return out
+
+
+class GroupPipe:
+    """frame -> multi-link job -> deframe for several links of ONE job (grdma_h2_group_pipe): one framing kernel and
+    one deframing kernel per step however many links.  specs: [(link, msgs, Parser, delivered_slices, events_cap), ...]
+    with msgs = [(payload device ptr, len, stream_id, flags), ...]; links and parsers distinct; the job has run once.
+    Links that are not listed are carried as before."""
+
+    def __init__(self, job, specs, max_frame=16384):
+        self.lib = _bind()
+        specs = list(specs)
+        arr = (H2LinkSpec * max(1, len(specs)))()
+        self._keep = []
+        for i, (link, msgs, parser, delivered, cap) in enumerate(specs):
+            m = (H2Msg * max(1, len(msgs)))()
+            for k, (p, n, sid, fl) in enumerate(msgs):
+                m[k].payload, m[k].len, m[k].stream_id, m[k].flags = p, n, sid, fl
+            self._keep.append((m, parser))
+            arr[i].link, arr[i].msgs, arr[i].nmsgs, arr[i].parser = link, m, len(msgs), parser.h
+            arr[i].delivered_slices, arr[i].events_cap = delivered, cap
+        self.n = len(specs)
+        self.events_caps = [sp[4] for sp in specs]
+        self.job = job  # (kept alive)
+        self.h = self.lib.grdma_h2_group_pipe_create(job.h, arr, len(specs), max_frame)
+        if not self.h:
+            raise GrdmaError("h2 group pipe refused: %s" % self.lib.grdma_last_error().decode())
+
+    def enqueue(self):
+        check(self.lib.grdma_h2_group_pipe_enqueue(self.h))
+
+    def sync(self):
+        """-> one dict per spec with the keys of Pipe.sync (frame_us / deframe_us are the batch's)"""
+        out = (u64 * (14 * self.n))()
+        check(self.lib.grdma_h2_group_pipe_sync(self.h, out, 14 * self.n))
+        return [dict(zip(SYNC_KEYS, [int(x) for x in out[14 * i:14 * i + 14]])) for i in range(self.n)]
+
+    def events(self, i):
+        cap = max(1, self.events_caps[i])
+        ev = (H2Event * cap)()
+        m = check(self.lib.grdma_h2_group_pipe_events(self.h, i, ev, cap))
+        return [(e.kind, e.a, e.b, e.c, e.d, e.slice) for e in ev[:m]]
+
+    def slice_table(self, i, cap=1 << 16):
+        arr = (Slice * cap)()
+        n = check(self.lib.grdma_h2_group_pipe_slice_table(self.h, i, arr, cap))
+        return [(int(arr[k].ptr or 0), int(arr[k].len)) for k in range(n)]
+
+    def hook_counts(self):
+        """(kernels in front of, kernels behind) the job's rounds inside its graph"""
+        return job_hook_counts(self.job)
+
+    def close(self):
+        if self.h:
+            self.lib.grdma_h2_group_pipe_destroy(self.h)
+            self.h = None
+
+
+def job_hook_counts(job):
+    out = (C.c_uint32 * 2)()
+    check(_bind().grdma_job_hook_counts(job.h, out))
+    return int(out[0]), int(out[1])
+
+
 class Assembler:
     """Received gRPC messages, contiguous in a ring over `arena` (grdma_h2_asm): a DeviceBuffer-like object (.ptr,
     .nbytes) or a torch uint8 tensor on the device.  max_message_bytes = 0: no limit."""
@@ -289,7 +403,9 @@ class Reply:
 
 class Pipe:
     """frame -> streaming job -> deframe as one enqueued device pipeline (grdma_h2_pipe).
-    msgs: list of (payload device ptr, len, stream_id, flags); the job must have been run once."""
+    msgs: list of (payload device ptr, len, stream_id, flags); the job must have been run once.
+    link: the one link of the job this pipe serves.  A job carries one pipe: for more than one link of one job use
+    GroupPipe (a second Pipe on another link would replace this one's kernels in the job's graph)."""
 
     @staticmethod
     def _bind_pipe(lib):
@@ -346,8 +462,7 @@ class Pipe:
         out = (u64 * 14)()
         ev = (H2Event * self.events_cap)() if want_events else None
         check(self.lib.grdma_h2_pipe_sync(self.h, out, ev, self.events_cap if want_events else 0))
-        r = dict(zip(("framed", "frame_overflow", "events", "deframe_overflow", "parsed", "h2_error", "frame_us", "deframe_us", "bulk_steps", "bulk_frames", "t_wait", "t_bulk", "t_total", "t_serial"),
-                     [int(x) for x in out]))
+        r = dict(zip(SYNC_KEYS, [int(x) for x in out]))
         bs = (u64 * 2)()
         check(self.lib.grdma_h2_pipe_boundary_stats(self.h, bs))
         r["boundary_steps"], r["t_boundary"] = int(bs[0]), int(bs[1])

@@ -53,6 +53,7 @@ class StreamJob:
         for i, (p, n) in enumerate(slices):
             arr[i].ptr, arr[i].len = p, n
         self.slices_cap = slices_cap
+        self._ends = [(tx, rx)]  # (kept alive: the job's kernels work on the pairs' rings)
         self.h = self.lib.grdma_stream_job_create(tx.h, rx.h, arr, len(slices), rx_dst_ptr,
                                                   rx_dst_cap, slices_cap, max_rounds)
         if not self.h:
@@ -122,6 +123,7 @@ class MultiStreamJob(StreamJob):
         """links: list of (tx Pair, rx Pair, slices [(ptr,len)...], dst ptr, dst cap, slices cap)."""
         self.lib = _bind()
         n = len(links)
+        self._ends = [(l[0], l[1]) for l in links]  # (kept alive: the job's kernels work on the pairs' rings)
         txs = (C.c_void_p * n)(*[l[0].h for l in links])
         rxs = (C.c_void_p * n)(*[l[1].h for l in links])
         total = sum(len(l[2]) for l in links)

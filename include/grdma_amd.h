@@ -648,6 +648,31 @@ int grdma_h2_parser_chunk_dbg(grdma_h2_parser* p, uint64_t* out, uint64_t cap_wo
 int64_t grdma_h2_deframe(grdma_h2_parser* p, const void* d_arena, const grdma_read_slice* slices,
                          uint64_t n, grdma_h2_event* events_out, uint64_t cap, int* h2_error);
 
+/* The delivered slices of MANY transports in one launch (k_h2_deframe_links: one workgroup per item): what a pollset
+ * of many connections hands over at once.  Per item the events, the parser state and the stream map are exactly those
+ * of grdma_h2_deframe on that item alone; a connection error, an event overflow or an empty list (n == 0) of one item
+ * leaves the others untouched, and every item reports for itself (n_events, h2_error).  One upload, one launch, one
+ * download -- of every item's whole event capacity, so give tight caps.  Always the sequential deframer per transport
+ * (the chunked one stays a single-transport path).  Not thread-safe: one call at a time per process (the call owns a
+ * process-wide device block, and the grdma_h2_* calls share one stream).  A parser belongs to one user at a time: while
+ * a pipe runs an assembler behind it, the pipe's steps own its state and the batch refuses it; a parser listed in a
+ * pipe or group pipe without assembler may be used here between steps (the call is ordered behind the last step).
+ * Returns 0, or -GRDMA_ERR_INVALID (nothing ran): n_items outside 1 .. GRDMA_H2_BATCH_MAX, an item without parser or
+ * arena, slices NULL with n > 0, events_out NULL with cap > 0, the same parser twice, a parser whose assembler is
+ * attached to a pipe. */
+#define GRDMA_H2_BATCH_MAX 256
+typedef struct grdma_h2_deframe_item {
+  grdma_h2_parser* parser;          /* distinct per item */
+  const void* d_arena;              /* the arena this transport's slices point into */
+  const grdma_read_slice* slices;   /* host array, as grdma_h2_deframe takes it */
+  uint64_t n;
+  grdma_h2_event* events_out;       /* host, may be NULL (then cap = 0) */
+  uint64_t cap;
+  int64_t n_events;                 /* out: events, or -GRDMA_ERR_CAPACITY for this item */
+  int h2_error;                     /* out: this transport's connection error */
+} grdma_h2_deframe_item;
+int grdma_h2_deframe_batch(grdma_h2_deframe_item* items, uint32_t n_items);
+
 /* HTTP/2 inside the device pipeline: per step, k_h2_frame_index + k_h2_frame_emit rebuild the slice list of the job's
  * link from the message table (grpc_chttp2_encode_data, frame_data.cc:64-90), the streaming job
  * carries it through the connection, and k_h2_deframe parses the slices the job delivered
@@ -750,6 +775,43 @@ grdma_h2_pipe* grdma_h2_pipe_create_reply(grdma_stream_job* job_back, uint32_t l
 /* the slice table the pipe's job sends from (what the framing stage last wrote), after the enqueued steps have ended:
  * the number of entries, or -GRDMA_ERR_CAPACITY if more than cap */
 int64_t grdma_h2_pipe_slice_table(grdma_h2_pipe* p, grdma_slice* out, uint64_t cap);
+
+/* ---- HTTP/2 on several links of ONE job (the group pipe) ----
+ * grdma_h2_pipe serves one link, and a job carries one set of kernels in front of and behind its rounds: a second
+ * grdma_h2_pipe on another link of the same job replaces the first one's.  The group pipe is the pipe of n links of a
+ * multi-link job (up to GRDMA_H2_BATCH_MAX): a step rewrites the slice tables of the listed links from their message
+ * tables (k_h2_frame_links, ONE kernel for all of them), the job carries all its links, and the listed links' delivered
+ * slices are parsed (k_h2_deframe_links, ONE kernel) -- by default both inside the job's graph, one launch per step
+ * however many links; with GRDMA_H2_PIPE_FUSED=0 enqueued around the launch, with per-stage timing.  Links that are
+ * not listed are carried as before, their tables untouched.  Both directions of a bidirectional pair are two specs
+ * with two parsers.  The job has run once; delivered_slices is what that run delivered on the link.  A step parses
+ * what THAT step delivered: the deframing kernel reads the count the job's drain leaves on the device (at small rings
+ * a step starts at another ring phase than the recorded run and may deliver a slice more or less), and
+ * grdma_h2_group_pipe_sync's "slices parsed" word is that count.  (grdma_h2_pipe parses the recorded count.)
+ * Create returns NULL (grdma_last_error says why) for: n == 0, a link index out of range or listed twice, a parser
+ * listed twice, nmsgs 0 or above 4096, max_frame 0 or >= 2^24, a job that already carries such kernels (another pipe).
+ * Not here (yet): assemblers and replies on a group pipe, the chunked deframer inside the batch (every transport is
+ * parsed sequentially), flow control and HPACK (as for grdma_h2_pipe). */
+typedef struct grdma_h2_link_spec {
+  uint32_t link;                 /* index into the job's links; distinct */
+  const grdma_h2_msg* msgs;
+  uint64_t nmsgs;                /* 1 .. 4096 */
+  grdma_h2_parser* parser;       /* distinct */
+  uint64_t delivered_slices;     /* of this link in the recorded run */
+  uint64_t events_cap;
+} grdma_h2_link_spec;
+typedef struct grdma_h2_group_pipe grdma_h2_group_pipe;
+grdma_h2_group_pipe* grdma_h2_group_pipe_create(grdma_stream_job* job, const grdma_h2_link_spec* specs, uint32_t n,
+                                                uint32_t max_frame);
+int grdma_h2_group_pipe_enqueue(grdma_h2_group_pipe* p);
+/* waits for the last step; out: 14 words per spec, the words of grdma_h2_pipe_sync (the two timing words are the
+ * batch's, repeated); -GRDMA_ERR_INVALID when out_words < 14 n */
+int grdma_h2_group_pipe_sync(grdma_h2_group_pipe* p, uint64_t* out, uint64_t out_words);
+/* the events of spec i in the last step: their number, or -GRDMA_ERR_CAPACITY if more than cap */
+int64_t grdma_h2_group_pipe_events(grdma_h2_group_pipe* p, uint32_t i, grdma_h2_event* out, uint64_t cap);
+/* the slice table the job sends from on spec i's link, as grdma_h2_pipe_slice_table */
+int64_t grdma_h2_group_pipe_slice_table(grdma_h2_group_pipe* p, uint32_t i, grdma_slice* out, uint64_t cap);
+void grdma_h2_group_pipe_destroy(grdma_h2_group_pipe* p);   /* removes the kernels from the job's graph */
 
 /* ---- GRPCProfiler: include/grpcpp/stats_time.h:11-44,111-122, src/core/lib/debug/stats_time.cc ----
  * The reference's scope profiler with its op names in its order: nanoseconds per op per thread slot,
