@@ -427,6 +427,18 @@ struct h2_batch_buf {
   uint64_t cap = 0;
 };
 h2_batch_buf g_batch;
+bool h2_batch_reserve(uint64_t total, hipStream_t st) {
+  if (total <= g_batch.cap) return true;
+  if (hipStreamSynchronize(st) != hipSuccess) return false;  // (the previous call's block goes)
+  hipFree(g_batch.d);
+  g_batch.d = nullptr;
+  g_batch.cap = 0;
+  uint64_t want = 1 << 16;
+  while (want < total) want *= 2;
+  if (hipMalloc((void**)&g_batch.d, want) != hipSuccess) return false;
+  g_batch.cap = want;
+  return true;
+}
 }  // namespace
 
 int grdma_h2_deframe_batch(grdma_h2_deframe_item* items, uint32_t n_items) {
@@ -452,16 +464,7 @@ int grdma_h2_deframe_batch(grdma_h2_deframe_item* items, uint32_t n_items) {
   const uint64_t o_res = o_sl + sizeof(grdma_slice_out) * n_sl;
   const uint64_t o_ev = up16(o_res + sizeof(grdma_h2_deframe_result) * n_items);
   const uint64_t total = o_ev + sizeof(grdma_h2_event) * n_ev + 16;
-  if (total > g_batch.cap) {
-    if (hipStreamSynchronize(st) != hipSuccess) return -GRDMA_ERR_HIP;  // (the previous call's block goes)
-    hipFree(g_batch.d);
-    g_batch.d = nullptr;
-    g_batch.cap = 0;
-    uint64_t want = 1 << 16;
-    while (want < total) want *= 2;
-    if (hipMalloc((void**)&g_batch.d, want) != hipSuccess) return -GRDMA_ERR_HIP;
-    g_batch.cap = want;
-  }
+  if (!h2_batch_reserve(total, st)) return -GRDMA_ERR_HIP;
   uint8_t* const d = g_batch.d;
   std::vector<uint8_t> up(o_ev, 0), down(total - o_res);  // (the result blocks go up zeroed: a call never reports another's)
   auto* tab = reinterpret_cast<grdma_h2_link_deframe*>(up.data());
@@ -1302,7 +1305,14 @@ struct grdma_h2_group_pipe {
   hipEvent_t framed = nullptr, job_done = nullptr, deframed = nullptr;
   hipEvent_t t_f0 = nullptr, t_f1 = nullptr, t_d0 = nullptr, t_d1 = nullptr;
   bool launched = false, fused = false, timed = false;
+  grdma_job_hook pre, post;           // the framing and the deframing kernel in the job's graph (fused)
+  std::vector<grdma_h2_asm*> asms;    // per spec, NULL = none (grdma_h2_group_pipe_attach_assemblers)
+  h2a_link* d_atab = nullptr;         // the links with an assembler, in spec order
+  h2a_call* d_calls = nullptr;        // their call blocks
+  uint32_t n_asm = 0;
 };
+static void h2_asm_links_enqueue(const h2a_link* d_tab, uint32_t n, hipStream_t st);
+static void h2_group_detach(grdma_h2_group_pipe* p);
 
 static grdma_h2_group_pipe* h2_group_refuse(grdma_h2_group_pipe* p, const char* why) {
   grdma_h2_group_pipe_destroy(p);
@@ -1429,6 +1439,8 @@ grdma_h2_group_pipe* grdma_h2_group_pipe_create(grdma_stream_job* job, const grd
       grdma_h2_group_pipe_destroy(p);
       return nullptr;
     }
+    p->pre = pre;
+    p->post = post;
     p->fused = true;
   }
   return p;
@@ -1447,6 +1459,9 @@ void grdma_h2_group_pipe_destroy(grdma_h2_group_pipe* p) {
     hipFree(l.d_ev);
   }
   if (p->fused && p->job) grdma_job_set_hooks(p->job, nullptr, 0, nullptr, 0);
+  h2_group_detach(p);
+  hipFree(p->d_atab);
+  hipFree(p->d_calls);
   hipFree(p->d_ftab);
   hipFree(p->d_dtab);
   hipFree(p->d_fres);
@@ -1475,7 +1490,7 @@ int grdma_h2_group_pipe_enqueue(grdma_h2_group_pipe* p) {
     }
     p->launched = true;
   };
-  if (p->fused) {  // one graph launch: k_h2_frame_links -> the job's rounds -> k_h2_deframe_links
+  if (p->fused) {  // one graph launch: k_h2_frame_links -> the job's rounds -> k_h2_deframe_links [-> the six k_h2_asm_*_links]
     if (!wait_parsers()) return -GRDMA_ERR_HIP;
     const int rc = grdma_stream_job_launch(p->job);
     if (rc < 0) return rc;
@@ -1502,6 +1517,7 @@ int grdma_h2_group_pipe_enqueue(grdma_h2_group_pipe* p) {
   hipEventRecord(p->t_d0, p->job_stream);
   hipLaunchKernelGGL(k_h2_deframe_links, dim3(n), dim3(H2_DEFRAME_THREADS), 0, p->job_stream,
                      (const grdma_h2_link_deframe*)p->d_dtab);
+  if (p->n_asm) h2_asm_links_enqueue(p->d_atab, p->n_asm, p->job_stream);
   hipEventRecord(p->t_d1, p->job_stream);
   if (hipEventRecord(p->deframed, p->job_stream) != hipSuccess) return -GRDMA_ERR_HIP;
   done();
@@ -1569,5 +1585,284 @@ int64_t grdma_h2_group_pipe_slice_table(grdma_h2_group_pipe* p, uint32_t i, grdm
   return (int64_t)l.count;
 }
 
-}  // extern "C"
+// ---- the message assembler on many links (k_h2_asm_*_links, csrc/grdma_h2_asm.h) -----------------------------------
+// Six launches for any number of links: the plan's one-workgroup stages of the links run side by side.
+static_assert(H2A_LINKS_MAX == GRDMA_H2_BATCH_MAX, "the assembler's link table is the batch's");
 
+static void h2_asm_links_enqueue(const h2a_link* d_tab, uint32_t n, hipStream_t st) {
+  hipLaunchKernelGGL(k_h2_asm_tiles_links, dim3(n * H2A_LINK_GRID), dim3(H2A_THREADS), 0, st, d_tab, n);
+  hipLaunchKernelGGL(k_h2_asm_carry_links, dim3(n), dim3(H2A_ONE_THREADS), 0, st, d_tab);
+  hipLaunchKernelGGL(k_h2_asm_begin_links, dim3(n * H2A_LINK_GRID), dim3(H2A_THREADS), 0, st, d_tab, n);
+  hipLaunchKernelGGL(k_h2_asm_bytes_links, dim3(n * H2A_LINK_GRID), dim3(H2A_THREADS), 0, st, d_tab, n);
+  hipLaunchKernelGGL(k_h2_asm_finish_links, dim3(n), dim3(H2A_ONE_THREADS), 0, st, d_tab);
+  hipLaunchKernelGGL(k_h2_asm_copy_links, dim3(H2A_GRID), dim3(H2A_THREADS), 0, st, d_tab, n);
+}
+
+// the same six kernels as post hooks of a fused group pipe's graph, behind k_h2_deframe_links
+static uint32_t h2_asm_links_hooks(const h2a_link* d_tab, uint32_t n, grdma_job_hook* out) {
+  const void* fns[6] = {(const void*)k_h2_asm_tiles_links, (const void*)k_h2_asm_carry_links, (const void*)k_h2_asm_begin_links,
+                        (const void*)k_h2_asm_bytes_links, (const void*)k_h2_asm_finish_links, (const void*)k_h2_asm_copy_links};
+  const uint32_t grids[6] = {n * H2A_LINK_GRID, n, n * H2A_LINK_GRID, n * H2A_LINK_GRID, n, H2A_GRID};
+  const uint32_t threads[6] = {H2A_THREADS, H2A_ONE_THREADS, H2A_THREADS, H2A_THREADS, H2A_ONE_THREADS, H2A_THREADS};
+  for (int k = 0; k < 6; k++) {
+    memset(&out[k], 0, sizeof(out[k]));
+    out[k].fn = fns[k];
+    out[k].grid = grids[k];
+    out[k].threads = threads[k];
+    out[k].args[0] = (uint64_t)(uintptr_t)d_tab;
+    out[k].args[1] = n;
+  }
+  return 6;
+}
+
+namespace {
+// timing events of the batched assembly (plan | copy) and the pinned table of grdma_h2_asm_release_batch with the event
+// of its last upload (the table is reused: the next call waits for that upload)
+struct h2_links_ctx {
+  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, rel_up = nullptr;
+  h2a_link_release* h_rel = nullptr;
+  h2a_link_release* d_rel = nullptr;
+  bool rel_pending = false;
+};
+h2_links_ctx* h2_links() {
+  static h2_links_ctx c;
+  static const bool ok = hipEventCreate(&c.e0) == hipSuccess && hipEventCreate(&c.e1) == hipSuccess &&
+                         hipEventCreate(&c.e2) == hipSuccess &&
+                         hipEventCreateWithFlags(&c.rel_up, hipEventDisableTiming) == hipSuccess &&
+                         hipHostMalloc((void**)&c.h_rel, sizeof(h2a_link_release) * GRDMA_H2_BATCH_MAX) == hipSuccess &&
+                         hipMalloc((void**)&c.d_rel, sizeof(h2a_link_release) * GRDMA_H2_BATCH_MAX) == hipSuccess;
+  return ok ? &c : nullptr;
+}
+}  // namespace
+
+int grdma_h2_deframe_messages_batch(grdma_h2_messages_item* items, uint32_t n_items) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!items || n_items == 0 || n_items > GRDMA_H2_BATCH_MAX)
+    return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 messages batch: 1 .. GRDMA_H2_BATCH_MAX items");
+  uint64_t n_sl = 0, n_ev = 0;
+  bool want_events = false;
+  for (uint32_t i = 0; i < n_items; i++) {
+    const grdma_h2_messages_item& it = items[i];
+    if (!it.parser || !it.d_arena || (!it.slices && it.n) || it.cap == 0 || (!it.msgs_out && it.msgs_cap))
+      return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 messages batch: an item without parser, arena, slices, event capacity or descriptor array");
+    if (!it.assembler) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 messages batch: an item without assembler");
+    if (it.assembler->parser != it.parser) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 messages batch: an assembler of another parser");
+    if (it.assembler->attached || it.parser->asm_attached)
+      return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 messages batch: an assembler attached to a pipe");
+    for (uint32_t k = 0; k < i; k++) {
+      if (items[k].parser == it.parser) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 messages batch: the same parser twice");
+      if (items[k].assembler == it.assembler) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 messages batch: the same assembler twice");
+    }
+    n_sl += it.n;
+    n_ev += it.cap;
+    want_events = want_events || it.events_out;
+  }
+  h2_host_ctx* hc = h2_ctx();
+  h2_links_ctx* lc = h2_links();
+  if (!hc || !lc) return -GRDMA_ERR_HIP;
+  hipStream_t st = hc->stream;
+  for (uint32_t i = 0; i < n_items; i++)
+    if (!h2_asm_prepare(items[i].assembler, items[i].cap)) return -GRDMA_ERR_HIP;
+  // layout (every part 16-byte aligned): deframe table, assembler table, call blocks, slice lists, results, event segments
+  auto up16 = [](uint64_t v) { return (v + 15) & ~15ull; };
+  const uint64_t o_atab = up16(sizeof(grdma_h2_link_deframe) * n_items);
+  const uint64_t o_call = o_atab + up16(sizeof(h2a_link) * n_items);
+  const uint64_t o_sl = o_call + up16(sizeof(h2a_call) * n_items);
+  const uint64_t o_res = o_sl + sizeof(grdma_slice_out) * n_sl;
+  const uint64_t o_ev = up16(o_res + sizeof(grdma_h2_deframe_result) * n_items);
+  const uint64_t total = o_ev + sizeof(grdma_h2_event) * n_ev + 16;
+  if (!h2_batch_reserve(total, st)) return -GRDMA_ERR_HIP;
+  uint8_t* const d = g_batch.d;
+  // (the result blocks go up zeroed; the events come down only when an item asks for them)
+  std::vector<uint8_t> up(o_ev, 0), down((want_events ? total : o_ev) - o_res);
+  auto* dtab = reinterpret_cast<grdma_h2_link_deframe*>(up.data());
+  auto* atab = reinterpret_cast<h2a_link*>(up.data() + o_atab);
+  auto* calls = reinterpret_cast<h2a_call*>(up.data() + o_call);
+  auto* sl = reinterpret_cast<grdma_slice_out*>(up.data() + o_sl);
+  static_assert(sizeof(grdma_read_slice) == sizeof(grdma_slice_out), "layout");
+  uint64_t a_sl = 0, a_ev = 0;
+  for (uint32_t i = 0; i < n_items; i++) {
+    const grdma_h2_messages_item& it = items[i];
+    if (it.n) memcpy(sl + a_sl, it.slices, sizeof(grdma_slice_out) * it.n);
+    grdma_h2_link_deframe& q = dtab[i];
+    q.n_step = nullptr;  // (the caller's list: its length is the count)
+    q.res = reinterpret_cast<grdma_h2_deframe_result*>(d + o_res) + i;
+    q.gp = it.parser->d;
+    q.arena = static_cast<const uint8_t*>(it.d_arena);
+    q.slices = reinterpret_cast<const grdma_slice_out*>(d + o_sl) + a_sl;
+    q.nslices = it.n;
+    q.ev = reinterpret_cast<grdma_h2_event*>(d + o_ev) + a_ev;
+    q.ev_cap = it.cap;
+    calls[i] = h2a_call{q.ev, q.res, q.slices, q.arena, it.cap, 0};
+    atab[i].A = it.assembler->d;
+    atab[i].call = reinterpret_cast<const h2a_call*>(d + o_call) + i;
+    a_sl += it.n;
+    a_ev += it.cap;
+  }
+  // behind each parser's previous deframing (a pipe step on another stream)
+  for (uint32_t i = 0; i < n_items; i++) {
+    grdma_h2_parser* p = items[i].parser;
+    if (p->last_deframed && p->last_stream != st && hipStreamWaitEvent(st, p->last_deframed, 0) != hipSuccess) return -GRDMA_ERR_HIP;
+  }
+  if (hipMemcpyAsync(d, up.data(), o_ev, hipMemcpyHostToDevice, st) != hipSuccess) return -GRDMA_ERR_HIP;
+  hipEventRecord(hc->e0, st);
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_h2_deframe_links, dim3(n_items), dim3(H2_DEFRAME_THREADS), 0, st, (const grdma_h2_link_deframe*)d);
+  hipEventRecord(hc->e1, st);
+  // the assembly: the plan (five kernels), then the copy, timed apart
+  const h2a_link* d_atab = reinterpret_cast<const h2a_link*>(d + o_atab);
+  hipEventRecord(lc->e0, st);
+  hipLaunchKernelGGL(k_h2_asm_tiles_links, dim3(n_items * H2A_LINK_GRID), dim3(H2A_THREADS), 0, st, d_atab, n_items);
+  hipLaunchKernelGGL(k_h2_asm_carry_links, dim3(n_items), dim3(H2A_ONE_THREADS), 0, st, d_atab);
+  hipLaunchKernelGGL(k_h2_asm_begin_links, dim3(n_items * H2A_LINK_GRID), dim3(H2A_THREADS), 0, st, d_atab, n_items);
+  hipLaunchKernelGGL(k_h2_asm_bytes_links, dim3(n_items * H2A_LINK_GRID), dim3(H2A_THREADS), 0, st, d_atab, n_items);
+  hipLaunchKernelGGL(k_h2_asm_finish_links, dim3(n_items), dim3(H2A_ONE_THREADS), 0, st, d_atab);
+  hipEventRecord(lc->e1, st);
+  hipLaunchKernelGGL(k_h2_asm_copy_links, dim3(H2A_GRID), dim3(H2A_THREADS), 0, st, d_atab, n_items);
+  hipEventRecord(lc->e2, st);
+  if (hipGetLastError() != hipSuccess) {
+    hipStreamSynchronize(st);
+    return grdma_fail_msg(GRDMA_ERR_HIP, "h2 messages batch: a launch was rejected");
+  }
+  // one download of the results (and the events); then every assembler's block, and the descriptors from where each
+  // assembler keeps them (its own buffer: the kernels are the single call's, which reports from there)
+  std::vector<h2a_dev> hs(n_items);
+  if (hipMemcpyAsync(down.data(), d + o_res, down.size(), hipMemcpyDeviceToHost, st) != hipSuccess) return -GRDMA_ERR_HIP;
+  for (uint32_t i = 0; i < n_items; i++)
+    if (hipMemcpyAsync(&hs[i], items[i].assembler->d, sizeof(h2a_dev), hipMemcpyDeviceToHost, st) != hipSuccess) return -GRDMA_ERR_HIP;
+  if (hipStreamSynchronize(st) != hipSuccess) return -GRDMA_ERR_HIP;
+  float ms = 0, plan_ms = 0, copy_ms = 0;
+  if (hipEventElapsedTime(&ms, hc->e0, hc->e1) == hipSuccess) g_h2_last_kernel_us = 1e3 * ms;
+  if (hipEventElapsedTime(&plan_ms, lc->e0, lc->e1) != hipSuccess) plan_ms = 0;
+  if (hipEventElapsedTime(&copy_ms, lc->e1, lc->e2) != hipSuccess) copy_ms = 0;
+  const auto* res = reinterpret_cast<const grdma_h2_deframe_result*>(down.data());
+  const auto* ev = reinterpret_cast<const grdma_h2_event*>(down.data() + (o_ev - o_res));
+  a_ev = 0;
+  bool more = false;
+  for (uint32_t i = 0; i < n_items; i++) {
+    grdma_h2_messages_item& it = items[i];
+    const h2a_dev& h = hs[i];
+    const uint64_t m = res[i].nevents < it.cap ? res[i].nevents : it.cap;
+    if (it.events_out && m) memcpy(it.events_out, ev + a_ev, sizeof(grdma_h2_event) * m);
+    it.h2_error = (int)res[i].error;
+    it.n_events = res[i].overflow ? -(int64_t)GRDMA_ERR_CAPACITY : (int64_t)m;
+    it.assembler->plan_ms = plan_ms;  // (the batch's, repeated)
+    it.assembler->copy_ms = copy_ms;
+    if (res[i].overflow || h.skip || h.ndesc > it.msgs_cap || h.ndesc > h.desc_cap) {
+      it.n_msgs = -(int64_t)GRDMA_ERR_CAPACITY;
+    } else {
+      it.n_msgs = (int64_t)h.ndesc;
+      if (h.ndesc) {
+        if (hipMemcpyAsync(it.msgs_out, h.desc, sizeof(grdma_h2_rx_msg) * h.ndesc, hipMemcpyDeviceToHost, st) != hipSuccess)
+          return -GRDMA_ERR_HIP;
+        more = true;
+      }
+    }
+    a_ev += it.cap;
+  }
+  if (more && hipStreamSynchronize(st) != hipSuccess) return -GRDMA_ERR_HIP;
+  return 0;
+}
+
+int grdma_h2_asm_release_batch(grdma_h2_asm* const* asms, const uint64_t* counts, uint32_t n) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!asms || !counts || n == 0 || n > GRDMA_H2_BATCH_MAX)
+    return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 release batch: 1 .. GRDMA_H2_BATCH_MAX assemblers");
+  for (uint32_t i = 0; i < n; i++) {
+    if (!asms[i]) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 release batch: a null assembler");
+    if (asms[i]->attached) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 release batch: an assembler attached to a pipe");
+    for (uint32_t k = 0; k < i; k++)
+      if (asms[k] == asms[i]) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 release batch: the same assembler twice");
+  }
+  h2_host_ctx* hc = h2_ctx();
+  h2_links_ctx* lc = h2_links();
+  if (!hc || !lc) return -GRDMA_ERR_HIP;
+  hipStream_t st = hc->stream;
+  // behind the last standalone call (same stream) and the last pipe step of every parser
+  for (uint32_t i = 0; i < n; i++) {
+    grdma_h2_parser* p = asms[i]->parser;
+    if (p->last_deframed && hipStreamWaitEvent(st, p->last_deframed, 0) != hipSuccess) return -GRDMA_ERR_HIP;
+  }
+  if (lc->rel_pending && hipEventSynchronize(lc->rel_up) != hipSuccess) return -GRDMA_ERR_HIP;
+  for (uint32_t i = 0; i < n; i++) lc->h_rel[i] = h2a_link_release{asms[i]->d, counts[i]};
+  if (hipMemcpyAsync(lc->d_rel, lc->h_rel, sizeof(h2a_link_release) * n, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipEventRecord(lc->rel_up, st) != hipSuccess)
+    return -GRDMA_ERR_HIP;
+  lc->rel_pending = true;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_h2_asm_release_links, dim3(n), dim3(64), 0, st, (const h2a_link_release*)lc->d_rel);
+  return hipGetLastError() == hipSuccess ? 0 : -GRDMA_ERR_HIP;
+}
+
+static void h2_group_detach(grdma_h2_group_pipe* p) {
+  for (grdma_h2_asm*& a : p->asms)
+    if (a) {
+      a->parser->asm_attached--;
+      a->attached--;
+      a = nullptr;
+    }
+  p->n_asm = 0;
+}
+
+int grdma_h2_group_pipe_attach_assemblers(grdma_h2_group_pipe* p, grdma_h2_asm* const* asms, uint32_t n) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!p || !asms) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: a pipe and an assembler list");
+  if (n != p->links.size()) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: one assembler entry per link spec");
+  if (p->n_asm) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: assemblers are attached already");
+  uint32_t have = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    grdma_h2_asm* a = asms[i];
+    if (!a) continue;
+    if (a->parser != p->links[i].parser) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: an assembler of another parser than its link's");
+    if (a->attached || a->parser->asm_attached) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: an assembler attached already");
+    for (uint32_t k = 0; k < i; k++)
+      if (asms[k] == a) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: the same assembler twice");
+    have++;
+  }
+  if (!have) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: no assembler in the list");
+  if (p->launched && h2_group_wait(p) != 0) return -GRDMA_ERR_HIP;
+  std::vector<h2a_call> calls;
+  std::vector<h2a_link> tab;
+  if ((!p->d_atab && hipMalloc((void**)&p->d_atab, sizeof(h2a_link) * n) != hipSuccess) ||
+      (!p->d_calls && hipMalloc((void**)&p->d_calls, sizeof(h2a_call) * n) != hipSuccess))
+    return -GRDMA_ERR_HIP;
+  for (uint32_t i = 0; i < n; i++) {
+    if (!asms[i]) continue;
+    const h2_group_link& l = p->links[i];
+    if (!h2_asm_prepare(asms[i], l.ev_cap ? l.ev_cap : 1)) return -GRDMA_ERR_HIP;
+    // (a step first releases everything reported before it, as a single pipe's does)
+    tab.push_back(h2a_link{asms[i]->d, p->d_calls + calls.size()});
+    calls.push_back(h2a_call{l.d_ev, p->d_dres + i, l.d_slices, l.dst, l.ev_cap, 1});
+  }
+  if (hipMemcpy(p->d_calls, calls.data(), sizeof(h2a_call) * have, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(p->d_atab, tab.data(), sizeof(h2a_link) * have, hipMemcpyHostToDevice) != hipSuccess)
+    return -GRDMA_ERR_HIP;
+  if (p->fused) {
+    grdma_job_hook post[7];
+    post[0] = p->post;
+    const uint32_t n_post = 1 + h2_asm_links_hooks(p->d_atab, have, post + 1);
+    if (grdma_job_set_hooks(p->job, &p->pre, 1, post, n_post) != 0) return -GRDMA_ERR_HIP;
+  }
+  p->asms.assign(asms, asms + n);
+  p->n_asm = have;
+  for (grdma_h2_asm* a : p->asms)
+    if (a) {
+      a->attached++;
+      a->parser->asm_attached++;
+    }
+  return 0;
+}
+
+int64_t grdma_h2_group_pipe_messages(grdma_h2_group_pipe* p, uint32_t i, grdma_h2_rx_msg* out, uint64_t cap) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!p || i >= p->asms.size() || !p->asms[i] || (!out && cap)) return -GRDMA_ERR_INVALID;
+  if (int rc = h2_group_wait(p)) return rc;
+  h2a_dev h;
+  if (hipMemcpy(&h, p->asms[i]->d, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -GRDMA_ERR_HIP;
+  if (h.skip || h.ndesc > cap || h.ndesc > h.desc_cap) return -GRDMA_ERR_CAPACITY;
+  if (h.ndesc && hipMemcpy(out, h.desc, sizeof(grdma_h2_rx_msg) * h.ndesc, hipMemcpyDeviceToHost) != hipSuccess)
+    return -GRDMA_ERR_HIP;
+  return (int64_t)h.ndesc;
+}
+
+}  // extern "C"

@@ -29,6 +29,11 @@ class H2DeframeItem(C.Structure):
                 ("events_out", C.POINTER(H2Event)), ("cap", u64), ("n_events", C.c_int64), ("h2_error", C.c_int)]
 
 
+class H2MessagesItem(C.Structure):
+    _fields_ = H2DeframeItem._fields_ + [("assembler", C.c_void_p), ("msgs_out", C.POINTER(H2RxMsg)), ("msgs_cap", u64),
+                                         ("n_msgs", C.c_int64)]
+
+
 class H2LinkSpec(C.Structure):
     _fields_ = [("link", C.c_uint32), ("msgs", C.POINTER(H2Msg)), ("nmsgs", u64), ("parser", C.c_void_p),
                 ("delivered_slices", u64), ("events_cap", u64)]
@@ -124,6 +129,14 @@ def _bind():
         lib.grdma_h2_group_pipe_slice_table.restype = C.c_int64
         lib.grdma_h2_group_pipe_slice_table.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Slice), u64]
         lib.grdma_h2_group_pipe_destroy.argtypes = [C.c_void_p]
+        lib.grdma_h2_deframe_messages_batch.restype = C.c_int
+        lib.grdma_h2_deframe_messages_batch.argtypes = [C.POINTER(H2MessagesItem), C.c_uint32]
+        lib.grdma_h2_asm_release_batch.restype = C.c_int
+        lib.grdma_h2_asm_release_batch.argtypes = [C.POINTER(C.c_void_p), C.POINTER(u64), C.c_uint32]
+        lib.grdma_h2_group_pipe_attach_assemblers.restype = C.c_int
+        lib.grdma_h2_group_pipe_attach_assemblers.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32]
+        lib.grdma_h2_group_pipe_messages.restype = C.c_int64
+        lib.grdma_h2_group_pipe_messages.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(H2RxMsg), u64]
         lib.grdma_job_hook_counts.restype = C.c_int   # (not in include/grdma_amd.h: the job's side of the pipes)
         lib.grdma_job_hook_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         _bound = True
@@ -263,6 +276,48 @@ def deframe_batch(items, caps=None):
     return out
 
 
+def deframe_messages_batch(items, want_events=False, ev_caps=None, msgs_caps=None):
+    """deframe + assemble for many transports in seven launches (grdma_h2_deframe_messages_batch).  items: [(Parser,
+    Assembler, arena device ptr, [(offset, len), ...]), ...] with distinct parsers and assemblers; ev_caps / msgs_caps:
+    per item (default: what Parser.deframe_messages takes).  -> per item (h2 error, [Msg...]) or, with want_events,
+    (h2 error, [Msg...], events); every item reports for itself: where its events or descriptors did not fit, the
+    list is the integer -GRDMA_ERR_CAPACITY (-5) instead."""
+    lib = _bind()
+    n = len(items)
+    arr = (H2MessagesItem * max(1, n))()
+    keep = []
+    for i, (parser, asm, arena, slices) in enumerate(items):
+        sl = (ReadSlice * max(1, len(slices)))()
+        for k, (o, l) in enumerate(slices):
+            sl[k].off, sl[k].len = o, l
+        cap = (ev_caps[i] if ev_caps is not None else None) or min(sum(l for _, l in slices) * 2 + 64, 1 << 20)
+        mcap = (msgs_caps[i] if msgs_caps is not None else None) or cap
+        ev = (H2Event * cap)() if want_events else None
+        out = (H2RxMsg * mcap)()
+        keep.append((sl, ev, out))
+        arr[i].parser, arr[i].d_arena, arr[i].slices, arr[i].n = parser.h, arena, sl, len(slices)
+        arr[i].events_out, arr[i].cap = ev, cap
+        arr[i].assembler, arr[i].msgs_out, arr[i].msgs_cap = (asm.h if asm is not None else None), out, mcap
+    check(lib.grdma_h2_deframe_messages_batch(arr, n))
+    res = []
+    for i in range(n):
+        m, k = int(arr[i].n_msgs), int(arr[i].n_events)
+        r = (int(arr[i].h2_error), _msgs(keep[i][2], m) if m >= 0 else m)
+        if want_events:
+            r += ([(e.kind, e.a, e.b, e.c, e.d, e.slice) for e in keep[i][1][:k]] if k >= 0 else k,)
+        res.append(r)
+    return res
+
+
+def release_batch(pairs):
+    """Assembler.release for many assemblers in one launch (grdma_h2_asm_release_batch): [(Assembler, n), ...]"""
+    lib = _bind()
+    n = len(pairs)
+    hs = (C.c_void_p * max(1, n))(*[a.h for a, _ in pairs])
+    cs = (u64 * max(1, n))(*[c for _, c in pairs])
+    check(lib.grdma_h2_asm_release_batch(hs, cs, n))
+
+
 class GroupPipe:
     """frame -> multi-link job -> deframe for several links of ONE job (grdma_h2_group_pipe): one framing kernel and
     one deframing kernel per step however many links.  specs: [(link, msgs, Parser, delivered_slices, events_cap), ...]
@@ -311,6 +366,22 @@ class GroupPipe:
     def hook_counts(self):
         """(kernels in front of, kernels behind) the job's rounds inside its graph"""
         return job_hook_counts(self.job)
+
+    def attach_assemblers(self, asms):
+        """one Assembler (of the spec's parser) or None per spec: every later step assembles the messages of those
+        links, six more kernels however many links (grdma_h2_group_pipe_attach_assemblers).  Close the pipe before
+        the assemblers."""
+        asms = list(asms)
+        hs = (C.c_void_p * max(1, len(asms)))(*[a.h if a is not None else None for a in asms])
+        check(self.lib.grdma_h2_group_pipe_attach_assemblers(self.h, hs, len(asms)))
+        self.assemblers = asms  # (kept alive)
+
+    def messages(self, i, cap=None):
+        """the messages of spec i in the last synced step"""
+        cap = cap or max(1, self.events_caps[i])
+        out = (H2RxMsg * cap)()
+        m = check(self.lib.grdma_h2_group_pipe_messages(self.h, i, out, cap))
+        return _msgs(out, m)
 
     def close(self):
         if self.h:

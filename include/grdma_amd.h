@@ -736,6 +736,40 @@ int grdma_h2_pipe_attach_assembler(grdma_h2_pipe* p, grdma_h2_asm* a);
 /* the descriptors of the last synced step: their number, or -GRDMA_ERR_CAPACITY if more than cap */
 int64_t grdma_h2_pipe_messages(grdma_h2_pipe* p, grdma_h2_rx_msg* out, uint64_t cap);
 
+/* grdma_h2_deframe_messages for MANY transports at once (k_h2_deframe_links, then the six k_h2_asm_*_links kernels over
+ * a table of the items' assemblers): seven launches for any n_items, the one-workgroup stages of the plan side by side.
+ * An item is a grdma_h2_deframe_item plus its assembler and descriptor array; cap sizes the device's event list
+ * (>= 1) and events_out may be NULL, as in the single call.  Per item the report is what grdma_h2_deframe_messages
+ * reports for that transport alone: h2_error, n_events (-GRDMA_ERR_CAPACITY on an event overflow), the events if asked
+ * for, n_msgs (-GRDMA_ERR_CAPACITY on an event overflow, more streams than a call plans, more descriptors than
+ * msgs_cap) and the descriptors.  Nothing is shared between the items: an overflow, NO_SPACE or a connection error of
+ * one leaves the others' descriptors and bytes what they would be alone.  One upload and one download of results and
+ * events; the descriptors come from each assembler's own buffer.  Ordered behind each parser's last pipe step; one call
+ * at a time per process, as grdma_h2_deframe_batch.
+ * Returns 0, or -GRDMA_ERR_INVALID (nothing ran, grdma_last_error says why): n_items outside 1 .. GRDMA_H2_BATCH_MAX,
+ * an item without parser, arena, assembler or event capacity, slices NULL with n > 0, msgs_out NULL with msgs_cap > 0,
+ * an assembler whose parser is not the item's, a parser or an assembler listed twice, an assembler attached to a pipe
+ * or group pipe. */
+typedef struct grdma_h2_messages_item {
+  grdma_h2_parser* parser;          /* distinct per item */
+  const void* d_arena;              /* the arena this transport's slices point into */
+  const grdma_read_slice* slices;   /* host array */
+  uint64_t n;
+  grdma_h2_event* events_out;       /* host, may be NULL: no event copy */
+  uint64_t cap;                     /* events the device's list holds, >= 1 */
+  int64_t n_events;                 /* out: events, or -GRDMA_ERR_CAPACITY for this item */
+  int h2_error;                     /* out: this transport's connection error */
+  grdma_h2_asm* assembler;          /* of `parser`; distinct per item */
+  grdma_h2_rx_msg* msgs_out;        /* host */
+  uint64_t msgs_cap;
+  int64_t n_msgs;                   /* out: descriptors, or -GRDMA_ERR_CAPACITY for this item */
+} grdma_h2_messages_item;
+int grdma_h2_deframe_messages_batch(grdma_h2_messages_item* items, uint32_t n_items);
+/* grdma_h2_asm_release for n assemblers in ONE launch (k_h2_asm_release_links): entry i releases the oldest counts[i]
+ * reported messages of asms[i].  -GRDMA_ERR_INVALID (nothing released): n outside 1 .. GRDMA_H2_BATCH_MAX, a NULL
+ * entry, an assembler listed twice or attached to a pipe or group pipe. */
+int grdma_h2_asm_release_batch(grdma_h2_asm* const* asms, const uint64_t* counts, uint32_t n);
+
 /* ---- Replies framed on the device from received-message descriptors (csrc/grdma_h2_reply.h) ----
  * What a data plane does with a received message without looking inside it: send it back (echo) or on to another
  * stream (a proxy).  The descriptors of the source assembler's LAST call are framed where they lie: the wire is what
@@ -790,8 +824,8 @@ int64_t grdma_h2_pipe_slice_table(grdma_h2_pipe* p, grdma_slice* out, uint64_t c
  * grdma_h2_group_pipe_sync's "slices parsed" word is that count.  (grdma_h2_pipe parses the recorded count.)
  * Create returns NULL (grdma_last_error says why) for: n == 0, a link index out of range or listed twice, a parser
  * listed twice, nmsgs 0 or above 4096, max_frame 0 or >= 2^24, a job that already carries such kernels (another pipe).
- * Not here (yet): assemblers and replies on a group pipe, the chunked deframer inside the batch (every transport is
- * parsed sequentially), flow control and HPACK (as for grdma_h2_pipe). */
+ * Not here (yet): replies on a group pipe, the chunked deframer inside the batch (every transport is parsed
+ * sequentially), flow control and HPACK (as for grdma_h2_pipe). */
 typedef struct grdma_h2_link_spec {
   uint32_t link;                 /* index into the job's links; distinct */
   const grdma_h2_msg* msgs;
@@ -811,7 +845,19 @@ int grdma_h2_group_pipe_sync(grdma_h2_group_pipe* p, uint64_t* out, uint64_t out
 int64_t grdma_h2_group_pipe_events(grdma_h2_group_pipe* p, uint32_t i, grdma_h2_event* out, uint64_t cap);
 /* the slice table the job sends from on spec i's link, as grdma_h2_pipe_slice_table */
 int64_t grdma_h2_group_pipe_slice_table(grdma_h2_group_pipe* p, uint32_t i, grdma_slice* out, uint64_t cap);
-void grdma_h2_group_pipe_destroy(grdma_h2_group_pipe* p);   /* removes the kernels from the job's graph */
+/* grdma_h2_pipe_attach_assembler for the group pipe: every later step assembles the messages of the listed links
+ * behind k_h2_deframe_links -- six more kernels (k_h2_asm_*_links) however many links, inside the job's graph when the
+ * pipe is fused (1 kernel in front, 1 + 6 behind), else enqueued behind the deframing on the job's stream.  n is the
+ * pipe's spec count; asms[i] belongs to spec i's parser, NULL = that link stays without.  A step first releases
+ * everything its assemblers reported before it.  While attached, grdma_h2_asm_release, grdma_h2_asm_release_batch and
+ * both batch calls refuse the assembler and grdma_h2_asm_destroy does nothing: destroy the pipe first.
+ * -GRDMA_ERR_INVALID (pipe and job as before): n other than the spec count, all entries NULL, an assembler of another
+ * parser than its spec's, one attached anywhere already, one listed twice, a second attach. */
+int grdma_h2_group_pipe_attach_assemblers(grdma_h2_group_pipe* p, grdma_h2_asm* const* asms, uint32_t n);
+/* the descriptors of spec i in the last synced step, as grdma_h2_pipe_messages: their number, -GRDMA_ERR_CAPACITY if
+ * more than cap, -GRDMA_ERR_INVALID for a spec without assembler */
+int64_t grdma_h2_group_pipe_messages(grdma_h2_group_pipe* p, uint32_t i, grdma_h2_rx_msg* out, uint64_t cap);
+void grdma_h2_group_pipe_destroy(grdma_h2_group_pipe* p);   /* removes the kernels from the job's graph, detaches the assemblers */
 
 /* ---- GRPCProfiler: include/grpcpp/stats_time.h:11-44,111-122, src/core/lib/debug/stats_time.cc ----
  * The reference's scope profiler with its op names in its order: nanoseconds per op per thread slot,
