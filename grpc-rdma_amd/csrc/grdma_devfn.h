@@ -168,13 +168,19 @@ __device__ __forceinline__ void wave_copy_tile(uint8_t* dst, const uint8_t* src,
 typedef const __attribute__((address_space(1))) u32x4* g_u32x4_c;
 typedef __attribute__((address_space(1))) u32x4* g_u32x4;
 
+// What wave_copy_tile_g moves with all its loads in flight: four 16-byte units per lane.
+#define GRDMA_COPY_G_BYTES (4ull * 64ull * 16ull)
+
 // wave_copy_tile for tiles whose source and destination are known to be global memory
-// (HBM or mapped host memory), n <= GRDMA_TILE_BYTES.  All loads of the tile -- at most
+// (HBM or mapped host memory), n <= GRDMA_COPY_G_BYTES.  All loads of the tile -- at most
 // four 16-byte units per lane -- are issued before the first store: a load -> wait ->
-// store -> load chain costs one memory round trip per unit.
+// store -> load chain costs one memory round trip per unit.  A longer n is moved by
+// wave_copy_tile, unit by unit (the four registers hold 256 units and no more: through the
+// HTTP/2 message assembler's first version the guard stood at GRDMA_TILE_BYTES, and the units
+// from 256 on of such a tile were neither loaded nor stored -- tests/test_zz_gpu_movers.py).
 __device__ __forceinline__ void wave_copy_tile_g(uint8_t* dst, const uint8_t* src, uint64_t n,
                                                  int lane) {
-  if (n > GRDMA_TILE_BYTES) {  // (not produced by the planners: tiles are cut at GRDMA_TILE_BYTES)
+  if (n > GRDMA_COPY_G_BYTES) {  // (not produced by the callers: they cut their tiles at GRDMA_COPY_G_BYTES)
     wave_copy_tile(dst, src, n, lane);
     return;
   }
@@ -552,10 +558,18 @@ __device__ __forceinline__ grdma_seg plan_seg(const grdma_plan* plan, uint32_t i
   return grdma_seg{xwg_ld64<true>(w), xwg_ld64<true>(w + 1), xwg_ld64<true>(w + 2), xwg_ld64<true>(w + 3)};
 }
 
+// the widest sampling stride (as a shift) a plan of GRDMA_MAX_SEGS segments needs with lds_n slots
+constexpr uint32_t plan_max_shift(uint32_t lds_n) {
+  uint32_t s = 0;
+  while (((uint32_t)GRDMA_MAX_SEGS >> s) + 1 > lds_n) s++;
+  return s;
+}
+
 template <uint32_t LDS_N, bool CONTIG, uint32_t TILE, bool SC1 = false>
 __device__ __forceinline__ void run_plan_tiles(const grdma_plan* plan, uint32_t wave,
                                                uint32_t nwaves, int lane, const plan_hdr* hdr = nullptr) {
   __shared__ uint32_t s_prefix[LDS_N + 1];
+  static_assert(plan_max_shift(LDS_N) <= 7, "the window search probes a stride of at most two waves' width");
   // (hdr: the header as plan_wait_ready fetched it)
   const uint32_t nsegs = hdr ? hdr->nsegs : xwg_ld32<SC1>(&plan->nsegs);
   const uint32_t ntiles = hdr ? hdr->ntiles : xwg_ld32<SC1>(&plan->ntiles);
@@ -623,6 +637,18 @@ __device__ __forceinline__ void run_plan_tiles(const grdma_plan* plan, uint32_t 
       const int last = 63 - __builtin_clzll(le);  // lane 0 always qualifies (pk == p0 <= t)
       seg += (uint32_t)last;
       p0 = __shfl(pk, last, 64);
+      if (plan_max_shift(LDS_N) > 6 && shift > 6) {
+        // a stride of 128 entries (256 slots, GRDMA_MAX_SEGS segments): the wave probes its upper half as well
+        const uint32_t k2 = (lo << shift) + 64u + (uint32_t)lane;
+        const bool in2 = k2 < nsegs;
+        const uint32_t pk2 = in2 ? xwg_ld32<SC1>(&plan->tile_prefix[k2]) : 0xFFFFFFFFu;
+        const uint64_t le2 = __ballot(in2 && pk2 <= t);
+        if (le2) {
+          const int last2 = 63 - __builtin_clzll(le2);
+          seg = (lo << shift) + 64u + (uint32_t)last2;
+          p0 = __shfl(pk2, last2, 64);
+        }
+      }
     }
     pnext = shift ? xwg_ld32<SC1>(&plan->tile_prefix[seg + 1]) : s_prefix[seg + 1];
   }

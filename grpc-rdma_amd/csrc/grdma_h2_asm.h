@@ -38,6 +38,7 @@
 #endif
 #define H2A_GRANULE 256ull
 #define H2A_COPY_TILE 4096ull  // what wave_copy_tile_g moves with all its loads in flight (4 x 16 B per lane)
+static_assert(H2A_COPY_TILE == GRDMA_COPY_G_BYTES, "a copy tile of the assembler is what wave_copy_tile_g holds in registers");
 #define H2A_LDS_KEYS 4096u   // distinct streams with message events in one call, at most 3/4 of this
 #define H2A_NONE 0u
 #define H2A_OPEN 1u
