@@ -1100,12 +1100,14 @@ int64_t grdma_h2_pipe_messages(grdma_h2_pipe* p, grdma_h2_rx_msg* out, uint64_t 
 }
 
 // ---- replies framed from the descriptors (csrc/grdma_h2_reply.h) ---------------------------------------------
+struct grdma_h2_group_pipe;
 struct grdma_h2_reply {
   grdma_h2_asm* src = nullptr;
   h2r_dev* d = nullptr;
   h2r_dev h;                        // host copy of the configuration words
   grdma_h2_route* d_routes = nullptr;
   grdma_h2_pipe* pipe = nullptr;    // the reply pipe that frames through it (at most one: the scratch is one call's)
+  grdma_h2_group_pipe* gpipe = nullptr;  // ... or the group reply pipe (grdma_h2_group_pipe_create_reply)
   hipEvent_t e0 = nullptr, e1 = nullptr;
 };
 
@@ -1146,7 +1148,7 @@ static bool h2_reply_set_target(grdma_h2_reply* r, grdma_sge* out, uint64_t cap,
 }
 
 static bool h2_reply_bind_pipe(grdma_h2_reply* r, grdma_h2_pipe* p, uint64_t recorded_wire_bytes) {
-  if (r->pipe || !r->src->attached) return false;  // (the source of a reply pipe assembles in forward pipes)
+  if (r->pipe || r->gpipe || !r->src->attached) return false;  // (the source of a reply pipe assembles in forward pipes)
   if (!h2_reply_set_target(r, p->d_sges, p->count, p->d_hdr, p->hdr_cap, 1, p->count, recorded_wire_bytes, nullptr)) return false;
   r->pipe = p;
   r->src->reply_pipes++;
@@ -1223,7 +1225,7 @@ grdma_h2_reply* grdma_h2_reply_create(grdma_h2_asm* source, const grdma_h2_route
 }
 
 void grdma_h2_reply_destroy(grdma_h2_reply* r) {
-  if (!r || r->pipe) return;  // (the pipe's graph still runs the kernels on it: destroy the pipe first)
+  if (!r || r->pipe || r->gpipe) return;  // (the pipe's graph still runs the kernels on it: destroy the pipe first)
   h2_host_ctx* hc = h2_ctx();
   if (hc) hipStreamSynchronize(hc->stream);  // (standalone calls)
   r->src->replies--;
@@ -1240,7 +1242,7 @@ int64_t grdma_h2_reply_frame(grdma_h2_reply* r, grdma_slice* d_slices_out, uint6
                              uint64_t hdr_cap, uint64_t out[8]) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
   if (!r || !d_slices_out || !slices_cap || !d_hdr_arena || !hdr_cap || !out || ((uintptr_t)d_slices_out & 15) ||
-      ((uintptr_t)d_hdr_arena & 15) || r->pipe || r->src->attached)
+      ((uintptr_t)d_hdr_arena & 15) || r->pipe || r->gpipe || r->src->attached)
     return -GRDMA_ERR_INVALID;
   h2_host_ctx* hc = h2_ctx();
   if (!hc) return -GRDMA_ERR_HIP;
@@ -1262,6 +1264,88 @@ int64_t grdma_h2_reply_frame(grdma_h2_reply* r, grdma_slice* d_slices_out, uint6
   out[7] = hipEventElapsedTime(&ms, r->e0, r->e1) == hipSuccess ? (uint64_t)(ms * 1e3f) : 0;
   if (res[H2R_OVERFLOW]) return -GRDMA_ERR_CAPACITY;
   return (int64_t)res[H2R_SLICES];
+}
+
+// ---- the replies of many transports in two launches (k_h2_reply_plan_links, k_h2_reply_emit_links) ----------------
+// The batch block of the process holds the call: [table | one h2r_dev per item] goes up in one copy -- the item's
+// framer with the item's targets and a zeroed result block; scratch, routes and source stay the reply's own -- and the
+// h2r_dev blocks come down in one copy.  One call at a time, as the other batch calls.
+static_assert(H2R_LINKS_MAX == GRDMA_H2_BATCH_MAX, "the reply's link table is the batch's");
+
+int grdma_h2_reply_frame_batch(grdma_h2_reply_item* items, uint32_t n_items) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!items || n_items == 0 || n_items > GRDMA_H2_BATCH_MAX)
+    return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: 1 .. GRDMA_H2_BATCH_MAX items");
+  for (uint32_t i = 0; i < n_items; i++) {
+    const grdma_h2_reply_item& it = items[i];
+    if (!it.reply) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: an item without reply");
+    if (!it.d_slices_out || !it.slices_cap || !it.d_hdr_arena || !it.hdr_cap || ((uintptr_t)it.d_slices_out & 15) ||
+        ((uintptr_t)it.d_hdr_arena & 15))
+      return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: a null, zero or misaligned slice table or header arena");
+    if (it.reply->pipe || it.reply->gpipe) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: a reply bound to a reply pipe");
+    if (it.reply->src->attached)
+      return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: a source assembler attached to a pipe or group pipe");
+    for (uint32_t k = 0; k < i; k++) {
+      if (items[k].reply == it.reply) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: the same reply twice");
+      // (each reply has scratch of its own, so two of one source could run side by side; the rule is one item per
+      // transport, as in the other batch calls)
+      if (items[k].reply->src == it.reply->src)
+        return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: two replies of one source assembler");
+    }
+  }
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  hipStream_t st = hc->stream;
+  auto up16 = [](uint64_t v) { return (v + 15) & ~15ull; };
+  const uint64_t o_dev = up16(sizeof(h2r_link) * n_items);
+  const uint64_t total = o_dev + sizeof(h2r_dev) * n_items;
+  if (!h2_batch_reserve(total, st)) return -GRDMA_ERR_HIP;
+  uint8_t* const d = g_batch.d;
+  std::vector<uint8_t> up(total, 0);
+  std::vector<h2r_dev> down(n_items);
+  auto* tab = reinterpret_cast<h2r_link*>(up.data());
+  auto* devs = reinterpret_cast<h2r_dev*>(up.data() + o_dev);
+  for (uint32_t i = 0; i < n_items; i++) {
+    const grdma_h2_reply_item& it = items[i];
+    h2r_dev h = it.reply->h;
+    h.out = reinterpret_cast<grdma_sge*>(it.d_slices_out);
+    h.cap = it.slices_cap;
+    h.hdr = static_cast<uint8_t*>(it.d_hdr_arena);
+    h.hdr_cap = it.hdr_cap;
+    h.check_shape = h.want_slices = h.want_wire = 0;
+    memset(h.res, 0, sizeof(h.res));
+    devs[i] = h;
+    tab[i].R = reinterpret_cast<h2r_dev*>(d + o_dev) + i;
+  }
+  // behind each source parser's last deframing (a pipe step on another stream; the standalone calls share this stream)
+  for (uint32_t i = 0; i < n_items; i++) {
+    const grdma_h2_parser* p = items[i].reply->src->parser;
+    if (p->last_deframed && p->last_stream != st && hipStreamWaitEvent(st, p->last_deframed, 0) != hipSuccess) return -GRDMA_ERR_HIP;
+  }
+  if (hipMemcpyAsync(d, up.data(), total, hipMemcpyHostToDevice, st) != hipSuccess) return -GRDMA_ERR_HIP;
+  hipEventRecord(hc->e0, st);
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_h2_reply_plan_links, dim3(n_items), dim3(PLAN_THREADS), 0, st, (const h2r_link*)d);
+  hipLaunchKernelGGL(k_h2_reply_emit_links, dim3(H2R_GRID), dim3(H2_EMIT_THREADS), 0, st, (const h2r_link*)d, n_items);
+  if (hipGetLastError() != hipSuccess) {
+    hipStreamSynchronize(st);
+    return grdma_fail_msg(GRDMA_ERR_HIP, "h2 reply batch: a launch was rejected");
+  }
+  hipEventRecord(hc->e1, st);
+  if (hipMemcpyAsync(down.data(), d + o_dev, sizeof(h2r_dev) * n_items, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return -GRDMA_ERR_HIP;
+  float ms = 0;
+  const uint64_t us = hipEventElapsedTime(&ms, hc->e0, hc->e1) == hipSuccess ? (uint64_t)(ms * 1e3f) : 0;
+  g_h2_last_kernel_us = 1e3 * ms;
+  for (uint32_t i = 0; i < n_items; i++) {
+    grdma_h2_reply_item& it = items[i];
+    const uint64_t* res = down[i].res;
+    for (int k = 0; k < 7; k++) it.out[k] = res[k];
+    it.out[7] = us;  // (the batch's, repeated)
+    it.n_slices = res[H2R_OVERFLOW] ? -(int64_t)GRDMA_ERR_CAPACITY : (int64_t)res[H2R_SLICES];
+  }
+  return 0;
 }
 
 int64_t grdma_h2_pipe_slice_table(grdma_h2_pipe* p, grdma_slice* out, uint64_t cap) {
@@ -1305,7 +1389,11 @@ struct grdma_h2_group_pipe {
   hipEvent_t framed = nullptr, job_done = nullptr, deframed = nullptr;
   hipEvent_t t_f0 = nullptr, t_f1 = nullptr, t_d0 = nullptr, t_d1 = nullptr;
   bool launched = false, fused = false, timed = false;
-  grdma_job_hook pre, post;           // the framing and the deframing kernel in the job's graph (fused)
+  grdma_job_hook pre[2], post;        // the framing kernel(s) and the deframing kernel in the job's graph (fused)
+  uint32_t n_pre = 0;
+  // a group reply pipe (grdma_h2_group_pipe_create_reply): the framing stage is k_h2_reply_plan_links + k_h2_reply_emit_links
+  std::vector<grdma_h2_reply*> replies;  // per spec
+  h2r_link* d_rtab = nullptr;
   std::vector<grdma_h2_asm*> asms;    // per spec, NULL = none (grdma_h2_group_pipe_attach_assemblers)
   h2a_link* d_atab = nullptr;         // the links with an assembler, in spec order
   h2a_call* d_calls = nullptr;        // their call blocks
@@ -1313,6 +1401,7 @@ struct grdma_h2_group_pipe {
 };
 static void h2_asm_links_enqueue(const h2a_link* d_tab, uint32_t n, hipStream_t st);
 static void h2_group_detach(grdma_h2_group_pipe* p);
+static void h2_group_unbind_replies(grdma_h2_group_pipe* p);
 
 static grdma_h2_group_pipe* h2_group_refuse(grdma_h2_group_pipe* p, const char* why) {
   grdma_h2_group_pipe_destroy(p);
@@ -1320,26 +1409,38 @@ static grdma_h2_group_pipe* h2_group_refuse(grdma_h2_group_pipe* p, const char* 
   return nullptr;
 }
 
-grdma_h2_group_pipe* grdma_h2_group_pipe_create(grdma_stream_job* job, const grdma_h2_link_spec* specs, uint32_t n,
-                                                uint32_t max_frame) {
+// specs: the message tables of grdma_h2_group_pipe_create; rspecs: the replies of grdma_h2_group_pipe_create_reply
+// instead (exactly one of the two)
+static grdma_h2_group_pipe* h2_group_create(grdma_stream_job* job, const grdma_h2_link_spec* specs,
+                                            const grdma_h2_reply_link_spec* rspecs, uint32_t n, uint32_t max_frame) {
   if (grdma_device_count() <= 0) return nullptr;
-  if (!job || !specs || n == 0 || n > GRDMA_H2_BATCH_MAX) return h2_group_refuse(nullptr, "h2 group pipe: a job and 1 .. GRDMA_H2_BATCH_MAX link specs");
-  if (max_frame == 0 || max_frame >= (1u << 24)) return h2_group_refuse(nullptr, "h2 group pipe: max_frame out of range");
+  if (!job || (!specs && !rspecs) || n == 0 || n > GRDMA_H2_BATCH_MAX) return h2_group_refuse(nullptr, "h2 group pipe: a job and 1 .. GRDMA_H2_BATCH_MAX link specs");
+  if (specs && (max_frame == 0 || max_frame >= (1u << 24))) return h2_group_refuse(nullptr, "h2 group pipe: max_frame out of range");
+  auto link_of = [&](uint32_t i) { return specs ? specs[i].link : rspecs[i].link; };
+  auto parser_of = [&](uint32_t i) { return specs ? specs[i].parser : rspecs[i].parser_back; };
   for (uint32_t i = 0; i < n; i++) {
-    if (!specs[i].msgs || specs[i].nmsgs == 0 || specs[i].nmsgs > H2_FRAME_ONE_MAX)
+    if (specs && (!specs[i].msgs || specs[i].nmsgs == 0 || specs[i].nmsgs > H2_FRAME_ONE_MAX))
       return h2_group_refuse(nullptr, "h2 group pipe: 1 .. 4096 messages per link");
-    if (!specs[i].parser) return h2_group_refuse(nullptr, "h2 group pipe: a link without parser");
+    if (rspecs && !rspecs[i].reply) return h2_group_refuse(nullptr, "h2 group reply pipe: a link without reply");
+    if (!parser_of(i)) return h2_group_refuse(nullptr, "h2 group pipe: a link without parser");
     for (uint32_t k = 0; k < i; k++) {
-      if (specs[k].link == specs[i].link) return h2_group_refuse(nullptr, "h2 group pipe: a link listed twice");
-      if (specs[k].parser == specs[i].parser) return h2_group_refuse(nullptr, "h2 group pipe: a parser listed twice");
+      if (link_of(k) == link_of(i)) return h2_group_refuse(nullptr, "h2 group pipe: a link listed twice");
+      if (parser_of(k) == parser_of(i)) return h2_group_refuse(nullptr, "h2 group pipe: a parser listed twice");
+      if (rspecs && rspecs[k].reply == rspecs[i].reply) return h2_group_refuse(nullptr, "h2 group reply pipe: a reply listed twice");
     }
   }
   const uint32_t job_links = grdma_job_link_count(job);
   for (uint32_t i = 0; i < n; i++)
-    if (specs[i].link >= job_links) return h2_group_refuse(nullptr, "h2 group pipe: a link index out of range");
-  for (uint32_t i = 0; i < n; i++)
+    if (link_of(i) >= job_links) return h2_group_refuse(nullptr, "h2 group pipe: a link index out of range");
+  for (uint32_t i = 0; specs && i < n; i++)
     for (uint64_t k = 0; k < specs[i].nmsgs; k++)
       if (specs[i].msgs[k].len >= (1ull << 32)) return h2_group_refuse(nullptr, "h2 group pipe: a message of 4 GiB or more");
+  for (uint32_t i = 0; rspecs && i < n; i++) {
+    const grdma_h2_reply* r = rspecs[i].reply;
+    if (r->pipe || r->gpipe) return h2_group_refuse(nullptr, "h2 group reply pipe: a reply bound to a pipe already");
+    // (the source of a reply pipe assembles in forward pipes: a standalone source is framed by grdma_h2_reply_frame)
+    if (!r->src->attached) return h2_group_refuse(nullptr, "h2 group reply pipe: a source assembler that is not attached to a forward pipe");
+  }
   uint32_t have[2] = {0, 0};
   if (grdma_job_hook_counts(job, have) != 0) return nullptr;
   if (have[0] || have[1]) return h2_group_refuse(nullptr, "h2 group pipe: the job already carries hooks (another pipe's)");
@@ -1354,7 +1455,9 @@ grdma_h2_group_pipe* grdma_h2_group_pipe_create(grdma_stream_job* job, const grd
   std::vector<grdma_h2_link_frame> ftab(n);
   std::vector<grdma_h2_link_deframe> dtab(n);
   const uint64_t per = H2_EMIT_THREADS / 64;
+  std::vector<h2r_link> rtab(n);
   bool ok = hipMalloc((void**)&p->d_ftab, sizeof(grdma_h2_link_frame) * n) == hipSuccess &&
+            (!rspecs || hipMalloc((void**)&p->d_rtab, sizeof(h2r_link) * n) == hipSuccess) &&
             hipMalloc((void**)&p->d_dtab, sizeof(grdma_h2_link_deframe) * n) == hipSuccess &&
             hipMalloc((void**)&p->d_fres, sizeof(grdma_h2_frame_result) * n) == hipSuccess &&
             hipMalloc((void**)&p->d_dres, sizeof(grdma_h2_deframe_result) * n) == hipSuccess &&
@@ -1362,29 +1465,41 @@ grdma_h2_group_pipe* grdma_h2_group_pipe_create(grdma_stream_job* job, const grd
             hipMemset(p->d_dres, 0, sizeof(grdma_h2_deframe_result) * n) == hipSuccess;
   for (uint32_t i = 0; ok && i < n; i++) {
     h2_group_link& l = p->links[i];
-    const grdma_h2_link_spec& sp = specs[i];
     const uint64_t* d_step = nullptr;
     uint64_t slices_cap = 0;
-    if (grdma_job_link_view(job, sp.link, &l.d_sges, &l.count, &l.d_slices, &l.dst, &p->job_stream) != 0 ||
-        grdma_job_link_step_slices(job, sp.link, &d_step, &slices_cap) != 0)
+    if (grdma_job_link_view(job, link_of(i), &l.d_sges, &l.count, &l.d_slices, &l.dst, &p->job_stream) != 0 ||
+        grdma_job_link_step_slices(job, link_of(i), &d_step, &slices_cap) != 0)
       return h2_group_refuse(p, "h2 group pipe: a link index out of range");
-    l.link = sp.link;
-    l.parser = sp.parser;
-    l.nmsgs = sp.nmsgs;
-    l.delivered = sp.delivered_slices;
-    l.ev_cap = sp.events_cap;
+    l.link = link_of(i);
+    l.parser = parser_of(i);
+    l.nmsgs = specs ? specs[i].nmsgs : 0;
+    l.delivered = specs ? specs[i].delivered_slices : rspecs[i].delivered_slices;
+    l.ev_cap = specs ? specs[i].events_cap : rspecs[i].events_cap;
     l.hdr_cap = 32 * (l.count + 64);
-    std::vector<grdma_h2_msg_dev> tmp(sp.nmsgs);
-    for (uint64_t k = 0; k < sp.nmsgs; k++) {
-      tmp[k].payload = static_cast<const uint8_t*>(sp.msgs[k].payload);
-      tmp[k].len = sp.msgs[k].len;
-      tmp[k].stream_id = sp.msgs[k].stream_id;
-      tmp[k].flags = sp.msgs[k].flags;
-    }
-    ok = hipMalloc((void**)&l.d_msgs, sizeof(grdma_h2_msg_dev) * sp.nmsgs) == hipSuccess &&
-         hipMemcpy(l.d_msgs, tmp.data(), sizeof(grdma_h2_msg_dev) * sp.nmsgs, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMalloc((void**)&l.d_hdr, l.hdr_cap) == hipSuccess &&
+    ok = hipMalloc((void**)&l.d_hdr, l.hdr_cap) == hipSuccess &&
          hipMalloc((void**)&l.d_ev, sizeof(grdma_h2_event) * (l.ev_cap ? l.ev_cap : 1)) == hipSuccess;
+    if (specs) {
+      const grdma_h2_link_spec& sp = specs[i];
+      std::vector<grdma_h2_msg_dev> tmp(sp.nmsgs);
+      for (uint64_t k = 0; k < sp.nmsgs; k++) {
+        tmp[k].payload = static_cast<const uint8_t*>(sp.msgs[k].payload);
+        tmp[k].len = sp.msgs[k].len;
+        tmp[k].stream_id = sp.msgs[k].stream_id;
+        tmp[k].flags = sp.msgs[k].flags;
+      }
+      ok = ok && hipMalloc((void**)&l.d_msgs, sizeof(grdma_h2_msg_dev) * sp.nmsgs) == hipSuccess &&
+           hipMemcpy(l.d_msgs, tmp.data(), sizeof(grdma_h2_msg_dev) * sp.nmsgs, hipMemcpyHostToDevice) == hipSuccess;
+    } else if (ok) {
+      // the link's framer writes the link's slice table, and only a reply of the shape the job's graph was recorded for
+      grdma_h2_reply* r = rspecs[i].reply;
+      ok = h2_reply_set_target(r, l.d_sges, l.count, l.d_hdr, l.hdr_cap, 1, l.count, rspecs[i].recorded_wire_bytes, nullptr);
+      if (ok) {
+        r->gpipe = p;
+        r->src->reply_pipes++;
+        p->replies.push_back(r);
+        rtab[i].R = r->d;
+      }
+    }
     grdma_h2_link_frame& f = ftab[i];
     f.msgs = l.d_msgs;
     f.nmsgs = l.nmsgs;
@@ -1409,6 +1524,7 @@ grdma_h2_group_pipe* grdma_h2_group_pipe_create(grdma_stream_job* job, const grd
     q.n_step = d_step;
   }
   ok = ok && hipMemcpy(p->d_ftab, ftab.data(), sizeof(grdma_h2_link_frame) * n, hipMemcpyHostToDevice) == hipSuccess &&
+       (!rspecs || hipMemcpy(p->d_rtab, rtab.data(), sizeof(h2r_link) * n, hipMemcpyHostToDevice) == hipSuccess) &&
        hipMemcpy(p->d_dtab, dtab.data(), sizeof(grdma_h2_link_deframe) * n, hipMemcpyHostToDevice) == hipSuccess &&
        hipEventCreateWithFlags(&p->framed, hipEventDisableTiming) == hipSuccess &&
        hipEventCreateWithFlags(&p->job_done, hipEventDisableTiming) == hipSuccess &&
@@ -1423,31 +1539,69 @@ grdma_h2_group_pipe* grdma_h2_group_pipe_create(grdma_stream_job* job, const grd
   }
   const char* fe = getenv("GRDMA_H2_PIPE_FUSED");
   if (!fe || atoi(fe) != 0) {
-    grdma_job_hook pre, post;
-    memset(&pre, 0, sizeof(pre));
+    grdma_job_hook pre[2], post;
+    memset(pre, 0, sizeof(pre));
     memset(&post, 0, sizeof(post));
-    pre.fn = (const void*)k_h2_frame_links;
-    pre.grid = p->frame_grid;
-    pre.threads = H2_EMIT_THREADS;
-    pre.args[0] = (uint64_t)(uintptr_t)p->d_ftab;
-    pre.args[1] = n;
+    uint32_t n_pre = 1;
+    if (rspecs) {  // a linear chain in front of the job's first round, as the single reply pipe's
+      pre[0].fn = (const void*)k_h2_reply_plan_links;
+      pre[0].grid = n;
+      pre[0].threads = PLAN_THREADS;
+      pre[1].fn = (const void*)k_h2_reply_emit_links;
+      pre[1].grid = H2R_GRID;
+      pre[1].threads = H2_EMIT_THREADS;
+      pre[0].args[0] = pre[1].args[0] = (uint64_t)(uintptr_t)p->d_rtab;
+      pre[1].args[1] = n;
+      n_pre = 2;
+    } else {
+      pre[0].fn = (const void*)k_h2_frame_links;
+      pre[0].grid = p->frame_grid;
+      pre[0].threads = H2_EMIT_THREADS;
+      pre[0].args[0] = (uint64_t)(uintptr_t)p->d_ftab;
+      pre[0].args[1] = n;
+    }
     post.fn = (const void*)k_h2_deframe_links;
     post.grid = n;
     post.threads = H2_DEFRAME_THREADS;
     post.args[0] = (uint64_t)(uintptr_t)p->d_dtab;
-    if (grdma_job_set_hooks(job, &pre, 1, &post, 1) != 0) {
+    if (grdma_job_set_hooks(job, pre, n_pre, &post, 1) != 0) {
       grdma_h2_group_pipe_destroy(p);
       return nullptr;
     }
-    p->pre = pre;
+    memcpy(p->pre, pre, sizeof(pre));
+    p->n_pre = n_pre;
     p->post = post;
     p->fused = true;
   }
   return p;
 }
 
+grdma_h2_group_pipe* grdma_h2_group_pipe_create(grdma_stream_job* job, const grdma_h2_link_spec* specs, uint32_t n,
+                                                uint32_t max_frame) {
+  if (!specs) return h2_group_refuse(nullptr, "h2 group pipe: a job and 1 .. GRDMA_H2_BATCH_MAX link specs");
+  return h2_group_create(job, specs, nullptr, n, max_frame);
+}
+
+grdma_h2_group_pipe* grdma_h2_group_pipe_create_reply(grdma_stream_job* job_back, const grdma_h2_reply_link_spec* specs,
+                                                      uint32_t n) {
+  if (!specs) return h2_group_refuse(nullptr, "h2 group pipe: a job and 1 .. GRDMA_H2_BATCH_MAX link specs");
+  return h2_group_create(job_back, nullptr, specs, n, 0);
+}
+
+// a group reply pipe lets go of its replies (its streams are synchronised: nothing gathers from the sources' arenas)
+static void h2_group_unbind_replies(grdma_h2_group_pipe* p) {
+  for (grdma_h2_reply* r : p->replies) {
+    if (r->src->last_read == p->deframed || r->src->last_read == p->job_done) r->src->last_read = nullptr;
+    r->src->reply_pipes--;
+    r->gpipe = nullptr;
+  }
+  p->replies.clear();
+}
+
 void grdma_h2_group_pipe_destroy(grdma_h2_group_pipe* p) {
   if (!p) return;
+  for (const grdma_h2_asm* a : p->asms)
+    if (h2_asm_read_by_reply_pipes(a)) return;  // (a reply pipe's job gathers from this pipe's arenas: destroy that one first)
   if (p->launched) {
     hipStreamSynchronize(p->frame_stream);
     hipStreamSynchronize(p->job_stream);
@@ -1459,7 +1613,9 @@ void grdma_h2_group_pipe_destroy(grdma_h2_group_pipe* p) {
     hipFree(l.d_ev);
   }
   if (p->fused && p->job) grdma_job_set_hooks(p->job, nullptr, 0, nullptr, 0);
+  h2_group_unbind_replies(p);
   h2_group_detach(p);
+  hipFree(p->d_rtab);
   hipFree(p->d_atab);
   hipFree(p->d_calls);
   hipFree(p->d_ftab);
@@ -1490,11 +1646,33 @@ int grdma_h2_group_pipe_enqueue(grdma_h2_group_pipe* p) {
     }
     p->launched = true;
   };
-  if (p->fused) {  // one graph launch: k_h2_frame_links -> the job's rounds -> k_h2_deframe_links [-> the six k_h2_asm_*_links]
-    if (!wait_parsers()) return -GRDMA_ERR_HIP;
+  // a reply step reads what the forward steps assembled: behind every distinct source parser's last deframing
+  auto wait_sources = [&](hipStream_t st) {
+    for (size_t i = 0; i < p->replies.size(); i++) {
+      const grdma_h2_parser* fp = p->replies[i]->src->parser;
+      bool seen = false;
+      for (size_t k = 0; k < i && !seen; k++) seen = p->replies[k]->src->parser == fp;
+      if (!seen && fp->last_deframed && fp->last_stream != st && hipStreamWaitEvent(st, fp->last_deframed, 0) != hipSuccess)
+        return false;
+    }
+    return true;
+  };
+  // ... and a step's release (at the start of its assembly) waits for the last reply step that gathers from the arena
+  auto wait_readers = [&]() {
+    for (const grdma_h2_asm* a : p->asms)
+      if (hipEvent_t rd = h2_asm_last_read(a))
+        if (hipStreamWaitEvent(p->job_stream, rd, 0) != hipSuccess) return false;
+    return true;
+  };
+  auto sources_read_until = [&](hipEvent_t read_done) {
+    for (grdma_h2_reply* r : p->replies) r->src->last_read = read_done;
+  };
+  if (p->fused) {  // one graph launch: the framing kernel(s) -> the job's rounds -> k_h2_deframe_links [-> the six k_h2_asm_*_links]
+    if (!wait_parsers() || !wait_sources(p->job_stream) || !wait_readers()) return -GRDMA_ERR_HIP;
     const int rc = grdma_stream_job_launch(p->job);
     if (rc < 0) return rc;
     if (hipEventRecord(p->deframed, p->job_stream) != hipSuccess) return -GRDMA_ERR_HIP;
+    sources_read_until(p->deframed);
     p->timed = false;
     done();
     return 0;
@@ -1503,15 +1681,24 @@ int grdma_h2_group_pipe_enqueue(grdma_h2_group_pipe* p) {
   // framing overwrites the slice tables the job's previous step read
   if (p->launched && hipStreamWaitEvent(p->frame_stream, p->job_done, 0) != hipSuccess) return -GRDMA_ERR_HIP;
   if (hipMemsetAsync(p->d_fres, 0, sizeof(grdma_h2_frame_result) * n, p->frame_stream) != hipSuccess) return -GRDMA_ERR_HIP;
+  if (!wait_sources(p->frame_stream)) return -GRDMA_ERR_HIP;
   hipEventRecord(p->t_f0, p->frame_stream);
-  hipLaunchKernelGGL(k_h2_frame_links, dim3(p->frame_grid), dim3(H2_EMIT_THREADS), 0, p->frame_stream,
-                     (const grdma_h2_link_frame*)p->d_ftab, n);
+  if (p->d_rtab) {
+    hipLaunchKernelGGL(k_h2_reply_plan_links, dim3(n), dim3(PLAN_THREADS), 0, p->frame_stream, (const h2r_link*)p->d_rtab);
+    hipLaunchKernelGGL(k_h2_reply_emit_links, dim3(H2R_GRID), dim3(H2_EMIT_THREADS), 0, p->frame_stream,
+                       (const h2r_link*)p->d_rtab, n);
+  } else {
+    hipLaunchKernelGGL(k_h2_frame_links, dim3(p->frame_grid), dim3(H2_EMIT_THREADS), 0, p->frame_stream,
+                       (const grdma_h2_link_frame*)p->d_ftab, n);
+  }
   hipEventRecord(p->t_f1, p->frame_stream);
   if (hipEventRecord(p->framed, p->frame_stream) != hipSuccess) return -GRDMA_ERR_HIP;
   if (hipStreamWaitEvent(p->job_stream, p->framed, 0) != hipSuccess) return -GRDMA_ERR_HIP;
+  if (!wait_readers()) return -GRDMA_ERR_HIP;
   const int rc = grdma_stream_job_launch(p->job);
   if (rc < 0) return rc;
   if (hipEventRecord(p->job_done, p->job_stream) != hipSuccess) return -GRDMA_ERR_HIP;
+  sources_read_until(p->job_done);
   // the deframing goes behind the job on the job's stream (csrc: why the single pipe does the same by default)
   if (!wait_parsers()) return -GRDMA_ERR_HIP;
   hipEventRecord(p->t_d0, p->job_stream);
@@ -1539,6 +1726,8 @@ int grdma_h2_group_pipe_sync(grdma_h2_group_pipe* p, uint64_t* out, uint64_t out
   if (hipMemcpy(fr.data(), p->d_fres, sizeof(grdma_h2_frame_result) * n, hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(dr.data(), p->d_dres, sizeof(grdma_h2_deframe_result) * n, hipMemcpyDeviceToHost) != hipSuccess)
     return -GRDMA_ERR_HIP;
+  for (size_t i = 0; i < p->replies.size(); i++)  // (a link's overflow 2: its step had another shape than the recorded one)
+    if (!h2_reply_result(p->replies[i], &fr[i])) return -GRDMA_ERR_HIP;
   float fms = 0, dms = 0;
   uint64_t f_us = 0, d_us = 0;
   if (p->launched && p->timed && hipEventElapsedTime(&fms, p->t_f0, p->t_f1) == hipSuccess) f_us = (uint64_t)(fms * 1e3f);
@@ -1841,7 +2030,7 @@ int grdma_h2_group_pipe_attach_assemblers(grdma_h2_group_pipe* p, grdma_h2_asm* 
     grdma_job_hook post[7];
     post[0] = p->post;
     const uint32_t n_post = 1 + h2_asm_links_hooks(p->d_atab, have, post + 1);
-    if (grdma_job_set_hooks(p->job, &p->pre, 1, post, n_post) != 0) return -GRDMA_ERR_HIP;
+    if (grdma_job_set_hooks(p->job, p->pre, p->n_pre, post, n_post) != 0) return -GRDMA_ERR_HIP;
   }
   p->asms.assign(asms, asms + n);
   p->n_asm = have;

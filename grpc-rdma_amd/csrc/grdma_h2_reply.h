@@ -18,6 +18,9 @@
 //   k_h2_reply_emit   fixed grid.  Waves take messages by static grid-stride (wave w: messages w, w + W, ...) and lay
 //                     each one out with h2_emit_message.  Writes nothing when the plan reported an overflow or, in a
 //                     pipe, a shape other than the one the job's graph was recorded for.
+// The many-link forms k_h2_reply_plan_links / k_h2_reply_emit_links (a table of framers: the replies of a batch, the
+// links of a group reply pipe) are at the end of this file; the plan's body is one source text for both plan kernels,
+// csrc/grdma_h2_reply_plan.inc.
 #ifndef GRDMA_H2_REPLY_H
 #define GRDMA_H2_REPLY_H
 #include "grdma_h2_asm.h"
@@ -67,81 +70,7 @@ __device__ __forceinline__ uint32_t h2r_route(const h2r_dev* R, uint32_t id) {
 }
 
 __global__ __launch_bounds__(PLAN_THREADS) void k_h2_reply_plan(h2r_dev* R) {
-  __shared__ uint64_t s_wave[PLAN_THREADS / 64];
-  const h2a_dev* A = R->src;
-  const uint64_t tid = threadIdx.x;
-  // (a call the assembler skipped left no descriptors; more than the tables hold: nothing is framed)
-  const bool bad = A->skip != 0 || A->ndesc > A->desc_cap || A->ndesc > R->max_messages;
-  const uint64_t nd = bad ? 0 : A->ndesc;
-  const grdma_h2_rx_msg* desc = A->desc;
-  grdma_h2_msg_dev* msgs = R->msgs;
-  // 1. kept or dropped, the kept ones compacted in descriptor order
-  uint64_t kept = 0, my_status = 0, my_unrouted = 0;
-  for (uint64_t d0 = 0; d0 < nd; d0 += PLAN_THREADS) {
-    const uint64_t i = d0 + tid;
-    uint64_t keep = 0;
-    grdma_h2_msg_dev m{nullptr, 0, 0, 0};
-    if (i < nd) {
-      const grdma_h2_rx_msg d = desc[i];
-      if (d.status != GRDMA_H2_MSG_OK) {
-        my_status++;
-      } else {
-        const uint32_t to = h2r_route(R, d.stream_id);
-        if (to == 0) {
-          my_unrouted++;
-        } else {
-          keep = 1;
-          m.payload = A->arena + d.offset;
-          m.len = d.length;
-          m.stream_id = to;
-          m.flags = d.flags & 1;
-        }
-      }
-    }
-    uint64_t tot;
-    const uint64_t x = block_excl_scan(keep, s_wave, &tot);
-    if (keep) msgs[kept + x] = m;
-    kept += tot;
-  }
-  uint64_t n_status, n_unrouted;
-  block_excl_scan(my_status, s_wave, &n_status);
-  block_excl_scan(my_unrouted, s_wave, &n_unrouted);
-  __syncthreads();  // the compacted table is complete: sizes look at a message's neighbours
-  // 2. sizes and positions over the compacted table (the loop of k_h2_frame_index)
-  const uint32_t max_frame = R->max_frame;
-  uint64_t base_sl = 0, base_hdr = 0, base_wire = 0;
-  for (uint64_t m0 = 0; m0 < kept; m0 += PLAN_THREADS) {
-    const uint64_t i = m0 + tid;
-    uint64_t n_sl = 0, n_hdr = 0, n_wire = 0;
-    uint32_t mode = 0;
-    if (i < kept) h2_msg_size(msgs, i, max_frame, &n_sl, &n_hdr, &n_wire, &mode);
-    uint64_t tot_sl, tot_hdr, tot_wire;
-    const uint64_t x_sl = block_excl_scan(n_sl, s_wave, &tot_sl);
-    const uint64_t x_hdr = block_excl_scan(n_hdr, s_wave, &tot_hdr);
-    block_excl_scan(n_wire, s_wave, &tot_wire);
-    if (i < kept) {
-      grdma_h2_msg_pos q;
-      q.sl = base_sl + x_sl;
-      q.hdr = base_hdr + x_hdr;
-      q.mode = mode;
-      q.pad = 0;
-      R->pos[i] = q;
-    }
-    base_sl += tot_sl;
-    base_hdr += tot_hdr;
-    base_wire += tot_wire;
-  }
-  if (tid == 0) {
-    uint64_t overflow = (bad || base_sl > R->cap || base_hdr > R->hdr_cap) ? 1 : 0;
-    if (!bad && R->check_shape && (base_sl != R->want_slices || base_wire != R->want_wire)) overflow = 2;
-    R->res[H2R_KEPT] = kept;
-    R->res[H2R_DROPPED_STATUS] = n_status;
-    R->res[H2R_UNROUTED] = n_unrouted;
-    R->res[H2R_SLICES] = base_sl;
-    R->res[H2R_HDR_BYTES] = base_hdr;
-    R->res[H2R_WIRE_BYTES] = base_wire;
-    R->res[H2R_OVERFLOW] = overflow;
-  }
+#include "grdma_h2_reply_plan.inc"
 }
 
 __global__ __launch_bounds__(H2_EMIT_THREADS) void k_h2_reply_emit(const h2r_dev* R) {
@@ -157,6 +86,60 @@ __global__ __launch_bounds__(H2_EMIT_THREADS) void k_h2_reply_emit(const h2r_dev
   const uint64_t cap = R->cap, hdr_cap = R->hdr_cap;
   for (uint64_t i = (uint64_t)blockIdx.x * (H2_EMIT_THREADS / 64) + (threadIdx.x >> 6); i < n; i += waves)
     h2_emit_message(msgs, i, n, max_frame, out, cap, hdr, hdr_cap, pos[i], lane);
+}
+
+// ---- the two kernels over a table of L <= H2R_LINKS_MAX links (replies of a batch, links of a group reply pipe): two
+// launches however many links.  Nothing is shared between the links -- every entry has its own h2r_dev, scratch, source
+// assembler and targets -- so an overflow, a shape mismatch or a skipped assembler call stay with their link.  The entry
+// is loaded with a uniform index: it sits in scalar registers, as the single kernels' parameter does.
+//   plan   grid L: workgroup l is the one plan workgroup of link l -- L plans side by side
+//   emit   a fixed grid; the messages of ALL links by one static grid-stride, so an idle or failed link idles nobody:
+//          every workgroup builds the exclusive prefix of the links' kept counts in LDS (one block scan; a link whose
+//          result block reports an overflow contributes 0), a wave finds the link of its message by binary search over
+//          it (wave-uniform: the link's pointers stay scalar) and lays the message out with that link's tables
+// The kernel boundary is the only agent-scope hand-over; inside a workgroup barriers only.
+#define H2R_LINKS_MAX 256  // (= GRDMA_H2_BATCH_MAX, include/grdma_amd.h; one thread per link in the emit's block scan)
+struct h2r_link {
+  h2r_dev* R;
+};
+static_assert(H2R_LINKS_MAX <= H2_EMIT_THREADS, "k_h2_reply_emit_links scans one link per thread");
+
+__global__ __launch_bounds__(PLAN_THREADS) void k_h2_reply_plan_links(const h2r_link* __restrict__ tab) {
+  h2r_dev* const R = tab[blockIdx.x].R;
+#include "grdma_h2_reply_plan.inc"
+}
+
+__global__ __launch_bounds__(H2_EMIT_THREADS) void k_h2_reply_emit_links(const h2r_link* __restrict__ tab, uint32_t nlinks) {
+  __shared__ uint64_t s_pre[H2R_LINKS_MAX + 1];  // exclusive prefix of the links' kept messages; [nlinks]: the total
+  __shared__ uint64_t s_wave[H2_EMIT_THREADS / 64];
+  const int lane = threadIdx.x & 63;
+  const uint32_t wv = uni32(threadIdx.x >> 6);
+  uint64_t mine = 0;
+  if (threadIdx.x < nlinks) {
+    const h2r_dev* const R = tab[threadIdx.x].R;
+    if (!R->res[H2R_OVERFLOW]) mine = R->res[H2R_KEPT];
+  }
+  const uint64_t incl = wave_incl_scan(mine, lane);
+  if (lane == 63) s_wave[wv] = incl;
+  __syncthreads();
+  uint64_t base = 0;
+  for (uint32_t w = 0; w < wv; w++) base += s_wave[w];
+  if (threadIdx.x == 0) s_pre[0] = 0;
+  s_pre[threadIdx.x + 1] = base + incl;
+  __syncthreads();
+  const uint64_t T = s_pre[nlinks];
+  const uint64_t waves = (uint64_t)gridDim.x * (H2_EMIT_THREADS / 64);
+  for (uint64_t g = (uint64_t)blockIdx.x * (H2_EMIT_THREADS / 64) + wv; g < T; g += waves) {
+    uint32_t ll = 0, lh = nlinks;  // the last link whose prefix <= g (a link without messages shares its prefix with the next)
+    while (lh - ll > 1) {
+      const uint32_t mid = (ll + lh) / 2;
+      if (uni64(s_pre[mid]) <= g) ll = mid;
+      else lh = mid;
+    }
+    const h2r_dev* const R = tab[ll].R;
+    const uint64_t i = g - uni64(s_pre[ll]);
+    h2_emit_message(R->msgs, i, R->res[H2R_KEPT], R->max_frame, R->out, R->cap, R->hdr, R->hdr_cap, R->pos[i], lane);
+  }
 }
 
 }  // namespace

@@ -39,6 +39,16 @@ class H2LinkSpec(C.Structure):
                 ("delivered_slices", u64), ("events_cap", u64)]
 
 
+class H2ReplyItem(C.Structure):
+    _fields_ = [("reply", C.c_void_p), ("d_slices_out", C.c_void_p), ("slices_cap", u64), ("d_hdr_arena", C.c_void_p),
+                ("hdr_cap", u64), ("out", u64 * 8), ("n_slices", C.c_int64)]
+
+
+class H2ReplyLinkSpec(C.Structure):
+    _fields_ = [("link", C.c_uint32), ("reply", C.c_void_p), ("parser_back", C.c_void_p), ("delivered_slices", u64),
+                ("events_cap", u64), ("recorded_wire_bytes", u64)]
+
+
 MSG_OK, MSG_TOO_LARGE, MSG_NO_SPACE, MSG_TRUNCATED = 0, 1, 2, 3
 SYNC_KEYS = ("framed", "frame_overflow", "events", "deframe_overflow", "parsed", "h2_error", "frame_us", "deframe_us",
              "bulk_steps", "bulk_frames", "t_wait", "t_bulk", "t_total", "t_serial")
@@ -137,6 +147,10 @@ def _bind():
         lib.grdma_h2_group_pipe_attach_assemblers.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32]
         lib.grdma_h2_group_pipe_messages.restype = C.c_int64
         lib.grdma_h2_group_pipe_messages.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(H2RxMsg), u64]
+        lib.grdma_h2_reply_frame_batch.restype = C.c_int
+        lib.grdma_h2_reply_frame_batch.argtypes = [C.POINTER(H2ReplyItem), C.c_uint32]
+        lib.grdma_h2_group_pipe_create_reply.restype = C.c_void_p
+        lib.grdma_h2_group_pipe_create_reply.argtypes = [C.c_void_p, C.POINTER(H2ReplyLinkSpec), C.c_uint32]
         lib.grdma_job_hook_counts.restype = C.c_int   # (not in include/grdma_amd.h: the job's side of the pipes)
         lib.grdma_job_hook_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         _bound = True
@@ -318,11 +332,60 @@ def release_batch(pairs):
     check(lib.grdma_h2_asm_release_batch(hs, cs, n))
 
 
+def reply_frame_batch(items):
+    """Reply.frame for many transports in two launches (grdma_h2_reply_frame_batch).  items: [(Reply, slices device ptr,
+    slices cap, header arena device ptr, header cap), ...] with distinct replies of distinct, unattached source
+    assemblers.  -> per item (slice count, dict of Reply.REPLY_STATS); every item reports for itself: where its caps
+    overflowed, the count is the integer -GRDMA_ERR_CAPACITY (-5) and nothing of that item was written.  frame_us is
+    the batch's, repeated.  The stats also land in each Reply's .last_stats."""
+    lib = _bind()
+    n = len(items)
+    arr = (H2ReplyItem * max(1, n))()
+    for i, (reply, sl, cap, hdr, hdr_cap) in enumerate(items):
+        arr[i].reply = reply.h if reply is not None else None
+        arr[i].d_slices_out, arr[i].slices_cap, arr[i].d_hdr_arena, arr[i].hdr_cap = sl, cap, hdr, hdr_cap
+    check(lib.grdma_h2_reply_frame_batch(arr, n))
+    res = []
+    for i in range(n):
+        st = dict(zip(Reply.REPLY_STATS, [int(x) for x in arr[i].out]))
+        items[i][0].last_stats = st
+        res.append((int(arr[i].n_slices), st))
+    return res
+
+
 class GroupPipe:
     """frame -> multi-link job -> deframe for several links of ONE job (grdma_h2_group_pipe): one framing kernel and
     one deframing kernel per step however many links.  specs: [(link, msgs, Parser, delivered_slices, events_cap), ...]
     with msgs = [(payload device ptr, len, stream_id, flags), ...]; links and parsers distinct; the job has run once.
     Links that are not listed are carried as before."""
+
+    @classmethod
+    def reply(cls, job_back, specs):
+        """A group pipe whose framing stage is one Reply per link (grdma_h2_group_pipe_create_reply): a step frames, per
+        link, what the last enqueued step of that reply's forward pipe reported, sends it through `job_back` and
+        deframes it.  specs: [(link, Reply, back Parser, delivered_slices, events_cap, recorded_wire_bytes), ...].  A
+        link whose step has another shape than the job's recorded run keeps its table and reports frame_overflow 2; the
+        others go on.  Close it before the forward pipes and before the replies."""
+        self = cls.__new__(cls)
+        self.lib = _bind()
+        specs = list(specs)
+        arr = (H2ReplyLinkSpec * max(1, len(specs)))()
+        self._keep = []
+        for i, (link, reply, parser, delivered, cap, wire) in enumerate(specs):
+            self._keep.append((reply, parser))
+            arr[i].link, arr[i].reply = link, (reply.h if reply is not None else None)
+            arr[i].parser_back = parser.h if parser is not None else None
+            arr[i].delivered_slices, arr[i].events_cap, arr[i].recorded_wire_bytes = delivered, cap, wire
+        self.n = len(specs)
+        self.events_caps = [sp[4] for sp in specs]
+        self.job = job_back
+        self.h = self.lib.grdma_h2_group_pipe_create_reply(job_back.h if job_back is not None else None, arr, len(specs))
+        if not self.h:
+            raise GrdmaError("h2 group reply pipe refused: %s" % self.lib.grdma_last_error().decode())
+        self.reply_framers = [sp[1] for sp in specs]
+        for r in self.reply_framers:
+            r.assembler._reply_pipes = getattr(r.assembler, "_reply_pipes", 0) + 1
+        return self
 
     def __init__(self, job, specs, max_frame=16384):
         self.lib = _bind()
@@ -384,9 +447,16 @@ class GroupPipe:
         return _msgs(out, m)
 
     def close(self):
+        """does nothing while a reply pipe reads one of this pipe's assemblers (grdma_h2_group_pipe_destroy does not
+        either): close that one first, then call close again"""
         if self.h:
+            if any(a is not None and getattr(a, "_reply_pipes", 0) for a in getattr(self, "assemblers", [])):
+                return
             self.lib.grdma_h2_group_pipe_destroy(self.h)
             self.h = None
+            for r in getattr(self, "reply_framers", []):
+                r.assembler._reply_pipes -= 1
+            self.reply_framers = []
 
 
 def job_hook_counts(job):

@@ -794,6 +794,28 @@ void grdma_h2_reply_destroy(grdma_h2_reply* r);
  * attached to a pipe (grdma_h2_pipe_create_reply frames that one). */
 int64_t grdma_h2_reply_frame(grdma_h2_reply* r, grdma_slice* d_slices_out, uint64_t slices_cap,
                              void* d_hdr_arena, uint64_t hdr_cap, uint64_t out[8]);
+/* grdma_h2_reply_frame for MANY transports at once (k_h2_reply_plan_links, k_h2_reply_emit_links over a table of the
+ * items' framers): two launches for any n_items, the one-workgroup plans side by side, the messages of all items laid
+ * out by one grid.  One upload of the table and the per-item targets, one download of the result blocks; ordered
+ * behind each source parser's last deframing.  Per item the report (out[0..6], n_slices) and the bytes written are
+ * exactly what grdma_h2_reply_frame gives for that reply alone; out[7] is the batch's framing time, repeated.  Nothing
+ * is shared between the items: an item whose slices or header arena overflow its caps, whose call reported more than
+ * max_messages descriptors or whose source skipped its last call gets n_slices = -GRDMA_ERR_CAPACITY and nothing of it
+ * is written; the others are framed as they would be alone.  One call at a time per process, as grdma_h2_deframe_batch.
+ * Returns 0, or -GRDMA_ERR_INVALID (nothing ran, grdma_last_error says why): n_items outside 1 .. GRDMA_H2_BATCH_MAX,
+ * a NULL reply, a reply listed twice, two replies of one source assembler (one item per transport), a null, zero or
+ * misaligned slice table or header arena (as in the single call), a source attached to a pipe or group pipe, a reply
+ * bound to a reply pipe. */
+typedef struct grdma_h2_reply_item {
+  grdma_h2_reply* reply;            /* distinct; its source assembler distinct and not attached to a pipe */
+  grdma_slice* d_slices_out;        /* device, 16-byte aligned */
+  uint64_t slices_cap;
+  void* d_hdr_arena;                /* device, 16-byte aligned */
+  uint64_t hdr_cap;
+  uint64_t out[8];                  /* the words of grdma_h2_reply_frame; out[7] is the batch's time, repeated */
+  int64_t n_slices;                 /* out: slice count, or -GRDMA_ERR_CAPACITY for this item alone */
+} grdma_h2_reply_item;
+int grdma_h2_reply_frame_batch(grdma_h2_reply_item* items, uint32_t n_items);
 /* A pipe whose framing stage is the reply: a step frames what the LAST ENQUEUED step of the forward pipes (the pipes
  * `reply`'s source assembler is attached to) reported, sends it through job_back and deframes it with parser_back.
  * Everything else is grdma_h2_pipe: enqueue, sync, attach_assembler, messages, destroy.  job_back has run once over a
@@ -824,8 +846,8 @@ int64_t grdma_h2_pipe_slice_table(grdma_h2_pipe* p, grdma_slice* out, uint64_t c
  * grdma_h2_group_pipe_sync's "slices parsed" word is that count.  (grdma_h2_pipe parses the recorded count.)
  * Create returns NULL (grdma_last_error says why) for: n == 0, a link index out of range or listed twice, a parser
  * listed twice, nmsgs 0 or above 4096, max_frame 0 or >= 2^24, a job that already carries such kernels (another pipe).
- * Not here (yet): replies on a group pipe, the chunked deframer inside the batch (every transport is parsed
- * sequentially), flow control and HPACK (as for grdma_h2_pipe). */
+ * Not here (yet): the chunked deframer inside the batch (every transport is parsed sequentially), flow control and
+ * HPACK (as for grdma_h2_pipe). */
 typedef struct grdma_h2_link_spec {
   uint32_t link;                 /* index into the job's links; distinct */
   const grdma_h2_msg* msgs;
@@ -857,7 +879,37 @@ int grdma_h2_group_pipe_attach_assemblers(grdma_h2_group_pipe* p, grdma_h2_asm* 
 /* the descriptors of spec i in the last synced step, as grdma_h2_pipe_messages: their number, -GRDMA_ERR_CAPACITY if
  * more than cap, -GRDMA_ERR_INVALID for a spec without assembler */
 int64_t grdma_h2_group_pipe_messages(grdma_h2_group_pipe* p, uint32_t i, grdma_h2_rx_msg* out, uint64_t cap);
-void grdma_h2_group_pipe_destroy(grdma_h2_group_pipe* p);   /* removes the kernels from the job's graph, detaches the assemblers */
+/* removes the kernels from the job's graph, detaches the assemblers, unbinds the replies of a group reply pipe; does
+ * nothing while a reply pipe or group reply pipe reads one of this pipe's assemblers: destroy that one first */
+void grdma_h2_group_pipe_destroy(grdma_h2_group_pipe* p);
+
+/* grdma_h2_pipe_create_reply for n links of ONE back job: a group pipe whose framing stage is the listed replies --
+ * k_h2_reply_plan_links and k_h2_reply_emit_links, two kernels in front of the job's rounds however many links
+ * (grdma_job_hook_counts = (2, 1), (2, 7) with assemblers attached on the back side; with GRDMA_H2_PIPE_FUSED=0
+ * enqueued in front of the launch inside the framing timing events).  A step frames, per link, what the LAST ENQUEUED
+ * step of that reply's forward pipe or forward group pipe reported, sends it over the link and deframes it with
+ * parser_back.  The object is grdma_h2_group_pipe: enqueue, sync, events, slice_table, attach_assemblers, messages and
+ * destroy work on it unchanged.  job_back has run once over slice lists of the lengths the replies will have;
+ * delivered_slices and recorded_wire_bytes are that run's per link.  The shape is checked PER LINK: a link whose step
+ * has another slice count or other wire bytes writes nothing and re-sends its previous table, and sync reports frame
+ * overflow 2 for that spec only; the other links of the step are framed, sent and parsed as usual.  Ordering is by
+ * events: the step waits for every distinct source parser's last deframing, and a forward step's release (single pipe
+ * or group pipe) waits for the last reply step that gathers from its arena.  grdma_h2_pipe_destroy and
+ * grdma_h2_group_pipe_destroy of a forward pipe do nothing while this pipe reads one of its assemblers: destroy this
+ * one first, then the forward pipes, then the replies.
+ * NULL (grdma_last_error says why) for: what grdma_h2_group_pipe_create refuses of job, n, links and parsers, a NULL
+ * reply, a reply listed twice or bound to a pipe already, a source assembler that is not attached to a forward pipe,
+ * a job that already carries hooks. */
+typedef struct grdma_h2_reply_link_spec {
+  uint32_t link;                  /* index into job_back's links; distinct */
+  grdma_h2_reply* reply;          /* distinct, not bound; its source assembles in a forward pipe or group pipe */
+  grdma_h2_parser* parser_back;   /* distinct */
+  uint64_t delivered_slices;      /* of this link in the recorded run */
+  uint64_t events_cap;
+  uint64_t recorded_wire_bytes;   /* what the recorded run sent on this link */
+} grdma_h2_reply_link_spec;
+grdma_h2_group_pipe* grdma_h2_group_pipe_create_reply(grdma_stream_job* job_back,
+                                                      const grdma_h2_reply_link_spec* specs, uint32_t n);
 
 /* ---- GRPCProfiler: include/grpcpp/stats_time.h:11-44,111-122, src/core/lib/debug/stats_time.cc ----
  * The reference's scope profiler with its op names in its order: nanoseconds per op per thread slot,
