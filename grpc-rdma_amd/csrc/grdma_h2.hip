@@ -1,6 +1,7 @@
 // HTTP/2 DATA framing (K6/K7) and deframing (K8/K9) on the device.
 //
-// TX  k_h2_frame_index + k_h2_frame_emit   build, in HBM, the slice list chttp2 hands to
+// TX  k_h2_frame_one (tables of more than 4096 messages: k_h2_frame_index + k_h2_frame_emit)
+//                    builds, in HBM, the slice list chttp2 hands to
 //                    grpc_endpoint_write for a batch of gRPC messages:
 //                    5-byte message header (chttp2_transport.cc:1502-1510), 9-byte
 //                    DATA frame headers (grpc_chttp2_encode_data, frame_data.cc:64-90),
@@ -119,34 +120,124 @@ static bool h2_chunks_prepare(grdma_h2_parser* p, uint64_t ev_cap, hipStream_t s
   return ok;
 }
 
-// The deframing of one list of delivered slices, enqueued on st: over chunks when the parser has the buffers (plan,
-// the chunks side by side, then the merge -- or the sequential deframer over the whole list when the chain did not hold), else the sequential deframer alone.
-static void h2_enqueue_deframe(grdma_h2_parser* p, const uint8_t* arena, const grdma_slice_out* d_slices, uint64_t n,
-                               grdma_h2_event* d_ev, uint64_t ev_cap, grdma_h2_deframe_result* d_res, hipStream_t st,
-                               bool chunked) {
-  if (!chunked || n < H2_CHUNK_MIN_SLICES) {
-    hipLaunchKernelGGL(k_h2_deframe, dim3(1), dim3(H2_DEFRAME_THREADS), 0, st, p->d, arena, d_slices, n, d_ev, ev_cap, d_res);
-    return;
-  }
-  hipLaunchKernelGGL(k_h2_deframe_chunks, dim3((unsigned)p->chunks_want), dim3(H2_DEFRAME_THREADS), 0, st, p->d, p->d_chunks,
-                     arena, d_slices, n);
-  hipLaunchKernelGGL(k_h2_merge_or_deframe, dim3(H2_MERGE_GRID), dim3(H2_DEFRAME_THREADS), 0, st, p->d, p->d_chunks, arena,
-                     d_slices, n, d_ev, ev_cap, d_res);
+// --------------------------------------------------------------------- stages
+// A stage is one kernel chain as a list of grdma_job_hook records (csrc/grdma_dev.h: the kernel, its launch shape, its
+// parameters).  A chain is written down ONCE, by one of the builders below, and the list is used both ways: as kernel
+// nodes of a streaming job's graph (grdma_job_set_hooks) and launched on a stream (h2_launch).  The standalone calls,
+// the batch calls and both kinds of pipe (csrc/grdma_h2_host_pipe.inc) take their kernels from here and nowhere else.
+typedef std::vector<grdma_job_hook> h2_stage;
+
+static uint64_t h2_slot(const void* p) { return (uint64_t)(uintptr_t)p; }
+static uint64_t h2_slot(uint64_t v) { return v; }
+// one record: the arguments are held against the kernel's parameter list (their number, and each converts to its type)
+template <typename... P, typename... A>
+static grdma_job_hook h2_rec(void (*k)(P...), uint32_t grid, uint32_t threads, A... a) {
+  static_assert(sizeof...(P) == sizeof...(A) && sizeof...(P) <= GRDMA_JOB_HOOK_ARGS, "one argument per kernel parameter");
+  return grdma_job_hook{(const void*)k, grid, threads, {h2_slot(static_cast<P>(a))...}};
 }
 
-// The framing of one message table, enqueued on st: sizes and positions, then one wave per message (grdma_h2_kernels.h).
-static void h2_enqueue_frame(const grdma_h2_msg_dev* d_msgs, uint64_t n, uint32_t max_frame, grdma_sge* out, uint64_t cap,
-                             uint8_t* hdr, uint64_t hdr_cap, grdma_h2_msg_pos* d_pos, grdma_h2_frame_result* d_res,
-                             hipStream_t st) {
-  const uint64_t per = H2_EMIT_THREADS / 64;
-  if (n <= H2_FRAME_ONE_MAX) {  // one launch: every workgroup sums what lies in front of its messages itself
-    hipLaunchKernelGGL(k_h2_frame_one, dim3((unsigned)((n + per - 1) / per)), dim3(H2_EMIT_THREADS), 0, st, d_msgs, n, max_frame,
-                       out, cap, hdr, hdr_cap, d_res);
-    return;
+// n records launched on st, in order (the runtime reads as many parameter slots as the kernel has); the first launch
+// the runtime refuses ends it
+static hipError_t h2_launch(const grdma_job_hook* recs, size_t n, hipStream_t st) {
+  for (size_t i = 0; i < n; i++) {
+    void* args[GRDMA_JOB_HOOK_ARGS];
+    for (uint32_t a = 0; a < GRDMA_JOB_HOOK_ARGS; a++) args[a] = const_cast<uint64_t*>(&recs[i].args[a]);
+    const hipError_t e = hipLaunchKernel(recs[i].fn, dim3(recs[i].grid), dim3(recs[i].threads), args, 0, st);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();  // (reported here: no later call finds it)
+      return e;
+    }
   }
-  hipLaunchKernelGGL(k_h2_frame_index, dim3(1), dim3(256), 0, st, d_msgs, n, max_frame, cap, hdr_cap, d_pos, d_res);
-  hipLaunchKernelGGL(k_h2_frame_emit, dim3((unsigned)((n + per - 1) / per)), dim3(H2_EMIT_THREADS), 0, st, d_msgs, n, max_frame,
-                     out, cap, hdr, hdr_cap, (const grdma_h2_msg_pos*)d_pos);
+  return hipSuccess;
+}
+static hipError_t h2_launch(const h2_stage& s, hipStream_t st) { return h2_launch(s.data(), s.size(), st); }
+
+// The framing of one message table: one launch in which every workgroup sums what lies in front of its messages itself;
+// above H2_FRAME_ONE_MAX messages sizes and positions first, then one wave per message (grdma_h2_kernels.h).
+static h2_stage h2_stage_frame(const grdma_h2_msg_dev* d_msgs, uint64_t n, uint32_t max_frame, grdma_sge* out, uint64_t cap,
+                               uint8_t* hdr, uint64_t hdr_cap, grdma_h2_msg_pos* d_pos, grdma_h2_frame_result* d_res) {
+  const uint64_t per = H2_EMIT_THREADS / 64;
+  const uint32_t grid = (uint32_t)((n + per - 1) / per);
+  if (n <= H2_FRAME_ONE_MAX)
+    return {h2_rec(k_h2_frame_one, grid, H2_EMIT_THREADS, d_msgs, n, max_frame, out, cap, hdr, hdr_cap, d_res)};
+  return {h2_rec(k_h2_frame_index, 1, 256, d_msgs, n, max_frame, cap, hdr_cap, d_pos, d_res),
+          h2_rec(k_h2_frame_emit, grid, H2_EMIT_THREADS, d_msgs, n, max_frame, out, cap, hdr, hdr_cap, d_pos)};
+}
+// ... of the message tables of many links (grid: the workgroups of all links, grdma_h2_link_frame::wg0)
+static h2_stage h2_stage_frame_links(const grdma_h2_link_frame* d_tab, uint32_t n, uint32_t grid) {
+  return {h2_rec(k_h2_frame_links, grid, H2_EMIT_THREADS, d_tab, n)};
+}
+
+// The deframing of one list of delivered slices: over chunks when the parser has the buffers (chunked: h2_chunks_prepare
+// said so) and the list is long enough -- plan, the chunks side by side, then the merge, or the sequential deframer over
+// the whole list when the chain did not hold -- else the sequential deframer alone.
+static h2_stage h2_stage_deframe(const grdma_h2_parser* p, const uint8_t* arena, const grdma_slice_out* d_slices, uint64_t n,
+                                 grdma_h2_event* d_ev, uint64_t ev_cap, grdma_h2_deframe_result* d_res, bool chunked) {
+  if (!chunked || n < H2_CHUNK_MIN_SLICES)
+    return {h2_rec(k_h2_deframe, 1, H2_DEFRAME_THREADS, p->d, arena, d_slices, n, d_ev, ev_cap, d_res)};
+  return {h2_rec(k_h2_deframe_chunks, (uint32_t)p->chunks_want, H2_DEFRAME_THREADS, p->d, p->d_chunks, arena, d_slices, n),
+          h2_rec(k_h2_merge_or_deframe, H2_MERGE_GRID, H2_DEFRAME_THREADS, p->d, p->d_chunks, arena, d_slices, n, d_ev, ev_cap,
+                 d_res)};
+}
+// ... of the lists of n links, one workgroup each
+static h2_stage h2_stage_deframe_links(const grdma_h2_link_deframe* d_tab, uint32_t n) {
+  return {h2_rec(k_h2_deframe_links, n, H2_DEFRAME_THREADS, d_tab)};
+}
+
+// The assembly of one call behind its deframing (csrc/grdma_h2_asm.h): the plan, records [0, 5), then the copy.
+static h2_stage h2_stage_asm(h2a_dev* d, const h2a_call* d_call) {
+  return {h2_rec(k_h2_asm_tiles, H2A_GRID, H2A_THREADS, d, d_call),
+          h2_rec(k_h2_asm_carry, 1, H2A_ONE_THREADS, d, d_call),
+          h2_rec(k_h2_asm_begin, H2A_GRID, H2A_THREADS, d, d_call),
+          h2_rec(k_h2_asm_bytes, H2A_GRID, H2A_THREADS, d, d_call),
+          h2_rec(k_h2_asm_finish, 1, H2A_ONE_THREADS, d, d_call),
+          h2_rec(k_h2_asm_copy, H2A_GRID, H2A_THREADS, d, d_call)};
+}
+// ... of n links in the same six launches: the plan's one-workgroup stages of the links run side by side
+static_assert(H2A_LINKS_MAX == GRDMA_H2_BATCH_MAX, "the assembler's link table is the batch's");
+static h2_stage h2_stage_asm_links(const h2a_link* d_tab, uint32_t n) {
+  return {h2_rec(k_h2_asm_tiles_links, n * H2A_LINK_GRID, H2A_THREADS, d_tab, n),
+          h2_rec(k_h2_asm_carry_links, n, H2A_ONE_THREADS, d_tab),
+          h2_rec(k_h2_asm_begin_links, n * H2A_LINK_GRID, H2A_THREADS, d_tab, n),
+          h2_rec(k_h2_asm_bytes_links, n * H2A_LINK_GRID, H2A_THREADS, d_tab, n),
+          h2_rec(k_h2_asm_finish_links, n, H2A_ONE_THREADS, d_tab),
+          h2_rec(k_h2_asm_copy_links, H2A_GRID, H2A_THREADS, d_tab, n)};
+}
+static const size_t H2_ASM_PLAN = 5;  // records of an assembler stage in front of its copy (timed apart by the standalone calls)
+
+// The reply framer of one transport (csrc/grdma_h2_reply.h): plan, then emit -- in front of a job a linear chain.
+static h2_stage h2_stage_reply(h2r_dev* d) {
+  return {h2_rec(k_h2_reply_plan, 1, PLAN_THREADS, d), h2_rec(k_h2_reply_emit, H2R_GRID, H2_EMIT_THREADS, d)};
+}
+// ... of n links in the same two launches
+static_assert(H2R_LINKS_MAX == GRDMA_H2_BATCH_MAX, "the reply's link table is the batch's");
+static h2_stage h2_stage_reply_links(const h2r_link* d_tab, uint32_t n) {
+  return {h2_rec(k_h2_reply_plan_links, n, PLAN_THREADS, d_tab), h2_rec(k_h2_reply_emit_links, H2R_GRID, H2_EMIT_THREADS, d_tab, n)};
+}
+
+// st goes behind the parser's last deframing by a pipe (the parser state is handed from one deframing to the next),
+// unless that one was enqueued on st itself.  (Only pipe steps leave last_deframed, on a job's or a deframe stream: for
+// the standalone calls, on the stream of their own, the exception never holds and they always wait.)
+static bool h2_wait_parser(hipStream_t st, const grdma_h2_parser* p) {
+  return !p->last_deframed || p->last_stream == st || hipStreamWaitEvent(st, p->last_deframed, 0) == hipSuccess;
+}
+
+// a host message table in the device's form
+static std::vector<grdma_h2_msg_dev> h2_msg_table(const grdma_h2_msg* msgs, uint64_t n) {
+  std::vector<grdma_h2_msg_dev> tab(n);
+  for (uint64_t i = 0; i < n; i++) {
+    tab[i].payload = static_cast<const uint8_t*>(msgs[i].payload);
+    tab[i].len = msgs[i].len;
+    tab[i].stream_id = msgs[i].stream_id;
+    tab[i].flags = msgs[i].flags;
+  }
+  return tab;
+}
+// ... uploaded to a device table of its own (a pipe's: the caller frees it)
+static bool h2_upload_msgs(const grdma_h2_msg* msgs, uint64_t n, grdma_h2_msg_dev** d_msgs) {
+  const std::vector<grdma_h2_msg_dev> tab = h2_msg_table(msgs, n);
+  return hipMalloc((void**)d_msgs, sizeof(grdma_h2_msg_dev) * n) == hipSuccess &&
+         hipMemcpy(*d_msgs, tab.data(), sizeof(grdma_h2_msg_dev) * n, hipMemcpyHostToDevice) == hipSuccess;
 }
 
 static double g_h2_last_kernel_us = 0;
@@ -222,14 +313,9 @@ int64_t grdma_h2_frame_messages(const grdma_h2_msg* msgs, uint64_t n, uint32_t m
     return -GRDMA_ERR_INVALID;
   h2_host_ctx* hc = h2_ctx();
   if (!hc) return -GRDMA_ERR_HIP;
-  std::vector<grdma_h2_msg_dev> tmp(n);
-  for (uint64_t i = 0; i < n; i++) {
-    tmp[i].payload = static_cast<const uint8_t*>(msgs[i].payload);
-    tmp[i].len = msgs[i].len;
-    tmp[i].stream_id = msgs[i].stream_id;
-    tmp[i].flags = msgs[i].flags;
+  for (uint64_t i = 0; i < n; i++)
     if (msgs[i].len >= (1ull << 32)) return -GRDMA_ERR_INVALID;  // 32-bit message length field
-  }
+  const std::vector<grdma_h2_msg_dev> tmp = h2_msg_table(msgs, n);
   static grdma_h2_msg_dev* d_msgs = nullptr;
   static uint64_t msgs_cap = 0;
   static grdma_h2_frame_result* d_res = nullptr;
@@ -243,10 +329,10 @@ int64_t grdma_h2_frame_messages(const grdma_h2_msg* msgs, uint64_t n, uint32_t m
       hipMemsetAsync(d_res, 0, sizeof(grdma_h2_frame_result), st) != hipSuccess)
     return -GRDMA_ERR_HIP;
   hipEventRecord(hc->e0, st);
-  h2_enqueue_frame(d_msgs, n, max_frame, reinterpret_cast<grdma_sge*>(d_slices_out), slices_cap,
-                   static_cast<uint8_t*>(d_hdr_arena), hdr_cap, d_pos, d_res, st);
+  const hipError_t launched = h2_launch(h2_stage_frame(d_msgs, n, max_frame, reinterpret_cast<grdma_sge*>(d_slices_out), slices_cap,
+                                                       static_cast<uint8_t*>(d_hdr_arena), hdr_cap, d_pos, d_res), st);
   hipEventRecord(hc->e1, st);
-  if (hipMemcpyAsync(&h_res, d_res, sizeof(h_res), hipMemcpyDeviceToHost, st) != hipSuccess ||
+  if (launched != hipSuccess || hipMemcpyAsync(&h_res, d_res, sizeof(h_res), hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess)
     return -GRDMA_ERR_HIP;
   float ms = 0;
@@ -394,9 +480,11 @@ int64_t grdma_h2_deframe(grdma_h2_parser* p, const void* d_arena, const grdma_re
     return -GRDMA_ERR_HIP;
   const bool chunked = n >= H2_CHUNK_MIN_SLICES && h2_chunks_prepare(p, cap, st);
   hipEventRecord(hc->e0, st);
-  h2_enqueue_deframe(p, static_cast<const uint8_t*>(d_arena), p->d_sl, n, p->d_ev, cap, p->d_res, st, chunked);
+  const hipError_t launched =
+      h2_launch(h2_stage_deframe(p, static_cast<const uint8_t*>(d_arena), p->d_sl, n, p->d_ev, cap, p->d_res, chunked), st);
   hipEventRecord(hc->e1, st);
-  if (hipMemcpyAsync(&h_res, p->d_res, sizeof(h_res), hipMemcpyDeviceToHost, st) != hipSuccess ||
+  if (launched != hipSuccess ||
+      hipMemcpyAsync(&h_res, p->d_res, sizeof(h_res), hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess)
     return -GRDMA_ERR_HIP;
   float ms = 0;
@@ -486,15 +574,11 @@ int grdma_h2_deframe_batch(grdma_h2_deframe_item* items, uint32_t n_items) {
     a_ev += it.cap;
   }
   // behind each parser's previous deframing (a pipe step on another stream)
-  for (uint32_t i = 0; i < n_items; i++) {
-    grdma_h2_parser* p = items[i].parser;
-    if (p->last_deframed && p->last_stream != st && hipStreamWaitEvent(st, p->last_deframed, 0) != hipSuccess) return -GRDMA_ERR_HIP;
-  }
+  for (uint32_t i = 0; i < n_items; i++)
+    if (!h2_wait_parser(st, items[i].parser)) return -GRDMA_ERR_HIP;
   if (hipMemcpyAsync(d, up.data(), o_ev, hipMemcpyHostToDevice, st) != hipSuccess) return -GRDMA_ERR_HIP;
   hipEventRecord(hc->e0, st);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(k_h2_deframe_links, dim3(n_items), dim3(H2_DEFRAME_THREADS), 0, st, (const grdma_h2_link_deframe*)d);
-  if (hipGetLastError() != hipSuccess) {
+  if (h2_launch(h2_stage_deframe_links((const grdma_h2_link_deframe*)d, n_items), st) != hipSuccess) {
     hipStreamSynchronize(st);
     return grdma_fail_msg(GRDMA_ERR_HIP, "h2 batch: the launch of k_h2_deframe_links was rejected");
   }
@@ -515,329 +599,6 @@ int grdma_h2_deframe_batch(grdma_h2_deframe_item* items, uint32_t n_items) {
     it.n_events = res[i].overflow ? -(int64_t)GRDMA_ERR_CAPACITY : (int64_t)m;
     a_ev += it.cap;
   }
-  return 0;
-}
-
-// ---- HTTP/2 inside the device pipeline ------------------------------------------------------
-// frame (k_h2_frame_index + k_h2_frame_emit rebuild the job's slice list from the message table) -> the streaming job
-// -> deframe (the deframer over the slices the job delivered), all enqueued.  By default the two stages are kernel
-// nodes of the job's own graph (one launch per step); with GRDMA_H2_PIPE_FUSED=0, and under the engine schedule, they
-// are enqueued around the job's launch, ordered by events, with per-stage event timing.
-struct grdma_stream_job;
-int grdma_job_link_view(grdma_stream_job* j, uint32_t link, grdma_sge** d_sges, uint64_t* count,
-                        grdma_slice_out** d_slices, uint8_t** dst, hipStream_t* stream);
-extern "C" uint32_t grdma_job_link_count(grdma_stream_job* j);
-extern "C" int grdma_job_link_step_slices(grdma_stream_job* j, uint32_t link, const uint64_t** d_count, uint64_t* cap);
-int grdma_stream_job_launch(grdma_stream_job* j);
-extern "C" int grdma_job_set_hooks(grdma_stream_job* j, const grdma_job_hook* pre, uint32_t n_pre, const grdma_job_hook* post,
-                                   uint32_t n_post);
-extern "C" int grdma_job_hook_counts(grdma_stream_job* j, uint32_t out[2]);
-
-struct grdma_h2_pipe {
-  grdma_stream_job* job = nullptr;
-  grdma_h2_parser* parser = nullptr;
-  grdma_sge* d_sges = nullptr;
-  uint64_t count = 0;
-  grdma_slice_out* d_slices = nullptr;
-  uint8_t* dst = nullptr;
-  hipStream_t job_stream = nullptr, frame_stream = nullptr, deframe_stream = nullptr;
-  hipEvent_t framed = nullptr, job_done = nullptr, deframed = nullptr;
-  hipEvent_t t_f0 = nullptr, t_d0 = nullptr, t_f1 = nullptr, t_d1 = nullptr;  // kernel start / end stamps of the last step
-  grdma_h2_msg_dev* d_msgs = nullptr;
-  grdma_h2_msg_pos* d_pos = nullptr;
-  uint64_t nmsgs = 0;
-  uint32_t max_frame = 16384;
-  uint8_t* d_hdr = nullptr;
-  uint64_t hdr_cap = 0;
-  grdma_h2_frame_result* d_fres = nullptr;
-  grdma_h2_deframe_result* d_dres = nullptr;
-  grdma_h2_event* d_ev = nullptr;
-  uint64_t ev_cap = 0, delivered = 0;
-  uint64_t boundary_steps = 0, t_boundary = 0;  // of the last synced step
-  bool launched = false;
-  bool chunked = false;  // the parser has chunk buffers for this pipe's event capacity
-  bool fused = false;    // framing and deframing are nodes of the job's graph (one launch per step)
-  bool timed = false;    // the last step recorded the per-stage timing events
-  grdma_h2_asm* asm_ = nullptr;  // the message assembler behind the deframer (grdma_h2_pipe_attach_assembler)
-  h2a_call* d_call = nullptr;    // where this pipe's deframer leaves its output, for the assembler
-  grdma_h2_reply* reply = nullptr;  // a reply pipe (grdma_h2_pipe_create_reply): the framing stage is csrc/grdma_h2_reply.h
-  grdma_job_hook pre[2], post[2];
-  uint32_t n_pre = 0, n_post = 0;
-};
-
-namespace {
-hipStream_t g_pipe_frame_stream = nullptr, g_pipe_deframe_stream = nullptr;
-}
-static void h2_asm_detach(grdma_h2_pipe* p);
-static void h2_asm_enqueue(grdma_h2_asm* a, const h2a_call* d_call, hipStream_t st);
-// reply pipes and the pipes they read from (defined with grdma_h2_reply below)
-static bool h2_asm_read_by_reply_pipes(const grdma_h2_asm* a);
-static hipEvent_t h2_asm_last_read(const grdma_h2_asm* a);
-static bool h2_reply_bind_pipe(grdma_h2_reply* r, grdma_h2_pipe* p, uint64_t recorded_wire_bytes);
-static void h2_reply_unbind_pipe(grdma_h2_pipe* p);
-static int h2_reply_wait_source(grdma_h2_pipe* p, hipStream_t st);
-static void h2_reply_enqueue(grdma_h2_reply* r, hipStream_t st);
-static void h2_reply_step_enqueued(grdma_h2_pipe* p, hipEvent_t read_done);
-static uint32_t h2_reply_hooks(grdma_h2_reply* r, grdma_job_hook* out);
-static bool h2_reply_result(grdma_h2_reply* r, grdma_h2_frame_result* fr);
-
-// msgs / nmsgs / max_frame: the host message table of grdma_h2_pipe_create; reply: the framing stage of
-// grdma_h2_pipe_create_reply instead
-static grdma_h2_pipe* h2_pipe_create(grdma_stream_job* job, uint32_t link, const grdma_h2_msg* msgs, uint64_t nmsgs,
-                                     uint32_t max_frame, grdma_h2_parser* parser, uint64_t delivered_slices,
-                                     uint64_t events_cap, grdma_h2_reply* reply, uint64_t recorded_wire_bytes) {
-  if (grdma_device_count() <= 0 || !job || !parser) return nullptr;
-  if (!reply && (!msgs || !nmsgs || max_frame == 0 || max_frame >= (1u << 24))) return nullptr;
-  if (!g_pipe_frame_stream &&
-      (hipStreamCreateWithFlags(&g_pipe_frame_stream, hipStreamNonBlocking) != hipSuccess ||
-       hipStreamCreateWithFlags(&g_pipe_deframe_stream, hipStreamNonBlocking) != hipSuccess))
-    return nullptr;
-  grdma_h2_pipe* p = new grdma_h2_pipe();
-  p->job = job;
-  p->parser = parser;
-  p->nmsgs = nmsgs;
-  p->max_frame = max_frame;
-  p->delivered = delivered_slices;
-  p->ev_cap = events_cap;
-  p->frame_stream = g_pipe_frame_stream;      // shared by all pipes: framings are ordered among themselves
-  p->deframe_stream = g_pipe_deframe_stream;  // shared: the parser state is handed from one deframing to the next
-  std::vector<grdma_h2_msg_dev> tmp(nmsgs);
-  for (uint64_t i = 0; i < nmsgs; i++) {
-    tmp[i].payload = static_cast<const uint8_t*>(msgs[i].payload);
-    tmp[i].len = msgs[i].len;
-    tmp[i].stream_id = msgs[i].stream_id;
-    tmp[i].flags = msgs[i].flags;
-  }
-  bool ok = grdma_job_link_view(job, link, &p->d_sges, &p->count, &p->d_slices, &p->dst, &p->job_stream) == 0;
-  // The deframing goes behind the job on the JOB's stream unless GRDMA_H2_DEFRAME_STREAM=1 asks for a stream of its
-  // own: the next job does not start before the deframing has ended either way (measured: kernels of the two streams
-  // do not run side by side), and a hand-over between streams costs ~20 us of idle device on each side of it.
-  static const bool own_stream = [] { const char* e = getenv("GRDMA_H2_DEFRAME_STREAM"); return e && atoi(e) != 0; }();
-  if (ok && !own_stream) p->deframe_stream = p->job_stream;
-  p->hdr_cap = 32 * (p->count + 64);
-  // (a reply pipe has no message table of its own: the reply's plan builds one per step)
-  ok = ok && (reply || (hipMalloc((void**)&p->d_msgs, sizeof(grdma_h2_msg_dev) * nmsgs) == hipSuccess &&
-                       hipMalloc((void**)&p->d_pos, sizeof(grdma_h2_msg_pos) * nmsgs) == hipSuccess &&
-                       hipMemcpy(p->d_msgs, tmp.data(), sizeof(grdma_h2_msg_dev) * nmsgs, hipMemcpyHostToDevice) == hipSuccess)) &&
-       hipMalloc((void**)&p->d_hdr, p->hdr_cap) == hipSuccess &&
-       hipMalloc((void**)&p->d_fres, sizeof(grdma_h2_frame_result)) == hipSuccess &&
-       hipMalloc((void**)&p->d_dres, sizeof(grdma_h2_deframe_result)) == hipSuccess &&
-       hipMalloc((void**)&p->d_ev, sizeof(grdma_h2_event) * (events_cap ? events_cap : 1)) == hipSuccess &&
-       hipEventCreateWithFlags(&p->framed, hipEventDisableTiming) == hipSuccess &&
-       hipEventCreateWithFlags(&p->job_done, hipEventDisableTiming) == hipSuccess &&
-       hipEventCreateWithFlags(&p->deframed, hipEventDisableTiming) == hipSuccess &&
-       hipEventCreate(&p->t_f0) == hipSuccess && hipEventCreate(&p->t_f1) == hipSuccess &&
-       hipEventCreate(&p->t_d0) == hipSuccess && hipEventCreate(&p->t_d1) == hipSuccess;
-  ok = ok && (!reply || h2_reply_bind_pipe(reply, p, recorded_wire_bytes));
-  if (!ok) {
-    grdma_h2_pipe_destroy(p);
-    return nullptr;
-  }
-  p->chunked = delivered_slices >= H2_CHUNK_MIN_SLICES && h2_chunks_prepare(parser, events_cap, p->deframe_stream);
-  // Framing and deframing as nodes of the job's own graph (default; GRDMA_H2_PIPE_FUSED=0: stages enqueued around the
-  // graph launch, with per-stage event timing): a graph boundary costs ~15-20 us of idle device on each side.
-  const char* fe = getenv("GRDMA_H2_PIPE_FUSED");
-  if (!fe || atoi(fe) != 0) {
-    auto arg = [](uint64_t v) { return v; };
-    auto ptr = [](const void* q) { return (uint64_t)(uintptr_t)q; };
-    grdma_job_hook pre[2], post[2];
-    memset(pre, 0, sizeof(pre));
-    memset(post, 0, sizeof(post));
-    const uint64_t per = H2_EMIT_THREADS / 64;
-    uint32_t n_pre = 2;
-    if (p->reply) {
-      n_pre = h2_reply_hooks(p->reply, pre);
-    } else if (p->nmsgs <= H2_FRAME_ONE_MAX) {
-      pre[0] = grdma_job_hook{(const void*)k_h2_frame_one, (uint32_t)((p->nmsgs + per - 1) / per), H2_EMIT_THREADS,
-                              {ptr(p->d_msgs), arg(p->nmsgs), arg(p->max_frame), ptr(p->d_sges), arg(p->count), ptr(p->d_hdr),
-                               arg(p->hdr_cap), ptr(p->d_fres)}};
-      n_pre = 1;
-    } else {
-      pre[0] = grdma_job_hook{(const void*)k_h2_frame_index, 1, 256,
-                              {ptr(p->d_msgs), arg(p->nmsgs), arg(p->max_frame), arg(p->count), arg(p->hdr_cap), ptr(p->d_pos),
-                               ptr(p->d_fres)}};
-      pre[1] = grdma_job_hook{(const void*)k_h2_frame_emit, (uint32_t)((p->nmsgs + per - 1) / per), H2_EMIT_THREADS,
-                              {ptr(p->d_msgs), arg(p->nmsgs), arg(p->max_frame), ptr(p->d_sges), arg(p->count), ptr(p->d_hdr),
-                               arg(p->hdr_cap), ptr(p->d_pos)}};
-    }
-    uint32_t n_post;
-    if (p->chunked) {
-      post[0] = grdma_job_hook{(const void*)k_h2_deframe_chunks, (uint32_t)parser->chunks_want, H2_DEFRAME_THREADS,
-                               {ptr(parser->d), ptr(parser->d_chunks), ptr(p->dst), ptr(p->d_slices), arg(p->delivered)}};
-      post[1] = grdma_job_hook{(const void*)k_h2_merge_or_deframe, H2_MERGE_GRID, H2_DEFRAME_THREADS,
-                               {ptr(parser->d), ptr(parser->d_chunks), ptr(p->dst), ptr(p->d_slices), arg(p->delivered),
-                                ptr(p->d_ev), arg(p->ev_cap), ptr(p->d_dres)}};
-      n_post = 2;
-    } else {
-      post[0] = grdma_job_hook{(const void*)k_h2_deframe, 1, H2_DEFRAME_THREADS,
-                               {ptr(parser->d), ptr(p->dst), ptr(p->d_slices), arg(p->delivered), ptr(p->d_ev), arg(p->ev_cap),
-                                ptr(p->d_dres)}};
-      n_post = 1;
-    }
-    memcpy(p->pre, pre, sizeof(pre));
-    memcpy(p->post, post, sizeof(post));
-    p->n_pre = n_pre;
-    p->n_post = n_post;
-    if (grdma_job_set_hooks(job, pre, n_pre, post, n_post) != 0) {
-      grdma_h2_pipe_destroy(p);
-      return nullptr;
-    }
-    p->fused = true;
-    p->deframe_stream = p->job_stream;
-  }
-  return p;
-}
-
-grdma_h2_pipe* grdma_h2_pipe_create(grdma_stream_job* job, uint32_t link, const grdma_h2_msg* msgs, uint64_t nmsgs,
-                                    uint32_t max_frame, grdma_h2_parser* parser, uint64_t delivered_slices,
-                                    uint64_t events_cap) {
-  return h2_pipe_create(job, link, msgs, nmsgs, max_frame, parser, delivered_slices, events_cap, nullptr, 0);
-}
-
-grdma_h2_pipe* grdma_h2_pipe_create_reply(grdma_stream_job* job_back, uint32_t link, grdma_h2_reply* reply,
-                                          grdma_h2_parser* parser_back, uint64_t delivered_slices, uint64_t events_cap,
-                                          uint64_t recorded_wire_bytes) {
-  if (!reply) return nullptr;
-  return h2_pipe_create(job_back, link, nullptr, 0, 0, parser_back, delivered_slices, events_cap, reply, recorded_wire_bytes);
-}
-
-void grdma_h2_pipe_destroy(grdma_h2_pipe* p) {
-  if (!p) return;
-  if (h2_asm_read_by_reply_pipes(p->asm_)) return;  // (a reply pipe's job gathers from this pipe's arena: destroy that one first)
-  if (p->launched) {
-    hipStreamSynchronize(p->frame_stream);
-    hipStreamSynchronize(p->job_stream);
-    hipStreamSynchronize(p->deframe_stream);
-  }
-  if (p->parser && p->parser->last_deframed == p->deframed) p->parser->last_deframed = nullptr;  // (synchronised above)
-  if (p->fused && p->job) grdma_job_set_hooks(p->job, nullptr, 0, nullptr, 0);
-  h2_reply_unbind_pipe(p);
-  h2_asm_detach(p);
-  hipFree(p->d_call);
-  hipFree(p->d_msgs);
-  hipFree(p->d_pos);
-  hipFree(p->d_hdr);
-  hipFree(p->d_fres);
-  hipFree(p->d_dres);
-  hipFree(p->d_ev);
-  if (p->framed) hipEventDestroy(p->framed);
-  if (p->job_done) hipEventDestroy(p->job_done);
-  if (p->deframed) hipEventDestroy(p->deframed);
-  for (hipEvent_t e : {p->t_f0, p->t_f1, p->t_d0, p->t_d1})
-    if (e) hipEventDestroy(e);
-  delete p;
-}
-
-// One step on the job's captured graph (schedule 0: the only schedule since the link engine was retired).
-int grdma_h2_pipe_enqueue(grdma_h2_pipe* p, int schedule) {
-  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!p || schedule != 0) return -GRDMA_ERR_INVALID;
-  if (p->fused && schedule == 0) {
-    // one graph launch: [k_h2_frame_index, k_h2_frame_emit] -> the job's rounds -> [the deframer]; steps and pipes
-    // of one connection are ordered by the job's stream (a parser last used on another stream: by its event)
-    if (p->parser->last_deframed && p->parser->last_stream != p->job_stream &&
-        hipStreamWaitEvent(p->job_stream, p->parser->last_deframed, 0) != hipSuccess)
-      return -GRDMA_ERR_HIP;
-    // a reply step reads what the forward step assembled; a forward step's release waits for the reply step that
-    // still gathers from the arena
-    if (p->reply && h2_reply_wait_source(p, p->job_stream) != 0) return -GRDMA_ERR_HIP;
-    if (hipEvent_t rd = h2_asm_last_read(p->asm_))
-      if (hipStreamWaitEvent(p->job_stream, rd, 0) != hipSuccess) return -GRDMA_ERR_HIP;
-    const int rc = grdma_stream_job_launch(p->job);
-    if (rc < 0) return rc;
-    if (hipEventRecord(p->deframed, p->job_stream) != hipSuccess) return -GRDMA_ERR_HIP;
-    if (p->reply) h2_reply_step_enqueued(p, p->deframed);
-    p->parser->last_stream = p->job_stream;
-    p->parser->last_deframed = p->deframed;
-    p->launched = true;
-    p->timed = false;
-    return 0;
-  }
-  p->timed = true;
-  // framing overwrites the slice table the job's previous step read
-  if (p->launched && hipStreamWaitEvent(p->frame_stream, p->job_done, 0) != hipSuccess) return -GRDMA_ERR_HIP;
-  if (hipMemsetAsync(p->d_fres, 0, sizeof(grdma_h2_frame_result), p->frame_stream) != hipSuccess) return -GRDMA_ERR_HIP;
-  if (p->reply && h2_reply_wait_source(p, p->frame_stream) != 0) return -GRDMA_ERR_HIP;
-  hipEventRecord(p->t_f0, p->frame_stream);
-  if (p->reply)
-    h2_reply_enqueue(p->reply, p->frame_stream);
-  else
-    h2_enqueue_frame(p->d_msgs, p->nmsgs, p->max_frame, p->d_sges, p->count, p->d_hdr, p->hdr_cap, p->d_pos, p->d_fres,
-                     p->frame_stream);
-  hipEventRecord(p->t_f1, p->frame_stream);
-  if (hipEventRecord(p->framed, p->frame_stream) != hipSuccess) return -GRDMA_ERR_HIP;
-  // the job reads the slice table and overwrites what the previous deframing parsed
-  if (hipStreamWaitEvent(p->job_stream, p->framed, 0) != hipSuccess) return -GRDMA_ERR_HIP;
-  if (p->launched && p->deframe_stream != p->job_stream && hipStreamWaitEvent(p->job_stream, p->deframed, 0) != hipSuccess)
-    return -GRDMA_ERR_HIP;
-  const int rc = grdma_stream_job_launch(p->job);
-  if (rc < 0) return rc;
-  if (hipEventRecord(p->job_done, p->job_stream) != hipSuccess) return -GRDMA_ERR_HIP;
-  if (p->reply) h2_reply_step_enqueued(p, p->job_done);
-  if (p->deframe_stream != p->job_stream && hipStreamWaitEvent(p->deframe_stream, p->job_done, 0) != hipSuccess)
-    return -GRDMA_ERR_HIP;
-  if (p->parser->last_deframed && p->parser->last_stream != p->deframe_stream &&
-      hipStreamWaitEvent(p->deframe_stream, p->parser->last_deframed, 0) != hipSuccess)
-    return -GRDMA_ERR_HIP;  // (the parser state is handed from one deframing to the next)
-  hipEventRecord(p->t_d0, p->deframe_stream);
-  h2_enqueue_deframe(p->parser, p->dst, p->d_slices, p->delivered, p->d_ev, p->ev_cap, p->d_dres, p->deframe_stream, p->chunked);
-  if (hipEvent_t rd = h2_asm_last_read(p->asm_))  // (the release at the start of the assembly, behind the reply's gather)
-    if (hipStreamWaitEvent(p->deframe_stream, rd, 0) != hipSuccess) return -GRDMA_ERR_HIP;
-  if (p->asm_) h2_asm_enqueue(p->asm_, p->d_call, p->deframe_stream);
-  hipEventRecord(p->t_d1, p->deframe_stream);
-  if (hipEventRecord(p->deframed, p->deframe_stream) != hipSuccess) return -GRDMA_ERR_HIP;
-  p->parser->last_stream = p->deframe_stream;
-  p->parser->last_deframed = p->deframed;
-  p->launched = true;
-  return 0;
-}
-
-// Wait for the last step and report it: out = {slices framed, frame overflow, events, deframe
-// overflow, slices parsed, h2 error, framing kernel us, deframing kernel us, bulk steps, frames
-// parsed by bulk steps, then the deframer's device-clock ticks: waiting for the look-ahead ring,
-// in bulk steps, total, in the byte-wise path}; events_out (may be NULL) receives up to cap events.
-int grdma_h2_pipe_sync(grdma_h2_pipe* p, uint64_t out[14], grdma_h2_event* events_out, uint64_t cap) {
-  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!p || !out) return -GRDMA_ERR_INVALID;
-  if (hipStreamSynchronize(p->frame_stream) != hipSuccess || hipStreamSynchronize(p->job_stream) != hipSuccess ||
-      hipStreamSynchronize(p->deframe_stream) != hipSuccess)
-    return -GRDMA_ERR_HIP;
-  grdma_h2_frame_result fr;
-  grdma_h2_deframe_result dr;
-  if (hipMemcpy(&fr, p->d_fres, sizeof(fr), hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(&dr, p->d_dres, sizeof(dr), hipMemcpyDeviceToHost) != hipSuccess)
-    return -GRDMA_ERR_HIP;
-  if (p->reply && !h2_reply_result(p->reply, &fr)) return -GRDMA_ERR_HIP;  // (overflow 2: not the recorded shape)
-  out[0] = fr.nslices;
-  out[1] = fr.overflow;
-  out[2] = dr.nevents;
-  out[3] = dr.overflow;
-  out[4] = dr.slices_done;
-  out[5] = (uint64_t)dr.error;
-  out[8] = dr.bulk_steps;
-  out[9] = dr.bulk_frames;
-  out[10] = dr.t_wait;
-  out[11] = dr.t_bulk;
-  out[12] = dr.t_total;
-  out[13] = dr.t_serial;
-  p->boundary_steps = dr.boundary_steps;
-  p->t_boundary = dr.t_boundary;
-  float fms = 0, dms = 0;
-  out[6] = out[7] = 0;
-  if (p->launched && p->timed && hipEventElapsedTime(&fms, p->t_f0, p->t_f1) == hipSuccess) out[6] = (uint64_t)(fms * 1e3f);
-  if (p->launched && p->timed && hipEventElapsedTime(&dms, p->t_d0, p->t_d1) == hipSuccess) out[7] = (uint64_t)(dms * 1e3f);
-  const uint64_t m = std::min<uint64_t>(std::min<uint64_t>(dr.nevents, cap), p->ev_cap);
-  if (events_out && m && hipMemcpy(events_out, p->d_ev, sizeof(grdma_h2_event) * m, hipMemcpyDeviceToHost) != hipSuccess)
-    return -GRDMA_ERR_HIP;
-  return 0;
-}
-
-
-// {message starts taken by the boundary step, device-clock ticks inside it} of the last synced step
-int grdma_h2_pipe_boundary_stats(grdma_h2_pipe* p, uint64_t out[2]) {
-  if (!p || !out) return -GRDMA_ERR_INVALID;
-  out[0] = p->boundary_steps;
-  out[1] = p->t_boundary;
   return 0;
 }
 
@@ -901,40 +662,16 @@ static bool h2_asm_prepare(grdma_h2_asm* a, uint64_t ev_cap) {
                    hipMemcpyHostToDevice) == hipSuccess && ok;
 }
 
-// the assembly of one call, enqueued on st behind its deframing
-static void h2_asm_enqueue(grdma_h2_asm* a, const h2a_call* d_call, hipStream_t st) {
-  h2a_dev* d = a->d;
-  hipLaunchKernelGGL(k_h2_asm_tiles, dim3(H2A_GRID), dim3(H2A_THREADS), 0, st, d, d_call);
-  hipLaunchKernelGGL(k_h2_asm_carry, dim3(1), dim3(H2A_ONE_THREADS), 0, st, d, d_call);
-  hipLaunchKernelGGL(k_h2_asm_begin, dim3(H2A_GRID), dim3(H2A_THREADS), 0, st, d, d_call);
-  hipLaunchKernelGGL(k_h2_asm_bytes, dim3(H2A_GRID), dim3(H2A_THREADS), 0, st, d, d_call);
-  hipLaunchKernelGGL(k_h2_asm_finish, dim3(1), dim3(H2A_ONE_THREADS), 0, st, d, d_call);
-  hipLaunchKernelGGL(k_h2_asm_copy, dim3(H2A_GRID), dim3(H2A_THREADS), 0, st, d, d_call);
-}
-
-// the same six kernels as post hooks of a fused pipe's graph, behind the deframer's
-static uint32_t h2_asm_hooks(grdma_h2_asm* a, const h2a_call* d_call, grdma_job_hook* out) {
-  const void* fns[6] = {(const void*)k_h2_asm_tiles, (const void*)k_h2_asm_carry, (const void*)k_h2_asm_begin,
-                        (const void*)k_h2_asm_bytes, (const void*)k_h2_asm_finish, (const void*)k_h2_asm_copy};
-  const uint32_t grids[6] = {H2A_GRID, 1, H2A_GRID, H2A_GRID, 1, H2A_GRID};
-  const uint32_t threads[6] = {H2A_THREADS, H2A_ONE_THREADS, H2A_THREADS, H2A_THREADS, H2A_ONE_THREADS, H2A_THREADS};
-  for (int k = 0; k < 6; k++) {
-    memset(&out[k], 0, sizeof(out[k]));
-    out[k].fn = fns[k];
-    out[k].grid = grids[k];
-    out[k].threads = threads[k];
-    out[k].args[0] = (uint64_t)(uintptr_t)a->d;
-    out[k].args[1] = (uint64_t)(uintptr_t)d_call;
-  }
-  return 6;
-}
-
-static void h2_asm_detach(grdma_h2_pipe* p) {
-  if (p->asm_) {
-    p->asm_->parser->asm_attached--;
-    p->asm_->attached--;
-    p->asm_ = nullptr;
-  }
+// The descriptors an assembler reports, from its block h as the caller read it behind the assembly: copied to out on st
+// (the caller synchronises st when the count is not 0), or with a blocking copy when st is NULL.  Returns their
+// number, -GRDMA_ERR_CAPACITY when the call was skipped or they do not fit.
+static int64_t h2_asm_descriptors(const h2a_dev& h, grdma_h2_rx_msg* out, uint64_t cap, hipStream_t st) {
+  if (h.skip || h.ndesc > cap || h.ndesc > h.desc_cap) return -GRDMA_ERR_CAPACITY;
+  const size_t bytes = sizeof(grdma_h2_rx_msg) * h.ndesc;
+  if (h.ndesc && (st ? hipMemcpyAsync(out, h.desc, bytes, hipMemcpyDeviceToHost, st)
+                     : hipMemcpy(out, h.desc, bytes, hipMemcpyDeviceToHost)) != hipSuccess)
+    return -GRDMA_ERR_HIP;
+  return (int64_t)h.ndesc;
 }
 
 grdma_h2_asm* grdma_h2_asm_create(grdma_h2_parser* parser, void* d_arena, uint64_t arena_bytes,
@@ -998,22 +735,18 @@ int64_t grdma_h2_deframe_messages(grdma_h2_parser* p, grdma_h2_asm* a, const voi
       (n && hipMemcpyAsync(p->d_sl, slices, sizeof(grdma_slice_out) * n, hipMemcpyHostToDevice, st) != hipSuccess))
     return -GRDMA_ERR_HIP;
   const bool chunked = n >= H2_CHUNK_MIN_SLICES && h2_chunks_prepare(p, ev_cap, st);
-  h2_enqueue_deframe(p, static_cast<const uint8_t*>(d_arena), p->d_sl, n, p->d_ev, ev_cap, p->d_res, st, chunked);
-  // the assembly: the plan (five kernels), then the copy, timed apart
-  h2a_dev* d = a->d;
+  hipError_t launched = h2_launch(h2_stage_deframe(p, static_cast<const uint8_t*>(d_arena), p->d_sl, n, p->d_ev, ev_cap, p->d_res, chunked), st);
+  // the assembly: the plan, then the copy, timed apart
+  const h2_stage assembly = h2_stage_asm(a->d, a->d_call);
   hipEventRecord(a->e0, st);
-  hipLaunchKernelGGL(k_h2_asm_tiles, dim3(H2A_GRID), dim3(H2A_THREADS), 0, st, d, (const h2a_call*)a->d_call);
-  hipLaunchKernelGGL(k_h2_asm_carry, dim3(1), dim3(H2A_ONE_THREADS), 0, st, d, (const h2a_call*)a->d_call);
-  hipLaunchKernelGGL(k_h2_asm_begin, dim3(H2A_GRID), dim3(H2A_THREADS), 0, st, d, (const h2a_call*)a->d_call);
-  hipLaunchKernelGGL(k_h2_asm_bytes, dim3(H2A_GRID), dim3(H2A_THREADS), 0, st, d, (const h2a_call*)a->d_call);
-  hipLaunchKernelGGL(k_h2_asm_finish, dim3(1), dim3(H2A_ONE_THREADS), 0, st, d, (const h2a_call*)a->d_call);
+  if (launched == hipSuccess) launched = h2_launch(assembly.data(), H2_ASM_PLAN, st);
   hipEventRecord(a->e1, st);
-  hipLaunchKernelGGL(k_h2_asm_copy, dim3(H2A_GRID), dim3(H2A_THREADS), 0, st, d, (const h2a_call*)a->d_call);
+  if (launched == hipSuccess) launched = h2_launch(assembly.data() + H2_ASM_PLAN, assembly.size() - H2_ASM_PLAN, st);
   hipEventRecord(a->e2, st);
   grdma_h2_deframe_result h_res;
   h2a_dev h;
-  if (hipMemcpyAsync(&h_res, p->d_res, sizeof(h_res), hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+  if (launched != hipSuccess || hipMemcpyAsync(&h_res, p->d_res, sizeof(h_res), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(&h, a->d, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
     return -GRDMA_ERR_HIP;
   if (hipEventElapsedTime(&a->plan_ms, a->e0, a->e1) != hipSuccess) a->plan_ms = 0;
   if (hipEventElapsedTime(&a->copy_ms, a->e1, a->e2) != hipSuccess) a->copy_ms = 0;
@@ -1023,12 +756,10 @@ int64_t grdma_h2_deframe_messages(grdma_h2_parser* p, grdma_h2_asm* a, const voi
       (hipMemcpyAsync(events_out, p->d_ev, sizeof(grdma_h2_event) * m, hipMemcpyDeviceToHost, st) != hipSuccess ||
        hipStreamSynchronize(st) != hipSuccess))
     return -GRDMA_ERR_HIP;
-  if (h_res.overflow || h.skip) return -GRDMA_ERR_CAPACITY;
-  if (h.ndesc > msgs_cap || h.ndesc > h.desc_cap) return -GRDMA_ERR_CAPACITY;
-  if (h.ndesc && (hipMemcpyAsync(msgs_out, h.desc, sizeof(grdma_h2_rx_msg) * h.ndesc, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                  hipStreamSynchronize(st) != hipSuccess))
-    return -GRDMA_ERR_HIP;
-  return (int64_t)h.ndesc;
+  if (h_res.overflow) return -GRDMA_ERR_CAPACITY;
+  const int64_t nmsgs = h2_asm_descriptors(h, msgs_out, msgs_cap, st);
+  if (nmsgs > 0 && hipStreamSynchronize(st) != hipSuccess) return -GRDMA_ERR_HIP;
+  return nmsgs;
 }
 
 int grdma_h2_asm_release(grdma_h2_asm* a, uint64_t count) {
@@ -1037,10 +768,9 @@ int grdma_h2_asm_release(grdma_h2_asm* a, uint64_t count) {
   h2_host_ctx* hc = h2_ctx();
   if (!hc) return -GRDMA_ERR_HIP;
   // behind the last standalone call (same stream) and the last pipe step of the parser
-  if (a->parser->last_deframed && hipStreamWaitEvent(hc->stream, a->parser->last_deframed, 0) != hipSuccess)
-    return -GRDMA_ERR_HIP;
-  hipLaunchKernelGGL(k_h2_asm_release, dim3(1), dim3(64), 0, hc->stream, a->d, count);
-  return hipGetLastError() == hipSuccess ? 0 : -GRDMA_ERR_HIP;
+  if (!h2_wait_parser(hc->stream, a->parser)) return -GRDMA_ERR_HIP;
+  const grdma_job_hook release = h2_rec(k_h2_asm_release, 1, 64, a->d, count);
+  return h2_launch(&release, 1, hc->stream) == hipSuccess ? 0 : -GRDMA_ERR_HIP;
 }
 
 int grdma_h2_asm_stats(grdma_h2_asm* a, uint64_t out[8]) {
@@ -1049,8 +779,7 @@ int grdma_h2_asm_stats(grdma_h2_asm* a, uint64_t out[8]) {
   h2_host_ctx* hc = h2_ctx();
   if (!hc) return -GRDMA_ERR_HIP;
   h2a_dev h;
-  if (a->parser->last_deframed && hipStreamWaitEvent(hc->stream, a->parser->last_deframed, 0) != hipSuccess)
-    return -GRDMA_ERR_HIP;
+  if (!h2_wait_parser(hc->stream, a->parser)) return -GRDMA_ERR_HIP;
   if (hipMemcpyAsync(&h, a->d, sizeof(h), hipMemcpyDeviceToHost, hc->stream) != hipSuccess ||
       hipStreamSynchronize(hc->stream) != hipSuccess)
     return -GRDMA_ERR_HIP;
@@ -1065,69 +794,16 @@ int grdma_h2_asm_stats(grdma_h2_asm* a, uint64_t out[8]) {
   return 0;
 }
 
-int grdma_h2_pipe_attach_assembler(grdma_h2_pipe* p, grdma_h2_asm* a) {
-  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!p || !a || a->parser != p->parser || p->asm_) return -GRDMA_ERR_INVALID;
-  if (p->launched && hipStreamSynchronize(p->deframe_stream) != hipSuccess) return -GRDMA_ERR_HIP;
-  if (!h2_asm_prepare(a, p->ev_cap ? p->ev_cap : 1)) return -GRDMA_ERR_HIP;
-  const h2a_call call{p->d_ev, p->d_dres, p->d_slices, p->dst, p->ev_cap, 1};
-  if (!p->d_call && hipMalloc((void**)&p->d_call, sizeof(h2a_call)) != hipSuccess) return -GRDMA_ERR_HIP;
-  if (hipMemcpy(p->d_call, &call, sizeof(call), hipMemcpyHostToDevice) != hipSuccess) return -GRDMA_ERR_HIP;
-  if (p->fused) {
-    grdma_job_hook post[8];
-    memcpy(post, p->post, sizeof(grdma_job_hook) * p->n_post);
-    const uint32_t n_post = p->n_post + h2_asm_hooks(a, p->d_call, post + p->n_post);
-    if (grdma_job_set_hooks(p->job, p->pre, p->n_pre, post, n_post) != 0) return -GRDMA_ERR_HIP;
-  }
-  p->asm_ = a;
-  a->attached++;
-  a->parser->asm_attached++;
-  return 0;
-}
-
-int64_t grdma_h2_pipe_messages(grdma_h2_pipe* p, grdma_h2_rx_msg* out, uint64_t cap) {
-  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!p || !p->asm_ || (!out && cap)) return -GRDMA_ERR_INVALID;
-  h2a_dev h;
-  // the step's assembly ends with its deframing event (fused: the job's graph; else the deframe stream)
-  if ((p->launched && hipEventSynchronize(p->deframed) != hipSuccess) || hipStreamSynchronize(p->deframe_stream) != hipSuccess ||
-      hipMemcpy(&h, p->asm_->d, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess)
-    return -GRDMA_ERR_HIP;
-  if (h.skip || h.ndesc > cap || h.ndesc > h.desc_cap) return -GRDMA_ERR_CAPACITY;
-  if (h.ndesc && hipMemcpy(out, h.desc, sizeof(grdma_h2_rx_msg) * h.ndesc, hipMemcpyDeviceToHost) != hipSuccess)
-    return -GRDMA_ERR_HIP;
-  return (int64_t)h.ndesc;
-}
-
 // ---- replies framed from the descriptors (csrc/grdma_h2_reply.h) ---------------------------------------------
-struct grdma_h2_group_pipe;
+struct h2_step_seq;
 struct grdma_h2_reply {
   grdma_h2_asm* src = nullptr;
   h2r_dev* d = nullptr;
   h2r_dev h;                        // host copy of the configuration words
   grdma_h2_route* d_routes = nullptr;
-  grdma_h2_pipe* pipe = nullptr;    // the reply pipe that frames through it (at most one: the scratch is one call's)
-  grdma_h2_group_pipe* gpipe = nullptr;  // ... or the group reply pipe (grdma_h2_group_pipe_create_reply)
+  h2_step_seq* seq = nullptr;       // the steps of the reply pipe, single or group, that frames through it (at most one: the scratch is one call's)
   hipEvent_t e0 = nullptr, e1 = nullptr;
 };
-
-static void h2_reply_enqueue(grdma_h2_reply* r, hipStream_t st) {
-  hipLaunchKernelGGL(k_h2_reply_plan, dim3(1), dim3(PLAN_THREADS), 0, st, r->d);
-  hipLaunchKernelGGL(k_h2_reply_emit, dim3(H2R_GRID), dim3(H2_EMIT_THREADS), 0, st, (const h2r_dev*)r->d);
-}
-
-// the same two kernels as pre hooks of the back job's graph: a linear chain in front of its first round
-static uint32_t h2_reply_hooks(grdma_h2_reply* r, grdma_job_hook* out) {
-  memset(out, 0, 2 * sizeof(grdma_job_hook));
-  out[0].fn = (const void*)k_h2_reply_plan;
-  out[0].grid = 1;
-  out[0].threads = PLAN_THREADS;
-  out[1].fn = (const void*)k_h2_reply_emit;
-  out[1].grid = H2R_GRID;
-  out[1].threads = H2_EMIT_THREADS;
-  out[0].args[0] = out[1].args[0] = (uint64_t)(uintptr_t)r->d;
-  return 2;
-}
 
 // where the calls frame to, and (a pipe) the shape they must have: the words of h2r_dev from `out` to the result block
 static bool h2_reply_set_target(grdma_h2_reply* r, grdma_sge* out, uint64_t cap, uint8_t* hdr, uint64_t hdr_cap,
@@ -1146,38 +822,6 @@ static bool h2_reply_set_target(grdma_h2_reply* r, grdma_sge* out, uint64_t cap,
   return (st ? hipMemcpyAsync(dst, src, len, hipMemcpyHostToDevice, st) : hipMemcpy(dst, src, len, hipMemcpyHostToDevice)) ==
          hipSuccess;
 }
-
-static bool h2_reply_bind_pipe(grdma_h2_reply* r, grdma_h2_pipe* p, uint64_t recorded_wire_bytes) {
-  if (r->pipe || r->gpipe || !r->src->attached) return false;  // (the source of a reply pipe assembles in forward pipes)
-  if (!h2_reply_set_target(r, p->d_sges, p->count, p->d_hdr, p->hdr_cap, 1, p->count, recorded_wire_bytes, nullptr)) return false;
-  r->pipe = p;
-  r->src->reply_pipes++;
-  p->reply = r;
-  p->max_frame = r->h.max_frame;
-  return true;
-}
-
-static void h2_reply_unbind_pipe(grdma_h2_pipe* p) {
-  grdma_h2_reply* r = p->reply;
-  if (!r) return;
-  // (the pipe's streams are synchronised: nothing gathers from the source's arena any more)
-  if (r->src->last_read == p->deframed || r->src->last_read == p->job_done) r->src->last_read = nullptr;
-  r->src->reply_pipes--;
-  r->pipe = nullptr;
-  p->reply = nullptr;
-}
-
-static bool h2_asm_read_by_reply_pipes(const grdma_h2_asm* a) { return a && a->reply_pipes != 0; }
-static hipEvent_t h2_asm_last_read(const grdma_h2_asm* a) { return a ? a->last_read : nullptr; }
-
-// the reply's plan goes behind the assembly of the last forward step enqueued (the forward parser's event)
-static int h2_reply_wait_source(grdma_h2_pipe* p, hipStream_t st) {
-  const grdma_h2_parser* fp = p->reply->src->parser;
-  if (fp->last_deframed && fp->last_stream != st && hipStreamWaitEvent(st, fp->last_deframed, 0) != hipSuccess) return -1;
-  return 0;
-}
-
-static void h2_reply_step_enqueued(grdma_h2_pipe* p, hipEvent_t read_done) { p->reply->src->last_read = read_done; }
 
 static bool h2_reply_result(grdma_h2_reply* r, grdma_h2_frame_result* fr) {
   uint64_t res[8];
@@ -1225,7 +869,7 @@ grdma_h2_reply* grdma_h2_reply_create(grdma_h2_asm* source, const grdma_h2_route
 }
 
 void grdma_h2_reply_destroy(grdma_h2_reply* r) {
-  if (!r || r->pipe || r->gpipe) return;  // (the pipe's graph still runs the kernels on it: destroy the pipe first)
+  if (!r || r->seq) return;  // (the pipe's graph still runs the kernels on it: destroy the pipe first)
   h2_host_ctx* hc = h2_ctx();
   if (hc) hipStreamSynchronize(hc->stream);  // (standalone calls)
   r->src->replies--;
@@ -1242,7 +886,7 @@ int64_t grdma_h2_reply_frame(grdma_h2_reply* r, grdma_slice* d_slices_out, uint6
                              uint64_t hdr_cap, uint64_t out[8]) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
   if (!r || !d_slices_out || !slices_cap || !d_hdr_arena || !hdr_cap || !out || ((uintptr_t)d_slices_out & 15) ||
-      ((uintptr_t)d_hdr_arena & 15) || r->pipe || r->gpipe || r->src->attached)
+      ((uintptr_t)d_hdr_arena & 15) || r->seq || r->src->attached)
     return -GRDMA_ERR_INVALID;
   h2_host_ctx* hc = h2_ctx();
   if (!hc) return -GRDMA_ERR_HIP;
@@ -1252,11 +896,11 @@ int64_t grdma_h2_reply_frame(grdma_h2_reply* r, grdma_slice* d_slices_out, uint6
                            hdr_cap, 0, 0, 0, st))
     return -GRDMA_ERR_HIP;
   hipEventRecord(r->e0, st);
-  h2_reply_enqueue(r, st);
+  const hipError_t launched = h2_launch(h2_stage_reply(r->d), st);
   hipEventRecord(r->e1, st);
   uint64_t res[8];
-  if (hipMemcpyAsync(res, reinterpret_cast<uint8_t*>(r->d) + offsetof(h2r_dev, res), sizeof(res), hipMemcpyDeviceToHost, st) !=
-          hipSuccess ||
+  if (launched != hipSuccess ||
+      hipMemcpyAsync(res, reinterpret_cast<uint8_t*>(r->d) + offsetof(h2r_dev, res), sizeof(res), hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess)
     return -GRDMA_ERR_HIP;
   float ms = 0;
@@ -1266,11 +910,10 @@ int64_t grdma_h2_reply_frame(grdma_h2_reply* r, grdma_slice* d_slices_out, uint6
   return (int64_t)res[H2R_SLICES];
 }
 
-// ---- the replies of many transports in two launches (k_h2_reply_plan_links, k_h2_reply_emit_links) ----------------
+// ---- the replies of many transports in two launches (h2_stage_reply_links) ------------------------------------------
 // The batch block of the process holds the call: [table | one h2r_dev per item] goes up in one copy -- the item's
 // framer with the item's targets and a zeroed result block; scratch, routes and source stay the reply's own -- and the
 // h2r_dev blocks come down in one copy.  One call at a time, as the other batch calls.
-static_assert(H2R_LINKS_MAX == GRDMA_H2_BATCH_MAX, "the reply's link table is the batch's");
 
 int grdma_h2_reply_frame_batch(grdma_h2_reply_item* items, uint32_t n_items) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
@@ -1282,7 +925,7 @@ int grdma_h2_reply_frame_batch(grdma_h2_reply_item* items, uint32_t n_items) {
     if (!it.d_slices_out || !it.slices_cap || !it.d_hdr_arena || !it.hdr_cap || ((uintptr_t)it.d_slices_out & 15) ||
         ((uintptr_t)it.d_hdr_arena & 15))
       return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: a null, zero or misaligned slice table or header arena");
-    if (it.reply->pipe || it.reply->gpipe) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: a reply bound to a reply pipe");
+    if (it.reply->seq) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: a reply bound to a reply pipe");
     if (it.reply->src->attached)
       return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: a source assembler attached to a pipe or group pipe");
     for (uint32_t k = 0; k < i; k++) {
@@ -1318,16 +961,11 @@ int grdma_h2_reply_frame_batch(grdma_h2_reply_item* items, uint32_t n_items) {
     tab[i].R = reinterpret_cast<h2r_dev*>(d + o_dev) + i;
   }
   // behind each source parser's last deframing (a pipe step on another stream; the standalone calls share this stream)
-  for (uint32_t i = 0; i < n_items; i++) {
-    const grdma_h2_parser* p = items[i].reply->src->parser;
-    if (p->last_deframed && p->last_stream != st && hipStreamWaitEvent(st, p->last_deframed, 0) != hipSuccess) return -GRDMA_ERR_HIP;
-  }
+  for (uint32_t i = 0; i < n_items; i++)
+    if (!h2_wait_parser(st, items[i].reply->src->parser)) return -GRDMA_ERR_HIP;
   if (hipMemcpyAsync(d, up.data(), total, hipMemcpyHostToDevice, st) != hipSuccess) return -GRDMA_ERR_HIP;
   hipEventRecord(hc->e0, st);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(k_h2_reply_plan_links, dim3(n_items), dim3(PLAN_THREADS), 0, st, (const h2r_link*)d);
-  hipLaunchKernelGGL(k_h2_reply_emit_links, dim3(H2R_GRID), dim3(H2_EMIT_THREADS), 0, st, (const h2r_link*)d, n_items);
-  if (hipGetLastError() != hipSuccess) {
+  if (h2_launch(h2_stage_reply_links((const h2r_link*)d, n_items), st) != hipSuccess) {
     hipStreamSynchronize(st);
     return grdma_fail_msg(GRDMA_ERR_HIP, "h2 reply batch: a launch was rejected");
   }
@@ -1348,461 +986,7 @@ int grdma_h2_reply_frame_batch(grdma_h2_reply_item* items, uint32_t n_items) {
   return 0;
 }
 
-int64_t grdma_h2_pipe_slice_table(grdma_h2_pipe* p, grdma_slice* out, uint64_t cap) {
-  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!p || (!out && cap)) return -GRDMA_ERR_INVALID;
-  if (p->count > cap) return -GRDMA_ERR_CAPACITY;
-  static_assert(sizeof(grdma_slice) == sizeof(grdma_sge), "layout");
-  if (hipStreamSynchronize(p->frame_stream) != hipSuccess || hipStreamSynchronize(p->job_stream) != hipSuccess ||
-      (p->count && hipMemcpy(out, p->d_sges, sizeof(grdma_sge) * p->count, hipMemcpyDeviceToHost) != hipSuccess))
-    return -GRDMA_ERR_HIP;
-  return (int64_t)p->count;
-}
-
-// ---- HTTP/2 on several links of ONE job (the group pipe) -----------------------------------------------------------
-// A job carries one set of hooks (grdma_job_set_hooks assigns): the stages of all listed links are ONE framing kernel
-// over a table of links (k_h2_frame_links) in front of the job and ONE deframing kernel (k_h2_deframe_links) behind
-// it -- one launch per step however many links.  Links that are not listed keep their tables and are carried as before.
-struct h2_group_link {
-  uint32_t link = 0;
-  grdma_h2_parser* parser = nullptr;
-  grdma_sge* d_sges = nullptr;
-  uint64_t count = 0;
-  grdma_slice_out* d_slices = nullptr;
-  uint8_t* dst = nullptr;
-  grdma_h2_msg_dev* d_msgs = nullptr;
-  uint64_t nmsgs = 0;
-  uint8_t* d_hdr = nullptr;
-  uint64_t hdr_cap = 0;
-  grdma_h2_event* d_ev = nullptr;
-  uint64_t ev_cap = 0, delivered = 0;
-};
-struct grdma_h2_group_pipe {
-  grdma_stream_job* job = nullptr;
-  std::vector<h2_group_link> links;
-  hipStream_t job_stream = nullptr, frame_stream = nullptr;
-  grdma_h2_link_frame* d_ftab = nullptr;
-  grdma_h2_link_deframe* d_dtab = nullptr;
-  grdma_h2_frame_result* d_fres = nullptr;    // one per listed link
-  grdma_h2_deframe_result* d_dres = nullptr;  // one per listed link
-  uint32_t frame_grid = 0;
-  hipEvent_t framed = nullptr, job_done = nullptr, deframed = nullptr;
-  hipEvent_t t_f0 = nullptr, t_f1 = nullptr, t_d0 = nullptr, t_d1 = nullptr;
-  bool launched = false, fused = false, timed = false;
-  grdma_job_hook pre[2], post;        // the framing kernel(s) and the deframing kernel in the job's graph (fused)
-  uint32_t n_pre = 0;
-  // a group reply pipe (grdma_h2_group_pipe_create_reply): the framing stage is k_h2_reply_plan_links + k_h2_reply_emit_links
-  std::vector<grdma_h2_reply*> replies;  // per spec
-  h2r_link* d_rtab = nullptr;
-  std::vector<grdma_h2_asm*> asms;    // per spec, NULL = none (grdma_h2_group_pipe_attach_assemblers)
-  h2a_link* d_atab = nullptr;         // the links with an assembler, in spec order
-  h2a_call* d_calls = nullptr;        // their call blocks
-  uint32_t n_asm = 0;
-};
-static void h2_asm_links_enqueue(const h2a_link* d_tab, uint32_t n, hipStream_t st);
-static void h2_group_detach(grdma_h2_group_pipe* p);
-static void h2_group_unbind_replies(grdma_h2_group_pipe* p);
-
-static grdma_h2_group_pipe* h2_group_refuse(grdma_h2_group_pipe* p, const char* why) {
-  grdma_h2_group_pipe_destroy(p);
-  grdma_fail_msg(GRDMA_ERR_INVALID, why);
-  return nullptr;
-}
-
-// specs: the message tables of grdma_h2_group_pipe_create; rspecs: the replies of grdma_h2_group_pipe_create_reply
-// instead (exactly one of the two)
-static grdma_h2_group_pipe* h2_group_create(grdma_stream_job* job, const grdma_h2_link_spec* specs,
-                                            const grdma_h2_reply_link_spec* rspecs, uint32_t n, uint32_t max_frame) {
-  if (grdma_device_count() <= 0) return nullptr;
-  if (!job || (!specs && !rspecs) || n == 0 || n > GRDMA_H2_BATCH_MAX) return h2_group_refuse(nullptr, "h2 group pipe: a job and 1 .. GRDMA_H2_BATCH_MAX link specs");
-  if (specs && (max_frame == 0 || max_frame >= (1u << 24))) return h2_group_refuse(nullptr, "h2 group pipe: max_frame out of range");
-  auto link_of = [&](uint32_t i) { return specs ? specs[i].link : rspecs[i].link; };
-  auto parser_of = [&](uint32_t i) { return specs ? specs[i].parser : rspecs[i].parser_back; };
-  for (uint32_t i = 0; i < n; i++) {
-    if (specs && (!specs[i].msgs || specs[i].nmsgs == 0 || specs[i].nmsgs > H2_FRAME_ONE_MAX))
-      return h2_group_refuse(nullptr, "h2 group pipe: 1 .. 4096 messages per link");
-    if (rspecs && !rspecs[i].reply) return h2_group_refuse(nullptr, "h2 group reply pipe: a link without reply");
-    if (!parser_of(i)) return h2_group_refuse(nullptr, "h2 group pipe: a link without parser");
-    for (uint32_t k = 0; k < i; k++) {
-      if (link_of(k) == link_of(i)) return h2_group_refuse(nullptr, "h2 group pipe: a link listed twice");
-      if (parser_of(k) == parser_of(i)) return h2_group_refuse(nullptr, "h2 group pipe: a parser listed twice");
-      if (rspecs && rspecs[k].reply == rspecs[i].reply) return h2_group_refuse(nullptr, "h2 group reply pipe: a reply listed twice");
-    }
-  }
-  const uint32_t job_links = grdma_job_link_count(job);
-  for (uint32_t i = 0; i < n; i++)
-    if (link_of(i) >= job_links) return h2_group_refuse(nullptr, "h2 group pipe: a link index out of range");
-  for (uint32_t i = 0; specs && i < n; i++)
-    for (uint64_t k = 0; k < specs[i].nmsgs; k++)
-      if (specs[i].msgs[k].len >= (1ull << 32)) return h2_group_refuse(nullptr, "h2 group pipe: a message of 4 GiB or more");
-  for (uint32_t i = 0; rspecs && i < n; i++) {
-    const grdma_h2_reply* r = rspecs[i].reply;
-    if (r->pipe || r->gpipe) return h2_group_refuse(nullptr, "h2 group reply pipe: a reply bound to a pipe already");
-    // (the source of a reply pipe assembles in forward pipes: a standalone source is framed by grdma_h2_reply_frame)
-    if (!r->src->attached) return h2_group_refuse(nullptr, "h2 group reply pipe: a source assembler that is not attached to a forward pipe");
-  }
-  uint32_t have[2] = {0, 0};
-  if (grdma_job_hook_counts(job, have) != 0) return nullptr;
-  if (have[0] || have[1]) return h2_group_refuse(nullptr, "h2 group pipe: the job already carries hooks (another pipe's)");
-  if (!g_pipe_frame_stream &&
-      (hipStreamCreateWithFlags(&g_pipe_frame_stream, hipStreamNonBlocking) != hipSuccess ||
-       hipStreamCreateWithFlags(&g_pipe_deframe_stream, hipStreamNonBlocking) != hipSuccess))
-    return nullptr;
-  grdma_h2_group_pipe* p = new grdma_h2_group_pipe();
-  p->job = job;
-  p->frame_stream = g_pipe_frame_stream;
-  p->links.resize(n);
-  std::vector<grdma_h2_link_frame> ftab(n);
-  std::vector<grdma_h2_link_deframe> dtab(n);
-  const uint64_t per = H2_EMIT_THREADS / 64;
-  std::vector<h2r_link> rtab(n);
-  bool ok = hipMalloc((void**)&p->d_ftab, sizeof(grdma_h2_link_frame) * n) == hipSuccess &&
-            (!rspecs || hipMalloc((void**)&p->d_rtab, sizeof(h2r_link) * n) == hipSuccess) &&
-            hipMalloc((void**)&p->d_dtab, sizeof(grdma_h2_link_deframe) * n) == hipSuccess &&
-            hipMalloc((void**)&p->d_fres, sizeof(grdma_h2_frame_result) * n) == hipSuccess &&
-            hipMalloc((void**)&p->d_dres, sizeof(grdma_h2_deframe_result) * n) == hipSuccess &&
-            hipMemset(p->d_fres, 0, sizeof(grdma_h2_frame_result) * n) == hipSuccess &&
-            hipMemset(p->d_dres, 0, sizeof(grdma_h2_deframe_result) * n) == hipSuccess;
-  for (uint32_t i = 0; ok && i < n; i++) {
-    h2_group_link& l = p->links[i];
-    const uint64_t* d_step = nullptr;
-    uint64_t slices_cap = 0;
-    if (grdma_job_link_view(job, link_of(i), &l.d_sges, &l.count, &l.d_slices, &l.dst, &p->job_stream) != 0 ||
-        grdma_job_link_step_slices(job, link_of(i), &d_step, &slices_cap) != 0)
-      return h2_group_refuse(p, "h2 group pipe: a link index out of range");
-    l.link = link_of(i);
-    l.parser = parser_of(i);
-    l.nmsgs = specs ? specs[i].nmsgs : 0;
-    l.delivered = specs ? specs[i].delivered_slices : rspecs[i].delivered_slices;
-    l.ev_cap = specs ? specs[i].events_cap : rspecs[i].events_cap;
-    l.hdr_cap = 32 * (l.count + 64);
-    ok = hipMalloc((void**)&l.d_hdr, l.hdr_cap) == hipSuccess &&
-         hipMalloc((void**)&l.d_ev, sizeof(grdma_h2_event) * (l.ev_cap ? l.ev_cap : 1)) == hipSuccess;
-    if (specs) {
-      const grdma_h2_link_spec& sp = specs[i];
-      std::vector<grdma_h2_msg_dev> tmp(sp.nmsgs);
-      for (uint64_t k = 0; k < sp.nmsgs; k++) {
-        tmp[k].payload = static_cast<const uint8_t*>(sp.msgs[k].payload);
-        tmp[k].len = sp.msgs[k].len;
-        tmp[k].stream_id = sp.msgs[k].stream_id;
-        tmp[k].flags = sp.msgs[k].flags;
-      }
-      ok = ok && hipMalloc((void**)&l.d_msgs, sizeof(grdma_h2_msg_dev) * sp.nmsgs) == hipSuccess &&
-           hipMemcpy(l.d_msgs, tmp.data(), sizeof(grdma_h2_msg_dev) * sp.nmsgs, hipMemcpyHostToDevice) == hipSuccess;
-    } else if (ok) {
-      // the link's framer writes the link's slice table, and only a reply of the shape the job's graph was recorded for
-      grdma_h2_reply* r = rspecs[i].reply;
-      ok = h2_reply_set_target(r, l.d_sges, l.count, l.d_hdr, l.hdr_cap, 1, l.count, rspecs[i].recorded_wire_bytes, nullptr);
-      if (ok) {
-        r->gpipe = p;
-        r->src->reply_pipes++;
-        p->replies.push_back(r);
-        rtab[i].R = r->d;
-      }
-    }
-    grdma_h2_link_frame& f = ftab[i];
-    f.msgs = l.d_msgs;
-    f.nmsgs = l.nmsgs;
-    f.out = l.d_sges;
-    f.cap = l.count;
-    f.hdr = l.d_hdr;
-    f.hdr_cap = l.hdr_cap;
-    f.res = p->d_fres + i;
-    f.max_frame = max_frame;
-    f.wg0 = p->frame_grid;
-    p->frame_grid += (uint32_t)((l.nmsgs + per - 1) / per);
-    // the step's own slice count, as the job's drain leaves it on the device (the recorded run's count is what the
-    // caller expects; a step at another ring phase may deliver a slice more or less), bounded by the table
-    grdma_h2_link_deframe& q = dtab[i];
-    q.res = p->d_dres + i;
-    q.gp = l.parser->d;
-    q.arena = l.dst;
-    q.slices = l.d_slices;
-    q.nslices = slices_cap;
-    q.ev = l.d_ev;
-    q.ev_cap = l.ev_cap;
-    q.n_step = d_step;
-  }
-  ok = ok && hipMemcpy(p->d_ftab, ftab.data(), sizeof(grdma_h2_link_frame) * n, hipMemcpyHostToDevice) == hipSuccess &&
-       (!rspecs || hipMemcpy(p->d_rtab, rtab.data(), sizeof(h2r_link) * n, hipMemcpyHostToDevice) == hipSuccess) &&
-       hipMemcpy(p->d_dtab, dtab.data(), sizeof(grdma_h2_link_deframe) * n, hipMemcpyHostToDevice) == hipSuccess &&
-       hipEventCreateWithFlags(&p->framed, hipEventDisableTiming) == hipSuccess &&
-       hipEventCreateWithFlags(&p->job_done, hipEventDisableTiming) == hipSuccess &&
-       hipEventCreateWithFlags(&p->deframed, hipEventDisableTiming) == hipSuccess &&
-       hipEventCreate(&p->t_f0) == hipSuccess && hipEventCreate(&p->t_f1) == hipSuccess &&
-       hipEventCreate(&p->t_d0) == hipSuccess && hipEventCreate(&p->t_d1) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    grdma_h2_group_pipe_destroy(p);
-    grdma_fail_msg(GRDMA_ERR_HIP, "h2 group pipe: device allocation failed");
-    return nullptr;
-  }
-  const char* fe = getenv("GRDMA_H2_PIPE_FUSED");
-  if (!fe || atoi(fe) != 0) {
-    grdma_job_hook pre[2], post;
-    memset(pre, 0, sizeof(pre));
-    memset(&post, 0, sizeof(post));
-    uint32_t n_pre = 1;
-    if (rspecs) {  // a linear chain in front of the job's first round, as the single reply pipe's
-      pre[0].fn = (const void*)k_h2_reply_plan_links;
-      pre[0].grid = n;
-      pre[0].threads = PLAN_THREADS;
-      pre[1].fn = (const void*)k_h2_reply_emit_links;
-      pre[1].grid = H2R_GRID;
-      pre[1].threads = H2_EMIT_THREADS;
-      pre[0].args[0] = pre[1].args[0] = (uint64_t)(uintptr_t)p->d_rtab;
-      pre[1].args[1] = n;
-      n_pre = 2;
-    } else {
-      pre[0].fn = (const void*)k_h2_frame_links;
-      pre[0].grid = p->frame_grid;
-      pre[0].threads = H2_EMIT_THREADS;
-      pre[0].args[0] = (uint64_t)(uintptr_t)p->d_ftab;
-      pre[0].args[1] = n;
-    }
-    post.fn = (const void*)k_h2_deframe_links;
-    post.grid = n;
-    post.threads = H2_DEFRAME_THREADS;
-    post.args[0] = (uint64_t)(uintptr_t)p->d_dtab;
-    if (grdma_job_set_hooks(job, pre, n_pre, &post, 1) != 0) {
-      grdma_h2_group_pipe_destroy(p);
-      return nullptr;
-    }
-    memcpy(p->pre, pre, sizeof(pre));
-    p->n_pre = n_pre;
-    p->post = post;
-    p->fused = true;
-  }
-  return p;
-}
-
-grdma_h2_group_pipe* grdma_h2_group_pipe_create(grdma_stream_job* job, const grdma_h2_link_spec* specs, uint32_t n,
-                                                uint32_t max_frame) {
-  if (!specs) return h2_group_refuse(nullptr, "h2 group pipe: a job and 1 .. GRDMA_H2_BATCH_MAX link specs");
-  return h2_group_create(job, specs, nullptr, n, max_frame);
-}
-
-grdma_h2_group_pipe* grdma_h2_group_pipe_create_reply(grdma_stream_job* job_back, const grdma_h2_reply_link_spec* specs,
-                                                      uint32_t n) {
-  if (!specs) return h2_group_refuse(nullptr, "h2 group pipe: a job and 1 .. GRDMA_H2_BATCH_MAX link specs");
-  return h2_group_create(job_back, nullptr, specs, n, 0);
-}
-
-// a group reply pipe lets go of its replies (its streams are synchronised: nothing gathers from the sources' arenas)
-static void h2_group_unbind_replies(grdma_h2_group_pipe* p) {
-  for (grdma_h2_reply* r : p->replies) {
-    if (r->src->last_read == p->deframed || r->src->last_read == p->job_done) r->src->last_read = nullptr;
-    r->src->reply_pipes--;
-    r->gpipe = nullptr;
-  }
-  p->replies.clear();
-}
-
-void grdma_h2_group_pipe_destroy(grdma_h2_group_pipe* p) {
-  if (!p) return;
-  for (const grdma_h2_asm* a : p->asms)
-    if (h2_asm_read_by_reply_pipes(a)) return;  // (a reply pipe's job gathers from this pipe's arenas: destroy that one first)
-  if (p->launched) {
-    hipStreamSynchronize(p->frame_stream);
-    hipStreamSynchronize(p->job_stream);
-  }
-  for (h2_group_link& l : p->links) {
-    if (l.parser && l.parser->last_deframed == p->deframed) l.parser->last_deframed = nullptr;  // (synchronised above)
-    hipFree(l.d_msgs);
-    hipFree(l.d_hdr);
-    hipFree(l.d_ev);
-  }
-  if (p->fused && p->job) grdma_job_set_hooks(p->job, nullptr, 0, nullptr, 0);
-  h2_group_unbind_replies(p);
-  h2_group_detach(p);
-  hipFree(p->d_rtab);
-  hipFree(p->d_atab);
-  hipFree(p->d_calls);
-  hipFree(p->d_ftab);
-  hipFree(p->d_dtab);
-  hipFree(p->d_fres);
-  hipFree(p->d_dres);
-  for (hipEvent_t e : {p->framed, p->job_done, p->deframed, p->t_f0, p->t_f1, p->t_d0, p->t_d1})
-    if (e) hipEventDestroy(e);
-  delete p;
-}
-
-int grdma_h2_group_pipe_enqueue(grdma_h2_group_pipe* p) {
-  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!p) return -GRDMA_ERR_INVALID;
-  const uint32_t n = (uint32_t)p->links.size();
-  // every parser's state is handed over from its previous deframing (a pipe step or a call on another stream)
-  auto wait_parsers = [&]() {
-    for (h2_group_link& l : p->links)
-      if (l.parser->last_deframed && l.parser->last_stream != p->job_stream &&
-          hipStreamWaitEvent(p->job_stream, l.parser->last_deframed, 0) != hipSuccess)
-        return false;
-    return true;
-  };
-  auto done = [&]() {
-    for (h2_group_link& l : p->links) {
-      l.parser->last_stream = p->job_stream;
-      l.parser->last_deframed = p->deframed;
-    }
-    p->launched = true;
-  };
-  // a reply step reads what the forward steps assembled: behind every distinct source parser's last deframing
-  auto wait_sources = [&](hipStream_t st) {
-    for (size_t i = 0; i < p->replies.size(); i++) {
-      const grdma_h2_parser* fp = p->replies[i]->src->parser;
-      bool seen = false;
-      for (size_t k = 0; k < i && !seen; k++) seen = p->replies[k]->src->parser == fp;
-      if (!seen && fp->last_deframed && fp->last_stream != st && hipStreamWaitEvent(st, fp->last_deframed, 0) != hipSuccess)
-        return false;
-    }
-    return true;
-  };
-  // ... and a step's release (at the start of its assembly) waits for the last reply step that gathers from the arena
-  auto wait_readers = [&]() {
-    for (const grdma_h2_asm* a : p->asms)
-      if (hipEvent_t rd = h2_asm_last_read(a))
-        if (hipStreamWaitEvent(p->job_stream, rd, 0) != hipSuccess) return false;
-    return true;
-  };
-  auto sources_read_until = [&](hipEvent_t read_done) {
-    for (grdma_h2_reply* r : p->replies) r->src->last_read = read_done;
-  };
-  if (p->fused) {  // one graph launch: the framing kernel(s) -> the job's rounds -> k_h2_deframe_links [-> the six k_h2_asm_*_links]
-    if (!wait_parsers() || !wait_sources(p->job_stream) || !wait_readers()) return -GRDMA_ERR_HIP;
-    const int rc = grdma_stream_job_launch(p->job);
-    if (rc < 0) return rc;
-    if (hipEventRecord(p->deframed, p->job_stream) != hipSuccess) return -GRDMA_ERR_HIP;
-    sources_read_until(p->deframed);
-    p->timed = false;
-    done();
-    return 0;
-  }
-  p->timed = true;
-  // framing overwrites the slice tables the job's previous step read
-  if (p->launched && hipStreamWaitEvent(p->frame_stream, p->job_done, 0) != hipSuccess) return -GRDMA_ERR_HIP;
-  if (hipMemsetAsync(p->d_fres, 0, sizeof(grdma_h2_frame_result) * n, p->frame_stream) != hipSuccess) return -GRDMA_ERR_HIP;
-  if (!wait_sources(p->frame_stream)) return -GRDMA_ERR_HIP;
-  hipEventRecord(p->t_f0, p->frame_stream);
-  if (p->d_rtab) {
-    hipLaunchKernelGGL(k_h2_reply_plan_links, dim3(n), dim3(PLAN_THREADS), 0, p->frame_stream, (const h2r_link*)p->d_rtab);
-    hipLaunchKernelGGL(k_h2_reply_emit_links, dim3(H2R_GRID), dim3(H2_EMIT_THREADS), 0, p->frame_stream,
-                       (const h2r_link*)p->d_rtab, n);
-  } else {
-    hipLaunchKernelGGL(k_h2_frame_links, dim3(p->frame_grid), dim3(H2_EMIT_THREADS), 0, p->frame_stream,
-                       (const grdma_h2_link_frame*)p->d_ftab, n);
-  }
-  hipEventRecord(p->t_f1, p->frame_stream);
-  if (hipEventRecord(p->framed, p->frame_stream) != hipSuccess) return -GRDMA_ERR_HIP;
-  if (hipStreamWaitEvent(p->job_stream, p->framed, 0) != hipSuccess) return -GRDMA_ERR_HIP;
-  if (!wait_readers()) return -GRDMA_ERR_HIP;
-  const int rc = grdma_stream_job_launch(p->job);
-  if (rc < 0) return rc;
-  if (hipEventRecord(p->job_done, p->job_stream) != hipSuccess) return -GRDMA_ERR_HIP;
-  sources_read_until(p->job_done);
-  // the deframing goes behind the job on the job's stream (csrc: why the single pipe does the same by default)
-  if (!wait_parsers()) return -GRDMA_ERR_HIP;
-  hipEventRecord(p->t_d0, p->job_stream);
-  hipLaunchKernelGGL(k_h2_deframe_links, dim3(n), dim3(H2_DEFRAME_THREADS), 0, p->job_stream,
-                     (const grdma_h2_link_deframe*)p->d_dtab);
-  if (p->n_asm) h2_asm_links_enqueue(p->d_atab, p->n_asm, p->job_stream);
-  hipEventRecord(p->t_d1, p->job_stream);
-  if (hipEventRecord(p->deframed, p->job_stream) != hipSuccess) return -GRDMA_ERR_HIP;
-  done();
-  return 0;
-}
-
-static int h2_group_wait(grdma_h2_group_pipe* p) {
-  if (hipStreamSynchronize(p->frame_stream) != hipSuccess || hipStreamSynchronize(p->job_stream) != hipSuccess) return -GRDMA_ERR_HIP;
-  return 0;
-}
-
-int grdma_h2_group_pipe_sync(grdma_h2_group_pipe* p, uint64_t* out, uint64_t out_words) {
-  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!p || !out || out_words < 14 * p->links.size()) return -GRDMA_ERR_INVALID;
-  if (int rc = h2_group_wait(p)) return rc;
-  const size_t n = p->links.size();
-  std::vector<grdma_h2_frame_result> fr(n);
-  std::vector<grdma_h2_deframe_result> dr(n);
-  if (hipMemcpy(fr.data(), p->d_fres, sizeof(grdma_h2_frame_result) * n, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(dr.data(), p->d_dres, sizeof(grdma_h2_deframe_result) * n, hipMemcpyDeviceToHost) != hipSuccess)
-    return -GRDMA_ERR_HIP;
-  for (size_t i = 0; i < p->replies.size(); i++)  // (a link's overflow 2: its step had another shape than the recorded one)
-    if (!h2_reply_result(p->replies[i], &fr[i])) return -GRDMA_ERR_HIP;
-  float fms = 0, dms = 0;
-  uint64_t f_us = 0, d_us = 0;
-  if (p->launched && p->timed && hipEventElapsedTime(&fms, p->t_f0, p->t_f1) == hipSuccess) f_us = (uint64_t)(fms * 1e3f);
-  if (p->launched && p->timed && hipEventElapsedTime(&dms, p->t_d0, p->t_d1) == hipSuccess) d_us = (uint64_t)(dms * 1e3f);
-  for (size_t i = 0; i < n; i++) {
-    uint64_t* o = out + 14 * i;
-    o[0] = fr[i].nslices;
-    o[1] = fr[i].overflow;
-    o[2] = dr[i].nevents;
-    o[3] = dr[i].overflow;
-    o[4] = dr[i].slices_done;
-    o[5] = (uint64_t)dr[i].error;
-    o[6] = f_us;  // (the batch's, repeated)
-    o[7] = d_us;
-    o[8] = dr[i].bulk_steps;
-    o[9] = dr[i].bulk_frames;
-    o[10] = dr[i].t_wait;
-    o[11] = dr[i].t_bulk;
-    o[12] = dr[i].t_total;
-    o[13] = dr[i].t_serial;
-  }
-  return 0;
-}
-
-int64_t grdma_h2_group_pipe_events(grdma_h2_group_pipe* p, uint32_t i, grdma_h2_event* out, uint64_t cap) {
-  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!p || i >= p->links.size() || (!out && cap)) return -GRDMA_ERR_INVALID;
-  if (int rc = h2_group_wait(p)) return rc;
-  grdma_h2_deframe_result dr;
-  if (hipMemcpy(&dr, p->d_dres + i, sizeof(dr), hipMemcpyDeviceToHost) != hipSuccess) return -GRDMA_ERR_HIP;
-  const uint64_t m = std::min<uint64_t>(dr.nevents, p->links[i].ev_cap);
-  if (m > cap) return -GRDMA_ERR_CAPACITY;
-  if (m && hipMemcpy(out, p->links[i].d_ev, sizeof(grdma_h2_event) * m, hipMemcpyDeviceToHost) != hipSuccess) return -GRDMA_ERR_HIP;
-  return (int64_t)m;
-}
-
-int64_t grdma_h2_group_pipe_slice_table(grdma_h2_group_pipe* p, uint32_t i, grdma_slice* out, uint64_t cap) {
-  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!p || i >= p->links.size() || (!out && cap)) return -GRDMA_ERR_INVALID;
-  const h2_group_link& l = p->links[i];
-  if (l.count > cap) return -GRDMA_ERR_CAPACITY;
-  if (int rc = h2_group_wait(p)) return rc;
-  if (l.count && hipMemcpy(out, l.d_sges, sizeof(grdma_sge) * l.count, hipMemcpyDeviceToHost) != hipSuccess) return -GRDMA_ERR_HIP;
-  return (int64_t)l.count;
-}
-
-// ---- the message assembler on many links (k_h2_asm_*_links, csrc/grdma_h2_asm.h) -----------------------------------
-// Six launches for any number of links: the plan's one-workgroup stages of the links run side by side.
-static_assert(H2A_LINKS_MAX == GRDMA_H2_BATCH_MAX, "the assembler's link table is the batch's");
-
-static void h2_asm_links_enqueue(const h2a_link* d_tab, uint32_t n, hipStream_t st) {
-  hipLaunchKernelGGL(k_h2_asm_tiles_links, dim3(n * H2A_LINK_GRID), dim3(H2A_THREADS), 0, st, d_tab, n);
-  hipLaunchKernelGGL(k_h2_asm_carry_links, dim3(n), dim3(H2A_ONE_THREADS), 0, st, d_tab);
-  hipLaunchKernelGGL(k_h2_asm_begin_links, dim3(n * H2A_LINK_GRID), dim3(H2A_THREADS), 0, st, d_tab, n);
-  hipLaunchKernelGGL(k_h2_asm_bytes_links, dim3(n * H2A_LINK_GRID), dim3(H2A_THREADS), 0, st, d_tab, n);
-  hipLaunchKernelGGL(k_h2_asm_finish_links, dim3(n), dim3(H2A_ONE_THREADS), 0, st, d_tab);
-  hipLaunchKernelGGL(k_h2_asm_copy_links, dim3(H2A_GRID), dim3(H2A_THREADS), 0, st, d_tab, n);
-}
-
-// the same six kernels as post hooks of a fused group pipe's graph, behind k_h2_deframe_links
-static uint32_t h2_asm_links_hooks(const h2a_link* d_tab, uint32_t n, grdma_job_hook* out) {
-  const void* fns[6] = {(const void*)k_h2_asm_tiles_links, (const void*)k_h2_asm_carry_links, (const void*)k_h2_asm_begin_links,
-                        (const void*)k_h2_asm_bytes_links, (const void*)k_h2_asm_finish_links, (const void*)k_h2_asm_copy_links};
-  const uint32_t grids[6] = {n * H2A_LINK_GRID, n, n * H2A_LINK_GRID, n * H2A_LINK_GRID, n, H2A_GRID};
-  const uint32_t threads[6] = {H2A_THREADS, H2A_ONE_THREADS, H2A_THREADS, H2A_THREADS, H2A_ONE_THREADS, H2A_THREADS};
-  for (int k = 0; k < 6; k++) {
-    memset(&out[k], 0, sizeof(out[k]));
-    out[k].fn = fns[k];
-    out[k].grid = grids[k];
-    out[k].threads = threads[k];
-    out[k].args[0] = (uint64_t)(uintptr_t)d_tab;
-    out[k].args[1] = n;
-  }
-  return 6;
-}
+// ---- the message assembler on many links (h2_stage_asm_links, csrc/grdma_h2_asm.h) ---------------------------------
 
 namespace {
 // timing events of the batched assembly (plan | copy) and the pinned table of grdma_h2_asm_release_batch with the event
@@ -1889,27 +1073,20 @@ int grdma_h2_deframe_messages_batch(grdma_h2_messages_item* items, uint32_t n_it
     a_ev += it.cap;
   }
   // behind each parser's previous deframing (a pipe step on another stream)
-  for (uint32_t i = 0; i < n_items; i++) {
-    grdma_h2_parser* p = items[i].parser;
-    if (p->last_deframed && p->last_stream != st && hipStreamWaitEvent(st, p->last_deframed, 0) != hipSuccess) return -GRDMA_ERR_HIP;
-  }
+  for (uint32_t i = 0; i < n_items; i++)
+    if (!h2_wait_parser(st, items[i].parser)) return -GRDMA_ERR_HIP;
   if (hipMemcpyAsync(d, up.data(), o_ev, hipMemcpyHostToDevice, st) != hipSuccess) return -GRDMA_ERR_HIP;
   hipEventRecord(hc->e0, st);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(k_h2_deframe_links, dim3(n_items), dim3(H2_DEFRAME_THREADS), 0, st, (const grdma_h2_link_deframe*)d);
+  hipError_t launched = h2_launch(h2_stage_deframe_links((const grdma_h2_link_deframe*)d, n_items), st);
   hipEventRecord(hc->e1, st);
-  // the assembly: the plan (five kernels), then the copy, timed apart
-  const h2a_link* d_atab = reinterpret_cast<const h2a_link*>(d + o_atab);
+  // the assembly: the plan, then the copy, timed apart
+  const h2_stage assembly = h2_stage_asm_links(reinterpret_cast<const h2a_link*>(d + o_atab), n_items);
   hipEventRecord(lc->e0, st);
-  hipLaunchKernelGGL(k_h2_asm_tiles_links, dim3(n_items * H2A_LINK_GRID), dim3(H2A_THREADS), 0, st, d_atab, n_items);
-  hipLaunchKernelGGL(k_h2_asm_carry_links, dim3(n_items), dim3(H2A_ONE_THREADS), 0, st, d_atab);
-  hipLaunchKernelGGL(k_h2_asm_begin_links, dim3(n_items * H2A_LINK_GRID), dim3(H2A_THREADS), 0, st, d_atab, n_items);
-  hipLaunchKernelGGL(k_h2_asm_bytes_links, dim3(n_items * H2A_LINK_GRID), dim3(H2A_THREADS), 0, st, d_atab, n_items);
-  hipLaunchKernelGGL(k_h2_asm_finish_links, dim3(n_items), dim3(H2A_ONE_THREADS), 0, st, d_atab);
+  if (launched == hipSuccess) launched = h2_launch(assembly.data(), H2_ASM_PLAN, st);
   hipEventRecord(lc->e1, st);
-  hipLaunchKernelGGL(k_h2_asm_copy_links, dim3(H2A_GRID), dim3(H2A_THREADS), 0, st, d_atab, n_items);
+  if (launched == hipSuccess) launched = h2_launch(assembly.data() + H2_ASM_PLAN, assembly.size() - H2_ASM_PLAN, st);
   hipEventRecord(lc->e2, st);
-  if (hipGetLastError() != hipSuccess) {
+  if (launched != hipSuccess) {
     hipStreamSynchronize(st);
     return grdma_fail_msg(GRDMA_ERR_HIP, "h2 messages batch: a launch was rejected");
   }
@@ -1930,23 +1107,15 @@ int grdma_h2_deframe_messages_batch(grdma_h2_messages_item* items, uint32_t n_it
   bool more = false;
   for (uint32_t i = 0; i < n_items; i++) {
     grdma_h2_messages_item& it = items[i];
-    const h2a_dev& h = hs[i];
     const uint64_t m = res[i].nevents < it.cap ? res[i].nevents : it.cap;
     if (it.events_out && m) memcpy(it.events_out, ev + a_ev, sizeof(grdma_h2_event) * m);
     it.h2_error = (int)res[i].error;
     it.n_events = res[i].overflow ? -(int64_t)GRDMA_ERR_CAPACITY : (int64_t)m;
     it.assembler->plan_ms = plan_ms;  // (the batch's, repeated)
     it.assembler->copy_ms = copy_ms;
-    if (res[i].overflow || h.skip || h.ndesc > it.msgs_cap || h.ndesc > h.desc_cap) {
-      it.n_msgs = -(int64_t)GRDMA_ERR_CAPACITY;
-    } else {
-      it.n_msgs = (int64_t)h.ndesc;
-      if (h.ndesc) {
-        if (hipMemcpyAsync(it.msgs_out, h.desc, sizeof(grdma_h2_rx_msg) * h.ndesc, hipMemcpyDeviceToHost, st) != hipSuccess)
-          return -GRDMA_ERR_HIP;
-        more = true;
-      }
-    }
+    it.n_msgs = res[i].overflow ? -(int64_t)GRDMA_ERR_CAPACITY : h2_asm_descriptors(hs[i], it.msgs_out, it.msgs_cap, st);
+    if (it.n_msgs == -(int64_t)GRDMA_ERR_HIP) return -GRDMA_ERR_HIP;
+    more = more || it.n_msgs > 0;
     a_ev += it.cap;
   }
   if (more && hipStreamSynchronize(st) != hipSuccess) return -GRDMA_ERR_HIP;
@@ -1968,90 +1137,18 @@ int grdma_h2_asm_release_batch(grdma_h2_asm* const* asms, const uint64_t* counts
   if (!hc || !lc) return -GRDMA_ERR_HIP;
   hipStream_t st = hc->stream;
   // behind the last standalone call (same stream) and the last pipe step of every parser
-  for (uint32_t i = 0; i < n; i++) {
-    grdma_h2_parser* p = asms[i]->parser;
-    if (p->last_deframed && hipStreamWaitEvent(st, p->last_deframed, 0) != hipSuccess) return -GRDMA_ERR_HIP;
-  }
+  for (uint32_t i = 0; i < n; i++)
+    if (!h2_wait_parser(st, asms[i]->parser)) return -GRDMA_ERR_HIP;
   if (lc->rel_pending && hipEventSynchronize(lc->rel_up) != hipSuccess) return -GRDMA_ERR_HIP;
   for (uint32_t i = 0; i < n; i++) lc->h_rel[i] = h2a_link_release{asms[i]->d, counts[i]};
   if (hipMemcpyAsync(lc->d_rel, lc->h_rel, sizeof(h2a_link_release) * n, hipMemcpyHostToDevice, st) != hipSuccess ||
       hipEventRecord(lc->rel_up, st) != hipSuccess)
     return -GRDMA_ERR_HIP;
   lc->rel_pending = true;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(k_h2_asm_release_links, dim3(n), dim3(64), 0, st, (const h2a_link_release*)lc->d_rel);
-  return hipGetLastError() == hipSuccess ? 0 : -GRDMA_ERR_HIP;
+  const grdma_job_hook release = h2_rec(k_h2_asm_release_links, n, 64, lc->d_rel);
+  return h2_launch(&release, 1, st) == hipSuccess ? 0 : -GRDMA_ERR_HIP;
 }
 
-static void h2_group_detach(grdma_h2_group_pipe* p) {
-  for (grdma_h2_asm*& a : p->asms)
-    if (a) {
-      a->parser->asm_attached--;
-      a->attached--;
-      a = nullptr;
-    }
-  p->n_asm = 0;
-}
-
-int grdma_h2_group_pipe_attach_assemblers(grdma_h2_group_pipe* p, grdma_h2_asm* const* asms, uint32_t n) {
-  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!p || !asms) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: a pipe and an assembler list");
-  if (n != p->links.size()) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: one assembler entry per link spec");
-  if (p->n_asm) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: assemblers are attached already");
-  uint32_t have = 0;
-  for (uint32_t i = 0; i < n; i++) {
-    grdma_h2_asm* a = asms[i];
-    if (!a) continue;
-    if (a->parser != p->links[i].parser) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: an assembler of another parser than its link's");
-    if (a->attached || a->parser->asm_attached) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: an assembler attached already");
-    for (uint32_t k = 0; k < i; k++)
-      if (asms[k] == a) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: the same assembler twice");
-    have++;
-  }
-  if (!have) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: no assembler in the list");
-  if (p->launched && h2_group_wait(p) != 0) return -GRDMA_ERR_HIP;
-  std::vector<h2a_call> calls;
-  std::vector<h2a_link> tab;
-  if ((!p->d_atab && hipMalloc((void**)&p->d_atab, sizeof(h2a_link) * n) != hipSuccess) ||
-      (!p->d_calls && hipMalloc((void**)&p->d_calls, sizeof(h2a_call) * n) != hipSuccess))
-    return -GRDMA_ERR_HIP;
-  for (uint32_t i = 0; i < n; i++) {
-    if (!asms[i]) continue;
-    const h2_group_link& l = p->links[i];
-    if (!h2_asm_prepare(asms[i], l.ev_cap ? l.ev_cap : 1)) return -GRDMA_ERR_HIP;
-    // (a step first releases everything reported before it, as a single pipe's does)
-    tab.push_back(h2a_link{asms[i]->d, p->d_calls + calls.size()});
-    calls.push_back(h2a_call{l.d_ev, p->d_dres + i, l.d_slices, l.dst, l.ev_cap, 1});
-  }
-  if (hipMemcpy(p->d_calls, calls.data(), sizeof(h2a_call) * have, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(p->d_atab, tab.data(), sizeof(h2a_link) * have, hipMemcpyHostToDevice) != hipSuccess)
-    return -GRDMA_ERR_HIP;
-  if (p->fused) {
-    grdma_job_hook post[7];
-    post[0] = p->post;
-    const uint32_t n_post = 1 + h2_asm_links_hooks(p->d_atab, have, post + 1);
-    if (grdma_job_set_hooks(p->job, p->pre, p->n_pre, post, n_post) != 0) return -GRDMA_ERR_HIP;
-  }
-  p->asms.assign(asms, asms + n);
-  p->n_asm = have;
-  for (grdma_h2_asm* a : p->asms)
-    if (a) {
-      a->attached++;
-      a->parser->asm_attached++;
-    }
-  return 0;
-}
-
-int64_t grdma_h2_group_pipe_messages(grdma_h2_group_pipe* p, uint32_t i, grdma_h2_rx_msg* out, uint64_t cap) {
-  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!p || i >= p->asms.size() || !p->asms[i] || (!out && cap)) return -GRDMA_ERR_INVALID;
-  if (int rc = h2_group_wait(p)) return rc;
-  h2a_dev h;
-  if (hipMemcpy(&h, p->asms[i]->d, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -GRDMA_ERR_HIP;
-  if (h.skip || h.ndesc > cap || h.ndesc > h.desc_cap) return -GRDMA_ERR_CAPACITY;
-  if (h.ndesc && hipMemcpy(out, h.desc, sizeof(grdma_h2_rx_msg) * h.ndesc, hipMemcpyDeviceToHost) != hipSuccess)
-    return -GRDMA_ERR_HIP;
-  return (int64_t)h.ndesc;
-}
+#include "grdma_h2_host_pipe.inc"
 
 }  // extern "C"
