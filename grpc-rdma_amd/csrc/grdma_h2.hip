@@ -31,6 +31,7 @@
 #include "grdma_h2_kernels.h"
 #include "grdma_h2_asm.h"
 #include "grdma_h2_reply.h"
+#include "grdma_h2_fc.h"
 
 // --------------------------------------------------------------------- host API
 // Everything here runs on one non-blocking stream of its own and waits with
@@ -57,6 +58,10 @@ struct grdma_h2_parser {
   hipStream_t last_stream = nullptr;
   hipEvent_t last_deframed = nullptr;
   uint32_t asm_attached = 0;  // pipes that run an assembler of this parser behind their deframer
+  // receive flow control (csrc/grdma_h2_fc.h): the parser's ledger, and the standalone deframings it may account --
+  // their number and the event capacity of the last one (its events stay in d_ev / d_res until the next call)
+  struct grdma_h2_fc* fc = nullptr;
+  uint64_t standalone_calls = 0, standalone_ev_cap = 0;
 };
 
 // How many chunks a parser created without saying so cuts a long list into: GRDMA_H2_CHUNKS (default and at most 256, 0 or 1 = the
@@ -213,6 +218,14 @@ static h2_stage h2_stage_reply(h2r_dev* d) {
 static_assert(H2R_LINKS_MAX == GRDMA_H2_BATCH_MAX, "the reply's link table is the batch's");
 static h2_stage h2_stage_reply_links(const h2r_link* d_tab, uint32_t n) {
   return {h2_rec(k_h2_reply_plan_links, n, PLAN_THREADS, d_tab), h2_rec(k_h2_reply_emit_links, H2R_GRID, H2_EMIT_THREADS, d_tab, n)};
+}
+
+// The window ledger of one call behind its deframing (csrc/grdma_h2_fc.h): it reads the events only, so it may stand in
+// front of, behind or beside an assembler's stage.
+static h2_stage h2_stage_fc(h2fc_dev* d, const h2fc_call* d_call) {
+  return {h2_rec(k_h2_fc_clear, H2FC_GRID, H2FC_THREADS, d, d_call), h2_rec(k_h2_fc_keys, H2FC_GRID, H2FC_THREADS, d, d_call),
+          h2_rec(k_h2_fc_sums, H2FC_GRID, H2FC_THREADS, d, d_call), h2_rec(k_h2_fc_finish, 1, H2FC_ONE_THREADS, d, d_call),
+          h2_rec(k_h2_fc_emit, H2FC_GRID, H2FC_THREADS, d)};
 }
 
 // st goes behind the parser's last deframing by a pipe (the parser state is handed from one deframing to the next),
@@ -381,8 +394,10 @@ grdma_h2_parser* grdma_h2_parser_create(int expect_client_prefix, uint32_t max_f
                                    max_frame_size, 0xffffffffu, 0);
 }
 
+static void h2_fc_parser_gone(struct grdma_h2_fc* f);
 void grdma_h2_parser_destroy(grdma_h2_parser* p) {
   if (!p) return;
+  if (p->fc) h2_fc_parser_gone(p->fc);  // (the ledger outlives its parser as a husk: every call on it is refused)
   hipFree(p->d);
   hipFree(p->d_tab);
   hipFree(p->d_sl);
@@ -500,6 +515,8 @@ int64_t grdma_h2_deframe(grdma_h2_parser* p, const void* d_arena, const grdma_re
             hipStreamSynchronize(st) != hipSuccess))
     return -GRDMA_ERR_HIP;
   if (h2_error) *h2_error = (int)h_res.error;
+  p->standalone_calls++;
+  p->standalone_ev_cap = cap;
   return h_res.overflow ? -GRDMA_ERR_CAPACITY : (int64_t)m;
 }
 
@@ -538,6 +555,7 @@ int grdma_h2_deframe_batch(grdma_h2_deframe_item* items, uint32_t n_items) {
     if (!it.parser || !it.d_arena || (!it.slices && it.n) || (!it.events_out && it.cap))
       return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 batch: an item without parser, arena, slices or event array");
     if (it.parser->asm_attached) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 batch: a parser whose assembler is attached to a pipe");
+    if (it.parser->fc) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 batch: a parser with a flow-control ledger (single transport only)");
     for (uint32_t k = 0; k < i; k++)
       if (items[k].parser == it.parser) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 batch: the same parser twice");
     n_sl += it.n;
@@ -750,6 +768,8 @@ int64_t grdma_h2_deframe_messages(grdma_h2_parser* p, grdma_h2_asm* a, const voi
     return -GRDMA_ERR_HIP;
   if (hipEventElapsedTime(&a->plan_ms, a->e0, a->e1) != hipSuccess) a->plan_ms = 0;
   if (hipEventElapsedTime(&a->copy_ms, a->e1, a->e2) != hipSuccess) a->copy_ms = 0;
+  p->standalone_calls++;
+  p->standalone_ev_cap = ev_cap;
   if (h2_error) *h2_error = (int)h_res.error;
   const uint64_t m = h_res.nevents < ev_cap ? h_res.nevents : ev_cap;
   if (events_out && m &&
@@ -986,6 +1006,180 @@ int grdma_h2_reply_frame_batch(grdma_h2_reply_item* items, uint32_t n_items) {
   return 0;
 }
 
+// ---- receive flow control: the window ledger (csrc/grdma_h2_fc.h) -------------------------------------------------
+struct grdma_h2_pipe;
+struct grdma_h2_fc {
+  grdma_h2_parser* parser = nullptr;
+  h2fc_dev* d = nullptr;
+  h2fc_dev h;                      // host copy of the configuration words
+  h2fc_call* d_call = nullptr;     // standalone calls
+  grdma_h2_pipe* pipe = nullptr;   // the pipe whose steps account through it
+  uint64_t accounted = 0;          // parser->standalone_calls of the last call accounted
+  float last_ms = 0;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+};
+
+// The parser of f is being destroyed: standalone calls on f's stream have ended, and from now on f refuses every call
+// but destroy (its device block points into the parser's).  A ledger attached to a pipe stays with the pipe, whose
+// parser must outlive it as it must without a ledger.
+static void h2_fc_parser_gone(grdma_h2_fc* f) {
+  h2_host_ctx* hc = h2_ctx();
+  if (hc) hipStreamSynchronize(hc->stream);
+  f->parser = nullptr;
+}
+
+// the bit words of calls of up to ev_cap events (a resize drains the device: setup, not a hot path)
+static bool h2_fc_prepare(grdma_h2_fc* f, uint64_t ev_cap) {
+  if (ev_cap == 0) ev_cap = 1;
+  if (ev_cap <= f->h.scratch_ev) return true;
+  if (ev_cap >= 0xffffffffull) return false;  // (event indices are 32 bits in the scratch table)
+  if (hipDeviceSynchronize() != hipSuccess) return false;
+  h2fc_dev& h = f->h;
+  hipFree(h.mark);
+  hipFree(h.mark_pre);
+  h.mark = h.mark_pre = nullptr;
+  h.scratch_ev = 0;
+  const uint64_t words = (ev_cap + 31) / 32;
+  const bool ok = hipMalloc((void**)&h.mark, sizeof(uint32_t) * words) == hipSuccess &&
+                  hipMalloc((void**)&h.mark_pre, sizeof(uint32_t) * words) == hipSuccess;
+  if (ok) h.scratch_ev = ev_cap;
+  else (void)hipGetLastError();
+  const size_t off = offsetof(h2fc_dev, scratch_ev), len = offsetof(h2fc_dev, out) - off;
+  return hipMemcpy(reinterpret_cast<uint8_t*>(f->d) + off, reinterpret_cast<const uint8_t*>(&h) + off, len,
+                   hipMemcpyHostToDevice) == hipSuccess && ok;
+}
+
+// where the calls write: the words of h2fc_dev from `out` to the state
+static bool h2_fc_set_target(grdma_h2_fc* f, grdma_sge* out, uint64_t cap, uint8_t* hdr, uint64_t hdr_cap, hipStream_t st) {
+  h2fc_dev& h = f->h;
+  h.out = out;
+  h.cap = cap;
+  h.hdr = hdr;
+  h.hdr_cap = hdr_cap;
+  const size_t off = offsetof(h2fc_dev, out), len = offsetof(h2fc_dev, announced) - off;
+  uint8_t* dst = reinterpret_cast<uint8_t*>(f->d) + off;
+  const uint8_t* src = reinterpret_cast<const uint8_t*>(&h) + off;
+  return (st ? hipMemcpyAsync(dst, src, len, hipMemcpyHostToDevice, st) : hipMemcpy(dst, src, len, hipMemcpyHostToDevice)) ==
+         hipSuccess;
+}
+
+static grdma_h2_fc* h2_fc_refuse(const char* why) {
+  grdma_fail_msg(GRDMA_ERR_INVALID, why);
+  return nullptr;
+}
+
+grdma_h2_fc* grdma_h2_fc_create(grdma_h2_parser* parser, uint32_t stream_window, uint32_t conn_window, uint32_t conn_threshold,
+                                uint32_t max_updates) {
+  if (grdma_device_count() <= 0) return nullptr;
+  if (!parser) return h2_fc_refuse("h2 flow control: no parser");
+  if (parser->fc) return h2_fc_refuse("h2 flow control: the parser has a ledger already");
+  if (stream_window == 0 || stream_window > 0x7fffffffu) return h2_fc_refuse("h2 flow control: stream_window outside 1 .. 2^31 - 1");
+  if (conn_window < 65535 || conn_window > 0x7fffffffu) return h2_fc_refuse("h2 flow control: conn_window outside 65535 .. 2^31 - 1");
+  if (conn_threshold > conn_window) return h2_fc_refuse("h2 flow control: conn_threshold above conn_window");
+  if (max_updates == 0 || max_updates > (1u << 24)) return h2_fc_refuse("h2 flow control: max_updates outside 1 .. 2^24");
+  grdma_h2_fc* f = new grdma_h2_fc();
+  f->parser = parser;
+  memset(&f->h, 0, sizeof(f->h));
+  h2fc_dev& h = f->h;
+  h.gp = parser->d;
+  h.stream_window = stream_window;
+  h.conn_window = conn_window;
+  h.conn_threshold = conn_threshold;
+  h.max_updates = max_updates;
+  h.tab_mask = parser->slots - 1;
+  h.announced = (int64_t)conn_window;
+  const bool ok = hipMalloc((void**)&f->d, sizeof(h2fc_dev)) == hipSuccess &&
+                  hipMalloc((void**)&h.tab, sizeof(h2fc_slot) * parser->slots) == hipSuccess &&
+                  hipMalloc((void**)&h.upd, sizeof(h2fc_upd) * max_updates) == hipSuccess &&
+                  hipMalloc((void**)&f->d_call, sizeof(h2fc_call)) == hipSuccess &&
+                  hipMemcpy(f->d, &h, sizeof(h), hipMemcpyHostToDevice) == hipSuccess &&
+                  hipEventCreate(&f->e0) == hipSuccess && hipEventCreate(&f->e1) == hipSuccess;
+  parser->fc = f;
+  if (!ok) {
+    (void)hipGetLastError();
+    grdma_h2_fc_destroy(f);
+    grdma_fail_msg(GRDMA_ERR_HIP, "h2 flow control: device allocation failed");
+    return nullptr;
+  }
+  return f;
+}
+
+void grdma_h2_fc_destroy(grdma_h2_fc* f) {
+  if (!f || f->pipe) return;  // (the pipe's graph still runs the kernels on it: destroy the pipe first)
+  h2_host_ctx* hc = h2_ctx();
+  if (hc) hipStreamSynchronize(hc->stream);  // (standalone calls)
+  if (f->parser) f->parser->fc = nullptr;
+  hipFree(f->h.tab);
+  hipFree(f->h.upd);
+  hipFree(f->h.mark);
+  hipFree(f->h.mark_pre);
+  hipFree(f->d);
+  hipFree(f->d_call);
+  for (hipEvent_t e : {f->e0, f->e1})
+    if (e) hipEventDestroy(e);
+  delete f;
+}
+
+int64_t grdma_h2_fc_account(grdma_h2_fc* f, grdma_slice* d_slices_out, uint64_t slices_cap, void* d_hdr_arena, uint64_t hdr_cap,
+                            uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!f || !out) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control: no ledger or no result array");
+  if (!d_slices_out || !slices_cap || !d_hdr_arena || !hdr_cap || ((uintptr_t)d_slices_out & 15) || ((uintptr_t)d_hdr_arena & 15))
+    return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control: a null, zero or misaligned slice table or header arena");
+  if (f->pipe) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control: the ledger is attached to a pipe (its steps account)");
+  grdma_h2_parser* p = f->parser;
+  if (!p) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control: the ledger's parser is gone");
+  if (p->standalone_calls == 0) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control: the parser has deframed nothing yet");
+  if (f->accounted == p->standalone_calls) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control: this call is accounted already");
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  if (!h2_fc_prepare(f, p->standalone_ev_cap)) return -GRDMA_ERR_HIP;
+  // the stream of the standalone deframings: the call is ordered behind the one it reads
+  // ... and behind the parser's last deframing by a pipe: k_h2_fc_finish reads the stream map that step may change
+  hipStream_t st = hc->stream;
+  if (!h2_wait_parser(st, p)) return -GRDMA_ERR_HIP;
+  const h2fc_call call{p->d_ev, p->d_res, p->standalone_ev_cap};
+  if (hipMemcpyAsync(f->d_call, &call, sizeof(call), hipMemcpyHostToDevice, st) != hipSuccess ||
+      !h2_fc_set_target(f, reinterpret_cast<grdma_sge*>(d_slices_out), slices_cap, static_cast<uint8_t*>(d_hdr_arena), hdr_cap, st))
+    return -GRDMA_ERR_HIP;
+  hipEventRecord(f->e0, st);
+  const hipError_t launched = h2_launch(h2_stage_fc(f->d, f->d_call), st);
+  hipEventRecord(f->e1, st);
+  uint64_t res[8];
+  if (launched != hipSuccess ||
+      hipMemcpyAsync(res, reinterpret_cast<uint8_t*>(f->d) + offsetof(h2fc_dev, res), sizeof(res), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return -GRDMA_ERR_HIP;
+  if (hipEventElapsedTime(&f->last_ms, f->e0, f->e1) != hipSuccess) f->last_ms = 0;
+  f->accounted = p->standalone_calls;
+  for (int i = 0; i < 8; i++) out[i] = res[i];
+  if (res[H2FC_OVERFLOW] == 2)
+    return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 flow control: the call's event list overflowed, its bytes cannot be accounted");
+  if (res[H2FC_OVERFLOW]) return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 flow control: more frames than max_updates, or a slice or header cap too small");
+  return (int64_t)res[H2FC_SLICES];
+}
+
+int grdma_h2_fc_stats(grdma_h2_fc* f, uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!f || !out) return -GRDMA_ERR_INVALID;
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  h2fc_dev h;
+  if (f->parser && !h2_wait_parser(hc->stream, f->parser)) return -GRDMA_ERR_HIP;
+  if (hipMemcpyAsync(&h, f->d, sizeof(h), hipMemcpyDeviceToHost, hc->stream) != hipSuccess ||
+      hipStreamSynchronize(hc->stream) != hipSuccess)
+    return -GRDMA_ERR_HIP;
+  out[0] = h.st_calls;
+  out[1] = h.st_conn_bytes;
+  out[2] = h.st_stream_bytes;
+  out[3] = h.st_frames;
+  out[4] = h.st_conn_over;
+  out[5] = h.st_stream_over | (h.lost ? 1ull << 63 : 0);
+  out[6] = (uint64_t)h.announced;
+  out[7] = (uint64_t)(f->last_ms * 1e6f);
+  return 0;
+}
+
 // ---- the message assembler on many links (h2_stage_asm_links, csrc/grdma_h2_asm.h) ---------------------------------
 
 namespace {
@@ -1020,6 +1214,7 @@ int grdma_h2_deframe_messages_batch(grdma_h2_messages_item* items, uint32_t n_it
       return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 messages batch: an item without parser, arena, slices, event capacity or descriptor array");
     if (!it.assembler) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 messages batch: an item without assembler");
     if (it.assembler->parser != it.parser) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 messages batch: an assembler of another parser");
+    if (it.parser->fc) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 messages batch: a parser with a flow-control ledger (single transport only)");
     if (it.assembler->attached || it.parser->asm_attached)
       return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 messages batch: an assembler attached to a pipe");
     for (uint32_t k = 0; k < i; k++) {

@@ -33,6 +33,7 @@ struct h2_step_seq {
   std::vector<grdma_h2_parser*> parsers;  // the step deframes with these: one per link of the pipe
   std::vector<grdma_h2_reply*> replies;   // a reply pipe: the step frames from these, one per link
   std::vector<grdma_h2_asm*> asms;        // the step assembles into these: empty, or one entry per link (NULL = none)
+  grdma_h2_fc* fc = nullptr;              // the single pipe: the window ledger that accounts every step's events
 };
 
 namespace {
@@ -80,15 +81,22 @@ static bool h2_seq_bind_reply(h2_step_seq* s, grdma_h2_reply* r, grdma_sge* d_sg
   return true;
 }
 
-// The assemblers' stage goes behind the deframing stage (fused: the job's graph is rebuilt with it); from now on a step
-// assembles into asms, one entry per parser of the pipe (NULL = none).
-static int h2_seq_attach(h2_step_seq* s, const h2_stage& assembly, grdma_h2_asm* const* asms, uint32_t n) {
+// One more stage behind what the step runs behind the job already -- the deframing stage and whatever was attached
+// before (fused: the job's graph is rebuilt with it).  Stages stand in the order they were attached in.
+static int h2_seq_append(h2_step_seq* s, const h2_stage& stage) {
   h2_stage post = s->post;
-  post.insert(post.end(), assembly.begin(), assembly.end());
+  post.insert(post.end(), stage.begin(), stage.end());
   if (s->fused &&
       grdma_job_set_hooks(s->job, s->pre.data(), (uint32_t)s->pre.size(), post.data(), (uint32_t)post.size()) != 0)
     return -GRDMA_ERR_HIP;
   s->post = post;
+  return 0;
+}
+
+// The assemblers' stage goes behind the deframing stage; from now on a step assembles into asms, one entry per parser
+// of the pipe (NULL = none).
+static int h2_seq_attach(h2_step_seq* s, const h2_stage& assembly, grdma_h2_asm* const* asms, uint32_t n) {
+  if (int rc = h2_seq_append(s, assembly)) return rc;
   s->asms.assign(asms, asms + n);
   for (grdma_h2_asm* a : s->asms)
     if (a) {
@@ -210,6 +218,8 @@ static void h2_seq_destroy(h2_step_seq* s) {
       a->attached--;
     }
   s->asms.clear();
+  if (s->fc) s->fc->pipe = nullptr;
+  s->fc = nullptr;
   for (hipEvent_t e : {s->framed, s->job_done, s->deframed, s->t_f0, s->t_f1, s->t_d0, s->t_d1})
     if (e) hipEventDestroy(e);
 }
@@ -269,6 +279,11 @@ struct grdma_h2_pipe {
   uint64_t ev_cap = 0;
   uint64_t boundary_steps = 0, t_boundary = 0;  // of the last synced step
   h2a_call* d_call = nullptr;  // where this pipe's deframer leaves its output, for the assembler
+  // the window ledger's call block and the window-update list of a step (grdma_h2_pipe_attach_flow_control)
+  h2fc_call* d_fc_call = nullptr;
+  grdma_sge* d_wu = nullptr;
+  uint8_t* d_wu_hdr = nullptr;
+  uint64_t wu_cap = 0;
 };
 
 // msgs / nmsgs / max_frame: the host message table of grdma_h2_pipe_create; reply: the framing stage of
@@ -329,6 +344,9 @@ void grdma_h2_pipe_destroy(grdma_h2_pipe* p) {
   if (!p || h2_seq_read_by_reply_pipes(&p->seq)) return;
   h2_seq_destroy(&p->seq);
   hipFree(p->d_call);
+  hipFree(p->d_fc_call);
+  hipFree(p->d_wu);
+  hipFree(p->d_wu_hdr);
   hipFree(p->d_msgs);
   hipFree(p->d_pos);
   hipFree(p->d_hdr);
@@ -404,6 +422,74 @@ int64_t grdma_h2_pipe_messages(grdma_h2_pipe* p, grdma_h2_rx_msg* out, uint64_t 
   return h2_seq_messages(&p->seq, p->seq.asms[0], out, cap);
 }
 
+// The window ledger's stage goes behind what the pipe runs behind its job at the time of the call: behind the deframer,
+// and behind the assembler's six kernels if that was attached first (in front of them if it comes later).  It reads the
+// events only, so either order gives the same bytes.  The pipe owns the window-update list: room for max_updates frames.
+int grdma_h2_pipe_attach_flow_control(grdma_h2_pipe* p, grdma_h2_fc* f) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!p || !f) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 pipe: a pipe and a ledger");
+  if (!p->seq.replies.empty()) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 pipe: a reply pipe carries no window ledger (not built)");
+  if (p->seq.fc) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 pipe: a ledger is attached already");
+  if (f->pipe) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 pipe: the ledger is attached to another pipe");
+  if (!f->parser) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 pipe: the ledger's parser is gone");
+  if (f->parser != p->seq.parsers[0]) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 pipe: the ledger of another parser than the pipe's");
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc || hipStreamSynchronize(hc->stream) != hipSuccess) return -GRDMA_ERR_HIP;  // (the ledger's standalone calls)
+  if (p->seq.launched && h2_seq_wait(&p->seq) != 0) return -GRDMA_ERR_HIP;
+  if (!h2_fc_prepare(f, p->ev_cap)) return -GRDMA_ERR_HIP;
+  p->wu_cap = (f->h.max_updates * H2FC_FRAME + H2_INLINED - 1) / H2_INLINED;
+  const h2fc_call call{p->d_ev, p->d_dres, p->ev_cap};
+  if ((!p->d_fc_call && hipMalloc((void**)&p->d_fc_call, sizeof(h2fc_call)) != hipSuccess) ||
+      (!p->d_wu && hipMalloc((void**)&p->d_wu, sizeof(grdma_sge) * p->wu_cap) != hipSuccess) ||
+      (!p->d_wu_hdr && hipMalloc((void**)&p->d_wu_hdr, 32 * p->wu_cap) != hipSuccess) ||
+      hipMemcpy(p->d_fc_call, &call, sizeof(call), hipMemcpyHostToDevice) != hipSuccess ||
+      !h2_fc_set_target(f, p->d_wu, p->wu_cap, p->d_wu_hdr, 32 * p->wu_cap, nullptr))
+    return -GRDMA_ERR_HIP;
+  if (int rc = h2_seq_append(&p->seq, h2_stage_fc(f->d, p->d_fc_call))) return rc;
+  p->seq.fc = f;
+  f->pipe = p;
+  return 0;
+}
+
+// the window-update list of the last step, after the enqueued steps have ended
+static int h2_pipe_wu_result(grdma_h2_pipe* p, uint64_t res[8]) {
+  if (int rc = h2_seq_wait(&p->seq)) return rc;
+  if (hipMemcpy(res, reinterpret_cast<uint8_t*>(p->seq.fc->d) + offsetof(h2fc_dev, res), 8 * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
+    return -GRDMA_ERR_HIP;
+  return 0;
+}
+
+int64_t grdma_h2_pipe_window_updates(grdma_h2_pipe* p, grdma_slice* slices_out, uint64_t cap, uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!p || !p->seq.fc || !out || (!slices_out && cap)) return -GRDMA_ERR_INVALID;
+  if (int rc = h2_pipe_wu_result(p, out)) return rc;
+  if (out[H2FC_OVERFLOW]) return -GRDMA_ERR_CAPACITY;
+  const uint64_t n = out[H2FC_SLICES];
+  if (n > cap) return -GRDMA_ERR_CAPACITY;
+  static_assert(sizeof(grdma_slice) == sizeof(grdma_sge), "layout");
+  if (n && hipMemcpy(slices_out, p->d_wu, sizeof(grdma_sge) * n, hipMemcpyDeviceToHost) != hipSuccess) return -GRDMA_ERR_HIP;
+  return (int64_t)n;
+}
+
+int64_t grdma_h2_pipe_window_update_bytes(grdma_h2_pipe* p, void* bytes_out, uint64_t cap) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!p || !p->seq.fc || (!bytes_out && cap)) return -GRDMA_ERR_INVALID;
+  uint64_t res[8];
+  if (int rc = h2_pipe_wu_result(p, res)) return rc;
+  if (res[H2FC_OVERFLOW] || res[H2FC_WIRE] > cap) return -GRDMA_ERR_CAPACITY;
+  const uint64_t n = res[H2FC_SLICES];
+  std::vector<uint8_t> arena(32 * n);
+  if (n && hipMemcpy(arena.data(), p->d_wu_hdr, arena.size(), hipMemcpyDeviceToHost) != hipSuccess) return -GRDMA_ERR_HIP;
+  uint8_t* dst = static_cast<uint8_t*>(bytes_out);
+  uint64_t done = 0;
+  for (uint64_t k = 0; k < n; k++) {  // (slice k holds wire bytes [23 k, 23 k + 23) at arena + 32 k)
+    const uint64_t len = std::min<uint64_t>(H2_INLINED, res[H2FC_WIRE] - done);
+    memcpy(dst + done, arena.data() + 32 * k, len);
+    done += len;
+  }
+  return (int64_t)done;
+}
+
 // ---- several links of ONE job (the group pipe) ---------------------------------------------------------------------
 // A job carries one set of hooks (grdma_job_set_hooks assigns): the stages of all listed links are ONE framing kernel
 // over a table of links in front of the job and ONE deframing kernel behind it -- one launch per step however many
@@ -452,6 +538,7 @@ static grdma_h2_group_pipe* h2_group_create(grdma_stream_job* job, const grdma_h
       return h2_group_refuse(nullptr, "h2 group pipe: 1 .. 4096 messages per link");
     if (rspecs && !rspecs[i].reply) return h2_group_refuse(nullptr, "h2 group reply pipe: a link without reply");
     if (!parser_of(i)) return h2_group_refuse(nullptr, "h2 group pipe: a link without parser");
+    if (parser_of(i)->fc) return h2_group_refuse(nullptr, "h2 group pipe: a parser with a flow-control ledger (single transport only)");
     for (uint32_t k = 0; k < i; k++) {
       if (link_of(k) == link_of(i)) return h2_group_refuse(nullptr, "h2 group pipe: a link listed twice");
       if (parser_of(k) == parser_of(i)) return h2_group_refuse(nullptr, "h2 group pipe: a parser listed twice");

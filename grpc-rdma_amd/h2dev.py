@@ -151,6 +151,19 @@ def _bind():
         lib.grdma_h2_reply_frame_batch.argtypes = [C.POINTER(H2ReplyItem), C.c_uint32]
         lib.grdma_h2_group_pipe_create_reply.restype = C.c_void_p
         lib.grdma_h2_group_pipe_create_reply.argtypes = [C.c_void_p, C.POINTER(H2ReplyLinkSpec), C.c_uint32]
+        lib.grdma_h2_fc_create.restype = C.c_void_p
+        lib.grdma_h2_fc_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
+        lib.grdma_h2_fc_destroy.argtypes = [C.c_void_p]
+        lib.grdma_h2_fc_account.restype = C.c_int64
+        lib.grdma_h2_fc_account.argtypes = [C.c_void_p, C.c_void_p, u64, C.c_void_p, u64, C.POINTER(u64)]
+        lib.grdma_h2_fc_stats.restype = C.c_int
+        lib.grdma_h2_fc_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
+        lib.grdma_h2_pipe_attach_flow_control.restype = C.c_int
+        lib.grdma_h2_pipe_attach_flow_control.argtypes = [C.c_void_p, C.c_void_p]
+        lib.grdma_h2_pipe_window_updates.restype = C.c_int64
+        lib.grdma_h2_pipe_window_updates.argtypes = [C.c_void_p, C.POINTER(Slice), u64, C.POINTER(u64)]
+        lib.grdma_h2_pipe_window_update_bytes.restype = C.c_int64
+        lib.grdma_h2_pipe_window_update_bytes.argtypes = [C.c_void_p, C.c_void_p, u64]
         lib.grdma_job_hook_counts.restype = C.c_int   # (not in include/grdma_amd.h: the job's side of the pipes)
         lib.grdma_job_hook_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         _bound = True
@@ -542,6 +555,62 @@ class Reply:
             self.h = None
 
 
+FC_CONN_OVERFLOW, FC_STREAM_OVERFLOW, FC_LOST = 1, 2, 4
+
+
+class FlowControl:
+    """Receive flow control of one transport on the device (grdma_h2_fc): the DATA bytes of a deframing counted
+    against stream_window / conn_window, and the WINDOW_UPDATE frames that return them.  One per parser."""
+
+    RESULT = ("frames", "slices", "wire_bytes", "conn_bytes", "stream_bytes", "violations", "first_violator", "overflow")
+    STATS = ("calls", "conn_bytes", "stream_bytes", "frames", "conn_overflows", "stream_overflows", "announced", "kernel_us")
+
+    def __init__(self, parser, stream_window=65535, conn_window=65535, conn_threshold=0, max_updates=4096):
+        self.lib = _bind()
+        self.parser = parser  # (kept alive)
+        self.max_updates = max_updates
+        self.h = self.lib.grdma_h2_fc_create(parser.h, stream_window, conn_window, conn_threshold, max_updates)
+        if not self.h:
+            raise GrdmaError("h2 flow control: " + (self.lib.grdma_last_error() or b"creation failed").decode())
+        self.last_result = None
+
+    def account(self, slices_ptr, cap, hdr_ptr, hdr_cap):
+        """accounts the parser's last standalone deframing -> ([(ptr, len), ...], result tuple (RESULT), wire bytes);
+        raises GrdmaError on a refusal or a capacity overflow -- the result of the failed call stays in .last_result"""
+        out = (u64 * 8)()
+        n = self.lib.grdma_h2_fc_account(self.h, slices_ptr, cap, hdr_ptr, hdr_cap, out)
+        self.last_result = tuple(int(x) for x in out)
+        n = check(n)
+        raw = C.create_string_buffer(max(1, 16 * n))
+        if n:
+            check(self.lib.grdma_copy_to_host(raw, slices_ptr, 16 * n))
+        sl = [(int.from_bytes(raw.raw[16 * i:16 * i + 8], "little"), int.from_bytes(raw.raw[16 * i + 8:16 * i + 16], "little"))
+              for i in range(n)]
+        wire = b""
+        for ptr, ln in sl:
+            buf = C.create_string_buffer(max(1, ln))
+            check(self.lib.grdma_copy_to_host(buf, ptr, ln))
+            wire += buf.raw[:ln]
+        return sl, self.last_result, wire
+
+    def stats(self):
+        """dict of STATS; `lost`: the sticky flag; announced: the connection window the peer knows (may be negative)"""
+        out = (u64 * 8)()
+        check(self.lib.grdma_h2_fc_stats(self.h, out))
+        r = dict(zip(FlowControl.STATS, [int(x) for x in out]))
+        r["kernel_us"] /= 1e3  # (the ABI word is nanoseconds)
+        r["lost"] = bool(r["stream_overflows"] >> 63)
+        r["stream_overflows"] &= (1 << 63) - 1
+        r["announced"] = r["announced"] - (1 << 64) if r["announced"] >> 63 else r["announced"]
+        return r
+
+    def close(self):
+        """does nothing while a pipe has the ledger attached (close the pipe first)"""
+        if self.h and not getattr(self, "_pipe", None):
+            self.lib.grdma_h2_fc_destroy(self.h)
+            self.h = None
+
+
 class Pipe:
     """frame -> streaming job -> deframe as one enqueued device pipeline (grdma_h2_pipe).
     msgs: list of (payload device ptr, len, stream_id, flags); the job must have been run once.
@@ -622,6 +691,25 @@ class Pipe:
         m = check(self.lib.grdma_h2_pipe_messages(self.h, out, cap))
         return _msgs(out, m)
 
+    def attach_flow_control(self, fc):
+        """every step accounts its events through the ledger fc (grdma_h2_pipe_attach_flow_control)"""
+        check(self.lib.grdma_h2_pipe_attach_flow_control(self.h, fc.h))
+        self.flow_control = fc  # (kept alive)
+        fc._pipe = self
+
+    def window_updates(self):
+        """the window-update list of the last step -> ([(ptr, len), ...], result tuple, wire bytes)"""
+        fc = self.flow_control
+        cap = (13 * fc.max_updates + 22) // 23
+        arr = (Slice * max(1, cap))()
+        out = (u64 * 8)()
+        n = self.lib.grdma_h2_pipe_window_updates(self.h, arr, cap, out)
+        res = tuple(int(x) for x in out)
+        n = check(n)
+        buf = C.create_string_buffer(max(1, res[2]))
+        m = check(self.lib.grdma_h2_pipe_window_update_bytes(self.h, buf, res[2]))
+        return [(int(arr[i].ptr or 0), int(arr[i].len)) for i in range(n)], res, buf.raw[:m]
+
     def close(self):
         if self.h:
             a = getattr(self, "assembler", None)
@@ -630,6 +718,9 @@ class Pipe:
                 raise GrdmaError("close the reply pipe that reads this pipe's assembler first")
             self.lib.grdma_h2_pipe_destroy(self.h)
             self.h = None
+            fc = getattr(self, "flow_control", None)
+            if fc is not None:
+                fc._pipe = None
             rf = getattr(self, "reply_framer", None)
             if rf is not None:
                 rf.assembler._reply_pipes -= 1

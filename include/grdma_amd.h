@@ -617,7 +617,8 @@ typedef struct grdma_h2_parser grdma_h2_parser;
  * RST_STREAM closes both; a stream leaves the map once both sides are closed
  * (grpc_chttp2_mark_stream_closed, chttp2_transport.cc:2194-2244) -- the caller reports the write
  * side with grdma_h2_parser_close_writes.  HPACK, SETTINGS, PING, GOAWAY and WINDOW_UPDATE payloads
- * are control plane and are skipped here.
+ * are control plane and are skipped here.  That holds for INCOMING WINDOW_UPDATE frames; our own -- the credit for the
+ * DATA bytes received -- are produced on the device by the window ledger (grdma_h2_fc below).
  * grdma_h2_parser_create(prefix, max) = create_ex(prefix ? SERVER | FIRST_FRAME : 0, max, 0xffffffff, 0).
  * table_slots: power of two >= 16 (0 = 4096); at most table_slots / 2 streams are live at once. */
 grdma_h2_parser* grdma_h2_parser_create(int expect_client_prefix, uint32_t max_frame_size);
@@ -832,6 +833,71 @@ grdma_h2_pipe* grdma_h2_pipe_create_reply(grdma_stream_job* job_back, uint32_t l
  * the number of entries, or -GRDMA_ERR_CAPACITY if more than cap */
 int64_t grdma_h2_pipe_slice_table(grdma_h2_pipe* p, grdma_slice* out, uint64_t cap);
 
+/* ---- Receive flow control on the device: the window ledger (csrc/grdma_h2_fc.h) ----
+ * The receive half of RFC 7540 6.9 for one transport: the DATA bytes of one deframing are counted against the windows
+ * our SETTINGS announced, and the WINDOW_UPDATE frames that return them are written on the device.  A fixed policy
+ * with the counting position of the reference's RecvData (init_data_frame_parser), not a port of flow_control.cc (no
+ * BDP estimate).  Input: the device event list of one deframing of the ledger's parser.
+ *  1. Connection.  Every DATA frame of the call counts with its whole frame size at its FRAME event, whatever its
+ *     stream (frames the deframer skips included; a frame whose payload continues in the next call counts once, in
+ *     the call that saw its header).  D = the call's sum.  D above the announced window: GRDMA_H2_FC_CONN_OVERFLOW.
+ *     The window goes down by D.  pending = conn_window - announced; pending > 0 and >= conn_threshold: one
+ *     WINDOW_UPDATE(stream 0, pending) and the announced window is conn_window again.
+ *  2. Streams are stateless across calls.  S = a stream's sum over the DATA frames DELIVERED to its data parser in
+ *     this call: status 0, in front of the stream's first STREAM_CLOSED event and, for a stream the call opened,
+ *     behind its STREAM_OPEN; a stream with neither event counts only if the parser's stream map holds it open for
+ *     reads (the deframer skips unknown and read-closed streams without saying so in the event).  S > stream_window:
+ *     GRDMA_H2_FC_STREAM_OVERFLOW, counted per stream, the first such stream (by its first counted frame) reported.
+ *     S > 0 and no STREAM_CLOSED event in the call: one WINDOW_UPDATE(stream, S).  A closed stream gets none; its
+ *     bytes counted for the connection.  (A stream whose reads were closed in an EARLIER call and that this call's
+ *     RST_STREAM removes is taken as open in front of that event: it gets no frame either way, only the violation
+ *     count can see its skipped bytes.)  An increment above 2^31 - 1 is cut to that.
+ *  3. Order: the connection's frame, then the streams in the order of their first counted DATA frame.
+ *  4. A call that ended with a connection error accounts and emits nothing.  A call whose event list overflowed (or
+ *     in which more streams were live, opened or closed than the stream map has slots) cannot be accounted: the sticky GRDMA_H2_FC_LOST flag
+ *     (in this and every later result block), -GRDMA_ERR_CAPACITY, overflow word 2, nothing else changes.  More than
+ *     max_updates frames, or a slice or header cap too small: overflow word 1, nothing is written, the window state
+ *     advances and the result block keeps the totals, so the caller sees what was not sent.
+ * Output: 13-byte frames (frame_window_update.cc) in a header arena, 32 bytes of arena per slice, as the slice list
+ * grpc_slice_buffer_add builds from them: the concatenated frames cut into 23-byte inlined slices, the last one
+ * shorter.  The list is an outbuf of its own: nothing merges across its end into what the caller sends behind it.
+ * Result block: {frames, slices, wire bytes, connection bytes counted, stream bytes credited, violations
+ * (GRDMA_H2_FC_*), first violating stream, overflow}.
+ * Not here: many links (grdma_h2_deframe_batch, grdma_h2_deframe_messages_batch and the group pipes refuse a parser
+ * that has a ledger), the frames inside a reply pipe's slice table, and the send half (the framers do not look at the
+ * peer's windows). */
+enum grdma_h2_fc_violation { GRDMA_H2_FC_CONN_OVERFLOW = 1, GRDMA_H2_FC_STREAM_OVERFLOW = 2, GRDMA_H2_FC_LOST = 4 };
+typedef struct grdma_h2_fc grdma_h2_fc;
+/* stream_window 1 .. 2^31-1 (what SETTINGS announced per stream), conn_window 65535 .. 2^31-1 (kept announced),
+ * conn_threshold 0 .. conn_window, max_updates 1 .. 2^24 (frames of one call).  One ledger per parser: NULL for a
+ * second one (grdma_last_error says why). */
+grdma_h2_fc* grdma_h2_fc_create(grdma_h2_parser* parser, uint32_t stream_window, uint32_t conn_window,
+                                uint32_t conn_threshold, uint32_t max_updates);
+/* does nothing while a pipe has the ledger attached: destroy the pipe first.  A ledger whose parser was destroyed
+ * first refuses every call (-GRDMA_ERR_INVALID) and can still be destroyed. */
+void grdma_h2_fc_destroy(grdma_h2_fc* fc);
+/* Accounts the LAST standalone deframing of the ledger's parser (grdma_h2_deframe or grdma_h2_deframe_messages),
+ * ordered behind it on the device (and behind the parser's last pipe step); call it before the stream map is changed,
+ * from the host or by a pipe step of the same parser: rule 2 looks streams up in the map as it is then.  Returns the slice count;
+ * out = the result block.  -GRDMA_ERR_INVALID (grdma_last_error says why): the same call accounted twice, no call yet,
+ * a ledger attached to a pipe, null, zero or misaligned (16 bytes) targets.  -GRDMA_ERR_CAPACITY: rule 4 (out is set). */
+int64_t grdma_h2_fc_account(grdma_h2_fc* fc, grdma_slice* d_slices_out, uint64_t slices_cap, void* d_hdr_arena,
+                            uint64_t hdr_cap, uint64_t out[8]);
+/* {calls accounted, connection bytes, stream bytes credited, frames emitted, connection overflows (calls), stream
+ * overflows (streams; bit 63: the LOST flag), the announced connection window (int64), kernel time of the last
+ * standalone call in NANOseconds (HIP events)} */
+int grdma_h2_fc_stats(grdma_h2_fc* fc, uint64_t out[8]);
+/* The ledger's five kernels become part of every step of a forward grdma_h2_pipe: behind the deframer, in attach order
+ * with the assembler's (it reads the events only, either order gives the same bytes).  Fused they are nodes of the
+ * job's graph (grdma_job_hook_counts' second word grows by 5), with GRDMA_H2_PIPE_FUSED=0 they are enqueued behind the
+ * deframer.  The pipe owns the output tables (room for max_updates frames).  -GRDMA_ERR_INVALID: the ledger of another
+ * parser, a reply pipe, a second attach, a ledger attached elsewhere. */
+int grdma_h2_pipe_attach_flow_control(grdma_h2_pipe* pipe, grdma_h2_fc* fc);
+/* the window-update list of the last step, after the enqueued steps have ended: the slice count and the result block */
+int64_t grdma_h2_pipe_window_updates(grdma_h2_pipe* pipe, grdma_slice* slices_out, uint64_t cap, uint64_t out[8]);
+/* ... and its wire image: the number of bytes */
+int64_t grdma_h2_pipe_window_update_bytes(grdma_h2_pipe* pipe, void* bytes_out, uint64_t cap);
+
 /* ---- HTTP/2 on several links of ONE job (the group pipe) ----
  * grdma_h2_pipe serves one link, and a job carries one set of kernels in front of and behind its rounds: a second
  * grdma_h2_pipe on another link of the same job replaces the first one's.  The group pipe is the pipe of n links of a
@@ -846,8 +912,8 @@ int64_t grdma_h2_pipe_slice_table(grdma_h2_pipe* p, grdma_slice* out, uint64_t c
  * grdma_h2_group_pipe_sync's "slices parsed" word is that count.  (grdma_h2_pipe parses the recorded count.)
  * Create returns NULL (grdma_last_error says why) for: n == 0, a link index out of range or listed twice, a parser
  * listed twice, nmsgs 0 or above 4096, max_frame 0 or >= 2^24, a job that already carries such kernels (another pipe).
- * Not here (yet): the chunked deframer inside the batch (every transport is parsed sequentially), flow control and
- * HPACK (as for grdma_h2_pipe). */
+ * Not here (yet): the chunked deframer inside the batch (every transport is parsed sequentially), flow control (a
+ * parser with a window ledger is refused) and HPACK. */
 typedef struct grdma_h2_link_spec {
   uint32_t link;                 /* index into the job's links; distinct */
   const grdma_h2_msg* msgs;
