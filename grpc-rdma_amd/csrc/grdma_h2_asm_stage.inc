@@ -45,7 +45,7 @@
   }
 #elif H2A_STAGE == 2  // k_h2_asm_carry
   __shared__ uint64_t ws[H2A_ONE_THREADS / 64];
-  __shared__ uint64_t s_found, s_c, s_cnt;
+  __shared__ uint64_t s_found, s_c;
   __shared__ uint32_t hkey[H2A_LDS_KEYS], hkind[H2A_LDS_KEYS], hidx[H2A_LDS_KEYS];
   __shared__ uint64_t hbytes[H2A_LDS_KEYS];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -153,14 +153,16 @@
     A->seq_base = A->seq;
     A->rec_base = A->rec_head;
     A->vh0 = vh;
-    A->seq += nbeg;
   }
   // the keyed scan over the tile aggregates: wave 0, 64 aggregates per step, running state per stream in LDS
   for (uint32_t s = tid; s < H2A_LDS_KEYS; s += H2A_ONE_THREADS) hkey[s] = 0;
-  if (tid == 0) s_cnt = 0;
   __syncthreads();
   if (tid < 64) {
     bool full = false;
+    // distinct streams so far.  Counted from a ballot, so every lane holds the same number: a counter in LDS that only
+    // the inserting lane bumps is, to the compiler, a value no other lane's code changed -- it may keep it in a
+    // register, and the lanes then disagree about `full`
+    uint32_t cnt = 0;
     // software pipeline: the aggregates of the next step and the slots of the one after are in flight while this one
     // is scanned (the loads are not used before the next iteration)
     uint32_t slot = 0, slot1 = 0;
@@ -185,6 +187,7 @@
         const uint64_t mm = __ballot(mem);
         // the stream's running state (first lane: find or insert)
         uint32_t hs = 0;
+        bool inserted = false;
         if (lane == first) {
           hs = (k >> 1) & (H2A_LDS_KEYS - 1);
           while (hkey[hs] != 0 && hkey[hs] != k) hs = (hs + 1) & (H2A_LDS_KEYS - 1);
@@ -193,9 +196,10 @@
             hkind[hs] = 0;
             hidx[hs] = 0;
             hbytes[hs] = 0;
-            s_cnt++;
+            inserted = true;
           }
         }
+        cnt += __ballot(inserted) ? 1u : 0u;
         hs = (uint32_t)__builtin_amdgcn_readlane((int)hs, first);
         const h2a_el base{hkind[hs], hidx[hs], hbytes[hs]};
         const h2a_el inc = h2a_wave_scan(mem ? el : h2a_el{0, 0, 0}, lane);
@@ -220,13 +224,22 @@
         }
         rem &= ~mm;
       }
-      full = s_cnt > H2A_LDS_KEYS / 4 * 3;
+      full = cnt > H2A_LDS_KEYS / 4 * 3;
       slot = slot1;
       kv = kv1;
       slot1 = slot2;
     }
     if (full) {
-      if (lane == 0) A->skip = 2;  // (more distinct streams than the plan holds: the call fails, nothing is assembled)
+      // more distinct streams than the plan holds: the call fails and nothing is assembled -- no descriptor, no byte, ring
+      // and seq as they were.  The deframer has consumed the call's bytes all the same, so a message a stream carried
+      // into the call can never be completed: it is dropped here (entry cleared, record freed) and never reported.
+      for (uint32_t s = lane; s <= A->tab_mask; s += 64) {
+        const h2a_carry c = A->tab[s];
+        if (!c.stream_id) continue;
+        if (c.rec != ~0ull) A->recs[c.rec % A->max_pending].freed = 1;
+        A->tab[s].stream_id = 0;
+      }
+      if (lane == 0) A->skip = 2;
     } else {
       // the final state of every stream the call touched, for k_h2_asm_finish
       uint64_t nf = 0;
@@ -240,7 +253,10 @@
         }
         nf += (uint64_t)__builtin_popcountll(um);
       }
-      if (lane == 0) A->nfin = nf;
+      if (lane == 0) {
+        A->nfin = nf;
+        A->seq += nbeg;  // (only a call that is assembled numbers its messages)
+      }
     }
   }
 #elif H2A_STAGE == 3  // k_h2_asm_begin

@@ -720,7 +720,14 @@ grdma_h2_asm* grdma_h2_asm_create(grdma_h2_parser* parser, void* d_arena, uint64
 void grdma_h2_asm_destroy(grdma_h2_asm* a);   /* does nothing while a pipe has it attached: destroy the pipes first */
 /* grdma_h2_deframe + the assembler; returns the number of descriptors written to msgs_out.  events_out may be NULL
  * (no event copy; ev_cap still sizes the device's event list).  -GRDMA_ERR_CAPACITY when events or descriptors
- * overflow their caps; -GRDMA_ERR_INVALID for bad arguments or an assembler attached to a pipe. */
+ * overflow their caps; -GRDMA_ERR_INVALID for bad arguments or an assembler attached to a pipe.
+ * A call plans at most 3072 distinct streams with message events.  One with more fails with -GRDMA_ERR_CAPACITY and
+ * assembles NOTHING: no descriptor, no byte of the arena, and the ring, its records, the reported count and the seq
+ * counter stay as they were (the call after it numbers its messages where the call before it stopped).  The deframer
+ * has consumed the bytes all the same (events_out and *h2_error are valid): the messages of the failed call are lost,
+ * and a message a stream carried into it is dropped -- its space is given back at the next release, no descriptor ever
+ * reports it, later bytes of it are ignored.  The same holds per item of grdma_h2_deframe_messages_batch and per step
+ * of a pipe (whose release of the earlier messages has happened by then). */
 int64_t grdma_h2_deframe_messages(grdma_h2_parser* p, grdma_h2_asm* a, const void* d_arena,
                                   const grdma_read_slice* slices, uint64_t n,
                                   grdma_h2_event* events_out, uint64_t ev_cap,

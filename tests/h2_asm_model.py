@@ -30,6 +30,15 @@ class AsmModel:
     def bytes_in_use(self):
         return self.vh - self.vt
 
+    def failed_call(self):
+        """a call that failed on the distinct-stream limit: nothing is assembled -- no descriptor, no byte, the ring, the
+        records and seq as they were.  The deframer consumed the call's bytes all the same, so what the streams carried
+        into the call can never complete: those messages are dropped, their records freed, and never reported."""
+        for m in self.carried.values():
+            if m["rec"] is not None:
+                self.recs[m["rec"]][3] = True
+        self.carried = {}
+
     def call(self, events, slices, h2_error=0):
         """events: (kind, a, b, c, d, slice) with MSG_BYTES offsets inside slices[slice]; -> [(desc tuple, bytes)]
         desc = (offset, length, seq, stream_id, status, flags); bytes = the payload of a complete OK message, else None"""
@@ -97,13 +106,18 @@ class AsmModel:
 
 
 def oracle_calls(calls, prefix=False, streams=(), max_frame=16384):
-    """calls: a list of calls, each a list of slice bytes -> [(h2 error, events with slice indices in the call)]"""
+    """calls: a list of calls, each a list of slice bytes -> [(h2 error, events with slice indices in the call)];
+    an entry ("open", ids) between two calls opens those streams there (a client starting calls) and yields nothing"""
     from oracle import pyorc
     p = pyorc.H2Parser(expect_client_prefix=prefix, max_frame_size=max_frame)
     for sid in streams:
         assert p.open_stream(sid) == 0
     out, err = [], 0
     for slices in calls:
+        if isinstance(slices, tuple) and slices[0] == "open":
+            for sid in slices[1]:
+                assert p.open_stream(sid) == 0
+            continue
         ev_call = []
         for i, s in enumerate(slices):
             if err:

@@ -92,10 +92,10 @@ class FH:
     """a device parser with its ledger, the oracle's parser and the model beside them"""
 
     def __init__(self, g, prefix=False, streams=(), stream_window=65535, conn_window=65535, conn_threshold=0,
-                 max_updates=64, cap=None, chunks=None, boundary_step=None):
+                 max_updates=64, cap=None, chunks=None, boundary_step=None, table_slots=0):
         from grpc_rdma_amd import h2dev
         self.g, self.h2dev = g, h2dev
-        self.parser = h2dev.Parser(prefix, chunks=chunks, boundary_step=boundary_step)
+        self.parser = h2dev.Parser(prefix, chunks=chunks, boundary_step=boundary_step, table_slots=table_slots)
         if streams:
             assert self.parser.open_streams(streams) == 0
         self.prefix, self.streams = prefix, tuple(streams)

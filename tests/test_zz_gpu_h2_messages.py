@@ -30,10 +30,10 @@ class Harness:
     """one device parser + assembler and the model beside it; feed() runs one call on both and checks it"""
 
     def __init__(self, g, arena_bytes, max_msg=4 << 20, max_pending=4096, prefix=False, streams=(), max_frame=16384,
-                 chunks=None, tensor=None):
+                 chunks=None, tensor=None, table_slots=0):
         from grpc_rdma_amd import h2dev
         self.g, self.h2dev = g, h2dev
-        self.parser = h2dev.Parser(prefix, max_frame, chunks=chunks)
+        self.parser = h2dev.Parser(prefix, max_frame, chunks=chunks, table_slots=table_slots)
         if streams:
             assert self.parser.open_streams(streams) == 0
         self.arena = tensor if tensor is not None else g.DeviceBuffer(data=bytes([SENTINEL]) * arena_bytes)
