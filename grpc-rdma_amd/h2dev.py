@@ -76,6 +76,26 @@ def _msgs(arr, n):
     return [Msg(int(m.offset), int(m.length), int(m.seq), int(m.stream_id), int(m.status), int(m.flags)) for m in arr[:n]]
 
 
+def _msg_array(msgs):
+    """[(payload device ptr, len, stream_id, flags), ...] as an H2Msg array (never of length 0)"""
+    arr = (H2Msg * max(1, len(msgs)))()
+    for i, (p, n, sid, fl) in enumerate(msgs):
+        arr[i].payload, arr[i].len, arr[i].stream_id, arr[i].flags = p, n, sid, fl
+    return arr
+
+
+def _slice_array(slices):
+    """[(offset, len), ...] as a ReadSlice array (never of length 0)"""
+    arr = (ReadSlice * max(1, len(slices)))()
+    for i, (o, l) in enumerate(slices):
+        arr[i].off, arr[i].len = o, l
+    return arr
+
+
+def _events(arr, m):
+    return [(e.kind, e.a, e.b, e.c, e.d, e.slice) for e in arr[:m]]
+
+
 _bound = False
 
 
@@ -100,6 +120,8 @@ def _bind():
         lib.grdma_h2_last_boundary_steps.argtypes = []
         lib.grdma_h2_parser_chunk_stats.restype = C.c_int
         lib.grdma_h2_parser_chunk_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
+        lib.grdma_h2_parser_chunk_dbg.restype = C.c_int
+        lib.grdma_h2_parser_chunk_dbg.argtypes = [C.c_void_p, C.POINTER(u64), u64]
         lib.grdma_h2_deframe.restype = C.c_int64
         lib.grdma_h2_deframe.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ReadSlice), u64,
                                          C.POINTER(H2Event), u64, C.POINTER(C.c_int)]
@@ -113,6 +135,12 @@ def _bind():
         lib.grdma_h2_asm_release.argtypes = [C.c_void_p, u64]
         lib.grdma_h2_asm_stats.restype = C.c_int
         lib.grdma_h2_asm_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
+        lib.grdma_h2_pipe_create.restype = C.c_void_p
+        lib.grdma_h2_pipe_create.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(H2Msg), u64, C.c_uint32, C.c_void_p, u64, u64]
+        lib.grdma_h2_pipe_enqueue.argtypes = [C.c_void_p, C.c_int]
+        lib.grdma_h2_pipe_sync.argtypes = [C.c_void_p, C.POINTER(u64), C.POINTER(H2Event), u64]
+        lib.grdma_h2_pipe_destroy.argtypes = [C.c_void_p]
+        lib.grdma_h2_pipe_boundary_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
         lib.grdma_h2_pipe_attach_assembler.restype = C.c_int
         lib.grdma_h2_pipe_attach_assembler.argtypes = [C.c_void_p, C.c_void_p]
         lib.grdma_h2_pipe_messages.restype = C.c_int64
@@ -173,11 +201,8 @@ def _bind():
 def frame_messages(msgs, max_frame, slices_dev_ptr, slices_cap, hdr_dev_ptr, hdr_cap):
     """msgs: list of (payload device ptr, len, stream_id, flags). -> (nslices, wire_bytes)."""
     lib = _bind()
-    arr = (H2Msg * len(msgs))()
-    for i, (p, n, sid, fl) in enumerate(msgs):
-        arr[i].payload, arr[i].len, arr[i].stream_id, arr[i].flags = p, n, sid, fl
     wire = u64(0)
-    n = check(lib.grdma_h2_frame_messages(arr, len(msgs), max_frame, slices_dev_ptr, slices_cap,
+    n = check(lib.grdma_h2_frame_messages(_msg_array(msgs), len(msgs), max_frame, slices_dev_ptr, slices_cap,
                                           hdr_dev_ptr, hdr_cap, C.byref(wire)))
     return n, wire.value
 
@@ -233,8 +258,6 @@ class Parser:
         """profiling aid: per chunk (start, cuts found, map copied, parsed, compared, slices) and the merge's stamps, in device-clock ticks relative to the earliest"""
         n = (kmax + 1) * 8
         out = (u64 * n)()
-        self.lib.grdma_h2_parser_chunk_dbg.restype = C.c_int
-        self.lib.grdma_h2_parser_chunk_dbg.argtypes = [C.c_void_p, C.POINTER(u64), u64]
         check(self.lib.grdma_h2_parser_chunk_dbg(self.h, out, n))
         rows = [[int(out[r * 8 + c]) for c in range(8)] for r in range(kmax + 1)]
         return rows
@@ -242,23 +265,19 @@ class Parser:
     def deframe(self, arena_dev_ptr, slices, cap=None):
         """slices: list of (offset, len) in the arena. -> (h2 error, events)"""
         n = len(slices)
-        arr = (ReadSlice * max(1, n))()
-        for i, (o, l) in enumerate(slices):
-            arr[i].off, arr[i].len = o, l
+        arr = _slice_array(slices)
         cap = cap or (sum(l for _, l in slices) * 2 + 64 if n else 64)
         cap = min(cap, 1 << 20)
         ev = (H2Event * cap)()
         err = C.c_int(0)
         m = check(self.lib.grdma_h2_deframe(self.h, arena_dev_ptr, arr, n, ev, cap, C.byref(err)))
         self.last_boundary_steps = int(self.lib.grdma_h2_last_boundary_steps())
-        return err.value, [(e.kind, e.a, e.b, e.c, e.d, e.slice) for e in ev[:m]]
+        return err.value, _events(ev, m)
 
     def deframe_messages(self, arena_dev_ptr, slices, assembler, want_events=False, ev_cap=None, msgs_cap=None):
         """deframe + assemble: -> (h2 error, [Msg...]) or (h2 error, [Msg...], events) with want_events"""
         n = len(slices)
-        arr = (ReadSlice * max(1, n))()
-        for i, (o, l) in enumerate(slices):
-            arr[i].off, arr[i].len = o, l
+        arr = _slice_array(slices)
         ev_cap = ev_cap or min(sum(l for _, l in slices) * 2 + 64 if n else 64, 1 << 20)
         msgs_cap = msgs_cap or ev_cap
         ev = (H2Event * ev_cap)() if want_events else None
@@ -269,7 +288,7 @@ class Parser:
         msgs = _msgs(out, m)
         if not want_events:
             return err.value, msgs
-        return err.value, msgs, [(e.kind, e.a, e.b, e.c, e.d, e.slice) for e in ev[:ev_cap] if e.kind]
+        return err.value, msgs, [e for e in _events(ev, ev_cap) if e[0]]
 
     def close(self):
         if self.h:
@@ -287,9 +306,7 @@ def deframe_batch(items, caps=None):
     arr = (H2DeframeItem * max(1, n))()
     keep = []
     for i, (parser, arena, slices) in enumerate(items):
-        sl = (ReadSlice * max(1, len(slices)))()
-        for k, (o, l) in enumerate(slices):
-            sl[k].off, sl[k].len = o, l
+        sl = _slice_array(slices)
         cap = (caps[i] if caps is not None else None) or min(sum(l for _, l in slices) * 2 + 64, 1 << 20)
         ev = (H2Event * cap)()
         keep.append((sl, ev))
@@ -299,7 +316,7 @@ def deframe_batch(items, caps=None):
     out = []
     for i in range(n):
         m = int(arr[i].n_events)
-        out.append((int(arr[i].h2_error), [(e.kind, e.a, e.b, e.c, e.d, e.slice) for e in keep[i][1][:m]] if m >= 0 else m))
+        out.append((int(arr[i].h2_error), _events(keep[i][1], m) if m >= 0 else m))
     return out
 
 
@@ -314,9 +331,7 @@ def deframe_messages_batch(items, want_events=False, ev_caps=None, msgs_caps=Non
     arr = (H2MessagesItem * max(1, n))()
     keep = []
     for i, (parser, asm, arena, slices) in enumerate(items):
-        sl = (ReadSlice * max(1, len(slices)))()
-        for k, (o, l) in enumerate(slices):
-            sl[k].off, sl[k].len = o, l
+        sl = _slice_array(slices)
         cap = (ev_caps[i] if ev_caps is not None else None) or min(sum(l for _, l in slices) * 2 + 64, 1 << 20)
         mcap = (msgs_caps[i] if msgs_caps is not None else None) or cap
         ev = (H2Event * cap)() if want_events else None
@@ -331,7 +346,7 @@ def deframe_messages_batch(items, want_events=False, ev_caps=None, msgs_caps=Non
         m, k = int(arr[i].n_msgs), int(arr[i].n_events)
         r = (int(arr[i].h2_error), _msgs(keep[i][2], m) if m >= 0 else m)
         if want_events:
-            r += ([(e.kind, e.a, e.b, e.c, e.d, e.slice) for e in keep[i][1][:k]] if k >= 0 else k,)
+            r += (_events(keep[i][1], k) if k >= 0 else k,)
         res.append(r)
     return res
 
@@ -406,9 +421,7 @@ class GroupPipe:
         arr = (H2LinkSpec * max(1, len(specs)))()
         self._keep = []
         for i, (link, msgs, parser, delivered, cap) in enumerate(specs):
-            m = (H2Msg * max(1, len(msgs)))()
-            for k, (p, n, sid, fl) in enumerate(msgs):
-                m[k].payload, m[k].len, m[k].stream_id, m[k].flags = p, n, sid, fl
+            m = _msg_array(msgs)
             self._keep.append((m, parser))
             arr[i].link, arr[i].msgs, arr[i].nmsgs, arr[i].parser = link, m, len(msgs), parser.h
             arr[i].delivered_slices, arr[i].events_cap = delivered, cap
@@ -432,7 +445,7 @@ class GroupPipe:
         cap = max(1, self.events_caps[i])
         ev = (H2Event * cap)()
         m = check(self.lib.grdma_h2_group_pipe_events(self.h, i, ev, cap))
-        return [(e.kind, e.a, e.b, e.c, e.d, e.slice) for e in ev[:m]]
+        return _events(ev, m)
 
     def slice_table(self, i, cap=1 << 16):
         arr = (Slice * cap)()
@@ -617,26 +630,13 @@ class Pipe:
     link: the one link of the job this pipe serves.  A job carries one pipe: for more than one link of one job use
     GroupPipe (a second Pipe on another link would replace this one's kernels in the job's graph)."""
 
-    @staticmethod
-    def _bind_pipe(lib):
-        lib.grdma_h2_pipe_create.restype = C.c_void_p
-        lib.grdma_h2_pipe_create.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(H2Msg), u64, C.c_uint32, C.c_void_p, u64, u64]
-        lib.grdma_h2_pipe_enqueue.argtypes = [C.c_void_p, C.c_int]
-        lib.grdma_h2_pipe_sync.argtypes = [C.c_void_p, C.POINTER(u64), C.POINTER(H2Event), u64]
-        lib.grdma_h2_pipe_destroy.argtypes = [C.c_void_p]
-        lib.grdma_h2_pipe_boundary_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
-
     def __init__(self, job, msgs, parser, delivered_slices, events_cap, link=0, max_frame=16384):
         self.lib = _bind()
-        lib = self.lib
-        Pipe._bind_pipe(lib)
-        arr = (H2Msg * len(msgs))()
-        for i, (p, n, sid, fl) in enumerate(msgs):
-            arr[i].payload, arr[i].len, arr[i].stream_id, arr[i].flags = p, n, sid, fl
         self.events_cap = events_cap
         self.delivered = delivered_slices
         self.parser = parser  # (kept alive)
-        self.h = lib.grdma_h2_pipe_create(job.h, link, arr, len(msgs), max_frame, parser.h, delivered_slices, events_cap)
+        self.h = self.lib.grdma_h2_pipe_create(job.h, link, _msg_array(msgs), len(msgs), max_frame, parser.h, delivered_slices,
+                                               events_cap)
         if not self.h:
             raise GrdmaError("h2 pipe allocation failed")
 
@@ -647,7 +647,6 @@ class Pipe:
         job's recorded run sent.  Close it before the forward pipes and before `reply`."""
         self = cls.__new__(cls)
         self.lib = _bind()
-        Pipe._bind_pipe(self.lib)
         self.events_cap = events_cap
         self.delivered = delivered_slices
         self.parser, self.reply_framer = parser, reply  # (kept alive)
@@ -677,7 +676,7 @@ class Pipe:
         check(self.lib.grdma_h2_pipe_boundary_stats(self.h, bs))
         r["boundary_steps"], r["t_boundary"] = int(bs[0]), int(bs[1])
         if want_events:
-            r["event_list"] = [(e.kind, e.a, e.b, e.c, e.d, e.slice) for e in ev[:min(r["events"], self.events_cap)]]
+            r["event_list"] = _events(ev, min(r["events"], self.events_cap))
         return r
 
     def attach_assembler(self, a):
