@@ -206,7 +206,9 @@ __device__ __forceinline__ bool rxf_body(const grdma_rx_op& op_in) {
   auto& s_sin = lds->f.sin;
   static_assert(RXFP(RXF_MAX) + 2 <= sizeof(lds->f.n) / sizeof(uint32_t), "padded record arrays fit");
   __shared__ uint32_t s_w[3][RXF_WAVES];
-  __shared__ uint32_t s_bad, s_vj, s_first, s_send, s_totn;
+  // (s_bad: the probe's verdict, read behind the probe's barrier; s_bad2: step 3's, read behind step 3's.  One word for
+  // both would let a wave that is already in step 3 set it before a slower wave has read the probe's verdict.)
+  __shared__ uint32_t s_bad, s_bad2, s_vj, s_first, s_send, s_totn;
 
   // ---- 0. state, preconditions (every thread reads the same words; nothing is stored before the probe passed)
   uint8_t* const ring = c->ring;
@@ -245,6 +247,7 @@ __device__ __forceinline__ bool rxf_body(const grdma_rx_op& op_in) {
   const bool idle = Lr == 0;  // nothing has arrived: the general planner records the would-block
   if (tid == 0) {
     s_bad = 0;
+    s_bad2 = 0;
     s_vj = 0xFFFFFFFFu;
     s_first = 0xFFFFFFFFu;
     s_send = 0;
@@ -374,7 +377,7 @@ __device__ __forceinline__ bool rxf_body(const grdma_rx_op& op_in) {
       j--;
       steps++;
     }
-    if (j > 0 && s_n[RXFP(j - 1)] < 2 * RXF_MINRD) s_bad = 1;  // a long run of small records: not this body's case
+    if (j > 0 && s_n[RXFP(j - 1)] < 2 * RXF_MINRD) s_bad2 = 1;  // a long run of small records: not this body's case
     const bool from_start = j == 0;  // my chain began at the drain's start: it may hold the slice that closes the open read
     uint32_t s = j == 0 ? s0 : 0;
     for (; j < i0; j++) s = rxf_space_after(s_n[RXFP(j)], s);
@@ -391,7 +394,7 @@ __device__ __forceinline__ bool rxf_body(const grdma_rx_op& op_in) {
     }
   }
   __syncthreads();
-  if (s_bad) {
+  if (s_bad2) {
     if (tid == 0) {
       atomicAdd(&g_rx_fast_drains[4], 1ull);
       res->pad0++;

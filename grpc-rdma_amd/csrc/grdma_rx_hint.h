@@ -77,7 +77,10 @@ __device__ __forceinline__ int rxh_body(const grdma_rx_op& op_in, const uint32_t
   grdma_plan* plan = op.plan;
   grdma_rx_result* res = op.result;
   __shared__ uint32_t s_w[4][RXM_WAVES];
-  __shared__ uint32_t s_bad, s_first, s_F;
+  // (s_bad: the table's verdict of step 1 and, behind step 2's barrier, step 4's; s_bad_ring: the probe's.  With one word
+  // a wave already probing could set it before a slower wave has read step 1's verdict: that wave would take reason 2,
+  // the others 0, and it would miss the barriers inside `if (!reason)` below.)
+  __shared__ uint32_t s_bad, s_bad_ring, s_first, s_F;
 
   // ---- 0. state, the table's header, preconditions
   uint8_t* const ring = c->ring;
@@ -114,6 +117,7 @@ __device__ __forceinline__ int rxh_body(const grdma_rx_op& op_in, const uint32_t
   const bool idle = Lr == 0;
   if (tid == 0) {
     s_bad = 0;
+    s_bad_ring = 0;
     s_first = RXM_NONE;
     s_F = RXM_NONE;
   }
@@ -188,12 +192,12 @@ __device__ __forceinline__ int rxh_body(const grdma_rx_op& op_in, const uint32_t
     const u32x2 fw = __builtin_amdgcn_raw_buffer_load_b64(rs, o_f, 0, 16);
     if (have) {
       const uint64_t h = ((uint64_t)hw.y << 32) | hw.x, f = ((uint64_t)fw.y << 32) | fw.x;
-      if (h != (uint64_t)n_mine || f != GRDMA_FOOTER) s_bad = 1;  // the ring does not hold what the table says
+      if (h != (uint64_t)n_mine || f != GRDMA_FOOTER) s_bad_ring = 1;  // the ring does not hold what the table says
     }
     // the first record that leaves no read open behind it (F), among the first RXM_PFX records
     if (tid < RXM_PFX && tid < V && H.n[tid] >= RXM_RESET) atomicMin(&s_F, tid);
     __syncthreads();
-    if (s_bad) reason = 3;
+    if (s_bad_ring) reason = 3;
   }
   const uint64_t t_probe = __builtin_amdgcn_s_memtime();
 

@@ -78,12 +78,17 @@ def _oracle_rounds(R, max_sge, slices, sends=1):
     return delivered, first_rounds, st, ring
 
 
-def _run_job(g, R, max_sge, slices, pipeline, flags=0, mode=None, sends=1, promise=False, fused_wire=None):
+def _run_job(g, R, max_sge, slices, pipeline, flags=0, mode=None, sends=1, promise=False, fused_wire=None, pairs=None):
+    """pairs: a connected (tx, rx) the caller keeps (pairs taken from the PairPool: tests/planner_sweep_lib.py); they are
+    left open"""
     from grpc_rdma_amd import stream as gs
     rng = random.Random(5)
     bufs = [g.DeviceBuffer(data=s, offset=rng.randrange(16)) for s in slices]
-    tx, rx = g.Pair(R, max_sge, flags), g.Pair(R, max_sge, flags)
-    g.connect_pairs(tx, rx)
+    if pairs is not None:
+        tx, rx = pairs
+    else:
+        tx, rx = g.Pair(R, max_sge, flags), g.Pair(R, max_sge, flags)
+        g.connect_pairs(tx, rx)
     N = sum(len(s) for s in slices)
     dst_cap = N + 32 * (2 * len(slices) + 64) + 4096
     dst = g.DeviceBuffer(nbytes=dst_cap)
@@ -118,8 +123,9 @@ def _run_job(g, R, max_sge, slices, pipeline, flags=0, mode=None, sends=1, promi
            "launches": [int(x) for x in last.launches_class], "ms": [float(x) for x in last.ms_class],
            "rounds_set": 2 * rounds + 4 if pipeline else rounds + 2}
     job.close()
-    tx.close()
-    rx.close()
+    if pairs is None:
+        tx.close()
+        rx.close()
     return out
 
 
