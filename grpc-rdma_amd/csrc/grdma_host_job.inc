@@ -1,4 +1,6 @@
-// The device-resident streaming job: links, schedules (sequential, paired), HIP graphs, the C ABI of grdma_stream_job_*.
+// The device-resident streaming job: links, the C ABI of grdma_stream_job_*, and the schedule of a job's rounds.  The
+// schedule is stated ONCE: job_stage_launch (what a stage launches) and job_schedule (sequential / paired / limit-driven:
+// the steps and what each waits for); job_build_graph, job_enqueue_chain and job_enqueue_streams only emit it.
 // (part of the host layer: textually included by grdma_pair.hip -- one translation unit, so that the pair
 //  structure and the helpers in its unnamed namespaces stay internal)
 // ---- device-resident streaming job -------------------------------------------------
@@ -77,10 +79,10 @@ struct grdma_stream_job {
   int rx_fast = 1;                    // drains of one-Send rounds go through k_rx_fast first (grdma_rx_fast.hip), the
                                       // general planner behind it only does what that kernel declined
                                       // (0: the general planner alone -- grdma_stream_job_run, after repeated declines)
-  std::vector<hipEvent_t> pev;        // dependency events of the pipelined schedule
+  std::vector<hipEvent_t> pev;        // dependency events of the streams emitter (job_enqueue_streams)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::vector<hipEvent_t> kev;
-  std::vector<int> kev_cls;                   // GRDMA_RUN_INSTRUMENTED_SCHEDULE: the class of the launch behind mark i
+  std::vector<int> kev_cls;                   // timed passes: the class of the launch between marks i and i + 1
   hipStream_t stream = nullptr;
   bool direct = false;
   uint64_t max_ring = 0;
@@ -152,10 +154,14 @@ inline bool job_mw(const grdma_stream_job* j) { return j->pipeline && j->rx_fast
 // several Sends per plan when the job is not pipelined -- a ring every round fills sees its credit at once here, a round
 // late on the paired schedule
 inline bool job_mw_seq(const grdma_stream_job* j) { return j->sends > 1 && !j->pipeline && j->rx_fast && j->tx_fast; }
-hipError_t job_launch_pair_mw(const grdma_rx_op* rxops, const grdma_tx_op* txops, const grdma_txf_ctl* ctls, uint32_t n, uint32_t g_rx,
-                              uint32_t g_tx, hipStream_t s) {
-  job_kargs a(rxops, txops, ctls, g_rx);
-  return hipLaunchKernel(grdma_kernel_fn_plan_pair_mw(), dim3(n, g_rx + g_tx), dim3(grdma_kernel_threads(0)), a.v, 0, s);
+// compute units of the current device (0: unknown)
+inline int job_device_cus() {
+  static const int cus = [] {
+    int dev = 0, c = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) c = 0;
+    return c;
+  }();
+  return cus;
 }
 // Promised credit (k_plan_pair_mw): the Send's workgroups of the planner pair's launch wait for the drain plan of the same
 // launch.  The invariant that keeps this wait, and every other wait between the workgroups of a job's launch, from
@@ -172,12 +178,7 @@ inline bool job_promise(const grdma_stream_job* j) {
   if (!j->promise || !job_mw(j) || j->direct) return false;
   static const bool resident_only = getenv("GRDMA_JOB_PROMISE_RESIDENT") && atoi(getenv("GRDMA_JOB_PROMISE_RESIDENT")) != 0;
   if (!resident_only) return true;
-  static const int cus = [] {
-    int dev = 0, c = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) c = 0;
-    return c;
-  }();
-  return (uint64_t)j->links.size() * (job_rx_groups(j) + job_tx_groups(j)) <= (uint64_t)cus;
+  return (uint64_t)j->links.size() * (job_rx_groups(j) + job_tx_groups(j)) <= (uint64_t)job_device_cus();
 }
 // Wire workgroups of the planner pair's launch (0: the wire is a k_copy launch of its own).  The planner kernel runs one
 // workgroup per CU (its LDS), a wave of it moves one tile at a time: only a round of a few MiB is moved as fast by W of
@@ -190,12 +191,7 @@ inline uint32_t job_wire_groups(const grdma_stream_job* j) {
 #ifdef GRDMA_WAVE_EMU
   return w;  // (the emulator runs the workgroups of a launch one after the other, in index order: the wire's first)
 #else
-  static const int cus = [] {
-    int dev = 0, c = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) c = 0;
-    return c;
-  }();
-  return (uint64_t)j->links.size() * (w + job_rx_groups(j) + job_tx_groups(j)) <= (uint64_t)cus ? w : 0;
+  return (uint64_t)j->links.size() * (w + job_rx_groups(j) + job_tx_groups(j)) <= (uint64_t)job_device_cus() ? w : 0;
 #endif
 }
 inline uint32_t job_pair_mode(const grdma_stream_job* j) {
@@ -206,31 +202,194 @@ inline uint32_t job_index_blocks(const grdma_stream_job* j) {  // k_tx_index: 10
   for (const grdma_job_link& l : j->links) most = std::max<uint64_t>(most, l.count);
   return (uint32_t)((most + 1023) / 1024);
 }
-// the send plan of round t: priced from the index of the slice buffer (built in front of the first round of a step), the
-// general planner in the same launch for what that declines
-hipError_t job_launch_tx_plan(grdma_stream_job* j, int k, uint64_t t, uint32_t n, hipStream_t s) {
-  if (!j->tx_fast) return grdma_launch_tx_plan(j->d_txop + k * n, n, s);
-  hipError_t e = hipSuccess;
-  if (t == 0 && job_index_needed(j)) e = grdma_launch_tx_index(j->d_txf, n, job_index_blocks(j), s);
-  if (e != hipSuccess) return e;
-  // (several Sends per plan: only the planners of grdma_tx_multi.h price those -- also in the eager passes)
-  if (j->sends > 1 && (job_mw(j) || job_mw_seq(j))) return job_launch_pair_mw(nullptr, j->d_txop + k * n, j->d_txf, n, 0, job_tx_groups(j), s);
-  return grdma_launch_tx_plan_job(j->d_txop + k * n, j->d_txf, n, s);
-}
-
-// the receive plan of a round: k_rx_plan_job = the straight-line steady-state body, then the general planner for what it declines
-hipError_t job_launch_rx_plan(grdma_stream_job* j, const grdma_rx_op* ops, uint32_t n, hipStream_t s) {
-  if (j->sends > 1 && (job_mw(j) || job_mw_seq(j))) return job_launch_pair_mw(ops, nullptr, j->d_txf, n, job_rx_groups(j), 0, s);
-  if (j->rx_fast) return grdma_launch_rx_plan_job(ops, n, s);
-  return grdma_launch_rx_plan(ops, n, s);
-}
-
-int job_enqueue(grdma_stream_job* j, hipStream_t s, bool instrument) {
+// ---- the schedule of a job, stated once ---------------------------------------------------------------------------
+// job_stage_launch says WHAT a stage of a round launches (kernel, grid, the five job_kargs values), job_schedule says IN
+// WHAT ORDER: the steps of a schedule in creation order, each with the steps it waits for.  The three emitters behind
+// them (a HIP graph, a chain on one stream, the streams) only walk that list -- docs/job_planners.md, "The host side".
+enum job_stage {
+  JOB_INDEX,           // k_tx_index in front of round 0: the index of the slice table the Sends are priced from
+  JOB_SEND_PLAN,       // P_t
+  JOB_GATHER,          // G_t
+  JOB_WIRE,            // W_t
+  JOB_DRAIN_PLAN,      // X_t
+  JOB_SCATTER,         // A_t
+  JOB_PAIR,            // X_t + P_{t+1} in one launch (k_plan_pair_mw), with or without the wire's workgroups
+  JOB_SCATTER_GATHER,  // A_t + G_{t+1} in one launch (k_rx_apply_gather)
+  JOB_COMMIT           // behind the last round: the connection's arrival report and the state lines (k_tx_commit)
+};
+enum job_schedule_kind { JOB_SEQUENTIAL, JOB_PAIRED, JOB_LIMIT_DRIVEN };
+// One launch.  fn == nullptr: the stage does not exist in this round (the wire of a direct wire, a wire the planner
+// pair's launch carries, an index that is kept).  cls is the time class of grdma_stream_result::ms_class; -1 = none: a
+// timed pass records no event behind it, so the index counts towards the send plan it precedes.
+struct job_launch {
+  int cls = -1;
+  const void* fn = nullptr;
+  dim3 grid;
+  uint32_t threads = 0;
+  const void *a0 = nullptr, *a1 = nullptr, *a2 = nullptr;
+  uint32_t split = 0;
+  const void* wire = nullptr;
+};
+// `as_graph`: the launches of a job's GRAPH (and of the timed chain that mirrors it) rather than of an eager pass.
+job_launch job_stage_launch(const grdma_stream_job* j, job_schedule_kind kind, bool as_graph, job_stage stage, uint64_t t) {
   const uint32_t n = (uint32_t)j->links.size();
   const uint32_t txb = job_copy_blocks(j, j->max_ring / 2), rxb = job_copy_blocks(j, j->max_ring);
+  const uint32_t pt = grdma_kernel_threads(0), ct = grdma_kernel_threads(1);
+  const void* txop = j->d_txop + job_opset(t) * n;
+  const void* rxop = j->d_rxop + job_opset(t) * n;
+  const void* gplans = j->d_plans;
+  const void* wplans = j->d_plans + n * (1 + (t & 1));
+  // several Sends per plan: only the planners of grdma_tx_multi.h / grdma_rx_multi.h handle those -- k_plan_pair_mw with
+  // the workgroups of one side alone (job_mw_seq: the sequential schedule; job_mw: the eager passes of a paired job)
+  const bool multi = j->sends > 1 && (job_mw(j) || job_mw_seq(j));
+  // few links with small rings: the wire rides in the planner pair's launch (the paired schedule only)
+  const uint32_t wg_wire = kind == JOB_PAIRED ? job_wire_groups(j) : 0;
+  auto make = [](int cls, const void* fn, dim3 grid, uint32_t threads, const void* a0, const void* a1 = nullptr,
+                 const void* a2 = nullptr, uint32_t split = 0, const void* wire = nullptr) {
+    job_launch l;
+    l.cls = cls; l.fn = fn; l.grid = grid; l.threads = threads;
+    l.a0 = a0; l.a1 = a1; l.a2 = a2; l.split = split; l.wire = wire;
+    return l;
+  };
+  switch (stage) {
+    case JOB_INDEX:  // (once per job unless the table may change between steps; only Sends priced from it need it)
+      if (t != 0 || !j->tx_fast || !job_index_needed(j)) return job_launch();
+      return make(-1, grdma_kernel_fn_tx_index(), dim3(job_index_blocks(j), n), grdma_tx_index_threads(), j->d_txf);
+    case JOB_SEND_PLAN: {
+      if (!j->tx_fast) return make(0, grdma_kernel_fn(0), dim3(n), pt, txop);
+      // ODDITY (kept): the first Send of a pipelined job's graph is priced by the planner pair's Send workgroups
+      // (k_plan_pair_mw with no drain); the eager passes give round 0 to k_tx_plan_job like every other round
+      const bool first_send_of_graph = as_graph && t == 0 && (j->pipeline || job_mw_seq(j));
+      if (first_send_of_graph || multi)
+        return make(0, grdma_kernel_fn_plan_pair_mw(), dim3(n, job_tx_groups(j)), pt, nullptr, txop, j->d_txf, 0u);
+      // priced from the index, the general planner behind it in the same launch for what that declines
+      return make(0, grdma_kernel_fn(6), dim3(n), grdma_tx_plan_job_threads(), txop, j->d_txf);
+    }
+    case JOB_GATHER:
+      return make(1, grdma_kernel_fn(1), dim3(txb, n), ct, gplans);
+    case JOB_WIRE:  // (a direct wire has no wire kernel: the gather writes the records into the peer ring)
+      if (j->direct || wg_wire) return job_launch();
+      return make(2, grdma_kernel_fn(1), dim3(txb, n), ct, wplans);
+    case JOB_DRAIN_PLAN:
+      // ODDITY (kept): the drain's planners alone get job_rx_groups as the split word, the Send's alone get 0
+      if (multi) return make(3, grdma_kernel_fn_plan_pair_mw(), dim3(n, job_rx_groups(j)), pt, rxop, nullptr, j->d_txf, job_rx_groups(j));
+      // k_rx_plan_job = the straight-line steady-state body, then the general planner for what it declines
+      if (j->rx_fast) return make(3, grdma_kernel_fn_rx_plan_job(), dim3(n), grdma_rx_plan_job_threads(), rxop);
+      return make(3, grdma_kernel_fn_rx_plan(), dim3(n), pt, rxop);
+    case JOB_SCATTER:
+      return make(4, grdma_kernel_fn(3), dim3(rxb, n), ct, rxop);
+    case JOB_PAIR: {  // the drain of round t and the Send of round t + 1 (none behind the last round)
+      const bool more = t + 1 < j->rounds;
+      return make(5, grdma_kernel_fn_plan_pair_mw(), dim3(n, wg_wire + job_rx_groups(j) + (more ? job_tx_groups(j) : 0)), pt, rxop,
+                  more ? j->d_txop + job_opset(t + 1) * n : nullptr, j->d_txf, job_pair_mode(j), wg_wire ? wplans : nullptr);
+    }
+    case JOB_SCATTER_GATHER:  // (both are ready behind the planner pair, neither touches the other's bytes)
+      return make(6, grdma_kernel_fn(8), dim3(std::max(rxb, txb), 2 * n), ct, rxop, gplans);
+    case JOB_COMMIT:
+      return make(-1, grdma_kernel_fn(5), dim3(n), 64, j->d_txconns);
+  }
+  return job_launch();
+}
+hipError_t job_launch_on(const job_launch& l, hipStream_t s) {
+  job_kargs a(l.a0, l.a1, l.a2, l.split, l.wire);
+  return hipLaunchKernel(l.fn, l.grid, dim3(l.threads), a.v, 0, s);
+}
+
+// A step of a schedule: a launch and the EARLIER steps (indices into the list) it waits for.
+struct job_step {
+  job_stage stage;
+  job_launch l;
+  std::vector<int> deps;
+};
+// The three schedules (t = round; P send plan, G gather, W wire, X drain plan, A scatter; W|G = the wire, or the gather
+// where the round has no wire launch).  Steps come in creation order -- per round P G W X A -- and absent stages are left
+// out, so every emitter sees only what is launched.
+//   sequential     P_t <- A_{t-1}    G_t <- P_t    W_t <- G_t    X_t <- (W|G)_t    A_t <- X_t
+//   paired         kernels of different branches of a graph do not overlap on this stack (measured), so the round is a
+//                  chain: [index] P_0 G_0, then per round W_t <- G_t, the planner pair X_t + P_{t+1} <- (W|G)_t, A_{t-1},
+//                  and A_t + G_{t+1} <- X_t (the plain scatter behind the last round): three launches per round, two
+//                  where the pair's launch carries the wire
+//   limit-driven   a pipelined job on the general planners.  The drain of round t walks exactly up to the tail its Send
+//                  computed (grdma_rx_op::limit_ptr), so round t + 1 may land in the ring while round t is walked:
+//                    P_t <- P_{t-1} (the sender's state), G_{t-1} (one gather plan), (W|G)_{t-2} (staging / wire plan
+//                           of this parity), A_{t-2} (credit lag of at most one round; implies X_{t-2}: the limit slot)
+//                    G_t <- P_t        W_t <- G_t
+//                    X_t <- (W|G)_t, X_{t-1} (the reader's state), A_{t-2} (scatter plan / result of this parity)
+//                    A_t <- X_t, A_{t-1} (credit reports stay in order)
+//                  the only cycle that spans rounds is A_{t-2} -> P_t -> G_t -> W_t -> X_t -> A_t: two rounds in flight
+//   all three      index <- nothing, P_0 <- index;    commit <- (W|G)_{R-1}, A_{R-1}
+// The sender may see the credit of a scatter a round later than on the sequential schedule; with rounds of at most
+// ring / 6 that never limits a Send.
+std::vector<job_step> job_schedule(const grdma_stream_job* j, job_schedule_kind kind, bool as_graph) {
+  const uint64_t R = j->rounds;
+  std::vector<job_step> steps;
+  std::vector<int> P(R, -1), G(R, -1), W(R, -1), X(R, -1), A(R, -1);  // the step that holds a stage of round t
+  auto add = [&](job_stage stage, uint64_t t, std::initializer_list<int> deps) -> int {
+    job_step s{stage, job_stage_launch(j, kind, as_graph, stage, t), {}};
+    if (!s.l.fn) return -1;
+    for (int d : deps)
+      if (d >= 0 && std::find(s.deps.begin(), s.deps.end(), d) == s.deps.end()) s.deps.push_back(d);  // (a node twice is an invalid argument)
+    steps.push_back(s);
+    return (int)steps.size() - 1;
+  };
+  auto at = [](const std::vector<int>& v, uint64_t t, uint64_t back) { return t >= back ? v[t - back] : -1; };
+  auto wire_at = [&](uint64_t t, uint64_t back) { return at(W, t, back) >= 0 ? at(W, t, back) : at(G, t, back); };
+  for (uint64_t t = 0; t < R; t++) {
+    const int index = t == 0 ? add(JOB_INDEX, 0, {}) : -1;
+    switch (kind) {
+      case JOB_SEQUENTIAL:
+        P[t] = add(JOB_SEND_PLAN, t, {index, at(A, t, 1)});
+        G[t] = add(JOB_GATHER, t, {P[t]});
+        W[t] = add(JOB_WIRE, t, {G[t]});
+        X[t] = add(JOB_DRAIN_PLAN, t, {wire_at(t, 0)});
+        A[t] = add(JOB_SCATTER, t, {X[t]});
+        break;
+      case JOB_PAIRED:
+        if (t == 0) {
+          P[0] = add(JOB_SEND_PLAN, 0, {index});
+          G[0] = add(JOB_GATHER, 0, {P[0]});
+        }
+        W[t] = add(JOB_WIRE, t, {G[t]});
+        X[t] = add(JOB_PAIR, t, {wire_at(t, 0), at(A, t, 1)});
+        if (t + 1 < R) {
+          P[t + 1] = X[t];
+          A[t] = G[t + 1] = add(JOB_SCATTER_GATHER, t, {X[t]});
+        } else {
+          A[t] = add(JOB_SCATTER, t, {X[t]});
+        }
+        break;
+      case JOB_LIMIT_DRIVEN:
+        P[t] = add(JOB_SEND_PLAN, t, {index, at(P, t, 1), at(G, t, 1), wire_at(t, 2), at(A, t, 2)});
+        G[t] = add(JOB_GATHER, t, {P[t]});
+        W[t] = add(JOB_WIRE, t, {G[t]});
+        X[t] = add(JOB_DRAIN_PLAN, t, {wire_at(t, 0), at(X, t, 1), at(A, t, 2)});
+        A[t] = add(JOB_SCATTER, t, {X[t], at(A, t, 1)});
+        break;
+    }
+  }
+  // the drains of the job were told how far to walk by their op (limit_ptr); the connection's own arrival report and
+  // the state lines follow once, behind the last round.  ODDITY (kept): a job of no rounds has an empty graph, its
+  // eager passes still launch the commit.
+  if (R > 0) add(JOB_COMMIT, R - 1, {wire_at(R, 1), A[R - 1]});
+  else if (!as_graph) add(JOB_COMMIT, 0, {});
+  return steps;
+}
+// the schedule of a job's graph
+inline job_schedule_kind job_graph_kind(const grdma_stream_job* j) {
+  return !j->pipeline ? JOB_SEQUENTIAL : job_mw(j) ? JOB_PAIRED : JOB_LIMIT_DRIVEN;
+}
+// GRDMA_RUN_INSTRUMENTED_SCHEDULE times the graph's own chain; only the paired schedule is one
+bool job_is_paired(const grdma_stream_job* j) { return job_mw(j) && j->rounds >= 1; }
+
+// ---- emitter 1 of 3: a chain on one stream -------------------------------------------------------------------------
+// The steps of a sequential or paired schedule one after the other (their creation order is their order).  `timed`: an
+// event in front of the first launch and behind every launch with a class, the classes in kev_cls -- what
+// grdma_stream_job_run turns into ms_class / launches_class.  GRDMA_RUN_INSTRUMENTED is the sequential chain (also of a
+// pipelined job), GRDMA_RUN_INSTRUMENTED_SCHEDULE the paired one with the graph's launches: the same work in the same
+// order as the graph, plus the time of each launch by itself.
+int job_enqueue_chain(grdma_stream_job* j, job_schedule_kind kind, bool as_graph, hipStream_t s, bool timed) {
   size_t e = 0;
   auto mark = [&]() -> int {
-    if (!instrument) return 0;
     if (e >= j->kev.size()) {
       hipEvent_t ev;
       HIP_TRY(hipEventCreate(&ev));
@@ -239,354 +398,102 @@ int job_enqueue(grdma_stream_job* j, hipStream_t s, bool instrument) {
     HIP_TRY(hipEventRecord(j->kev[e++], s));
     return 0;
   };
-  if (int rc = mark()) return rc;
-  for (uint64_t r = 0; r < j->rounds; r++) {
-    const int k = job_opset(r);
-    HIP_TRY(job_launch_tx_plan(j, k, r, n, s));
-    if (int rc = mark()) return rc;
-    HIP_TRY(grdma_launch_copy(j->d_plans, n, txb, s));
-    if (int rc = mark()) return rc;
-    if (!j->direct) HIP_TRY(grdma_launch_copy(j->d_plans + n * (1 + (r & 1)), n, txb, s));
-    if (int rc = mark()) return rc;
-    HIP_TRY(job_launch_rx_plan(j, j->d_rxop + k * n, n, s));
-    if (int rc = mark()) return rc;
-    HIP_TRY(grdma_launch_rx_apply(j->d_rxop + k * n, n, rxb, s));
+  if (timed) {
+    j->kev_cls.clear();
     if (int rc = mark()) return rc;
   }
-  // the drains of the job were told how far to walk by their op (limit_ptr); the connection's own arrival
-  // report and the state lines follow once, behind the last round
-  HIP_TRY(grdma_launch_tx_commit(j->d_txconns, nullptr, n, s));
+  for (const job_step& st : job_schedule(j, kind, as_graph)) {
+    HIP_TRY(job_launch_on(st.l, s));
+    if (!timed || st.l.cls < 0) continue;
+    if (int rc = mark()) return rc;
+    j->kev_cls.push_back(st.l.cls);
+  }
   return 0;
 }
 
-// GRDMA_RUN_INSTRUMENTED_SCHEDULE: the launches of the DEFAULT schedule of a streaming job -- the chain the graph
-// builder below makes of a paired job (planner pair; scatter + next gather; wire) -- one after the other on one
-// stream with an event between every two of them.  The graph's order is a chain already, so this is the same
-// work in the same order; what the events add is the time of each launch by itself (classes 5 = k_plan_pair_mw,
-// 6 = k_rx_apply_gather beside the five of the in-order pass).
-bool job_is_paired(const grdma_stream_job* j) {
-  return j->pipeline && j->rx_fast && j->tx_fast && j->rounds >= 1;
-}
-int job_enqueue_schedule_instrumented(grdma_stream_job* j, hipStream_t s) {
-  if (!job_is_paired(j))
-    return fail(GRDMA_ERR_INVALID, "GRDMA_RUN_INSTRUMENTED_SCHEDULE times the paired schedule (pipelined job, steady-state planners)");
-  const uint32_t n = (uint32_t)j->links.size();
-  const uint32_t txb = job_copy_blocks(j, j->max_ring / 2), rxb = job_copy_blocks(j, j->max_ring);
-  const uint32_t ct = grdma_kernel_threads(1);
-  const uint64_t R = j->rounds;
-  size_t e = 0;
-  j->kev_cls.clear();
-  auto mark = [&](int cls) -> int {
-    if (e >= j->kev.size()) {
-      hipEvent_t ev;
-      HIP_TRY(hipEventCreate(&ev));
-      j->kev.push_back(ev);
-    }
-    HIP_TRY(hipEventRecord(j->kev[e++], s));
-    if (cls >= 0) j->kev_cls.push_back(cls);
-    return 0;
-  };
-  auto launch = [&](const void* fn, dim3 grid, uint32_t threads, const void* a0, const void* a1, const void* a2,
-                    uint32_t a3 = 0, const void* a4 = nullptr) -> hipError_t {
-    job_kargs a(a0, a1, a2, a3, a4);
-    return hipLaunchKernel(fn, grid, dim3(threads), a.v, 0, s);
-  };
-  if (int rc = mark(-1)) return rc;
-  for (uint64_t t = 0; t < R; t++) {
-    const int k = job_opset(t);
-    const void* rxop = j->d_rxop + k * n;
-    const void* gplans = j->d_plans;
-    const void* wplans = j->d_plans + n * (1 + (t & 1));
-    if (t == 0) {  // (k_tx_index +) the Send priced by k_plan_pair_mw's small workgroups (as the graph does)
-      if (job_index_needed(j)) HIP_TRY(grdma_launch_tx_index(j->d_txf, n, job_index_blocks(j), s));
-      HIP_TRY(launch(grdma_kernel_fn_plan_pair_mw(), dim3(n, job_tx_groups(j)), grdma_kernel_threads(0), nullptr,
-                     j->d_txop + k * n, j->d_txf, 0u));
-      if (int rc = mark(0)) return rc;
-      HIP_TRY(launch(grdma_kernel_fn(1), dim3(txb, n), ct, gplans, nullptr, nullptr));
-      if (int rc = mark(1)) return rc;
-    }
-    const uint32_t wg_wire = job_wire_groups(j);
-    if (!j->direct && !wg_wire) {
-      HIP_TRY(launch(grdma_kernel_fn(1), dim3(txb, n), ct, wplans, nullptr, nullptr));
-      if (int rc = mark(2)) return rc;
-    }
-    const bool more = t + 1 < R;
-    const void* txop_next = j->d_txop + job_opset(t + 1) * n;
-    HIP_TRY(launch(grdma_kernel_fn_plan_pair_mw(), dim3(n, wg_wire + job_rx_groups(j) + (more ? job_tx_groups(j) : 0)),
-                   grdma_kernel_threads(0), rxop, more ? txop_next : nullptr, j->d_txf, job_pair_mode(j), wg_wire ? wplans : nullptr));
-    if (int rc = mark(5)) return rc;
-    if (more) {
-      HIP_TRY(launch(grdma_kernel_fn(8), dim3(std::max(rxb, txb), 2 * n), ct, rxop, gplans, nullptr));
-      if (int rc = mark(6)) return rc;
-    } else {
-      HIP_TRY(launch(grdma_kernel_fn(3), dim3(rxb, n), ct, rxop, nullptr, nullptr));
-      if (int rc = mark(4)) return rc;
-    }
-  }
-  HIP_TRY(grdma_launch_tx_commit(j->d_txconns, nullptr, n, s));
-  return 0;
-}
-
-// The same five kernels per round, scheduled as a software pipeline over four streams.
-// What has to stay ordered (t = round):
-//   plan_t -> gather_t -> wire_t -> rx_plan_t -> rx_apply_t      the data path of one round
-//   wire_{t-2} -> plan_t      two staging buffers (and wire plans) alternate; the one of
-//       this parity comes free when the round before last has left it
-//   rx_apply_{t-2} -> rx_plan_t   the scatter plan and result block of that parity are free
-//   rx_apply_{t-2} -> plan_t      the sender sees every credit but (possibly) the last one
-// Everything else overlaps: the send plan and gather of round t+1 run while round t is on
-// the wire and being walked, and the scatter of round t runs under round t+1.  The
-// sender may see the credit of a scatter one round later than in the sequential
-// schedule; with rounds of at most ring/6 that never limits a Send.
-// Every drain of a job walks only up to the tail its own Send computed (grdma_rx_op::limit_ptr), so round t + 1 may
-// land in the ring while round t is walked (no rx_plan_{t-1} -> wire_t) -- the graph builder's limit-driven schedule.
-int job_enqueue_pipelined(grdma_stream_job* j, hipStream_t s) {
-  const uint32_t n = (uint32_t)j->links.size();
-  const uint32_t txb = job_copy_blocks(j, j->max_ring / 2), rxb = job_copy_blocks(j, j->max_ring);
-  const uint64_t R = j->rounds;
+// ---- emitter 2 of 3: the limit-driven schedule as a software pipeline over four streams ---------------------------
+// Every stage has a home stream (send plan, gather, index and commit: the job's own; wire, drain plan and scatter: a
+// side stream each), a step waits for an event only where the step it depends on sits on another stream -- stream order
+// gives the rest, and adds W_{t-1} -> W_t.  The waits in front of the commit are the join of the side streams.
+int job_enqueue_streams(grdma_stream_job* j, hipStream_t s) {
+  const std::vector<job_step> steps = job_schedule(j, JOB_LIMIT_DRIVEN, false);
   if (!j->s_wire) {
     HIP_TRY(hipStreamCreateWithFlags(&j->s_wire, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&j->s_rxplan, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&j->s_apply, hipStreamNonBlocking));
   }
-  while (j->pev.size() < 4 * R + 1) {
+  while (j->pev.size() < steps.size() + 1) {  // one per step (used where another stream waits for it) and the fork
     hipEvent_t ev;
     HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     j->pev.push_back(ev);
   }
-  auto evG = [&](uint64_t t) { return j->pev[4 * t]; };      // gather_t done
-  auto evW = [&](uint64_t t) { return j->pev[4 * t + 1]; };  // round t is in the ring
-  auto evX = [&](uint64_t t) { return j->pev[4 * t + 2]; };  // rx_plan_t done
-  auto evA = [&](uint64_t t) { return j->pev[4 * t + 3]; };  // rx_apply_t done
-  hipStream_t sW = j->direct ? s : j->s_wire, sX = j->s_rxplan, sA = j->s_apply;
-  hipEvent_t fork = j->pev[4 * R];
+  auto home = [&](const job_step& st) {
+    return st.stage == JOB_WIRE ? j->s_wire : st.stage == JOB_DRAIN_PLAN ? j->s_rxplan : st.stage == JOB_SCATTER ? j->s_apply : s;
+  };
+  std::vector<bool> watched(steps.size(), false);
+  for (const job_step& st : steps)
+    for (int d : st.deps)
+      if (home(steps[d]) != home(st)) watched[d] = true;
+  // the fork: the side streams start behind whatever the job's stream was given before
+  hipEvent_t fork = j->pev[steps.size()];
   HIP_TRY(hipEventRecord(fork, s));
-  if (!j->direct) HIP_TRY(hipStreamWaitEvent(sW, fork, 0));
-  HIP_TRY(hipStreamWaitEvent(sX, fork, 0));
-  HIP_TRY(hipStreamWaitEvent(sA, fork, 0));
-  for (uint64_t t = 0; t < R; t++) {
-    const int k = job_opset(t);
-    if (j->direct) {
-      // (the gather writes the peer ring: the drain walks up to its round's tail, only the credit lag is bounded)
-      if (t >= 2) HIP_TRY(hipStreamWaitEvent(s, evA(t - 2), 0));
-      HIP_TRY(job_launch_tx_plan(j, k, t, n, s));
-      HIP_TRY(grdma_launch_copy(j->d_plans, n, txb, s));
-      HIP_TRY(hipEventRecord(evW(t), s));
-    } else {
-      if (t >= 2) {
-        HIP_TRY(hipStreamWaitEvent(s, evW(t - 2), 0));
-        HIP_TRY(hipStreamWaitEvent(s, evA(t - 2), 0));  // bounds the credit lag to one round
-      }
-      HIP_TRY(job_launch_tx_plan(j, k, t, n, s));
-      HIP_TRY(grdma_launch_copy(j->d_plans, n, txb, s));
-      HIP_TRY(hipEventRecord(evG(t), s));
-      HIP_TRY(hipStreamWaitEvent(sW, evG(t), 0));
-      HIP_TRY(grdma_launch_copy(j->d_plans + n * (1 + (t & 1)), n, txb, sW));
-      HIP_TRY(hipEventRecord(evW(t), sW));
-    }
-    HIP_TRY(hipStreamWaitEvent(sX, evW(t), 0));
-    if (t >= 2) HIP_TRY(hipStreamWaitEvent(sX, evA(t - 2), 0));
-    HIP_TRY(job_launch_rx_plan(j, j->d_rxop + k * n, n, sX));
-    HIP_TRY(hipEventRecord(evX(t), sX));
-    HIP_TRY(hipStreamWaitEvent(sA, evX(t), 0));
-    HIP_TRY(grdma_launch_rx_apply(j->d_rxop + k * n, n, rxb, sA));
-    HIP_TRY(hipEventRecord(evA(t), sA));
+  if (!j->direct) HIP_TRY(hipStreamWaitEvent(j->s_wire, fork, 0));
+  HIP_TRY(hipStreamWaitEvent(j->s_rxplan, fork, 0));
+  HIP_TRY(hipStreamWaitEvent(j->s_apply, fork, 0));
+  for (size_t i = 0; i < steps.size(); i++) {
+    for (int d : steps[i].deps)
+      if (home(steps[d]) != home(steps[i])) HIP_TRY(hipStreamWaitEvent(home(steps[i]), j->pev[d], 0));
+    HIP_TRY(job_launch_on(steps[i].l, home(steps[i])));
+    if (watched[i]) HIP_TRY(hipEventRecord(j->pev[i], home(steps[i])));
   }
-  // join the side streams back into the launch stream
-  if (R > 0) {
-    if (!j->direct) HIP_TRY(hipStreamWaitEvent(s, evW(R - 1), 0));
-    HIP_TRY(hipStreamWaitEvent(s, evX(R - 1), 0));
-    HIP_TRY(hipStreamWaitEvent(s, evA(R - 1), 0));
-  }
-  HIP_TRY(grdma_launch_tx_commit(j->d_txconns, nullptr, n, s));
   return 0;
 }
 
-// The job as an explicitly built HIP graph: 5 kernel nodes per round, edges exactly as
-// listed above (pipelined) or a plain chain (sequential).  Built node by node rather
-// than recorded from the streams: the dependency structure is known here, and it keeps
-// the replay independent of how a runtime records cross-stream joins.
+// ---- emitter 3 of 3: the job as an explicitly built HIP graph -----------------------------------------------------
+// One kernel node per step, its dependencies the nodes of the steps it waits for.  Built node by node rather than
+// recorded from the streams: the dependency structure is known here, and it keeps the replay independent of how a
+// runtime records cross-stream joins.  Nodes are added in the steps' order (a node's dependencies exist before it; the
+// runtime may assign branches by that order).  The pre-hooks are a chain in front of the job's roots, the post-hooks a
+// chain behind k_tx_commit, which every node of the job reaches.  Every node hands over GRDMA_JOB_HOOK_ARGS parameter
+// slots (job_kargs); a kernel with fewer ignores the rest.
 int job_build_graph(grdma_stream_job* j, hipGraph_t* out) {
-  const uint32_t n = (uint32_t)j->links.size();
-  const uint32_t txb = job_copy_blocks(j, j->max_ring / 2), rxb = job_copy_blocks(j, j->max_ring);
-  const uint64_t R = j->rounds;
+  const std::vector<job_step> steps = job_schedule(j, job_graph_kind(j), true);
   hipGraph_t g;
   HIP_TRY(hipGraphCreate(&g, 0));
-  std::vector<hipGraphNode_t> P(R), G(R), W(R), X(R), A(R);
-  // hook nodes: a chain of kernels; `after` (may be null) is what the first one waits for, the last one is returned
-  hipError_t hook_err = hipSuccess;
-  auto add_hooks = [&](std::vector<grdma_job_hook>& hooks, hipGraphNode_t after) -> hipGraphNode_t {
-    for (grdma_job_hook& h : hooks) {
-      void* args[GRDMA_JOB_HOOK_ARGS];
-      for (uint32_t a = 0; a < GRDMA_JOB_HOOK_ARGS; a++) args[a] = &h.args[a];
-      hipKernelNodeParams np;
-      memset(&np, 0, sizeof(np));
-      np.func = const_cast<void*>(h.fn);
-      np.gridDim = dim3(h.grid);
-      np.blockDim = dim3(h.threads);
-      np.kernelParams = args;
-      hipGraphNode_t node = nullptr;
-      const hipError_t he = hipGraphAddKernelNode(&node, g, after ? &after : nullptr, after ? 1 : 0, &np);
-      if (he != hipSuccess) {
-        hook_err = he;
-        return after;
-      }
-      after = node;
-    }
-    return after;
-  };
-  const hipGraphNode_t pre_last = R > 0 ? add_hooks(j->pre_hooks, nullptr) : nullptr;
-  // (every node hands over the parameters of job_kargs; a kernel with fewer ignores the rest)
-  auto add3 = [&](hipGraphNode_t* node, const void* fn, dim3 grid, uint32_t threads, const void* arg, const void* arg2,
-                  const void* arg3, std::initializer_list<hipGraphNode_t> deps, uint32_t arg4 = 0, const void* arg5 = nullptr) -> hipError_t {
-    std::vector<hipGraphNode_t> d;
-    for (hipGraphNode_t x : deps)
-      if (x && std::find(d.begin(), d.end(), x) == d.end()) d.push_back(x);  // (a node twice is an invalid argument)
-    if (d.empty() && pre_last) d.push_back(pre_last);  // a root of the job waits for the stage in front of it
-    job_kargs a(arg, arg2, arg3, arg4, arg5);
+  hipError_t e = hipSuccess;
+  auto add_node = [&](const void* fn, dim3 grid, uint32_t threads, void** params, const std::vector<hipGraphNode_t>& deps) -> hipGraphNode_t {
     hipKernelNodeParams np;
     memset(&np, 0, sizeof(np));
     np.func = const_cast<void*>(fn);
     np.gridDim = grid;
     np.blockDim = dim3(threads);
-    np.kernelParams = a.v;
-    return hipGraphAddKernelNode(node, g, d.empty() ? nullptr : d.data(), d.size(), &np);
+    np.kernelParams = params;
+    hipGraphNode_t node = nullptr;
+    if (e == hipSuccess) e = hipGraphAddKernelNode(&node, g, deps.empty() ? nullptr : deps.data(), deps.size(), &np);
+    return node;
   };
-  auto add2 = [&](hipGraphNode_t* node, const void* fn, dim3 grid, uint32_t threads, const void* arg, const void* arg2,
-                  std::initializer_list<hipGraphNode_t> deps) -> hipError_t {
-    return add3(node, fn, grid, threads, arg, arg2, nullptr, deps);
-  };
-  auto add = [&](hipGraphNode_t* node, const void* fn, dim3 grid, uint32_t threads, const void* arg,
-                 std::initializer_list<hipGraphNode_t> deps) -> hipError_t {
-    return add2(node, fn, grid, threads, arg, nullptr, deps);
-  };
-  const void* f_txp = grdma_kernel_fn(0);
-  const void* f_cpy = grdma_kernel_fn(1);
-  const void* f_rxp = grdma_kernel_fn_rx_plan();
-  const void* f_rxa = grdma_kernel_fn(3);
-  const uint32_t pt = grdma_kernel_threads(0), ct = grdma_kernel_threads(1);
-  const bool fast = j->rx_fast, tfast = j->tx_fast;
-  const void* f_txi = grdma_kernel_fn_tx_index();
-  const void* f_txj = grdma_kernel_fn(6);
-  const void* f_rxj = grdma_kernel_fn_rx_plan_job();
-  // P[t] = the send plan of round t: (the index of the slice buffer in front of round 0,) then k_tx_plan_job --
-  // the Send priced from the index, the general planner behind it in the same launch for what that declines
-  auto add_tx = [&](uint64_t t, const void* txop, std::initializer_list<hipGraphNode_t> deps) -> hipError_t {
-    if (!tfast) return add(&P[t], f_txp, dim3(n), pt, txop, deps);
-    if (t != 0 && job_mw_seq(j)) {  // (several Sends per plan, sequential schedule: the Send's planners alone)
-      std::vector<hipGraphNode_t> dq(deps);
-      dq.resize(4, nullptr);
-      return add3(&P[t], grdma_kernel_fn_plan_pair_mw(), dim3(n, job_tx_groups(j)), grdma_kernel_threads(0), nullptr, txop, j->d_txf,
-                  {dq[0], dq[1], dq[2], dq[3]}, 0u);
+  // hook nodes: a chain of kernels; `after` (may be null) is what the first one waits for, the last one is returned
+  auto add_hooks = [&](std::vector<grdma_job_hook>& hooks, hipGraphNode_t after) -> hipGraphNode_t {
+    for (grdma_job_hook& h : hooks) {
+      void* args[GRDMA_JOB_HOOK_ARGS];
+      for (uint32_t a = 0; a < GRDMA_JOB_HOOK_ARGS; a++) args[a] = &h.args[a];
+      after = add_node(h.fn, dim3(h.grid), h.threads, args, after ? std::vector<hipGraphNode_t>{after} : std::vector<hipGraphNode_t>{});
     }
-    if (t != 0) return add2(&P[t], f_txj, dim3(n), grdma_tx_plan_job_threads(), txop, j->d_txf, deps);
-    hipGraphNode_t pi = nullptr;
-    if (job_index_needed(j)) {  // (the slice table's index: once per job unless the table may change between steps)
-      hipError_t e2 = add(&pi, f_txi, dim3(job_index_blocks(j), n), grdma_tx_index_threads(), j->d_txf, deps);
-      if (e2 != hipSuccess) return e2;
-    }
-    std::vector<hipGraphNode_t> dv(deps);
-    dv.resize(4, nullptr);  // (round 0's dependencies: at most four, all null today)
-    const hipGraphNode_t d0 = pi ? pi : dv[0], d1 = pi ? nullptr : dv[1], d2 = pi ? nullptr : dv[2], d3 = pi ? nullptr : dv[3];
-    // (the first Send of a step priced by the small workgroups of the planner pair too: k_plan_pair_mw with no drain)
-    if (j->pipeline || job_mw_seq(j))
-      return add3(&P[t], grdma_kernel_fn_plan_pair_mw(), dim3(n, job_tx_groups(j)), grdma_kernel_threads(0), nullptr, txop,
-                  j->d_txf, {d0, d1, d2, d3}, 0u);
-    return add2(&P[t], f_txj, dim3(n), grdma_tx_plan_job_threads(), txop, j->d_txf, {d0, d1, d2, d3});
+    return after;
   };
-  // X[t] = the receive plan of round t: k_rx_plan_job -- the steady-state body, the general planner behind it
-  auto add_rx = [&](uint64_t t, const void* rxop, std::initializer_list<hipGraphNode_t> deps) -> hipError_t {
-    if (job_mw_seq(j)) {  // (the drain's planners alone: rxm_body / rxh_body, the general planner behind them)
-      std::vector<hipGraphNode_t> dq(deps);
-      dq.resize(4, nullptr);
-      return add3(&X[t], grdma_kernel_fn_plan_pair_mw(), dim3(n, job_rx_groups(j)), grdma_kernel_threads(0), rxop, nullptr, j->d_txf,
-                  {dq[0], dq[1], dq[2], dq[3]}, job_rx_groups(j));
+  std::vector<hipGraphNode_t> nodes(steps.size(), nullptr);
+  if (!steps.empty()) {
+    const hipGraphNode_t pre_last = add_hooks(j->pre_hooks, nullptr);
+    for (size_t i = 0; i < steps.size() && e == hipSuccess; i++) {
+      std::vector<hipGraphNode_t> deps;
+      for (int d : steps[i].deps) deps.push_back(nodes[d]);
+      if (deps.empty() && pre_last) deps.push_back(pre_last);  // a root of the job waits for the stage in front of it
+      const job_launch& l = steps[i].l;
+      job_kargs a(l.a0, l.a1, l.a2, l.split, l.wire);
+      nodes[i] = add_node(l.fn, l.grid, l.threads, a.v, deps);
     }
-    return add(&X[t], fast ? f_rxj : f_rxp, dim3(n), fast ? grdma_rx_plan_job_threads() : pt, rxop, deps);
-  };
-  auto at = [](std::vector<hipGraphNode_t>& v, uint64_t t, uint64_t back) -> hipGraphNode_t {
-    return t >= back ? v[t - back] : nullptr;
-  };
-  hipError_t e = hipSuccess;
-  for (uint64_t t = 0; t < R && e == hipSuccess; t++) {
-    const int k = job_opset(t);
-    const void* txop = j->d_txop + k * n;
-    const void* rxop = j->d_rxop + k * n;
-    const void* gplans = j->d_plans;
-    const void* wplans = j->d_plans + n * (1 + (t & 1));
-    if (!j->pipeline) {
-      hipGraphNode_t prev = at(A, t, 1);
-      e = add_tx(t, txop, {prev});
-      if (e == hipSuccess) e = add(&G[t], f_cpy, dim3(txb, n), ct, gplans, {P[t]});
-      hipGraphNode_t last = G[t];
-      W[t] = nullptr;
-      if (!j->direct && e == hipSuccess) {
-        e = add(&W[t], f_cpy, dim3(txb, n), ct, wplans, {G[t]});
-        last = W[t];
-      }
-      if (e == hipSuccess) e = add_rx(t, rxop, {last});
-      if (e == hipSuccess) e = add(&A[t], f_rxa, dim3(rxb, n), ct, rxop, {X[t]});
-    } else if (fast && tfast) {
-      // One launch for the drain of round t and the Send of round t + 1 (k_plan_pair_mw): kernels of different
-      // branches of a graph do not overlap on this stack (measured: even planner workgroups small enough to sit
-      // beside the copy kernels' run behind them), so the round is a chain -- and this one has four links:
-      //   G_t: P_t (= X_{t-1})      W_t: G_t      X_t + P_{t+1}: W_t, A_{t-1}      A_t: X_t
-      // (the scatter of round t and the gather of round t + 1 share a launch -- both are ready behind the planner pair,
-      // neither touches the other's bytes: G_{t+1} = A_t, three launches per round)
-      if (t == 0) e = add_tx(0, txop, {});
-      if (e == hipSuccess && t == 0) e = add(&G[t], f_cpy, dim3(txb, n), ct, gplans, {P[t], at(A, t, 1)});
-      // (a direct wire has no wire kernel: the gather writes the records into the peer ring, two launches per round)
-      // (few links with small rings: the wire rides in the planner pair's launch -- job_wire_groups, k_plan_pair_mw)
-      const uint32_t wg_wire = job_wire_groups(j);
-      W[t] = nullptr;
-      if (e == hipSuccess && !j->direct && !wg_wire) e = add(&W[t], f_cpy, dim3(txb, n), ct, wplans, {G[t]});
-      const bool more = t + 1 < R;
-      if (e == hipSuccess) {
-        const void* txop_next = j->d_txop + job_opset(t + 1) * n;
-        e = add3(&X[t], grdma_kernel_fn_plan_pair_mw(), dim3(n, wg_wire + job_rx_groups(j) + (more ? job_tx_groups(j) : 0)),
-                 grdma_kernel_threads(0), rxop, more ? txop_next : nullptr, j->d_txf, {W[t] ? W[t] : G[t], at(A, t, 1)},
-                 job_pair_mode(j), wg_wire ? wplans : nullptr);
-        if (more) P[t + 1] = X[t];
-      }
-      if (e == hipSuccess) {
-        if (more) {
-          e = add2(&A[t], grdma_kernel_fn(8), dim3(std::max(rxb, txb), 2 * n), ct, rxop, gplans, {X[t]});
-          G[t + 1] = A[t];
-        } else {
-          e = add(&A[t], f_rxa, dim3(rxb, n), ct, rxop, {X[t]});
-        }
-      }
-    } else {
-      // Limit-driven schedule (a pipelined job that grdma_stream_job_run switched off rx_fast or tx_fast after repeated
-      // declines): the drain of round t walks exactly up to the tail its Send computed (grdma_rx_op::limit_ptr), so
-      // round t + 1 may land in the ring while round t is being walked -- no edge rx_plan_{t-1} -> wire_t, both planners
-      // leave the wire's path.  What is left of the ordering:
-      //   P_t: P_{t-1} (the sender's state), G_{t-1} (one gather plan), W_{t-2} (staging / wire plan of
-      //        this parity), A_{t-2} (credit lag of at most one round; implies X_{t-2}: the limit slot)
-      //   G_t: P_t      W_t: G_t      X_t: W_t, X_{t-1} (the reader's state), A_{t-2} (scatter plan / result
-      //        of this parity)        A_t: X_t, A_{t-1} (credit reports stay in order)
-      // The only cycle that spans rounds is A_{t-2} -> P_t -> G_t -> W_t -> X_t -> A_t: two rounds in
-      // flight, (P + G + W + X + A) / 2 per round.
-      const hipGraphNode_t wprev2 = j->direct ? at(G, t, 2) : at(W, t, 2);
-      e = add_tx(t, txop, {at(P, t, 1), at(G, t, 1), wprev2, at(A, t, 2)});
-      if (e == hipSuccess) e = add(&G[t], f_cpy, dim3(txb, n), ct, gplans, {P[t]});
-      hipGraphNode_t last = G[t];
-      W[t] = nullptr;
-      if (!j->direct && e == hipSuccess) {
-        e = add(&W[t], f_cpy, dim3(txb, n), ct, wplans, {G[t]});
-        last = W[t];
-      }
-      if (e == hipSuccess) e = add_rx(t, rxop, {last, at(X, t, 1), at(A, t, 2)});
-      if (e == hipSuccess) e = add(&A[t], f_rxa, dim3(rxb, n), ct, rxop, {X[t], at(A, t, 1)});
-    }
+    add_hooks(j->post_hooks, nodes.back());  // (the commit is the last step)
   }
-  if (e == hipSuccess && R > 0) {
-    // behind the last round: the connection's arrival report and the state lines (k_tx_commit)
-    hipGraphNode_t cm = nullptr;
-    e = add2(&cm, grdma_kernel_fn(5), dim3(n), 64, j->d_txconns, nullptr, {W[R - 1] ? W[R - 1] : G[R - 1], A[R - 1]});
-    if (e == hipSuccess) add_hooks(j->post_hooks, cm);  // (every node of the job reaches k_tx_commit)
-  }
-  if (e == hipSuccess) e = hook_err;
   if (e != hipSuccess) {
     hipGraphDestroy(g);
     return fail(GRDMA_ERR_HIP, "graph construction failed: %s", hipGetErrorString(e));
@@ -905,13 +812,15 @@ int grdma_stream_job_run(grdma_stream_job* j, int mode, grdma_stream_result* out
   } else {
     HIP_TRY(hipEventRecord(j->ev0, s));
     if (mode == GRDMA_RUN_INSTRUMENTED_SCHEDULE) {
-      if (int rc = job_enqueue_schedule_instrumented(j, s)) return rc;
+      if (!job_is_paired(j))
+        return fail(GRDMA_ERR_INVALID, "GRDMA_RUN_INSTRUMENTED_SCHEDULE times the paired schedule (pipelined job, steady-state planners)");
+      if (int rc = job_enqueue_chain(j, JOB_PAIRED, true, s, true)) return rc;
     } else if (j->pipeline && mode == GRDMA_RUN_EAGER && !j->promise) {
       // (a promised-credit job's eager pass runs in order instead: the stream pipeline sees its credit a round late,
       //  the graph of such a job does not)
-      if (int rc = job_enqueue_pipelined(j, s)) return rc;
+      if (int rc = job_enqueue_streams(j, s)) return rc;
     } else {
-      if (int rc = job_enqueue(j, s, mode == GRDMA_RUN_INSTRUMENTED)) return rc;
+      if (int rc = job_enqueue_chain(j, JOB_SEQUENTIAL, false, s, mode == GRDMA_RUN_INSTRUMENTED)) return rc;
     }
     HIP_TRY(hipEventRecord(j->ev1, s));
   }
@@ -919,24 +828,13 @@ int grdma_stream_job_run(grdma_stream_job* j, int mode, grdma_stream_result* out
   float ms = 0;
   HIP_TRY(hipEventElapsedTime(&ms, j->ev0, j->ev1));
   out->ms_total = ms;
-  if (mode == GRDMA_RUN_INSTRUMENTED_SCHEDULE) {
-    for (size_t e = 0; e < j->kev_cls.size(); e++) {
+  if (mode == GRDMA_RUN_INSTRUMENTED_SCHEDULE || mode == GRDMA_RUN_INSTRUMENTED) {
+    for (size_t e = 0; e < j->kev_cls.size(); e++) {  // (the timed chain: event e in front of, e + 1 behind, launch e)
       float t = 0;
       HIP_TRY(hipEventElapsedTime(&t, j->kev[e], j->kev[e + 1]));
       out->ms_class[j->kev_cls[e]] += t;
       out->launches_class[j->kev_cls[e]]++;
     }
-  }
-  if (mode == GRDMA_RUN_INSTRUMENTED) {
-    size_t e = 0;
-    for (uint64_t r = 0; r < j->rounds; r++)
-      for (int cls = 0; cls < 5; cls++, e++) {
-        float t = 0;
-        HIP_TRY(hipEventElapsedTime(&t, j->kev[e], j->kev[e + 1]));
-        if (cls == 2 && j->direct) continue;
-        out->ms_class[cls] += t;
-        out->launches_class[cls]++;
-      }
   }
   out->done = 1;
   for (size_t i = 0; i < n; i++) {
@@ -1071,7 +969,8 @@ int grdma_job_hook_counts(grdma_stream_job* j, uint32_t out[2]) {
 int grdma_stream_job_launch_streams(grdma_stream_job* j) {
   if (int rc = require_ctx()) return rc;
   if (!j) return fail(GRDMA_ERR_INVALID, "null job");
-  return j->pipeline ? job_enqueue_pipelined(j, j->stream) : job_enqueue(j, j->stream, false);
+  // (unlike GRDMA_RUN_EAGER this does not look at the promised credit)
+  return j->pipeline ? job_enqueue_streams(j, j->stream) : job_enqueue_chain(j, JOB_SEQUENTIAL, false, j->stream, false);
 }
 
 int grdma_stream_job_sync(grdma_stream_job* j) {

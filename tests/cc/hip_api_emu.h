@@ -7,6 +7,7 @@
 // Graphs of kernel nodes run their nodes in the order they were added; the resident latency engine runs in a
 // thread of its own.  Not emulated: IPC handles, dma-buf export (they report an error).
 #pragma once
+#include <dlfcn.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -15,9 +16,11 @@
 #include <sys/mman.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <functional>
 #include <map>
 #include <mutex>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -59,6 +62,76 @@ inline std::recursive_mutex& launch_mutex() {
   static std::recursive_mutex m;
   return m;
 }
+// Optional launch recorder (tests/job_schedule_trace.py).  Off unless EMU_TRACE_FILE names a file; then every kernel
+// launch, graph node, graph launch, event record and stream wait appends one line:
+//   L fn grid[3] block[3] word[10] stream      hipLaunchKernel / hipLaunchKernelGGL (parameters beyond the kernel's: 0)
+//   N graph fn grid[3] block[3] word[10] : indices of the node's dependencies within its graph
+//   X graph stream        R event stream        W stream event
+// fn is the kernel's address relative to this library's base (the reader names it from the symbol table); a word that
+// points into a live allocation is written M<base>+<offset>, everything else as an integer.  The recorder knows
+// nothing of the product: numbering allocations, streams and events is the reader's business.
+struct tracer {
+  FILE* f = nullptr;
+  uintptr_t base = 0;
+  std::mutex mu;
+  std::map<uintptr_t, size_t> live;
+  int graphs = 0;
+};
+inline tracer& trace() {
+  static tracer t;
+  static const bool once = [] {
+    const char* p = getenv("EMU_TRACE_FILE");
+    Dl_info di;
+    if (p && p[0] && dladdr(reinterpret_cast<void*>(&launch_mutex), &di)) {
+      t.base = reinterpret_cast<uintptr_t>(di.dli_fbase);
+      t.f = fopen(p, "a");
+    }
+    return true;
+  }();
+  (void)once;
+  return t;
+}
+inline void trace_alloc(void* p, size_t n, bool on) {
+  if (!p || !trace().f) return;
+  std::lock_guard<std::mutex> lk(trace().mu);
+  if (on) trace().live[reinterpret_cast<uintptr_t>(p)] = n ? n : 1; else trace().live.erase(reinterpret_cast<uintptr_t>(p));
+}
+template <typename T>
+inline uint64_t trace_word(T v) {
+  uint64_t w = 0;
+  memcpy(&w, &v, sizeof(T) < 8 ? sizeof(T) : 8);
+  return w;
+}
+inline void trace_kernel(const char* head, const void* fn, dim3 g, dim3 b, const uint64_t* w, int nw, const std::string& tail) {
+  tracer& t = trace();
+  std::lock_guard<std::mutex> lk(t.mu);
+  fprintf(t.f, "%s %lx %u %u %u %u %u %u", head, (unsigned long)(reinterpret_cast<uintptr_t>(fn) - t.base), g.x, g.y, g.z, b.x, b.y, b.z);
+  for (int i = 0; i < 10; i++) {
+    const uint64_t v = i < nw ? w[i] : 0;
+    auto it = t.live.upper_bound(v);
+    if (it != t.live.begin() && v - (--it)->first < it->second) fprintf(t.f, " M%lx+%lu", (unsigned long)it->first, (unsigned long)(v - it->first));
+    else fprintf(t.f, " %lu", (unsigned long)v);
+  }
+  fprintf(t.f, " %s\n", tail.c_str());
+  fflush(t.f);
+}
+inline void trace_line(const char* what, const void* a, const void* b) {
+  if (!trace().f) return;
+  std::lock_guard<std::mutex> lk(trace().mu);
+  fprintf(trace().f, "%s %lx %lx\n", what, (unsigned long)reinterpret_cast<uintptr_t>(a), (unsigned long)reinterpret_cast<uintptr_t>(b));
+  fflush(trace().f);
+}
+inline std::string trace_hex(const void* p) {
+  char b[24];
+  snprintf(b, sizeof(b), "%lx", (unsigned long)reinterpret_cast<uintptr_t>(p));
+  return b;
+}
+template <typename... A>
+inline void trace_ggl(const void* fn, dim3 g, dim3 b, hipStream_t s, A... args) {
+  if (!trace().f) return;
+  const uint64_t w[sizeof...(A) + 1] = {trace_word(args)..., 0};
+  trace_kernel("L", fn, g, b, w, (int)sizeof...(A), trace_hex(s));
+}
 // Device memory.  With EMU_GUARD_ALLOC=1 every allocation ends right in front of an inaccessible page (the
 // start is 16-byte aligned, so an overrun of 16 bytes or more -- a vector load past the end of a ring, an arena,
 // a plan -- faults at once, with EMU_SEGV_TRACE=1 naming the kernel line); the GPU's coarse page mapping lets
@@ -78,11 +151,13 @@ inline void* dev_alloc(size_t n) {
     mprotect(m + body, page, PROT_NONE);
     char* p = m + body - need;
     memset(p, 0xA5, need);
+    trace_alloc(p, n, true);
     return p;
   }
   void* p = nullptr;
   if (posix_memalign(&p, 256, n ? n : 1) != 0) return nullptr;
   memset(p, 0xA5, n);  // device memory does not come zeroed
+  trace_alloc(p, n, true);
   return p;
 }
 // Fine-grained device memory (hipExtMallocWithFlags: the rings and connection blocks another PROCESS may map through a
@@ -108,12 +183,14 @@ inline void* dev_alloc_shared(size_t n) {
     return nullptr;
   }
   memset(p, 0xA5, len);
+  trace_alloc(p, n, true);
   std::lock_guard<std::mutex> lk(shared_mu());
   shared_blocks()[p] = shared_block{fd, len};
   return p;
 }
 inline void dev_free(void* p) {
   if (!p) return;
+  trace_alloc(p, 0, false);
   {
     std::lock_guard<std::mutex> lk(shared_mu());
     auto it = shared_blocks().find(p);
@@ -182,12 +259,12 @@ inline hipError_t hipStreamCreate(hipStream_t* s) { *s = reinterpret_cast<hipStr
 inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { return hipStreamCreate(s); }
 inline hipError_t hipStreamDestroy(hipStream_t s) { free(s); return hipSuccess; }
 inline hipError_t hipStreamSynchronize(hipStream_t s);  // (defined below: waits for a resident kernel on the stream)
-inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
+inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { emu::trace_line("W", s, e); return hipSuccess; }
 inline hipError_t hipStreamQuery(hipStream_t) { return hipSuccess; }  // (launches have completed when they return)
 inline hipError_t hipEventCreate(hipEvent_t* e) { *e = reinterpret_cast<hipEvent_t>(malloc(8)); return hipSuccess; }
 inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
 inline hipError_t hipEventDestroy(hipEvent_t e) { free(e); return hipSuccess; }
-inline hipError_t hipEventRecord(hipEvent_t, hipStream_t = nullptr) { return hipSuccess; }
+inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t s = nullptr) { emu::trace_line("R", e, s); return hipSuccess; }
 inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.001f; return hipSuccess; }
 
@@ -243,11 +320,17 @@ struct emu_graph_node {
 };
 struct emu_graph {
   std::vector<emu_graph_node*> nodes;
+  int id = 0;  // (the recorder's name of the graph: a pointer may come back after hipGraphDestroy)
 };
 struct emu_graph_exec {
   std::vector<emu_graph_node> nodes;
+  int id = 0;
 };
-inline hipError_t hipGraphCreate(hipGraph_t* g, unsigned) { *g = new emu_graph(); return hipSuccess; }
+inline hipError_t hipGraphCreate(hipGraph_t* g, unsigned) {
+  *g = new emu_graph();
+  (*g)->id = ++emu::trace().graphs;
+  return hipSuccess;
+}
 inline hipError_t hipGraphDestroy(hipGraph_t g) {
   if (g) {
     for (emu_graph_node* n : g->nodes) delete n;
@@ -255,11 +338,17 @@ inline hipError_t hipGraphDestroy(hipGraph_t g) {
   }
   return hipSuccess;
 }
-inline hipError_t hipGraphAddKernelNode(hipGraphNode_t* node, hipGraph_t g, const hipGraphNode_t*, size_t,
+inline hipError_t hipGraphAddKernelNode(hipGraphNode_t* node, hipGraph_t g, const hipGraphNode_t* deps, size_t ndeps,
                                         const hipKernelNodeParams* p) {
   // (the product always hands over EMU_GRAPH_NODE_ARGS parameter slots of 8 bytes; kernels with fewer ignore the rest)
   emu_graph_node* n = new emu_graph_node{p->func, p->gridDim, p->blockDim, {}};
   for (int i = 0; i < EMU_GRAPH_NODE_ARGS; i++) n->a[i] = *static_cast<uint64_t*>(p->kernelParams[i]);
+  if (emu::trace().f) {
+    std::string tail = ":";
+    for (size_t d = 0; d < ndeps; d++)
+      tail += " " + std::to_string(std::find(g->nodes.begin(), g->nodes.end(), deps[d]) - g->nodes.begin());
+    emu::trace_kernel(("N " + std::to_string(g->id)).c_str(), n->func, n->grid, n->block, n->a, EMU_GRAPH_NODE_ARGS, tail);
+  }
   g->nodes.push_back(n);
   *node = n;
   return hipSuccess;
@@ -267,10 +356,12 @@ inline hipError_t hipGraphAddKernelNode(hipGraphNode_t* node, hipGraph_t g, cons
 inline hipError_t hipGraphInstantiate(hipGraphExec_t* e, hipGraph_t g, void*, void*, size_t) {
   emu_graph_exec* x = new emu_graph_exec();
   for (emu_graph_node* n : g->nodes) x->nodes.push_back(*n);
+  x->id = g->id;
   *e = x;
   return hipSuccess;
 }
-inline hipError_t hipGraphLaunch(hipGraphExec_t e, hipStream_t) {
+inline hipError_t hipGraphLaunch(hipGraphExec_t e, hipStream_t s) {
+  emu::trace_line("X", reinterpret_cast<const void*>((uintptr_t)e->id), s);
   std::lock_guard<std::recursive_mutex> lk(emu::launch_mutex());
   for (const emu_graph_node& n : e->nodes) {
     // (integer / pointer parameters only: a kernel with fewer parameters ignores the registers and stack slots behind its own)
@@ -284,12 +375,13 @@ inline hipError_t hipGraphLaunch(hipGraphExec_t e, hipStream_t) {
 inline hipError_t hipGraphExecDestroy(hipGraphExec_t e) { delete e; return hipSuccess; }
 // hipLaunchKernel by function pointer (the instrumented schedule of a streaming job): same convention as a graph
 // node -- EMU_GRAPH_NODE_ARGS parameter slots of 8 bytes, a kernel with fewer ignores the rest
-inline hipError_t hipLaunchKernel(const void* func, dim3 grid, dim3 block, void** args, size_t, hipStream_t) {
+inline hipError_t hipLaunchKernel(const void* func, dim3 grid, dim3 block, void** args, size_t, hipStream_t s) {
   std::lock_guard<std::recursive_mutex> lk(emu::launch_mutex());
   typedef void (*fn_t)(uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t);
   fn_t f = reinterpret_cast<fn_t>(const_cast<void*>(func));
   uint64_t a[EMU_GRAPH_NODE_ARGS];
   for (int i = 0; i < EMU_GRAPH_NODE_ARGS; i++) a[i] = *static_cast<uint64_t*>(args[i]);
+  if (emu::trace().f) emu::trace_kernel("L", func, grid, block, a, EMU_GRAPH_NODE_ARGS, emu::trace_hex(s));
   emu::launch(grid, block, [=] { f(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9]); });
   return hipSuccess;
 }
@@ -331,6 +423,7 @@ inline void stream_wait(hipStream_t s) {
 }  // namespace emu
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...)                                          \
   do {                                                                                                       \
+    emu::trace_ggl(reinterpret_cast<const void*>(&kernel), dim3(grid), dim3(block), stream, __VA_ARGS__);    \
     if (emu::resident_kernel(#kernel)) {                                                                     \
       emu::launch_async(stream, dim3(grid), dim3(block), [=] { kernel(__VA_ARGS__); });                      \
     } else {                                                                                                 \

@@ -108,6 +108,14 @@ def test_round6_parity_cases_under_the_emulator(emu_lib):
                                   "mixed_message_sizes or (without_a_period and x2_small and staged)"], 7)
 
 
+def test_in_order_timed_pass_and_stream_launch_under_the_emulator(emu_lib):
+    """The chain emitter with events and the streams emitter of the job's schedule table (csrc/grdma_host_job.inc):
+    GRDMA_RUN_INSTRUMENTED and launch(streams=True) behind the usual three passes, both wires, sequential and pipelined,
+    against the oracle after each pass.  (The emulator's streams are synchronous: the ORDER the streams emitter asks for
+    is what tests/test_job_schedule_emu.py checks.)"""
+    run_gpu_tests(emu_lib, ["tests/test_gpu_stream_job.py", "-n", "4", "-k", "in_order_timed_pass_and_the_stream_launch"], 4)
+
+
 def test_concurrent_writer_and_poller_gpu_tests_under_the_emulator(emu_lib):
     """Records landing header-first / footer-last from a second thread while the receiver polls and reads; the
     background poller thread (one k_poll launch per pass, eventfd wakeups)."""

@@ -39,13 +39,13 @@ def _framed_slices(n_msgs, msg_len, seed):
 PASSES = 3  # the job is run three times on the same connection (eager, graph, graph)
 
 
-def _oracle_rounds(R, max_sge, slices, sends=1):
+def _oracle_passes(R, max_sge, slices, sends=1, passes=PASSES):
     """The reference loop on the CPU: one Send from the rdma_flush cursor, then endpoint
-    reads until one would block; repeat until the list is gone.  PASSES times over the
-    same link; returns the slices of the last pass and the rounds of the first."""
+    reads until one would block; repeat until the list is gone.  `passes` times over the
+    same link; returns (delivered slices, rounds, states, ring image) after every pass."""
     o = pyorc.OracleLink(R, max_sge)
-    first_rounds = None
-    for _ in range(PASSES):
+    out = []
+    for _ in range(passes):
         idx, byte = 0, 0
         delivered, rounds = [], 0
         while idx < len(slices):
@@ -70,17 +70,22 @@ def _oracle_rounds(R, max_sge, slices, sends=1):
                     break
                 delivered.append(s)
             assert rounds < 100000
-        if first_rounds is None:
-            first_rounds = rounds
-    st = (o.state(0), o.state(1))
-    ring = o.ring_mem(1)
+        out.append((delivered, rounds, (o.state(0), o.state(1)), o.ring_mem(1)))
     o.close()
-    return delivered, first_rounds, st, ring
+    return out
 
 
-def _run_job(g, R, max_sge, slices, pipeline, flags=0, mode=None, sends=1, promise=False, fused_wire=None, pairs=None):
+def _oracle_rounds(R, max_sge, slices, sends=1):
+    """PASSES passes of the reference loop; returns the slices of the last pass and the rounds of the first."""
+    per_pass = _oracle_passes(R, max_sge, slices, sends)
+    delivered, _rounds, st, ring = per_pass[-1]
+    return delivered, per_pass[0][1], st, ring
+
+
+def _run_job(g, R, max_sge, slices, pipeline, flags=0, mode=None, sends=1, promise=False, fused_wire=None, pairs=None, more_passes=()):
     """pairs: a connected (tx, rx) the caller keeps (pairs taken from the PairPool: tests/planner_sweep_lib.py); they are
-    left open"""
+    left open.  more_passes: passes behind the usual three -- a run mode, or "streams" for launch(streams=True) + sync();
+    out["more"] holds slices, ring, state and timed classes after each of them."""
     from grpc_rdma_amd import stream as gs
     rng = random.Random(5)
     bufs = [g.DeviceBuffer(data=s, offset=rng.randrange(16)) for s in slices]
@@ -115,13 +120,23 @@ def _run_job(g, R, max_sge, slices, pipeline, flags=0, mode=None, sends=1, promi
     for i in range(PASSES - 1):
         r = job.run(mode if (mode is not None and i == PASSES - 2) else gs.RUN_GRAPH)
         assert r.done and r.bytes_delivered == N and r.bytes_sent == N
-    last = r
-    ds = job.delivered_slices(0)
-    mem = dst.read(dst_cap)
-    got = [mem[o:o + n] for o, n in ds]
-    out = {"slices": got, "rounds": rounds, "ring": rx.ring_mem(), "tx": tx.state(), "rx": rx.state(), "wire_groups": job.wire_groups(),
-           "launches": [int(x) for x in last.launches_class], "ms": [float(x) for x in last.ms_class],
-           "rounds_set": 2 * rounds + 4 if pipeline else rounds + 2}
+    def snapshot(last):
+        ds = job.delivered_slices(0)
+        mem = dst.read(dst_cap)
+        return {"slices": [mem[o:o + n] for o, n in ds], "ring": rx.ring_mem(), "tx": tx.state(), "rx": rx.state(),
+                "launches": [int(x) for x in last.launches_class] if last else None,
+                "ms": [float(x) for x in last.ms_class] if last else None}
+    out = snapshot(r)
+    out.update({"rounds": rounds, "wire_groups": job.wire_groups(), "rounds_set": 2 * rounds + 4 if pipeline else rounds + 2, "more": []})
+    for m in more_passes:
+        if m == "streams":
+            job.launch(streams=True)
+            job.sync()
+            out["more"].append(snapshot(None))
+        else:
+            r = job.run(m)
+            assert r.done and r.bytes_delivered == N and r.bytes_sent == N
+            out["more"].append(snapshot(r))
     job.close()
     if pairs is None:
         tx.close()
@@ -575,6 +590,39 @@ def test_the_instrumented_schedule_is_the_graphs_chain(gpu, case, flags):
     assert la["tx_plan"] == 1 and la["gather"] == 1 and la["wire"] == (0 if (flags & 2 or got["wire_groups"]) else n), la
     assert la["rx_plan"] == 0
     assert all(m >= 0 for m in got["ms"])
+
+
+_ORACLE_FIVE_PASSES = []  # (the reference of the next test: computed once, shared by its four cases, never changed)
+
+
+@pytest.mark.parametrize("flags", [0, 2], ids=["staged", "direct"])
+@pytest.mark.parametrize("pipeline", [False, True], ids=["sequential", "pipelined"])
+def test_the_in_order_timed_pass_and_the_stream_launch_match_the_oracle(gpu, pipeline, flags):
+    """GRDMA_RUN_INSTRUMENTED (the five launches of every round in order, an event behind each) and
+    grdma_stream_job_launch_streams (the sequential chain, or the limit-driven schedule over four streams for a pipelined
+    job) behind the usual three passes, at the small ring with the reference's max_sge: slices, ring image and state
+    equal the oracle's rounds after each of the two passes.  The timed pass counts one launch per round in every class
+    -- none in `wire` on a direct wire, where the gather writes the peer ring."""
+    from grpc_rdma_amd import stream as gs
+    R, max_sge, n_msgs, msg_len = CASES[2]
+    slices = _framed_slices(n_msgs, msg_len, seed=R % 97)
+    if not _ORACLE_FIVE_PASSES:
+        _ORACLE_FIVE_PASSES.extend(_oracle_passes(R, max_sge, slices, passes=PASSES + 2))
+    got = _run_job(gpu, R, max_sge, slices, pipeline=pipeline, flags=flags, more_passes=(gs.RUN_INSTRUMENTED, "streams"))
+    for state, (exp, _rounds, (st0, st1), ring) in zip([got] + got["more"], _ORACLE_FIVE_PASSES[PASSES - 1:]):
+        assert state["slices"] == exp
+        assert state["ring"] == ring == bytes(R)
+        for k in ("remote_tail", "remote_head", "partial_write"):
+            assert state["tx"][k] == st0[k], k
+        for k in ("head", "moving_head", "remain", "internal_read_size"):
+            assert state["rx"][k] == st1[k], k
+    assert len(got["more"]) == 2
+    timed = got["more"][0]
+    la = dict(zip(gs.CLASS_NAMES, timed["launches"]))
+    n = got["rounds_set"]
+    assert la == {"tx_plan": n, "gather": n, "wire": 0 if flags & 2 else n, "rx_plan": n, "rx_apply": n, "plan_pair": 0,
+                  "scatter_gather": 0}, la
+    assert all(m >= 0 for m in timed["ms"])
 
 
 def test_the_instrumented_schedule_refuses_a_job_on_another_schedule(gpu):
