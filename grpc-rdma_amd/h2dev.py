@@ -118,6 +118,8 @@ def _bind():
         lib.grdma_h2_parser_live_streams.argtypes = [C.c_void_p]
         lib.grdma_h2_last_boundary_steps.restype = C.c_uint64
         lib.grdma_h2_last_boundary_steps.argtypes = []
+        lib.grdma_h2_last_deframe_stats.restype = None
+        lib.grdma_h2_last_deframe_stats.argtypes = [C.POINTER(u64)]
         lib.grdma_h2_parser_chunk_stats.restype = C.c_int
         lib.grdma_h2_parser_chunk_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
         lib.grdma_h2_parser_chunk_dbg.restype = C.c_int
@@ -272,6 +274,9 @@ class Parser:
         err = C.c_int(0)
         m = check(self.lib.grdma_h2_deframe(self.h, arena_dev_ptr, arr, n, ev, cap, C.byref(err)))
         self.last_boundary_steps = int(self.lib.grdma_h2_last_boundary_steps())
+        st = (u64 * 8)()
+        self.lib.grdma_h2_last_deframe_stats(st)
+        self.last_bulk_steps, self.last_bulk_frames = int(st[0]), int(st[1])  # bulk steps taken, frames parsed in them
         return err.value, _events(ev, m)
 
     def deframe_messages(self, arena_dev_ptr, slices, assembler, want_events=False, ev_cap=None, msgs_cap=None):

@@ -60,6 +60,13 @@ def test_chunked_deframer_gpu_tests_under_the_emulator(emu_lib):
     run_gpu_tests(emu_lib, ["tests/test_zz_gpu_h2_chunks.py", "-n", "4", "-k", "not bench_configuration"], 10)
 
 
+def test_h2_field_range_gpu_tests_under_the_emulator(emu_lib):
+    """Framer, deframer and the chains behind it at full-width stream ids, frame lengths and message lengths
+    (tests/test_zz_gpu_h2_fields.py): every case of the file, the 16 MiB messages included -- the
+    framer carries payload by reference and the deframer stages 32 bytes a slice, so they cost little here."""
+    run_gpu_tests(emu_lib, ["tests/test_zz_gpu_h2_fields.py", "-n", "4"], 109)
+
+
 def test_zero_copy_gpu_tests_under_the_emulator(emu_lib):
     run_gpu_tests(emu_lib, ["tests/test_zz_gpu_zerocopy.py"], 10)
 
