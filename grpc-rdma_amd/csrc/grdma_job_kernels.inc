@@ -47,11 +47,11 @@ void k_plan_pair_mw(const grdma_rx_op* rxops, const grdma_tx_op* txops, const gr
     credit_promised publish = {promise ? rop.plan : nullptr, ny - G + 1, false};
     rxh_pre pre;  // (the size table of the round, requested now: grdma_rx_hint.h)
     rxh_preload(rop, pre);
-    // (<false, true>: every workgroup's own entries write-through -- the general planner may rewrite them below)
-    int r = rxm_body<false, true>(rop, by, G, &ring_wait, &publish);
+    // (<true>: every workgroup's own entries write-through -- the general planner may rewrite them below)
+    int r = rxm_body<true>(rop, by, G, &ring_wait, &publish);
     if (r == 3) {  // (uniform over the whole grid: no workgroup has arrived yet)
       __syncthreads();
-      r = rxh_body<false, true>(rop, by, G, &pre, &ring_wait, &publish);
+      r = rxh_body<true>(rop, by, G, &pre, &ring_wait, &publish);
     }
     if (r == 0) return;  // (uniform: not the committing workgroup)
     if (r == 2) {
@@ -100,10 +100,10 @@ void k_plan_pair_mw(const grdma_rx_op* rxops, const grdma_tx_op* txops, const gr
 __global__ __launch_bounds__(PLAN_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void k_rx_plan_mw(const grdma_rx_op* rxops) {
   const grdma_rx_op& rop = rxops[blockIdx.x];
-  int r = rxm_body<false, true>(rop, blockIdx.y, gridDim.y);
+  int r = rxm_body<true>(rop, blockIdx.y, gridDim.y);
   if (r == 3) {
     __syncthreads();
-    r = rxh_body<false, true>(rop, blockIdx.y, gridDim.y);
+    r = rxh_body<true>(rop, blockIdx.y, gridDim.y);
   }
   if (r != 2) return;  // (uniform)
   rx_plan_body(rop);

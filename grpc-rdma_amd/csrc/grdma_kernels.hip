@@ -408,12 +408,6 @@ __attribute__((visibility("hidden"))) hipError_t grdma_launch_copy(const grdma_p
 }
 
 __attribute__((visibility("hidden"))) uint32_t grdma_tx_plan_job_threads(void) { return TXB_THREADS; }
-__attribute__((visibility("hidden"))) hipError_t grdma_launch_tx_plan_job(const grdma_tx_op* d_ops, const grdma_txf_ctl* d_ctls, uint32_t nops,
-                                                                   hipStream_t s) {
-  if (nops == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_tx_plan_job, dim3(nops), dim3(TXB_THREADS), 0, s, d_ops, d_ctls);
-  return hipGetLastError();
-}
 // diagnostics: Sends of streaming jobs planned by txf_body [0], left to the general planner [1]
 int grdma_tx_fast_sends_pair(uint64_t out[2]);  // (grdma_rx_plan.hip: the Sends planned inside the planner-pair launches)
 int grdma_tx_fast_sends(uint64_t out[2]) {

@@ -58,13 +58,10 @@ hipError_t grdma_launch_engine(grdma_engine_mbox*, grdma_watch_ctl*, uint64_t ep
 const void* grdma_kernel_fn(int which);          // 0 tx_plan, 1 copy, 3 rx_apply, 4 tx_plan_seq
 const void* grdma_kernel_fn_rx_plan(void);
 const void* grdma_kernel_fn_rx_plan_job(void);
-hipError_t grdma_launch_rx_plan_job(const grdma_rx_op*, uint32_t, hipStream_t);
 uint32_t grdma_rx_plan_job_threads(void);
 uint32_t grdma_tx_plan_job_threads(void);
 const void* grdma_kernel_fn_tx_index(void);
 uint32_t grdma_tx_index_threads(void);
-hipError_t grdma_launch_tx_index(grdma_txf_ctl*, uint32_t, uint32_t, hipStream_t);
-hipError_t grdma_launch_tx_plan_job(const grdma_tx_op*, const grdma_txf_ctl*, uint32_t, hipStream_t);
 const void* grdma_kernel_fn_plan_pair_mw(void);
 uint32_t grdma_rx_multi_groups(void);
 hipError_t grdma_launch_rx_plan_mw(const grdma_rx_op*, uint32_t, hipStream_t);

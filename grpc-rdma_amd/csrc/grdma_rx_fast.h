@@ -79,14 +79,17 @@ __device__ __forceinline__ rx_lds* rx_lds_get() {
   return &L;
 }
 
-// (the three functions below restate read_space_after / replay_record32 of grdma_rx_plan.hip)
+// The endpoint-read state machine over one record, once for every drain planner (the steady-state bodies, and the bulk
+// and wave tiers of the general planner in grdma_rx_plan.hip).
 // s = bytes of space left in the open read (0 = between reads) after a record of n bytes
-__device__ __forceinline__ uint32_t rxf_space_after(uint32_t n, uint32_t s) {
-  if (s == 0) return n >= RXF_MINRD ? 0 : RXF_MINRD - n;
-  if (n < s) return s - n;
+// (N: uint32_t where the ring is at most 2 GiB, uint64_t in the general planner's wave tier)
+template <class N>
+__device__ __forceinline__ uint32_t rxf_space_after(N n, uint32_t s) {
+  if (s == 0) return n >= RXF_MINRD ? 0 : RXF_MINRD - (uint32_t)n;
+  if (n < s) return s - (uint32_t)n;
   if (n == s) return 0;
-  const uint32_t r = n - s;
-  return r >= RXF_MINRD ? 0 : RXF_MINRD - r;
+  const N r = n - s;
+  return r >= RXF_MINRD ? 0 : RXF_MINRD - (uint32_t)r;
 }
 
 struct rxf_rec {
@@ -111,6 +114,30 @@ __device__ __forceinline__ rxf_rec rxf_replay(uint32_t n, uint32_t s_in) {
   }
   r.sl_cnt = (r.sl0 ? 1u : 0u) + (r.sl1 ? 1u : 0u);
   return r;
+}
+// One crossing of the credit threshold (PairPollable::Recv posts a status report whenever the bytes consumed since the
+// last one reach T = cap / 2, step by step: pair.cc:276-284).  The caller has found the record -- payload n, replay rp --
+// at which the drain's running consumption reaches thr; C2 = ring bytes of the drain consumed once that record is
+// finished.  Decides whether the crossing falls behind the record's first or its second Recv step; leaves the head
+// the report carries, the consumption it was posted at (base) and the next threshold.
+// (32-bit: the steady-state bodies'; the general planner's bulk tier keeps a 64-bit twin, grdma_rx_plan.hip)
+__device__ __forceinline__ void rxf_credit_step(uint32_t n, const rxf_rec& rp, uint64_t C2, uint64_t head, uint64_t cap, uint64_t T,
+                                                uint64_t& thr, uint64_t& base, uint64_t& credit, uint64_t& credit_head, bool& crossed) {
+  const uint32_t up = (n + 7u) & ~7u;
+  const uint64_t e = 16u + up;
+  const uint64_t cons2 = rp.c2 ? rp.c2 + (up - n + 8u) : 0;
+  const uint64_t C1 = C2 - cons2;
+  const uint64_t pos = (head + C2 - e) & (cap - 1);
+  if (rp.c2 && C1 >= thr) {  // crossed after the first step of a two-step record
+    credit_head = (pos + 8 + rp.c1) & (cap - 1);
+    base = C1;
+  } else {
+    credit_head = (pos + e) & (cap - 1);
+    base = C2;
+  }
+  credit++;
+  crossed = true;
+  thr = base + T;
 }
 __device__ __forceinline__ uint32_t rxf_al16(uint32_t v) { return (v + 15u) & ~15u; }
 __device__ __forceinline__ uint32_t rxf_tiles(uint32_t len, uint32_t ts) { return (len + (1u << ts) - 1u) >> ts; }
@@ -157,6 +184,124 @@ __device__ __forceinline__ rxf_layout rxf_lay(uint32_t n, uint32_t s_in, uint32_
     L.ntl += rxf_tiles(L.len[k], ts);
   }
   return L;
+}
+
+// What the commit of a steady-state drain adds to or falls back on: fetched early, in the round trip of other loads,
+// by the thread that may commit.
+struct rxf_counters {
+  uint64_t total_read, credit_msgs, rx_records, rx_rounds, seq;
+  uint32_t h1;
+  grdma_hostline* line;
+};
+__device__ __forceinline__ rxf_counters rxf_load_counters(const grdma_conn* c, const grdma_rx_result* res) {
+  return {c->total_read, c->credit_msgs, c->rx_records, c->rx_rounds, res->seq, c->rx_h1, c->line};
+}
+
+// What a committed steady-state drain leaves behind, written by ONE thread (thread 0 of rxf_body's workgroup, of the
+// committing workgroup of rxm_body / rxh_body): the short slice at the would-block, the plan header, connection state
+// and host line, cursors (`cursors`: a streaming job's, op.append != 0), history tail, result block with its zero
+// ranges and stamps, and last the sequence word.  The bodies differ in where the values come from, not in what is
+// written or in which order.
+// tail(h1, h2): the encoded sizes of the drain's last two records (h2 of a drain of one record: o.h1), asked for where
+// they are stored -- fetched ahead of the call they stay live across it, which costs k_rx_plan_job scratch memory.
+// nwg != 0 (the multi-workgroup bodies): dbg[10..13] are written too, with the three differences handed in.
+template <class Tail>
+__device__ __forceinline__ void rxf_commit(const grdma_rx_op& op, bool cursors, uint8_t* ring, uint64_t cap64, uint64_t head64, uint64_t mh0,
+                                           uint64_t irs0, uint32_t Lr, uint32_t ts,
+                                           uint32_t V, uint32_t tot_n, uint32_t tot_sl, uint32_t tot_sg, uint32_t tot_tl, uint32_t tot_by,
+                                           uint32_t short_len, uint32_t leftover_final,
+                                           uint64_t slice_idx0, uint64_t a_off0, uint64_t a_end, uint64_t hc, const Tail& tail,
+                                           bool crossed, uint64_t base, uint64_t credit, uint64_t credit_head, const rxf_counters& o,
+                                           uint64_t t_begin, uint64_t t_pattern, uint64_t t_probe, uint64_t t_state, uint64_t t_scan,
+                                           uint64_t t_emit, uint32_t P, uint32_t nwg, uint64_t d_arrived, uint64_t d_loaded,
+                                           uint64_t d_credit) {
+  grdma_conn* const c = op.conn;
+  grdma_plan* const plan = op.plan;
+  grdma_rx_result* const res = op.result;
+  grdma_slice_out* const out_slices = op.slices + slice_idx0;
+  const uint32_t nsl_final = tot_sl + (short_len ? 1u : 0u);
+  const uint64_t Ctot = Lr;
+  const uint64_t irs = crossed ? Ctot - base : irs0 + Ctot;
+  const uint64_t nh = (head64 + Lr) & (cap64 - 1);
+  if (short_len) {
+    out_slices[tot_sl].off = a_off0 + tot_by;
+    out_slices[tot_sl].len = short_len;
+  }
+  plan->nsegs = tot_sg;
+  plan->ntiles = tot_tl;
+  plan->tile_bytes = 1u << ts;
+  plan->tile_prefix[tot_sg] = tot_tl;
+  plan->bytes = tot_n;
+  plan->tag_base = (uint64_t)ring;
+  plan->tag_mask = cap64 - 1;
+  plan->blocks_done = 0;
+  c->head = nh;
+  c->moving_head = nh;
+  c->remain = 0;
+  if (o.line != nullptr) {
+    o.line->rx_head = nh;
+    o.line->rx_remain = 0;
+  }
+  c->internal_read_size = irs;
+  c->leftover_cap = leftover_final;
+  c->total_read = o.total_read + tot_n;
+  c->credit_msgs = o.credit_msgs + credit;
+  c->rx_records = o.rx_records + V;
+  if (nsl_final) c->rx_rounds = o.rx_rounds + 1;
+  if (cursors) {
+    c->rx_arena_off = a_end;
+    c->rx_slice_idx = slice_idx0 + nsl_final;
+  }
+  c->rx_hist_count = hc + V;
+  {
+    uint32_t h1, h2;
+    tail(h1, h2);
+    c->rx_h1 = h1;
+    c->rx_h2 = h2;
+  }
+  if (credit) c->status_send.remote_head = credit_head;
+  res->credit_head = credit_head;
+  res->nslices = nsl_final;
+  res->bytes = tot_n;
+  res->consumed = Lr;
+  res->records = V;
+  res->would_block = 1;
+  res->credit_sent = credit;
+  res->head = nh;
+  res->moving_head = nh;
+  res->remain = 0;
+  res->arena_used = a_end;
+  res->zero_off[0] = res->zero_off[1] = res->zero_len[0] = res->zero_len[1] = 0;
+  if (nh > mh0) {
+    res->zero_off[0] = mh0;
+    res->zero_len[0] = nh - mh0;
+  } else {
+    res->zero_off[0] = mh0;
+    res->zero_len[0] = cap64 - mh0;
+    res->zero_off[1] = 0;
+    res->zero_len[1] = nh;
+  }
+  res->dbg[0] = t_begin;
+  res->dbg[2] = t_pattern - t_begin;
+  res->dbg[3] = t_probe - t_begin;
+  res->dbg[4] = t_state - t_begin;
+  res->dbg[5] = t_scan - t_begin;
+  res->dbg[6] = t_emit - t_begin;
+  res->dbg[7] = V;
+  res->dbg[8] = P;
+  res->dbg[9] = 0xFA57;  // this stamp set comes from a steady-state body
+  if (nwg) {
+    res->dbg[10] = nwg;
+    res->dbg[11] = d_arrived;
+    res->dbg[12] = d_loaded;
+    res->dbg[13] = d_credit;
+  }
+  res->pad1++;
+  res->dbg[1] = __builtin_amdgcn_s_memtime();
+  atomicAdd(&g_rx_fast_drains[0], 1ull);
+  // (relaxed: the consumers of a streaming job's drain are later kernels of the graph; a release at system scope
+  // here would write the XCD's L2 back -- the plan just laid out -- before the kernel may end)
+  __hip_atomic_store(&res->seq, op.seq_next ? op.seq_next : o.seq + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // exclusive block scans of three u32 values at once (1024 threads); totals in tot[3]
@@ -223,11 +368,7 @@ __device__ __forceinline__ bool rxf_body(const grdma_rx_op& op_in) {
   const uint64_t slice_idx0 = op.append == 1 ? c->rx_slice_idx : 0;
   const uint64_t a_off0 = op.append == 1 ? c->rx_arena_off : 0;
   // (what thread 0 adds to at the very end: fetched now, in the same round trip as the state above)
-  const uint64_t o_total_read = c->total_read, o_credit_msgs = c->credit_msgs;
-  const uint64_t o_rx_records = c->rx_records, o_rx_rounds = c->rx_rounds;
-  const uint32_t o_h1 = c->rx_h1;
-  const uint64_t o_seq = res->seq;
-  grdma_hostline* const line = c->line;
+  const rxf_counters o = rxf_load_counters(c, res);
   constexpr int NH = GRDMA_RX_HIST / RXF_THREADS;
   uint32_t hv[NH];
 #pragma unroll
@@ -503,7 +644,7 @@ __device__ __forceinline__ bool rxf_body(const grdma_rx_op& op_in) {
   }
   const uint64_t t_emit = __builtin_amdgcn_s_memtime();
 
-  // ---- 6. credit (pair.cc:276-284), state, result: thread 0
+  // ---- 6. credit (rxf_credit_step), state, result (rxf_commit): thread 0
   __syncthreads();  // (s_totn is complete)
   if (tid == 0) {
     const uint32_t tot_n = s_totn;
@@ -521,95 +662,18 @@ __device__ __forceinline__ bool rxf_body(const grdma_rx_op& op_in) {
         if (enc_end(mid) >= thr) hi = mid; else lo = mid + 1;
       }
       const uint32_t n = s_n[RXFP(lo)];
-      const rxf_rec rp = rxf_replay(n, s_sin[RXFP(lo)]);
-      const uint64_t C2 = enc_end(lo);
-      const uint64_t e = 16u + ((n + 7u) & ~7u);
-      const uint64_t cons2 = rp.c2 ? rp.c2 + (((n + 7u) & ~7u) - n + 8u) : 0;
-      const uint64_t C1 = C2 - cons2;
-      const uint64_t pos = (head64 + C2 - e) & (cap64 - 1);
-      if (rp.c2 && C1 >= thr) {  // crossed after the first step of a two-step record
-        credit_head = (pos + 8 + rp.c1) & (cap64 - 1);
-        base = C1;
-      } else {
-        credit_head = (pos + e) & (cap64 - 1);
-        base = C2;
-      }
-      credit++;
-      crossed = true;
-      thr = base + T;
+      rxf_credit_step(n, rxf_replay(n, s_sin[RXFP(lo)]), enc_end(lo), head64, cap64, T, thr, base, credit, credit_head, crossed);
     }
-    const uint64_t irs = crossed ? Ctot - base : irs0 + Ctot;
-    const uint64_t nh = (head64 + Lr) & (cap64 - 1);
-    if (short_len) {
-      out_slices[tot_sl].off = a_off0 + tot_by;
-      out_slices[tot_sl].len = short_len;
-    }
-    plan->nsegs = tot_sg;
-    plan->ntiles = tot_tl;
-    plan->tile_bytes = 1u << ts;
-    plan->tile_prefix[tot_sg] = tot_tl;
-    plan->bytes = tot_n;
-    plan->tag_base = (uint64_t)ring;
-    plan->tag_mask = cap64 - 1;
-    plan->blocks_done = 0;
-    c->head = nh;
-    c->moving_head = nh;
-    c->remain = 0;
-    if (line != nullptr) {
-      line->rx_head = nh;
-      line->rx_remain = 0;
-    }
-    c->internal_read_size = irs;
-    c->leftover_cap = leftover_final;
-    c->total_read = o_total_read + tot_n;
-    c->credit_msgs = o_credit_msgs + credit;
-    c->rx_records = o_rx_records + V;
-    if (nsl_final) c->rx_rounds = o_rx_rounds + 1;
-    c->rx_arena_off = a_end;
-    c->rx_slice_idx = slice_idx0 + nsl_final;
-    c->rx_hist_count = hc + V;
-    {
-      const uint32_t ql = (V - 1) / P, rl = (V - 1) - ql * P;
-      c->rx_h1 = s_pat[rl];
-      c->rx_h2 = V >= 2 ? s_pat[rl ? rl - 1 : P - 1] : o_h1;
-    }
-    if (credit) c->status_send.remote_head = credit_head;
-    res->credit_head = credit_head;
-    res->nslices = nsl_final;
-    res->bytes = tot_n;
-    res->consumed = Lr;
-    res->records = V;
-    res->would_block = 1;
-    res->credit_sent = credit;
-    res->head = nh;
-    res->moving_head = nh;
-    res->remain = 0;
-    res->arena_used = a_end;
-    res->zero_off[0] = res->zero_off[1] = res->zero_len[0] = res->zero_len[1] = 0;
-    if (nh > mh0) {
-      res->zero_off[0] = mh0;
-      res->zero_len[0] = nh - mh0;
-    } else {
-      res->zero_off[0] = mh0;
-      res->zero_len[0] = cap64 - mh0;
-      res->zero_off[1] = 0;
-      res->zero_len[1] = nh;
-    }
-    res->dbg[0] = t_begin;
-    res->dbg[2] = t_pattern - t_begin;
-    res->dbg[3] = t_probe - t_begin;
-    res->dbg[4] = t_state - t_begin;
-    res->dbg[5] = t_scan - t_begin;
-    res->dbg[6] = t_emit - t_begin;
-    res->dbg[7] = V;
-    res->dbg[8] = P;
-    res->dbg[9] = 0xFA57;  // this stamp set comes from rxf_body
-    res->pad1++;
-    res->dbg[1] = __builtin_amdgcn_s_memtime();
-    atomicAdd(&g_rx_fast_drains[0], 1ull);
-    // (relaxed: the consumers of a streaming job's drain are later kernels of the graph; a release at system scope
-    // here would write the XCD's L2 back -- the plan just laid out -- before the kernel may end)
-    __hip_atomic_store(&res->seq, op.seq_next ? op.seq_next : o_seq + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    auto tail = [&](uint32_t& h1, uint32_t& h2) {
+      const uint32_t rl = (V - 1) - ((V - 1) / P) * P;
+      h1 = s_pat[rl];
+      h2 = V >= 2 ? s_pat[rl ? rl - 1 : P - 1] : o.h1;
+    };
+    rxf_commit(op, true /* op.append != 0: a precondition */, ring, cap64, head64, mh0, irs0, Lr, ts,  // the connection, the drain's span
+               V, tot_n, tot_sl, tot_sg, tot_tl, tot_by, short_len, leftover_final,  // what the drain took
+               slice_idx0, a_off0, a_end, hc, tail,                                  // cursors, history
+               crossed, base, credit, credit_head, o,                                // credit, counters
+               t_begin, t_pattern, t_probe, t_state, t_scan, t_emit, P, 0, 0, 0, 0);
   }
   return true;
 }

@@ -65,11 +65,11 @@ __device__ __forceinline__ void rxh_preload(const grdma_rx_op& op, rxh_pre& p) {
   }
 }
 
-template <bool WT = false, bool EWT = WT, class RingWait = ring_ready_now, class Publish = credit_unpublished>  // (see rxm_body)
+template <bool EWT = false, class RingWait = ring_ready_now, class Publish = credit_unpublished>  // (see rxm_body)
 __device__ __forceinline__ int rxh_body(const grdma_rx_op& op_in, const uint32_t wg, const uint32_t nwg, const rxh_pre* pre = nullptr,
                                         RingWait* ring_wait = nullptr, Publish* publish = nullptr) {
-  static_assert(sizeof(rx_lds_hint) <= sizeof(rx_lds) && !WT, "the tables fit the planners' LDS (not the small one of a write-through body)");
-  rx_lds_hint& H = *reinterpret_cast<rx_lds_hint*>(rx_tables<WT>());
+  static_assert(sizeof(rx_lds_hint) <= sizeof(rx_lds), "the tables fit the planners' LDS");
+  rx_lds_hint& H = *reinterpret_cast<rx_lds_hint*>(rx_lds_get());
   const grdma_rx_op op = op_in;
   const uint64_t t_begin = __builtin_amdgcn_s_memtime();
   const uint32_t tid = threadIdx.x;
@@ -329,17 +329,11 @@ __device__ __forceinline__ int rxh_body(const grdma_rx_op& op_in, const uint32_t
   }
   // ---- (round 6) the counters the commit adds to and the credit of the drain, by thread 0 of EVERY workgroup while its
   //      entries are on their way to the memory side (see rxm_body)
-  uint64_t o_total_read = 0, o_credit_msgs = 0, o_rx_records = 0, o_rx_rounds = 0, o_seq = 0;
-  uint32_t o_h1 = 0;
-  grdma_hostline* line = nullptr;
+  rxf_counters o = {};
   uint64_t base = 0, credit = 0, credit_head = 0;
   bool crossed = false;
   if (tid == 0 && !reason && committer) {
-    o_total_read = c->total_read; o_credit_msgs = c->credit_msgs;
-    o_rx_records = c->rx_records; o_rx_rounds = c->rx_rounds;
-    o_h1 = c->rx_h1;
-    o_seq = res->seq;
-    line = c->line;
+    o = rxf_load_counters(c, res);
     const uint64_t T = cap64 / 2, Ctot = Lr;
     uint64_t thr = T - irs0;
     while (Ctot >= thr) {
@@ -351,22 +345,7 @@ __device__ __forceinline__ int rxh_body(const grdma_rx_op& op_in, const uint32_t
       }
       const uint32_t n = H.n[lo];
       bool far = false;
-      const rxf_rec rp = rxf_replay(n, state_of(lo, &far));
-      const uint64_t C2 = H.x[lo + 1];
-      const uint64_t e = 16u + ((n + 7u) & ~7u);
-      const uint64_t cons2 = rp.c2 ? rp.c2 + (((n + 7u) & ~7u) - n + 8u) : 0;
-      const uint64_t C1 = C2 - cons2;
-      const uint64_t pos = (head64 + C2 - e) & (cap64 - 1);
-      if (rp.c2 && C1 >= thr) {  // crossed after the first step of a two-step record
-        credit_head = (pos + 8 + rp.c1) & (cap64 - 1);
-        base = C1;
-      } else {
-        credit_head = (pos + e) & (cap64 - 1);
-        base = C2;
-      }
-      credit++;
-      crossed = true;
-      thr = base + T;
+      rxf_credit_step(n, rxf_replay(n, state_of(lo, &far)), (uint64_t)H.x[lo + 1], head64, cap64, T, thr, base, credit, credit_head, crossed);
     }
   }
   const uint64_t t_emit = __builtin_amdgcn_s_memtime();
@@ -405,78 +384,17 @@ __device__ __forceinline__ int rxh_body(const grdma_rx_op& op_in, const uint32_t
       c->rx_hist[(uint32_t)((hc + i) % GRDMA_RX_HIST)] = 16u + ((H.n[i] + 7u) & ~7u);
     }
   }
-  // ---- 7. credit (pair.cc:276-284), state, result: thread 0
+  // ---- 7. state, result: thread 0 (rxf_commit, grdma_rx_fast.h)
   if (tid == 0) {
-    const uint64_t Ctot = Lr;
-    const uint64_t irs = crossed ? Ctot - base : irs0 + Ctot;
-    const uint64_t nh = (head64 + Lr) & (cap64 - 1);
-    if (short_len) {
-      out_slices[tot_sl].off = a_off0 + tot_by;
-      out_slices[tot_sl].len = short_len;
-    }
-    xwg_st32<WT>(&plan->nsegs, tot_sg);
-    xwg_st32<WT>(&plan->ntiles, tot_tl);
-    xwg_st32<WT>(&plan->tile_bytes, 1u << ts);
-    xwg_st32<WT>(&plan->tile_prefix[tot_sg], tot_tl);
-    plan->bytes = tot_n;
-    xwg_st64<WT>(&plan->tag_base, (uint64_t)ring);
-    xwg_st64<WT>(&plan->tag_mask, cap64 - 1);
-    xwg_st32<WT>(&plan->blocks_done, 0u);
-    c->head = nh;
-    c->moving_head = nh;
-    c->remain = 0;
-    if (line != nullptr) {
-      line->rx_head = nh;
-      line->rx_remain = 0;
-    }
-    c->internal_read_size = irs;
-    c->leftover_cap = leftover_final;
-    c->total_read = o_total_read + tot_n;
-    c->credit_msgs = o_credit_msgs + credit;
-    c->rx_records = o_rx_records + V;
-    if (nsl_final) c->rx_rounds = o_rx_rounds + 1;
-    c->rx_arena_off = a_end;
-    c->rx_slice_idx = slice_idx0 + nsl_final;
-    c->rx_hist_count = hc + V;
-    c->rx_h1 = 16u + ((H.n[V - 1] + 7u) & ~7u);
-    c->rx_h2 = V >= 2 ? 16u + ((H.n[V - 2] + 7u) & ~7u) : o_h1;
-    if (credit) c->status_send.remote_head = credit_head;
-    xwg_st64<WT>(&res->credit_head, credit_head);
-    res->nslices = nsl_final;
-    res->bytes = tot_n;
-    res->consumed = Lr;
-    res->records = V;
-    res->would_block = 1;
-    xwg_st64<WT>(&res->credit_sent, credit);
-    res->head = nh;
-    res->moving_head = nh;
-    res->remain = 0;
-    res->arena_used = a_end;
-    res->zero_off[0] = res->zero_off[1] = res->zero_len[0] = res->zero_len[1] = 0;
-    if (nh > mh0) {
-      res->zero_off[0] = mh0;
-      res->zero_len[0] = nh - mh0;
-    } else {
-      res->zero_off[0] = mh0;
-      res->zero_len[0] = cap64 - mh0;
-      res->zero_off[1] = 0;
-      res->zero_len[1] = nh;
-    }
-    res->dbg[0] = t_begin;
-    res->dbg[2] = t_pattern - t_begin;
-    res->dbg[3] = t_probe - t_begin;
-    res->dbg[4] = t_state - t_begin;
-    res->dbg[5] = t_scan - t_begin;
-    res->dbg[6] = t_emit - t_begin;
-    res->dbg[7] = V;
-    res->dbg[8] = 0;       // (no period)
-    res->dbg[9] = 0xFA57;  // this stamp set comes from a steady-state body
-    res->dbg[10] = nwg;
-    res->dbg[11] = res->dbg[12] = res->dbg[13] = 0;
-    res->pad1++;
-    res->dbg[1] = __builtin_amdgcn_s_memtime();
-    atomicAdd(&g_rx_fast_drains[0], 1ull);
-    __hip_atomic_store(&res->seq, op.seq_next ? op.seq_next : o_seq + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    auto tail = [&](uint32_t& h1, uint32_t& h2) {
+      h1 = 16u + ((H.n[V - 1] + 7u) & ~7u);
+      h2 = V >= 2 ? 16u + ((H.n[V - 2] + 7u) & ~7u) : o.h1;
+    };
+    rxf_commit(op, true /* op.append != 0: a precondition */, ring, cap64, head64, mh0, irs0, Lr, ts,  // the connection, the drain's span
+               V, tot_n, tot_sl, tot_sg, tot_tl, tot_by, short_len, leftover_final,  // what the drain took
+               slice_idx0, a_off0, a_end, hc, tail,                                  // cursors, history
+               crossed, base, credit, credit_head, o,                                // credit, counters
+               t_begin, t_pattern, t_probe, t_state, t_scan, t_emit, 0 /* no period */, nwg, 0, 0, 0);
     drain_close(plan, nwg);
   }
   return 1;

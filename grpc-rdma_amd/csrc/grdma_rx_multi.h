@@ -112,19 +112,6 @@ __device__ __forceinline__ void rxm_cyc(const rx_lds_multi& M, uint32_t P, uint3
   *by = q * M.qby[P] + M.qby[r];
 }
 
-// The tables of the multi-workgroup bodies: the receive planners' shared LDS (64 KB, the general planner's arrays).
-// (SMALL: an allocation of their own size, for a body that shares its launch with copy workgroups which must keep
-//  their occupancy -- round 4's fused round, retired; no kernel instantiates it now.)
-#define RXM_SMALL_LDS_BYTES 33024
-template <bool SMALL>
-__device__ __forceinline__ void* rx_tables() {
-  if (SMALL) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_small[RXM_SMALL_LDS_BYTES];
-    return s_small;
-  }
-  return rx_lds_get();
-}
-
 // Wire inside the planner pair's launch (k_plan_pair_mw; a job of few links with small rings): the wire's
 // workgroups -- the lowest blockIdx.y, dispatched first -- move the round into the peer ring, write their L2 back and
 // count in at the WIRE plan's arrival word; the drain's workgroups do everything that does not look at the ring, then
@@ -226,22 +213,21 @@ __device__ __forceinline__ void drain_close(grdma_plan* plan, uint32_t nwg) {
 // committed; 2: the committing one, and a workgroup declined -- the caller runs the general planner; 3: every workgroup alike
 // found the connection without a usable period and the round carries a size table -- the caller runs rxh_body (every
 // thread of the workgroup returns the same value).
-// WT: every plan and credit word is stored write-through and acknowledged before a workgroup leaves (grdma_devfn.h:
-// xwg_*), for a plan consumed inside the SAME launch; unused since round 4's fused round was retired -- every kernel
-// passes false, the plan's consumers are later launches.
+// The tables live in the receive planners' shared LDS (rx_lds_get: the general planner's arrays).
 // EWT: the entries a workgroup emits for its own records (segments, tile prefix, slices) are stored write-through
-// and acknowledged before it arrives, whatever WT says about the rest.  The kernels whose last workgroup runs the general
+// (grdma_devfn.h: xwg_*) and acknowledged before it arrives; everything else is a plain store, the plan's consumers are
+// later launches.  The kernels whose last workgroup runs the general
 // planner IN THE SAME LAUNCH when some workgroup declined (k_plan_pair_mw, k_rx_plan_mw) need it: that planner rewrites
 // the same slots from index 0, and entries left dirty in another XCD's L2 by a workgroup whose own probe passed would
 // be written back over them, or not, in no defined order when the kernel ends.
 // ring_wait (may be null): called once by every thread, before the body looks at the ring for the first time -- the
 // wire of the round may share the launch (ring_behind_wire); a body that returns 3 has not called it.
 // publish (may be null): called by the committing thread with the credit of the drain (credit_promised).
-template <bool WT = false, bool EWT = WT, class RingWait = ring_ready_now, class Publish = credit_unpublished>
+template <bool EWT = false, class RingWait = ring_ready_now, class Publish = credit_unpublished>
 __device__ __forceinline__ int rxm_body(const grdma_rx_op& op_in, const uint32_t wg, const uint32_t nwg, RingWait* ring_wait = nullptr,
                                         Publish* publish = nullptr) {
-  static_assert(sizeof(rx_lds_multi) <= sizeof(rx_lds) && sizeof(rx_lds_multi) <= RXM_SMALL_LDS_BYTES, "the tables fit their LDS");
-  rx_lds_multi& M = *reinterpret_cast<rx_lds_multi*>(rx_tables<WT>());
+  static_assert(sizeof(rx_lds_multi) <= sizeof(rx_lds), "the tables fit their LDS");
+  rx_lds_multi& M = *reinterpret_cast<rx_lds_multi*>(rx_lds_get());
   const grdma_rx_op op = op_in;
   const uint64_t t_begin = __builtin_amdgcn_s_memtime();
   const uint32_t tid = threadIdx.x;
@@ -692,17 +678,11 @@ __device__ __forceinline__ int rxm_body(const grdma_rx_op& op_in, const uint32_t
   //      workgroup that commits fetched the counters and walked the credit loop behind the arrival, 2 us at the tail of
   //      every planner launch (profiles/r06_plan_phases.txt: "commit loads", "credit").  Nothing of this is written
   //      before the last workgroup commits; the counters only ever change there.
-  uint64_t o_total_read = 0, o_credit_msgs = 0, o_rx_records = 0, o_rx_rounds = 0, o_seq = 0;
-  uint32_t o_h1 = 0;
-  grdma_hostline* line = nullptr;
+  rxf_counters o = {};
   uint64_t base = 0, credit = 0, credit_head = 0;
   bool crossed = false;
   if (tid == 0 && !reason && committer) {
-    o_total_read = c->total_read; o_credit_msgs = c->credit_msgs;
-    o_rx_records = c->rx_records; o_rx_rounds = c->rx_rounds;
-    o_h1 = c->rx_h1;
-    o_seq = res->seq;
-    line = c->line;
+    o = rxf_load_counters(c, res);
     auto enc_end = [&](uint32_t i) -> uint64_t {  // ring bytes consumed once record i is finished
       const uint32_t qi = divP(i), ri = i - qi * P;
       return (uint64_t)qi * SP + M.pre[ri] + M.pat[ri];
@@ -729,22 +709,7 @@ __device__ __forceinline__ int rxm_body(const grdma_rx_op& op_in, const uint32_t
       }
       uint32_t n;
       const uint32_t s_in = state_of(lo, &n);
-      const rxf_rec rp = rxf_replay(n, s_in);
-      const uint64_t C2 = enc_end(lo);
-      const uint64_t e = 16u + ((n + 7u) & ~7u);
-      const uint64_t cons2 = rp.c2 ? rp.c2 + (((n + 7u) & ~7u) - n + 8u) : 0;
-      const uint64_t C1 = C2 - cons2;
-      const uint64_t pos = (head64 + C2 - e) & (cap64 - 1);
-      if (rp.c2 && C1 >= thr) {  // crossed after the first step of a two-step record
-        credit_head = (pos + 8 + rp.c1) & (cap64 - 1);
-        base = C1;
-      } else {
-        credit_head = (pos + e) & (cap64 - 1);
-        base = C2;
-      }
-      credit++;
-      crossed = true;
-      thr = base + T;
+      rxf_credit_step(n, rxf_replay(n, s_in), enc_end(lo), head64, cap64, T, thr, base, credit, credit_head, crossed);
     }
   }
   const uint64_t t_emit = __builtin_amdgcn_s_memtime();
@@ -810,88 +775,22 @@ __device__ __forceinline__ int rxm_body(const grdma_rx_op& op_in, const uint32_t
       c->rx_hist[(uint32_t)((hc + i) % GRDMA_RX_HIST)] = M.pat[i - divP(i) * P];
     }
   }
-  // ---- 8. credit (pair.cc:276-284), state, result: thread 0 (as rxf_body, per-record values from the tables)
+  // ---- 8. state, result: thread 0 (rxf_commit, grdma_rx_fast.h; the payload total and the history tail from the tables)
   if (tid == 0) {
-    const uint64_t t_loaded = __builtin_amdgcn_s_memtime() + (o_seq & 0);
+    const uint64_t t_loaded = __builtin_amdgcn_s_memtime() + (o.seq & 0);
     const uint32_t tot_n = divP(V) * M.qn[P] + M.qn[V - divP(V) * P];  // payload bytes of the drain
-    const uint64_t Ctot = Lr;
     const uint64_t t_credit = __builtin_amdgcn_s_memtime();
-    const uint64_t irs = crossed ? Ctot - base : irs0 + Ctot;
-    const uint64_t nh = (head64 + Lr) & (cap64 - 1);
-    if (short_len) {
-      out_slices[tot_sl].off = a_off0 + tot_by;
-      out_slices[tot_sl].len = short_len;
-    }
-    xwg_st32<WT>(&plan->nsegs, tot_sg);
-    xwg_st32<WT>(&plan->ntiles, tot_tl);
-    xwg_st32<WT>(&plan->tile_bytes, 1u << ts);
-    xwg_st32<WT>(&plan->tile_prefix[tot_sg], tot_tl);
-    plan->bytes = tot_n;
-    xwg_st64<WT>(&plan->tag_base, (uint64_t)ring);
-    xwg_st64<WT>(&plan->tag_mask, cap64 - 1);
-    xwg_st32<WT>(&plan->blocks_done, 0u);
-    c->head = nh;
-    c->moving_head = nh;
-    c->remain = 0;
-    if (line != nullptr) {
-      line->rx_head = nh;
-      line->rx_remain = 0;
-    }
-    c->internal_read_size = irs;
-    c->leftover_cap = leftover_final;
-    c->total_read = o_total_read + tot_n;
-    c->credit_msgs = o_credit_msgs + credit;
-    c->rx_records = o_rx_records + V;
-    if (nsl_final) c->rx_rounds = o_rx_rounds + 1;
-    if (op.append) {  // (a streaming job's cursors)
-      c->rx_arena_off = a_end;
-      c->rx_slice_idx = slice_idx0 + nsl_final;
-    }
-    c->rx_hist_count = hc + V;
-    {
+    auto tail = [&](uint32_t& h1, uint32_t& h2) {
       const uint32_t rl = (V - 1) - divP(V - 1) * P;
-      c->rx_h1 = M.pat[rl];
-      c->rx_h2 = V >= 2 ? M.pat[rl ? rl - 1 : P - 1] : o_h1;
-    }
-    if (credit) c->status_send.remote_head = credit_head;
-    xwg_st64<WT>(&res->credit_head, credit_head);
-    res->nslices = nsl_final;
-    res->bytes = tot_n;
-    res->consumed = Lr;
-    res->records = V;
-    res->would_block = 1;
-    xwg_st64<WT>(&res->credit_sent, credit);
-    res->head = nh;
-    res->moving_head = nh;
-    res->remain = 0;
-    res->arena_used = a_end;
-    res->zero_off[0] = res->zero_off[1] = res->zero_len[0] = res->zero_len[1] = 0;
-    if (nh > mh0) {
-      res->zero_off[0] = mh0;
-      res->zero_len[0] = nh - mh0;
-    } else {
-      res->zero_off[0] = mh0;
-      res->zero_len[0] = cap64 - mh0;
-      res->zero_off[1] = 0;
-      res->zero_len[1] = nh;
-    }
-    res->dbg[0] = t_begin;
-    res->dbg[2] = t_pattern - t_begin;
-    res->dbg[3] = t_probe - t_begin;
-    res->dbg[4] = t_state - t_begin;
-    res->dbg[5] = t_scan - t_begin;
-    res->dbg[6] = t_emit - t_begin;
-    res->dbg[7] = V;
-    res->dbg[8] = P;
-    res->dbg[9] = 0xFA57;  // this stamp set comes from a steady-state body
-    res->dbg[10] = nwg;
-    res->dbg[11] = t_arrived - t_begin;
-    res->dbg[12] = t_loaded - t_begin;
-    res->dbg[13] = t_credit - t_begin;
-    res->pad1++;
-    res->dbg[1] = __builtin_amdgcn_s_memtime();
-    atomicAdd(&g_rx_fast_drains[0], 1ull);
-    __hip_atomic_store(&res->seq, op.seq_next ? op.seq_next : o_seq + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      h1 = M.pat[rl];
+      h2 = V >= 2 ? M.pat[rl ? rl - 1 : P - 1] : o.h1;
+    };
+    rxf_commit(op, op.append != 0, ring, cap64, head64, mh0, irs0, Lr, ts,  // the connection, the drain's span
+               V, tot_n, tot_sl, tot_sg, tot_tl, tot_by, short_len, leftover_final,  // what the drain took
+               slice_idx0, a_off0, a_end, hc, tail,                                  // cursors, history
+               crossed, base, credit, credit_head, o,                                // credit, counters
+               t_begin, t_pattern, t_probe, t_state, t_scan, t_emit, P, nwg, t_arrived - t_begin,
+               t_loaded - t_begin, t_credit - t_begin);
     drain_close(plan, nwg);
   }
   return 1;

@@ -52,6 +52,7 @@ namespace {
 #define CHAIN_CAP 128
 #define BULK_MAX 4096
 #define MINRD GRDMA_MIN_READ_SLICE
+static_assert(MINRD == RXF_MINRD, "one smallest read for every tier");
 
 __device__ unsigned long long g_express_drains = 0;  // diagnostics: drains served by the express path
 // profiling aid (grdma_rx_express_ticks): ticks of an express drain's phases, summed -- {state loaded, records known,
@@ -171,16 +172,6 @@ __device__ __forceinline__ uint32_t chain_round(chain_walker* w, uint64_t* chain
   return v;
 }
 
-// Transition of the endpoint-read state over one record of n bytes:
-// s = bytes of space left in an open 256-byte read (0 = between reads).
-__device__ __forceinline__ uint32_t read_space_after(uint64_t n, uint32_t s) {
-  if (s == 0) return n >= MINRD ? 0 : (uint32_t)(MINRD - n);
-  if (n < s) return s - (uint32_t)n;
-  if (n == s) return 0;
-  const uint64_t r = n - s;
-  return r >= MINRD ? 0 : (uint32_t)(MINRD - r);
-}
-
 // What one whole record does to the read sequence, given the incoming state.
 // (Plain scalars only: arrays indexed at run time would live in scratch memory.)
 struct rec_plan {
@@ -208,31 +199,8 @@ __device__ __forceinline__ rec_plan replay_record(uint64_t n, uint32_t s_in) {
   return r;
 }
 
-// The same in 32-bit arithmetic, for the bulk tier (ring <= 2 GiB there): half the
-// VALU work of the 64-bit form on the pass that is instruction-issue bound.
-struct rec_plan32 {
-  uint32_t c1, c2, sl0, sl1, sl_cnt;
-};
-__device__ __forceinline__ rec_plan32 replay_record32(uint32_t n, uint32_t s_in) {
-  rec_plan32 r;
-  r.c1 = n;
-  r.c2 = 0;
-  r.sl0 = r.sl1 = 0;
-  if (s_in == 0) {
-    if (n >= MINRD) r.sl0 = n;
-  } else if (n <= s_in) {
-    if (n == s_in) r.sl0 = MINRD;
-  } else {
-    r.c1 = s_in;
-    r.c2 = n - s_in;
-    r.sl0 = MINRD;
-    if (r.c2 >= MINRD) r.sl1 = r.c2;
-  }
-  r.sl_cnt = (r.sl0 ? 1u : 0u) + (r.sl1 ? 1u : 0u);
-  return r;
-}
-__device__ __forceinline__ uint32_t al16_32(uint32_t v) { return (v + 15u) & ~15u; }
-__device__ __forceinline__ uint32_t tiles_of32(uint32_t len, uint32_t ts) { return (len + (1u << ts) - 1u) >> ts; }
+// (The bulk tier -- ring <= 2 GiB there -- uses the 32-bit form, rxf_replay of grdma_rx_fast.h: half the VALU work of
+// the 64-bit one on the pass that is instruction-issue bound.)
 
 // The ring pieces of one record's steps: step 1 = pieces 0,1; step 2 = pieces 2,3
 // (the second piece of a step exists only when the step crosses the ring end).
@@ -275,11 +243,7 @@ struct rx_state {
   uint64_t hand_pos;
 };
 
-// SCRATCH: the big arrays (rx_lds_general, 64 KB) live in global memory instead of LDS -- the general planner as the
-// rarely-taken fallback inside a launch whose other workgroups cannot keep their occupancy beside a 64 KB LDS
-// allocation per workgroup (round 4's fused round, retired: no kernel instantiates SCRATCH = true now).  Same code, same results; slower.
-template <bool SCRATCH = false>
-__device__ __forceinline__ void rx_plan_body(const grdma_rx_op& op_in, rx_lds* scratch = nullptr) {
+__device__ __forceinline__ void rx_plan_body(const grdma_rx_op& op_in) {
   // (a private copy: fields read through the reference would be re-fetched from memory
   // after every store the compiler cannot prove unrelated)
   const grdma_rx_op op = op_in;
@@ -309,8 +273,7 @@ __device__ __forceinline__ void rx_plan_body(const grdma_rx_op& op_in, rx_lds* s
   __shared__ rx_state S;
   __shared__ uint64_t s_chain[CHAIN_CAP];
   // (the big arrays share their allocation with the steady-state body, which has finished when this one runs)
-  rx_lds* lds;
-  if constexpr (SCRATCH) lds = scratch; else lds = rx_lds_get();
+  rx_lds* const lds = rx_lds_get();
   auto& s_hist = lds->g.hist;
   // padded like the send plan's arrays: contiguous 16-record runs per thread
 #define RXP(i) ((i) + ((i) >> 4))
@@ -862,11 +825,11 @@ __device__ __forceinline__ void rx_plan_body(const grdma_rx_op& op_in, rx_lds* s
       uint32_t j = k0;
       while (j > 0 && s_n[RXP(j - 1)] < 2 * MINRD - 1) j--;
       uint32_t s = 0;
-      for (; j < k0; j++) s = read_space_after(s_n[RXP(j)], s);
+      for (; j < k0; j++) s = rxf_space_after(s_n[RXP(j)], s);
       uint32_t last_clean = 0;
       for (uint32_t k = k0; k < k0 + per0 && k < V; k++) {
         s_sin[RXP(k)] = (uint16_t)s;
-        s = read_space_after(s_n[RXP(k)], s);
+        s = rxf_space_after(s_n[RXP(k)], s);
         if (s == 0) last_clean = k + 1;
       }
       if (last_clean) atomicMax(&s_clean, last_clean);
@@ -895,13 +858,13 @@ __device__ __forceinline__ void rx_plan_body(const grdma_rx_op& op_in, rx_lds* s
       uint32_t t_pk = 0, t_tiles = 0;  // t_pk: slices | segments << 16 (<= 2 and 4 per record)
       for (uint32_t k = wbeg + lane; k < wend; k += 64) {
         const uint32_t n = s_n[RXP(k)];
-        const rec_plan32 rp = replay_record32(n, s_sin[RXP(k)]);
+        const rxf_rec rp = rxf_replay(n, s_sin[RXP(k)]);
         const uint32_t pay = (head32 + s_xenc[RXP(k)] + 8u) & mask32;
         // (the two steps of a record are contiguous in the ring AND in the arena -- step 1 fills
         // the open slice exactly, step 2 starts the next one right behind it -- so they travel
         // as ONE segment unless the record crosses the ring end)
         uint32_t sg = 1u;
-        uint32_t tl = tiles_of32(rp.c1 + rp.c2, ts);
+        uint32_t tl = rxf_tiles(rp.c1 + rp.c2, ts);
         if (pay + n > cap32 || pay + n < pay) {  // crosses the ring end: split the step(s) it cuts
           uint64_t o0, l0, o1, l1, o2, l2, o3, l3;
           split_step(pay, 0, rp.c1, cap, &o0, &l0, &o1, &l1);
@@ -909,7 +872,7 @@ __device__ __forceinline__ void rx_plan_body(const grdma_rx_op& op_in, rx_lds* s
           sg = (l0 ? 1u : 0u) + (l1 ? 1u : 0u) + (l2 ? 1u : 0u) + (l3 ? 1u : 0u);
           tl = tiles_of(l0, ts) + tiles_of(l1, ts) + tiles_of(l2, ts) + tiles_of(l3, ts);
         }
-        t_bytes += al16_32(rp.sl0) + al16_32(rp.sl1);
+        t_bytes += rxf_al16(rp.sl0) + rxf_al16(rp.sl1);
         t_pk += rp.sl_cnt + (sg << 16);
         t_tiles += tl;
         t_n += n;
@@ -946,7 +909,7 @@ __device__ __forceinline__ void rx_plan_body(const grdma_rx_op& op_in, rx_lds* s
       const bool act = k < wend;
       const uint32_t n = act ? s_n[RXP(k)] : 0;
       const uint32_t s_in = act ? s_sin[RXP(k)] : 0;
-      rec_plan32 rp = replay_record32(n, s_in);
+      rxf_rec rp = rxf_replay(n, s_in);
       if (!act) { rp.c1 = rp.c2 = 0; rp.sl_cnt = 0; rp.sl0 = rp.sl1 = 0; }
       const uint32_t pos = (head32 + (act ? s_xenc[RXP(k)] : 0)) & mask32, pay = (pos + 8u) & mask32;
       // pieces of the record in the ring: step 1 = pieces 0,1; step 2 = pieces 2,3 (the
@@ -966,9 +929,9 @@ __device__ __forceinline__ void rx_plan_body(const grdma_rx_op& op_in, rx_lds* s
       }
       const uint32_t my_sg = (l0 ? 1u : 0u) + (l1 ? 1u : 0u) + (l2 ? 1u : 0u) + (l3 ? 1u : 0u);
       const uint32_t my_pk = rp.sl_cnt | (my_sg << 16);
-      const uint32_t my_tiles = tiles_of32(l0, ts) + tiles_of32(l1, ts) + tiles_of32(l2, ts) + tiles_of32(l3, ts);
+      const uint32_t my_tiles = rxf_tiles(l0, ts) + rxf_tiles(l1, ts) + rxf_tiles(l2, ts) + rxf_tiles(l3, ts);
       // (the ring holds < 2^31 bytes in a bulk pass, so 32-bit scans of one step's bytes are exact)
-      const uint32_t my_bytes = al16_32(rp.sl0) + al16_32(rp.sl1);
+      const uint32_t my_bytes = rxf_al16(rp.sl0) + rxf_al16(rp.sl1);
       const uint32_t i_pk = wave_incl_scan_u32(my_pk);
       const uint32_t i_tiles = wave_incl_scan_u32(my_tiles);
       const uint32_t i_bytes = wave_incl_scan_u32(my_bytes);
@@ -991,7 +954,7 @@ __device__ __forceinline__ void rx_plan_body(const grdma_rx_op& op_in, rx_lds* s
           plan->segs[nsegs0 + x_sg] = {dst, (uint64_t)(ring + off), (uint64_t)len, fl};
           plan->tile_prefix[nsegs0 + x_sg] = x_tiles;
           x_sg++;
-          x_tiles += tiles_of32(len, ts);
+          x_tiles += rxf_tiles(len, ts);
           dst += len;
         };
         emit(o0, l0, 0);
@@ -1003,7 +966,7 @@ __device__ __forceinline__ void rx_plan_body(const grdma_rx_op& op_in, rx_lds* s
           out_slices[nsl0 + x_sl].off = sof;
           out_slices[nsl0 + x_sl].len = rp.sl0;
           x_sl++;
-          sof += al16_32(rp.sl0);
+          sof += rxf_al16(rp.sl0);
         }
         if (rp.sl1) {
           out_slices[nsl0 + x_sl].off = sof;
@@ -1027,6 +990,8 @@ __device__ __forceinline__ void rx_plan_body(const grdma_rx_op& op_in, rx_lds* s
         s_hist[(hc + k) % GRDMA_RX_HIST] = s_penc[RXP(k)];
     }
     // ---- credit accounting over the Recv steps (pair.cc:276-284), thread 0 ----------------
+    // (the 64-bit twin of rxf_credit_step, grdma_rx_fast.h, kept: through the shared function k_rx_plan came out longer
+    //  and k_rx_plan_job with a larger scratch segment -- profiles/drain_planner_refactor.md)
     if (tid == 0) {
       const uint64_t T = cap / 2;
       const uint64_t Ctot = s_xenc[RXP(cnt - 1)] + s_penc[RXP(cnt - 1)];
@@ -1211,8 +1176,8 @@ __device__ __forceinline__ void rx_plan_body(const grdma_rx_op& op_in, rx_lds* s
       const uint32_t from = below ? (64 - __builtin_clzll(below)) : 0;
       uint32_t s_in = 0;
       for (uint32_t i = from; i < (uint32_t)lane && act0; i++)
-        s_in = read_space_after(s_chain[chain_i + i], s_in);
-      const uint32_t s_out = read_space_after(n, s_in);
+        s_in = rxf_space_after(s_chain[chain_i + i], s_in);
+      const uint32_t s_out = rxf_space_after(n, s_in);
       const uint64_t clean = __ballot(act0 && s_out == 0);
       if (clean == 0) return 0;
       const uint32_t cnt = 64 - __builtin_clzll(clean);
@@ -1639,11 +1604,6 @@ extern "C" uint64_t grdma_express_drains(void) {
 extern "C" __attribute__((visibility("hidden"))) const void* grdma_kernel_fn_rx_plan(void) { return reinterpret_cast<const void*>(&k_rx_plan); }
 extern "C" __attribute__((visibility("hidden"))) const void* grdma_kernel_fn_rx_plan_job(void) { return reinterpret_cast<const void*>(&k_rx_plan_job); }
 extern "C" __attribute__((visibility("hidden"))) uint32_t grdma_rx_plan_job_threads(void) { return RXF_THREADS; }
-extern "C" __attribute__((visibility("hidden"))) hipError_t grdma_launch_rx_plan_job(const grdma_rx_op* d_ops, uint32_t nops, hipStream_t s) {
-  if (nops == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_rx_plan_job, dim3(nops), dim3(RXF_THREADS), 0, s, d_ops);
-  return hipGetLastError();
-}
 // diagnostics: drains rxf_body took, and the ones it left to the general planner by reason (g_rx_fast_drains)
 extern "C" int grdma_rx_fast_drains(uint64_t out[6]) {
   unsigned long long v[6] = {0, 0, 0, 0, 0, 0};

@@ -128,10 +128,4 @@ __global__ __launch_bounds__(TXF_THREADS) void k_tx_index(grdma_txf_ctl* ctls) {
 extern "C" {
 __attribute__((visibility("hidden"))) const void* grdma_kernel_fn_tx_index(void) { return reinterpret_cast<const void*>(&k_tx_index); }
 __attribute__((visibility("hidden"))) uint32_t grdma_tx_index_threads(void) { return TXF_THREADS; }
-// blocks = workgroups per connection: ceil(longest slice list / 1024)
-__attribute__((visibility("hidden"))) hipError_t grdma_launch_tx_index(grdma_txf_ctl* d_ctls, uint32_t n, uint32_t blocks, hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_tx_index, dim3(blocks ? blocks : 1, n), dim3(TXF_THREADS), 0, s, d_ctls);
-  return hipGetLastError();
-}
 }

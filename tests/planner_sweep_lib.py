@@ -9,7 +9,9 @@ RXF_PER 4, RXM_CHUNK 256, the tile size), never sampled at random, except family
 
 The reference is pyorc.OracleLink driven as tests/test_gpu_stream_job.py::_oracle_rounds drives it.  Rounds are kept at or
 below ring / 6 bytes, where the paired schedule's Sends are never credit-limited and the oracle's plain rounds apply to both
-schedules (as MULTI_CASES of that file).
+schedules (as MULTI_CASES of that file).  Of the receiver's state the driver compares what a drain's commit writes:
+head, moving_head, remain, internal_read_size, credit_msgs, leftover_cap (check_rx_state of that file) and total_read
+against the payload bytes of the case times the passes.
 
 WITNESSES.  In front of every drain the oracle gives the receiver's head, the sender's remote_tail, the read left open
 (leftover_cap), internal_read_size, and -- from the send cursor -- the payload sizes of the round's records.  From these
@@ -21,7 +23,7 @@ import ctypes as C
 import random
 
 from oracle import pyorc
-from tests.test_gpu_stream_job import PASSES, _advance, _fast_counts, _run_job, _table_cache_stats
+from tests.test_gpu_stream_job import PASSES, _advance, _fast_counts, _run_job, _table_cache_stats, check_rx_state, rx_state_of
 
 MINRD, RESET, LOOKBACK, PMAX, PER, CHUNK = 256, 512, 192, 512, 4, 256
 NONE = None   # (a witness that is absent: no such record in the drain)
@@ -184,7 +186,7 @@ def trace(case):
             assert rounds < 100000
         if first_rounds is None:
             first_rounds = rounds
-    out = {"slices": delivered, "rounds": first_rounds, "st": (o.state(0), o.state(1)), "ring": o.ring_mem(1), "drains": drains}
+    out = {"slices": delivered, "rounds": first_rounds, "st": (o.state(0), rx_state_of(o)), "ring": o.ring_mem(1), "drains": drains}
     o.close()
     _TRACES[key] = out
     return out
@@ -614,7 +616,7 @@ def lagged_trace(case):
     assert idx == len(slices), "the rounds given to the paired pass do not carry the whole list"
     sender.status_recv.remote_head = latest
     out = {"first": first, "rounds": rounds, "slices": delivered, "paired_rounds": paired_rounds, "used": len(sends),
-           "st": (o.state(0), o.state(1)), "ring": o.ring_mem(1), "sends": sends}
+           "st": (o.state(0), rx_state_of(o)), "ring": o.ring_mem(1), "sends": sends}
     o.close()
     _TRACES[key] = out
     return out
@@ -665,8 +667,7 @@ def run_case_lagged(g, case, wire):
         txs, rxs = tx.state(), rx.state()
         for k in ("remote_tail", "remote_head", "partial_write"):
             assert txs[k] == exp["st"][0][k], (k, tag)
-        for k in ("head", "moving_head", "remain", "internal_read_size"):
-            assert rxs[k] == exp["st"][1][k], (k, tag)
+        check_rx_state(rxs, exp["st"][1], tag, total_read=2 * N)   # (two passes: the sequential one, the paired chain)
         job.close()
     finally:
         tx.close()
@@ -717,6 +718,7 @@ def run_case(g, case, schedule, wire, pairs=None):
         return run_case_lagged(g, case, wire)
     exp = trace(case)
     before, tab0 = _fast_counts(g), _table_cache_stats(g)
+    read0 = pairs[1].state()["total_read"] if pairs is not None else 0
     got = _run_job(g, case.ring, case.max_sge, case.slices(), pipeline=paired, flags=2 if wire == "direct" else 0,
                    sends=case.sends, promise=case.promised and paired, pairs=pairs)
     after, tab1 = _fast_counts(g), _table_cache_stats(g)
@@ -729,8 +731,7 @@ def run_case(g, case, schedule, wire, pairs=None):
     st0, st1 = exp["st"]
     for k in ("remote_tail", "remote_head", "partial_write"):
         assert got["tx"][k] == st0[k], (k, tag)
-    for k in ("head", "moving_head", "remain", "internal_read_size"):
-        assert got["rx"][k] == st1[k], (k, tag)
+    check_rx_state(got["rx"], st1, tag, total_read=read0 + PASSES * sum(case.pattern) * case.reps)
     delta = [a - b for a, b in zip(after, before)]
     e = case.expect[schedule]
     if e == "taken":

@@ -39,6 +39,25 @@ def _framed_slices(n_msgs, msg_len, seed):
 PASSES = 3  # the job is run three times on the same connection (eager, graph, graph)
 
 
+RX_KEYS = ("head", "moving_head", "remain", "internal_read_size", "credit_msgs", "leftover_cap")
+
+
+def rx_state_of(o, side=1):
+    """The oracle's state of one side with the capacity of the read its last would-block left open beside it
+    (pyorc.OracleLink.state() does not carry leftover_cap)."""
+    return dict(o.state(side), leftover_cap=int(o.p[side].leftover_cap))
+
+
+def check_rx_state(got, exp, tag=None, total_read=None):
+    """What a drain's commit leaves in the connection, against the oracle: every key of RX_KEYS that `exp` holds (a dict
+    of rx_state_of), and total_read against the payload bytes the caller knows the passes delivered."""
+    for k in RX_KEYS:
+        if k in exp:
+            assert got[k] == exp[k], (k, got[k], exp[k], tag)
+    if total_read is not None:
+        assert got["total_read"] == total_read, ("total_read", got["total_read"], total_read, tag)
+
+
 def _oracle_passes(R, max_sge, slices, sends=1, passes=PASSES):
     """The reference loop on the CPU: one Send from the rdma_flush cursor, then endpoint
     reads until one would block; repeat until the list is gone.  `passes` times over the
@@ -70,7 +89,7 @@ def _oracle_passes(R, max_sge, slices, sends=1, passes=PASSES):
                     break
                 delivered.append(s)
             assert rounds < 100000
-        out.append((delivered, rounds, (o.state(0), o.state(1)), o.ring_mem(1)))
+        out.append((delivered, rounds, (o.state(0), rx_state_of(o)), o.ring_mem(1)))
     o.close()
     return out
 
@@ -165,8 +184,7 @@ def test_sequential_job_matches_oracle_rounds(gpu, case):
     assert got["ring"] == ring == bytes(R)
     for k in ("remote_tail", "remote_head", "partial_write"):
         assert got["tx"][k] == st0[k], k
-    for k in ("head", "moving_head", "remain", "internal_read_size"):
-        assert got["rx"][k] == st1[k], k
+    check_rx_state(got["rx"], st1)
 
 
 @pytest.mark.parametrize("flags", [0, 2], ids=["staged", "direct"])
@@ -238,8 +256,7 @@ def test_steady_state_drains_through_the_fast_planner_match_the_oracle(gpu, case
     assert got["ring"] == ring == bytes(R)
     for k in ("remote_tail", "remote_head", "partial_write"):
         assert got["tx"][k] == st0[k], k
-    for k in ("head", "moving_head", "remain", "internal_read_size"):
-        assert got["rx"][k] == st1[k], k
+    check_rx_state(got["rx"], st1)
     took = after[0] - before[0]
     assert took >= exp_rounds, "k_rx_fast took %d drains (declined by reason: %s)" % (
         took, [a - b for a, b in zip(after[1:6], before[1:6])])
@@ -287,8 +304,7 @@ def test_drains_of_several_workgroups_match_the_oracle(gpu, case, flags):
     assert got["ring"] == ring == bytes(R)
     for k in ("remote_tail", "remote_head", "partial_write"):
         assert got["tx"][k] == st0[k], k
-    for k in ("head", "moving_head", "remain", "internal_read_size"):
-        assert got["rx"][k] == st1[k], k
+    check_rx_state(got["rx"], st1)
     took = after[0] - before[0]
     if taken:
         assert took >= exp_rounds, "the steady-state bodies took %d drains (declined by reason: %s)" % (
@@ -349,8 +365,7 @@ def test_paired_schedule_with_promised_credit_equals_the_plain_oracle_rounds(gpu
     assert got["ring"] == ring == bytes(R)
     for k in ("remote_tail", "remote_head", "partial_write"):
         assert got["tx"][k] == st0[k], k
-    for k in ("head", "moving_head", "remain", "internal_read_size"):
-        assert got["rx"][k] == st1[k], k
+    check_rx_state(got["rx"], st1)
 
 
 @pytest.mark.parametrize("promise", [True, False], ids=["promised", "credit_a_round_late"])
@@ -384,8 +399,7 @@ def test_the_wire_inside_the_planner_pairs_launch_delivers_what_a_wire_launch_of
         assert on["ring"] == ring == bytes(R)
         for k in ("remote_tail", "remote_head", "partial_write"):
             assert on["tx"][k] == st0[k], k
-        for k in ("head", "moving_head", "remain", "internal_read_size"):
-            assert on["rx"][k] == st1[k], k
+        check_rx_state(on["rx"], st1)
 
 
 @pytest.mark.parametrize("case", [(1 << 20, 30, 64, 40, 200000), (1 << 22, 30, 64, 14, 1 << 20)], ids=["r1m_sge30x64", "r4m_sge30x64"])
@@ -415,8 +429,7 @@ def test_promised_credit_with_mixed_message_sizes_equals_the_plain_oracle_rounds
     assert got["ring"] == ring == bytes(R)
     for k in ("remote_tail", "remote_head", "partial_write"):
         assert got["tx"][k] == st0[k], k
-    for k in ("head", "moving_head", "remain", "internal_read_size"):
-        assert got["rx"][k] == st1[k], k
+    check_rx_state(got["rx"], st1)
 
 
 def test_three_links_of_one_job_with_two_sends_per_round_and_promised_credit(gpu):
@@ -465,8 +478,7 @@ def test_three_links_of_one_job_with_two_sends_per_round_and_promised_credit(gpu
         assert rx.ring_mem() == ring == bytes(R)
         for k in ("remote_tail", "remote_head", "partial_write"):
             assert tx.state()[k] == st0[k], (li, k)
-        for k in ("head", "moving_head", "remain", "internal_read_size"):
-            assert rx.state()[k] == st1[k], (li, k)
+        check_rx_state(rx.state(), st1, li)
     job.close()
     for tx, rx, *_ in keep:
         tx.close()
@@ -523,8 +535,7 @@ def test_many_sends_per_round_priced_as_one_cut_of_the_index_match_the_oracle(gp
         assert got["slices"] == exp
         for k in ("remote_tail", "remote_head", "partial_write"):
             assert got["tx"][k] == st0[k], k
-        for k in ("head", "moving_head", "remain", "internal_read_size"):
-            assert got["rx"][k] == st1[k], k
+        check_rx_state(got["rx"], st1)
 
 
 @pytest.mark.parametrize("flags", [0, 2], ids=["staged", "direct"])
@@ -557,8 +568,7 @@ def test_two_sends_per_round_in_one_plan_match_the_oracle(gpu, case, flags):
         assert got["slices"] == exp
         for k in ("remote_tail", "remote_head", "partial_write"):
             assert got["tx"][k] == st0[k], k
-        for k in ("head", "moving_head", "remain", "internal_read_size"):
-            assert got["rx"][k] == st1[k], k
+        check_rx_state(got["rx"], st1)
         if exact is True:
             assert after[0] - before[0] >= exp_rounds, "drains taken by the predicting bodies: %d of %d rounds per pass" % (
                 after[0] - before[0], exp_rounds)
@@ -579,8 +589,7 @@ def test_the_instrumented_schedule_is_the_graphs_chain(gpu, case, flags):
     assert got["ring"] == ring == bytes(R)
     for k in ("remote_tail", "remote_head", "partial_write"):
         assert got["tx"][k] == st0[k], k
-    for k in ("head", "moving_head", "remain", "internal_read_size"):
-        assert got["rx"][k] == st1[k], k
+    check_rx_state(got["rx"], st1)
     n = got["rounds_set"]
     la = dict(zip(gs.CLASS_NAMES, got["launches"]))
     assert la["plan_pair"] == n and la["scatter_gather"] == n - 1 and la["rx_apply"] == 1, la
@@ -614,8 +623,7 @@ def test_the_in_order_timed_pass_and_the_stream_launch_match_the_oracle(gpu, pip
         assert state["ring"] == ring == bytes(R)
         for k in ("remote_tail", "remote_head", "partial_write"):
             assert state["tx"][k] == st0[k], k
-        for k in ("head", "moving_head", "remain", "internal_read_size"):
-            assert state["rx"][k] == st1[k], k
+        check_rx_state(state["rx"], st1)
     assert len(got["more"]) == 2
     timed = got["more"][0]
     la = dict(zip(gs.CLASS_NAMES, timed["launches"]))
@@ -695,7 +703,7 @@ def _oracle_sequential_then_paired(R, max_sge, slices, paired_rounds):
         views.append(latest)
     assert idx == len(slices), "the rounds given to the paired pass do not carry the whole list"
     sender.status_recv.remote_head = latest  # (what the sender sees once the pass is over)
-    st = (o.state(0), o.state(1))
+    st = (o.state(0), rx_state_of(o))
     ring = o.ring_mem(1)
     o.close()
     return first, rounds, delivered, used, st, ring
@@ -741,8 +749,7 @@ def test_paired_schedule_at_a_credit_limited_ring_equals_the_oracle_with_the_cre
     txs, rxs = tx.state(), rx.state()
     for k in ("remote_tail", "remote_head", "partial_write"):
         assert txs[k] == st0[k], k
-    for k in ("head", "moving_head", "remain", "internal_read_size"):
-        assert rxs[k] == st1[k], k
+    check_rx_state(rxs, st1)
     job.close()
     tx.close()
     rx.close()
@@ -784,7 +791,7 @@ def test_bidirectional_job_both_directions_of_one_pair_in_the_same_launches(gpu,
                         break
                     delivered[d].append(s)
         exp = delivered
-    st = (o.state(0), o.state(1))
+    st = (rx_state_of(o, 0), rx_state_of(o, 1))
     rings = (o.ring_mem(0), o.ring_mem(1))
     o.close()
 
@@ -818,8 +825,9 @@ def test_bidirectional_job_both_directions_of_one_pair_in_the_same_launches(gpu,
     assert a.ring_mem() == rings[0] == bytes(R) and b.ring_mem() == rings[1] == bytes(R)
     for pair_, s_ in ((a, st[0]), (b, st[1])):
         ps = pair_.state()
-        for k in ("remote_tail", "remote_head", "partial_write", "head", "moving_head", "remain", "internal_read_size"):
+        for k in ("remote_tail", "remote_head", "partial_write"):
             assert ps[k] == s_[k], k
+        check_rx_state(ps, s_)
     job.close()
     a.close()
     b.close()
@@ -855,8 +863,7 @@ def test_drains_without_a_period_are_predicted_from_the_sends_sizes(gpu, case, f
     assert got["ring"] == ring == bytes(R)
     for k in ("remote_tail", "remote_head", "partial_write"):
         assert got["tx"][k] == st0[k], k
-    for k in ("head", "moving_head", "remain", "internal_read_size"):
-        assert got["rx"][k] == st1[k], k
+    check_rx_state(got["rx"], st1)
     took = after[0] - before[0]
     print("rounds %d, drains taken by a predicting body %d, declined by reason %s" % (exp_rounds, took, [a - b for a, b in zip(after[1:6], before[1:6])]))
     # (the eager first pass runs the sequential kernels, whose steady-state body needs a period: the graph passes count)
@@ -912,8 +919,7 @@ def test_one_drain_workgroup_declines_while_its_neighbours_accept(gpu, case, fla
     assert got["ring"] == ring == bytes(R)
     for k in ("remote_tail", "remote_head", "partial_write"):
         assert got["tx"][k] == st0[k], k
-    for k in ("head", "moving_head", "remain", "internal_read_size"):
-        assert got["rx"][k] == st1[k], k
+    check_rx_state(got["rx"], st1)
     mixed, unanimous = v1[0] - v0[0], v1[1] - v0[1]
     took = after[0] - before[0]
     print("drains: %d taken by the predicting bodies, %d mixed verdicts, %d unanimous declines; declines by reason %s" % (
@@ -1059,12 +1065,11 @@ def test_a_promised_credit_wait_that_runs_out_gives_the_promise_up_for_the_whole
         if exp is not None:
             assert [len(x) for x in got] == [len(x) for x in exp]
             assert got == exp
-            st0, st1 = link.o.state(0), link.o.state(1)
+            st0, st1 = link.o.state(0), rx_state_of(link.o)
             assert rx.ring_mem() == link.o.ring_mem(1)
             for k in ("remote_tail", "remote_head", "partial_write"):
                 assert txs[k] == st0[k], k
-            for k in ("head", "moving_head", "remain", "internal_read_size"):
-                assert rxs[k] == st1[k], k
+            check_rx_state(rxs, st1)
     finally:
         lib.grdma_debug_set_promise_wait(0)
         link.o.close()
@@ -1150,10 +1155,11 @@ def test_config3_bidirectional_job_on_every_link_matches_the_oracle(gpu, case, p
             assert [len(x) for x in got] == [len(x) for x in exp[d]], "pair %d direction %d" % (p, d)
             assert got == exp[d], "pair %d direction %d" % (p, d)
         assert a.ring_mem() == o.o.ring_mem(0) == bytes(R) and b.ring_mem() == o.o.ring_mem(1) == bytes(R), "pair %d" % p
-        for pair_, s_ in ((a, o.o.state(0)), (b, o.o.state(1))):
+        for pair_, s_ in ((a, rx_state_of(o.o, 0)), (b, rx_state_of(o.o, 1))):
             ps = pair_.state()
-            for k in ("remote_tail", "remote_head", "partial_write", "head", "moving_head", "remain", "internal_read_size"):
+            for k in ("remote_tail", "remote_head", "partial_write"):
                 assert ps[k] == s_[k], (p, k)
+            check_rx_state(ps, s_, p)
         o.o.close()
     print("rounds: sequential %d, paired %d of %d" % (rounds1, used_max, graph_rounds))
     if promise:
