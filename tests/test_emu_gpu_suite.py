@@ -143,6 +143,14 @@ def test_arrival_triggered_reads_under_the_emulator(emu_lib):
     run_gpu_tests(emu_lib, ["tests/test_zzz_gpu_watch_read.py", "-n", "4"], 13)
 
 
+def test_latency_sweep_gpu_tests_under_the_emulator(emu_lib):
+    """The latency engine's one-wave send and drain at their edges (tests/test_zzz_gpu_latency_sweep.py):
+    every case of the file -- the single-wave drain's limits, the open read, credit, the ring's end, max_reads 1 .. 3, the
+    fast lane and the unary branch of the Send, the ordered wire -- with the count of single-wave drains equal to the
+    predicate's and b's record-size history equal to the list of records sent."""
+    run_gpu_tests(emu_lib, ["tests/test_zzz_gpu_latency_sweep.py", "-n", "4"], 112)
+
+
 def test_nic_wire_back_end_over_the_verbs_stand_in(emu_lib):
     """Round 5: csrc/grdma_wire_verbs.cc -- memory registration (the ring through the dma-buf call), queue-pair bring-up,
     the <= 2 chained RDMA WRITEs of a Send, the 16-byte status write, completion reaping -- compiled against
