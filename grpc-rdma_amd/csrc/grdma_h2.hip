@@ -229,6 +229,15 @@ static h2_stage h2_stage_fc(h2fc_dev* d, const h2fc_call* d_call) {
           h2_rec(k_h2_fc_sums, H2FC_GRID, H2FC_THREADS, d, d_call), h2_rec(k_h2_fc_finish, 1, H2FC_ONE_THREADS, d, d_call),
           h2_rec(k_h2_fc_emit, H2FC_GRID, H2FC_THREADS, d)};
 }
+// ... of n links in the same five launches: every link a share of the grid, the one-workgroup stage side by side
+static_assert(H2FC_LINKS_MAX == GRDMA_H2_BATCH_MAX, "the ledger's link table is the batch's");
+static h2_stage h2_stage_fc_links(const h2fc_link* d_tab, uint32_t n) {
+  return {h2_rec(k_h2_links_fc_clear, n * H2FC_LINK_GRID, H2FC_THREADS, d_tab, n),
+          h2_rec(k_h2_links_fc_keys, n * H2FC_LINK_GRID, H2FC_THREADS, d_tab, n),
+          h2_rec(k_h2_links_fc_sums, n * H2FC_LINK_GRID, H2FC_THREADS, d_tab, n),
+          h2_rec(k_h2_links_fc_finish, n, H2FC_ONE_THREADS, d_tab),
+          h2_rec(k_h2_links_fc_emit, n * H2FC_LINK_GRID, H2FC_THREADS, d_tab, n)};
+}
 
 // st goes behind the parser's last deframing by a pipe (the parser state is handed from one deframing to the next),
 // unless that one was enqueued on st itself.  (Only pipe steps leave last_deframed, on a job's or a deframe stream: for

@@ -31,6 +31,14 @@ inline h2_deframe_block h2_deframe_block_layout(const h2_deframe_sizes& s, uint6
           b.add(s.result * n_items), b.add(s.event * n_events), b.total()};
 }
 
+// grdma_h2_fc_account_batch: [table | one call block per item]; all of it goes up.  (Targets and result blocks are
+// words of the ledgers' own device blocks: nothing of them lies here.)
+struct h2_fc_block { uint64_t tab, calls, end, total; };
+inline h2_fc_block h2_fc_block_layout(uint64_t link, uint64_t call, uint64_t n_items) {
+  h2_block b;
+  return {b.add(link * n_items), b.add(call * n_items), b.end, b.total()};
+}
+
 // grdma_h2_reply_frame_batch: [table | one h2r_dev per item]; all of it goes up, the h2r_dev blocks come down.
 struct h2_reply_block { uint64_t tab, devs, end, total; };
 inline h2_reply_block h2_reply_block_layout(uint64_t link, uint64_t dev, uint64_t n_items) {

@@ -713,13 +713,12 @@ int grdma_h2_reply_frame_batch(grdma_h2_reply_item* items, uint32_t n_items) {
 }
 
 // ---- receive flow control: the window ledger (csrc/grdma_h2_fc.h) -------------------------------------------------
-struct grdma_h2_pipe;
 struct grdma_h2_fc {
   grdma_h2_parser* parser = nullptr;
   h2fc_dev* d = nullptr;
   h2fc_dev h;                      // host copy of the configuration words
   h2fc_call* d_call = nullptr;     // standalone calls
-  grdma_h2_pipe* pipe = nullptr;   // the pipe whose steps account through it
+  h2_step_seq* seq = nullptr;      // the steps of the pipe, single or group, that account through it
   uint64_t accounted = 0;          // parser->standalone_calls of the last call accounted
   float last_ms = 0;
 };
@@ -803,7 +802,7 @@ grdma_h2_fc* grdma_h2_fc_create(grdma_h2_parser* parser, uint32_t stream_window,
 }
 
 void grdma_h2_fc_destroy(grdma_h2_fc* f) {
-  if (!f || f->pipe) return;  // (the pipe's graph still runs the kernels on it: destroy the pipe first)
+  if (!f || f->seq) return;  // (the pipe's graph still runs the kernels on it: destroy the pipe first)
   h2_host_ctx* hc = h2_ctx();
   if (hc) hipStreamSynchronize(hc->stream);  // (standalone calls)
   if (f->parser) f->parser->fc = nullptr;
@@ -822,7 +821,7 @@ int64_t grdma_h2_fc_account(grdma_h2_fc* f, grdma_slice* d_slices_out, uint64_t 
   if (!f || !out) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control: no ledger or no result array");
   if (!d_slices_out || !slices_cap || !d_hdr_arena || !hdr_cap || ((uintptr_t)d_slices_out & 15) || ((uintptr_t)d_hdr_arena & 15))
     return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control: a null, zero or misaligned slice table or header arena");
-  if (f->pipe) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control: the ledger is attached to a pipe (its steps account)");
+  if (f->seq) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control: the ledger is attached to a pipe (its steps account)");
   grdma_h2_parser* p = f->parser;
   if (!p) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control: the ledger's parser is gone");
   if (p->standalone_calls == 0) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control: the parser has deframed nothing yet");
@@ -850,6 +849,73 @@ int64_t grdma_h2_fc_account(grdma_h2_fc* f, grdma_slice* d_slices_out, uint64_t 
     return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 flow control: the call's event list overflowed, its bytes cannot be accounted");
   if (res[H2FC_OVERFLOW]) return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 flow control: more frames than max_updates, or a slice or header cap too small");
   return (int64_t)res[H2FC_SLICES];
+}
+
+// ---- the ledgers of many transports in five launches (h2_stage_fc_links) ---------------------------------------------
+// The batch block of the process holds [table | one call block per item] and goes up in one copy; every item's targets
+// are words of its ledger's own device block (64 bytes up per item, in the same section), as are its result words (64
+// bytes down per item behind the stage).  One call at a time, as the other batch calls.
+int grdma_h2_fc_account_batch(const grdma_h2_fc_item* items, uint32_t n_items, uint64_t* out) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!items || !out || n_items == 0 || n_items > GRDMA_H2_BATCH_MAX)
+    return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control batch: 1 .. GRDMA_H2_BATCH_MAX items and a result array");
+  for (uint32_t i = 0; i < n_items; i++) {
+    const grdma_h2_fc_item& it = items[i];
+    const grdma_h2_fc* f = it.fc;
+    if (!f) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control batch: an item without ledger");
+    for (uint32_t k = 0; k < i; k++)
+      if (items[k].fc == f) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control batch: the same ledger twice");
+    if (f->seq) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control batch: a ledger attached to a pipe (its steps account)");
+    const grdma_h2_parser* p = f->parser;
+    if (!p) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control batch: a ledger's parser is gone");
+    if (p->standalone_calls == 0) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control batch: a parser has deframed nothing yet");
+    if (f->accounted == p->standalone_calls) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control batch: a call is accounted already");
+    if (!it.d_slices_out || !it.slices_cap || !it.d_hdr_arena || !it.hdr_cap || ((uintptr_t)it.d_slices_out & 15) ||
+        ((uintptr_t)it.d_hdr_arena & 15))
+      return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control batch: a null, zero or misaligned slice table or header arena");
+  }
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  hipStream_t st = hc->stream;
+  for (uint32_t i = 0; i < n_items; i++)
+    if (!h2_fc_prepare(items[i].fc, items[i].fc->parser->standalone_ev_cap)) return -GRDMA_ERR_HIP;
+  const h2_fc_block L = h2_fc_block_layout(sizeof(h2fc_link), sizeof(h2fc_call), n_items);
+  if (!h2_batch_reserve(L.total, st)) return -GRDMA_ERR_HIP;
+  uint8_t* const d = g_batch.d;
+  std::vector<uint8_t> up(L.end, 0);
+  auto* tab = reinterpret_cast<h2fc_link*>(up.data() + L.tab);
+  auto* calls = reinterpret_cast<h2fc_call*>(up.data() + L.calls);
+  const h2_stage ledgers = h2_stage_fc_links(reinterpret_cast<const h2fc_link*>(d + L.tab), n_items);
+  h2_call c{"h2 flow control batch: a launch was rejected", {{d, up.data(), up.size()}}, {}, {h2_all(ledgers)}, {}};
+  for (uint32_t i = 0; i < n_items; i++) {
+    const grdma_h2_fc_item& it = items[i];
+    grdma_h2_fc* f = it.fc;
+    const grdma_h2_parser* p = f->parser;
+    calls[i] = h2fc_call{p->d_ev, p->d_res, p->standalone_ev_cap};
+    tab[i].F = f->d;
+    tab[i].call = reinterpret_cast<const h2fc_call*>(d + L.calls) + i;
+    // where the item's call writes: the words of h2fc_dev from `out` to the state, from the host mirror
+    f->h.out = reinterpret_cast<grdma_sge*>(it.d_slices_out);
+    f->h.cap = it.slices_cap;
+    f->h.hdr = static_cast<uint8_t*>(it.d_hdr_arena);
+    f->h.hdr_cap = it.hdr_cap;
+    c.up.push_back({reinterpret_cast<uint8_t*>(f->d) + offsetof(h2fc_dev, out), reinterpret_cast<const uint8_t*>(&f->h) + offsetof(h2fc_dev, out),
+                    offsetof(h2fc_dev, announced) - offsetof(h2fc_dev, out)});
+    c.down.push_back({out + 8 * (size_t)i, reinterpret_cast<const uint8_t*>(f->d) + offsetof(h2fc_dev, res), 8 * sizeof(uint64_t)});
+  }
+  // behind the standalone deframings (same stream) and each parser's last deframing by a pipe: the finish reads the
+  // stream map that step may change
+  for (uint32_t i = 0; i < n_items; i++)
+    if (!h2_wait_parser(st, items[i].fc->parser)) return -GRDMA_ERR_HIP;
+  if (int rc = h2_call_run(hc, &c)) return rc;
+  int ok = 0;
+  for (uint32_t i = 0; i < n_items; i++) {
+    grdma_h2_fc* f = items[i].fc;
+    f->last_ms = c.ms[0];  // (the batch's, repeated)
+    f->accounted = f->parser->standalone_calls;
+    ok += out[8 * (size_t)i + H2FC_OVERFLOW] == 0;
+  }
+  return ok;
 }
 
 int grdma_h2_fc_stats(grdma_h2_fc* f, uint64_t out[8]) {

@@ -33,7 +33,7 @@ struct h2_step_seq {
   std::vector<grdma_h2_parser*> parsers;  // the step deframes with these: one per link of the pipe
   std::vector<grdma_h2_reply*> replies;   // a reply pipe: the step frames from these, one per link
   std::vector<grdma_h2_asm*> asms;        // the step assembles into these: empty, or one entry per link (NULL = none)
-  grdma_h2_fc* fc = nullptr;              // the single pipe: the window ledger that accounts every step's events
+  std::vector<grdma_h2_fc*> fcs;          // the window ledgers that account every step's events: empty, or one entry per link (NULL = none)
 };
 
 namespace {
@@ -218,8 +218,9 @@ static void h2_seq_destroy(h2_step_seq* s) {
       a->attached--;
     }
   s->asms.clear();
-  if (s->fc) s->fc->pipe = nullptr;
-  s->fc = nullptr;
+  for (grdma_h2_fc* f : s->fcs)
+    if (f) f->seq = nullptr;
+  s->fcs.clear();
   for (hipEvent_t e : {s->framed, s->job_done, s->deframed, s->t_f0, s->t_f1, s->t_d0, s->t_d1})
     if (e) hipEventDestroy(e);
 }
@@ -429,8 +430,8 @@ int grdma_h2_pipe_attach_flow_control(grdma_h2_pipe* p, grdma_h2_fc* f) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
   if (!p || !f) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 pipe: a pipe and a ledger");
   if (!p->seq.replies.empty()) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 pipe: a reply pipe carries no window ledger (not built)");
-  if (p->seq.fc) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 pipe: a ledger is attached already");
-  if (f->pipe) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 pipe: the ledger is attached to another pipe");
+  if (!p->seq.fcs.empty()) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 pipe: a ledger is attached already");
+  if (f->seq) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 pipe: the ledger is attached to another pipe");
   if (!f->parser) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 pipe: the ledger's parser is gone");
   if (f->parser != p->seq.parsers[0]) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 pipe: the ledger of another parser than the pipe's");
   h2_host_ctx* hc = h2_ctx();
@@ -446,40 +447,37 @@ int grdma_h2_pipe_attach_flow_control(grdma_h2_pipe* p, grdma_h2_fc* f) {
       !h2_fc_set_target(f, p->d_wu, p->wu_cap, p->d_wu_hdr, 32 * p->wu_cap, nullptr))
     return -GRDMA_ERR_HIP;
   if (int rc = h2_seq_append(&p->seq, h2_stage_fc(f->d, p->d_fc_call))) return rc;
-  p->seq.fc = f;
-  f->pipe = p;
+  p->seq.fcs.assign(1, f);
+  f->seq = &p->seq;
   return 0;
 }
 
-// the window-update list of the last step, after the enqueued steps have ended
-static int h2_pipe_wu_result(grdma_h2_pipe* p, uint64_t res[8]) {
-  if (int rc = h2_seq_wait(&p->seq)) return rc;
-  if (hipMemcpy(res, reinterpret_cast<uint8_t*>(p->seq.fc->d) + offsetof(h2fc_dev, res), 8 * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
+// The window-update list a ledger left in a pipe's tables (d_wu, d_wu_hdr) in the last step, after the enqueued steps
+// have ended: the readers of the single pipe and, per link, of the group pipe.
+static int h2_seq_wu_result(const h2_step_seq* s, const grdma_h2_fc* f, uint64_t res[8]) {
+  if (int rc = h2_seq_wait(s)) return rc;
+  if (hipMemcpy(res, reinterpret_cast<const uint8_t*>(f->d) + offsetof(h2fc_dev, res), 8 * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
     return -GRDMA_ERR_HIP;
   return 0;
 }
-
-int64_t grdma_h2_pipe_window_updates(grdma_h2_pipe* p, grdma_slice* slices_out, uint64_t cap, uint64_t out[8]) {
-  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!p || !p->seq.fc || !out || (!slices_out && cap)) return -GRDMA_ERR_INVALID;
-  if (int rc = h2_pipe_wu_result(p, out)) return rc;
+static int64_t h2_seq_window_updates(const h2_step_seq* s, const grdma_h2_fc* f, const grdma_sge* d_wu, grdma_slice* slices_out,
+                                     uint64_t cap, uint64_t out[8]) {
+  if (int rc = h2_seq_wu_result(s, f, out)) return rc;
   if (out[H2FC_OVERFLOW]) return -GRDMA_ERR_CAPACITY;
   const uint64_t n = out[H2FC_SLICES];
   if (n > cap) return -GRDMA_ERR_CAPACITY;
   static_assert(sizeof(grdma_slice) == sizeof(grdma_sge), "layout");
-  if (n && hipMemcpy(slices_out, p->d_wu, sizeof(grdma_sge) * n, hipMemcpyDeviceToHost) != hipSuccess) return -GRDMA_ERR_HIP;
+  if (n && hipMemcpy(slices_out, d_wu, sizeof(grdma_sge) * n, hipMemcpyDeviceToHost) != hipSuccess) return -GRDMA_ERR_HIP;
   return (int64_t)n;
 }
-
-int64_t grdma_h2_pipe_window_update_bytes(grdma_h2_pipe* p, void* bytes_out, uint64_t cap) {
-  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!p || !p->seq.fc || (!bytes_out && cap)) return -GRDMA_ERR_INVALID;
+static int64_t h2_seq_window_update_bytes(const h2_step_seq* s, const grdma_h2_fc* f, const uint8_t* d_wu_hdr, void* bytes_out,
+                                          uint64_t cap) {
   uint64_t res[8];
-  if (int rc = h2_pipe_wu_result(p, res)) return rc;
+  if (int rc = h2_seq_wu_result(s, f, res)) return rc;
   if (res[H2FC_OVERFLOW] || res[H2FC_WIRE] > cap) return -GRDMA_ERR_CAPACITY;
   const uint64_t n = res[H2FC_SLICES];
   std::vector<uint8_t> arena(32 * n);
-  if (n && hipMemcpy(arena.data(), p->d_wu_hdr, arena.size(), hipMemcpyDeviceToHost) != hipSuccess) return -GRDMA_ERR_HIP;
+  if (n && hipMemcpy(arena.data(), d_wu_hdr, arena.size(), hipMemcpyDeviceToHost) != hipSuccess) return -GRDMA_ERR_HIP;
   uint8_t* dst = static_cast<uint8_t*>(bytes_out);
   uint64_t done = 0;
   for (uint64_t k = 0; k < n; k++) {  // (slice k holds wire bytes [23 k, 23 k + 23) at arena + 32 k)
@@ -488,6 +486,18 @@ int64_t grdma_h2_pipe_window_update_bytes(grdma_h2_pipe* p, void* bytes_out, uin
     done += len;
   }
   return (int64_t)done;
+}
+
+int64_t grdma_h2_pipe_window_updates(grdma_h2_pipe* p, grdma_slice* slices_out, uint64_t cap, uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!p || p->seq.fcs.empty() || !out || (!slices_out && cap)) return -GRDMA_ERR_INVALID;
+  return h2_seq_window_updates(&p->seq, p->seq.fcs[0], p->d_wu, slices_out, cap, out);
+}
+
+int64_t grdma_h2_pipe_window_update_bytes(grdma_h2_pipe* p, void* bytes_out, uint64_t cap) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!p || p->seq.fcs.empty() || (!bytes_out && cap)) return -GRDMA_ERR_INVALID;
+  return h2_seq_window_update_bytes(&p->seq, p->seq.fcs[0], p->d_wu_hdr, bytes_out, cap);
 }
 
 // ---- several links of ONE job (the group pipe) ---------------------------------------------------------------------
@@ -505,6 +515,10 @@ struct h2_group_link {
   uint64_t hdr_cap = 0;
   grdma_h2_event* d_ev = nullptr;
   uint64_t ev_cap = 0;
+  // the window-update list of a step, for a link with a ledger (grdma_h2_group_pipe_attach_flow_control)
+  grdma_sge* d_wu = nullptr;
+  uint8_t* d_wu_hdr = nullptr;
+  uint64_t wu_cap = 0;
 };
 struct grdma_h2_group_pipe {
   h2_step_seq seq;  // one parser per listed link; a group reply pipe: one reply per listed link
@@ -516,6 +530,8 @@ struct grdma_h2_group_pipe {
   grdma_h2_deframe_result* d_dres = nullptr;  // one per listed link
   h2a_link* d_atab = nullptr;   // the links with an assembler, in spec order (grdma_h2_group_pipe_attach_assemblers)
   h2a_call* d_calls = nullptr;  // their call blocks
+  h2fc_link* d_fctab = nullptr;     // the links with a ledger, in spec order (grdma_h2_group_pipe_attach_flow_control)
+  h2fc_call* d_fc_calls = nullptr;  // their call blocks
 };
 
 static grdma_h2_group_pipe* h2_group_refuse(grdma_h2_group_pipe* p, const char* why) {
@@ -651,7 +667,11 @@ void grdma_h2_group_pipe_destroy(grdma_h2_group_pipe* p) {
     hipFree(l.d_msgs);
     hipFree(l.d_hdr);
     hipFree(l.d_ev);
+    hipFree(l.d_wu);
+    hipFree(l.d_wu_hdr);
   }
+  hipFree(p->d_fctab);
+  hipFree(p->d_fc_calls);
   hipFree(p->d_rtab);
   hipFree(p->d_atab);
   hipFree(p->d_calls);
@@ -750,4 +770,71 @@ int64_t grdma_h2_group_pipe_messages(grdma_h2_group_pipe* p, uint32_t i, grdma_h
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
   if (!p || i >= p->seq.asms.size() || !p->seq.asms[i] || (!out && cap)) return -GRDMA_ERR_INVALID;
   return h2_seq_messages(&p->seq, p->seq.asms[i], out, cap);
+}
+
+// The window ledgers' stage for the links listed with one: five kernels (k_h2_links_fc_*) however many links, behind what
+// the pipe runs behind its job at the time of the call -- behind the assemblers' six if those were attached first, in
+// front of them otherwise (the ledgers read the events only, so either order gives the same bytes).  The pipe owns each
+// listed link's window-update list (room for that ledger's max_updates frames) and call block.  The create calls refuse
+// a parser that has a ledger, so a ledger joins a group pipe by being created on its link's parser AFTER the pipe, then
+// attached.  Ordering stays in h2_seq_enqueue: the stage adds no rule.
+int grdma_h2_group_pipe_attach_flow_control(grdma_h2_group_pipe* p, grdma_h2_fc* const* fcs, uint32_t n) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!p || !fcs) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: a pipe and a ledger list");
+  if (!p->seq.replies.empty()) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: a group reply pipe carries no window ledgers (not built)");
+  if (n != p->links.size()) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: one ledger entry per link spec");
+  if (!p->seq.fcs.empty()) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: ledgers are attached already");
+  uint32_t have = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    grdma_h2_fc* f = fcs[i];
+    if (!f) continue;
+    for (uint32_t k = 0; k < i; k++)
+      if (fcs[k] == f) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: the same ledger twice");
+    if (f->seq) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: a ledger attached to a pipe already");
+    if (!f->parser) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: a ledger whose parser is gone");
+    if (f->parser != p->seq.parsers[i]) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: the ledger of another parser than its link's");
+    have++;
+  }
+  if (!have) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 group pipe: no ledger in the list");
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc || hipStreamSynchronize(hc->stream) != hipSuccess) return -GRDMA_ERR_HIP;  // (the ledgers' standalone calls)
+  if (p->seq.launched && h2_seq_wait(&p->seq) != 0) return -GRDMA_ERR_HIP;
+  if ((!p->d_fctab && hipMalloc((void**)&p->d_fctab, sizeof(h2fc_link) * n) != hipSuccess) ||
+      (!p->d_fc_calls && hipMalloc((void**)&p->d_fc_calls, sizeof(h2fc_call) * n) != hipSuccess))
+    return -GRDMA_ERR_HIP;
+  std::vector<h2fc_call> calls;
+  std::vector<h2fc_link> tab;
+  for (uint32_t i = 0; i < n; i++) {
+    grdma_h2_fc* f = fcs[i];
+    if (!f) continue;
+    h2_group_link& l = p->links[i];
+    if (!h2_fc_prepare(f, l.ev_cap)) return -GRDMA_ERR_HIP;
+    l.wu_cap = (f->h.max_updates * H2FC_FRAME + H2_INLINED - 1) / H2_INLINED;
+    if ((!l.d_wu && hipMalloc((void**)&l.d_wu, sizeof(grdma_sge) * l.wu_cap) != hipSuccess) ||
+        (!l.d_wu_hdr && hipMalloc((void**)&l.d_wu_hdr, 32 * l.wu_cap) != hipSuccess) ||
+        !h2_fc_set_target(f, l.d_wu, l.wu_cap, l.d_wu_hdr, 32 * l.wu_cap, nullptr))
+      return -GRDMA_ERR_HIP;
+    tab.push_back(h2fc_link{f->d, p->d_fc_calls + calls.size()});
+    calls.push_back(h2fc_call{l.d_ev, p->d_dres + i, l.ev_cap});
+  }
+  if (hipMemcpy(p->d_fc_calls, calls.data(), sizeof(h2fc_call) * have, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(p->d_fctab, tab.data(), sizeof(h2fc_link) * have, hipMemcpyHostToDevice) != hipSuccess)
+    return -GRDMA_ERR_HIP;
+  if (int rc = h2_seq_append(&p->seq, h2_stage_fc_links(p->d_fctab, have))) return rc;
+  p->seq.fcs.assign(fcs, fcs + n);
+  for (grdma_h2_fc* f : p->seq.fcs)
+    if (f) f->seq = &p->seq;
+  return 0;
+}
+
+int64_t grdma_h2_group_pipe_window_updates(grdma_h2_group_pipe* p, uint32_t i, grdma_slice* slices_out, uint64_t cap, uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!p || i >= p->seq.fcs.size() || !p->seq.fcs[i] || !out || (!slices_out && cap)) return -GRDMA_ERR_INVALID;
+  return h2_seq_window_updates(&p->seq, p->seq.fcs[i], p->links[i].d_wu, slices_out, cap, out);
+}
+
+int64_t grdma_h2_group_pipe_window_update_bytes(grdma_h2_group_pipe* p, uint32_t i, void* bytes_out, uint64_t cap) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!p || i >= p->seq.fcs.size() || !p->seq.fcs[i] || (!bytes_out && cap)) return -GRDMA_ERR_INVALID;
+  return h2_seq_window_update_bytes(&p->seq, p->seq.fcs[i], p->links[i].d_wu_hdr, bytes_out, cap);
 }

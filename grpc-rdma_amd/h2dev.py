@@ -49,6 +49,11 @@ class H2ReplyLinkSpec(C.Structure):
                 ("events_cap", u64), ("recorded_wire_bytes", u64)]
 
 
+class H2FcItem(C.Structure):
+    _fields_ = [("fc", C.c_void_p), ("d_slices_out", C.c_void_p), ("slices_cap", u64), ("d_hdr_arena", C.c_void_p),
+                ("hdr_cap", u64)]
+
+
 MSG_OK, MSG_TOO_LARGE, MSG_NO_SPACE, MSG_TRUNCATED = 0, 1, 2, 3
 SYNC_KEYS = ("framed", "frame_overflow", "events", "deframe_overflow", "parsed", "h2_error", "frame_us", "deframe_us",
              "bulk_steps", "bulk_frames", "t_wait", "t_bulk", "t_total", "t_serial")
@@ -194,6 +199,14 @@ def _bind():
         lib.grdma_h2_pipe_window_updates.argtypes = [C.c_void_p, C.POINTER(Slice), u64, C.POINTER(u64)]
         lib.grdma_h2_pipe_window_update_bytes.restype = C.c_int64
         lib.grdma_h2_pipe_window_update_bytes.argtypes = [C.c_void_p, C.c_void_p, u64]
+        lib.grdma_h2_fc_account_batch.restype = C.c_int
+        lib.grdma_h2_fc_account_batch.argtypes = [C.POINTER(H2FcItem), C.c_uint32, C.POINTER(u64)]
+        lib.grdma_h2_group_pipe_attach_flow_control.restype = C.c_int
+        lib.grdma_h2_group_pipe_attach_flow_control.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32]
+        lib.grdma_h2_group_pipe_window_updates.restype = C.c_int64
+        lib.grdma_h2_group_pipe_window_updates.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Slice), u64, C.POINTER(u64)]
+        lib.grdma_h2_group_pipe_window_update_bytes.restype = C.c_int64
+        lib.grdma_h2_group_pipe_window_update_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, u64]
         lib.grdma_job_hook_counts.restype = C.c_int   # (not in include/grdma_amd.h: the job's side of the pipes)
         lib.grdma_job_hook_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         _bound = True
@@ -477,6 +490,33 @@ class GroupPipe:
         m = check(self.lib.grdma_h2_group_pipe_messages(self.h, i, out, cap))
         return _msgs(out, m)
 
+    def attach_flow_control(self, fcs):
+        """one FlowControl (of the spec's parser) or None per spec: every later step accounts the events of those links,
+        five more kernels however many links (grdma_h2_group_pipe_attach_flow_control).  The pipe refuses a parser that
+        has a ledger when it is created: create the pipe, then the FlowControl on the link's parser, then attach.
+        Close the pipe before the ledgers."""
+        fcs = list(fcs)
+        hs = (C.c_void_p * max(1, len(fcs)))(*[f.h if f is not None else None for f in fcs])
+        check(self.lib.grdma_h2_group_pipe_attach_flow_control(self.h, hs, len(fcs)))
+        self.flow_controls = fcs  # (kept alive)
+        for f in fcs:
+            if f is not None:
+                f._pipe = self
+
+    def window_updates(self, i):
+        """the window-update list of spec i in the last step -> ([(ptr, len), ...], result tuple, wire bytes)"""
+        fcs = getattr(self, "flow_controls", [])
+        fc = fcs[i] if i < len(fcs) else None
+        cap = (13 * fc.max_updates + 22) // 23 if fc is not None else 0   # (a spec without ledger: the call refuses)
+        arr = (Slice * max(1, cap))()
+        out = (u64 * 8)()
+        n = self.lib.grdma_h2_group_pipe_window_updates(self.h, i, arr, cap, out)
+        res = tuple(int(x) for x in out)
+        n = check(n)
+        buf = C.create_string_buffer(max(1, res[2]))
+        m = check(self.lib.grdma_h2_group_pipe_window_update_bytes(self.h, i, buf, res[2]))
+        return [(int(arr[k].ptr or 0), int(arr[k].len)) for k in range(n)], res, buf.raw[:m]
+
     def close(self):
         """does nothing while a reply pipe reads one of this pipe's assemblers (grdma_h2_group_pipe_destroy does not
         either): close that one first, then call close again"""
@@ -485,6 +525,10 @@ class GroupPipe:
                 return
             self.lib.grdma_h2_group_pipe_destroy(self.h)
             self.h = None
+            for f in getattr(self, "flow_controls", []):
+                if f is not None:
+                    f._pipe = None
+            self.flow_controls = []
             for r in getattr(self, "reply_framers", []):
                 r.assembler._reply_pipes -= 1
             self.reply_framers = []
@@ -627,6 +671,42 @@ class FlowControl:
         if self.h and not getattr(self, "_pipe", None):
             self.lib.grdma_h2_fc_destroy(self.h)
             self.h = None
+
+
+def account_batch(items):
+    """FlowControl.account for many transports in five launches (grdma_h2_fc_account_batch).  items: [(FlowControl,
+    slices device ptr, slices cap, header arena device ptr, header cap), ...] with distinct, unattached ledgers; each
+    accounts the last standalone deframing of its own parser.  -> per item ([(ptr, len), ...], result tuple
+    (FlowControl.RESULT), wire bytes); an item whose call was lost or overflowed a cap reports for itself: its result
+    tuple and None, nothing of it was written.  The result tuples also land in each ledger's .last_result."""
+    lib = _bind()
+    n = len(items)
+    arr = (H2FcItem * max(1, n))()
+    for i, (fc, sl, cap, hdr, hdr_cap) in enumerate(items):
+        arr[i].fc = fc.h if fc is not None else None
+        arr[i].d_slices_out, arr[i].slices_cap, arr[i].d_hdr_arena, arr[i].hdr_cap = sl, cap, hdr, hdr_cap
+    out = (u64 * (8 * max(1, n)))()
+    check(lib.grdma_h2_fc_account_batch(arr, n, out))
+    res = []
+    for i, (fc, sl_ptr, _, _, _) in enumerate(items):
+        r = tuple(int(x) for x in out[8 * i:8 * i + 8])
+        fc.last_result = r
+        if r[7]:
+            res.append((r, None))
+            continue
+        k = r[1]
+        raw = C.create_string_buffer(max(1, 16 * k))
+        if k:
+            check(lib.grdma_copy_to_host(raw, sl_ptr, 16 * k))
+        sl = [(int.from_bytes(raw.raw[16 * j:16 * j + 8], "little"), int.from_bytes(raw.raw[16 * j + 8:16 * j + 16], "little"))
+              for j in range(k)]
+        wire = b""
+        for ptr, ln in sl:
+            buf = C.create_string_buffer(max(1, ln))
+            check(lib.grdma_copy_to_host(buf, ptr, ln))
+            wire += buf.raw[:ln]
+        res.append((sl, r, wire))
+    return res
 
 
 class Pipe:

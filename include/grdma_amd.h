@@ -870,7 +870,8 @@ int64_t grdma_h2_pipe_slice_table(grdma_h2_pipe* p, grdma_slice* out, uint64_t c
  * shorter.  The list is an outbuf of its own: nothing merges across its end into what the caller sends behind it.
  * Result block: {frames, slices, wire bytes, connection bytes counted, stream bytes credited, violations
  * (GRDMA_H2_FC_*), first violating stream, overflow}.
- * Not here: many links (grdma_h2_deframe_batch, grdma_h2_deframe_messages_batch and the group pipes refuse a parser
+ * Many links: grdma_h2_fc_account_batch and grdma_h2_group_pipe_attach_flow_control below.
+ * Not here: ledgers in the batch deframers (grdma_h2_deframe_batch and grdma_h2_deframe_messages_batch refuse a parser
  * that has a ledger), the frames inside a reply pipe's slice table, and the send half (the framers do not look at the
  * peer's windows). */
 enum grdma_h2_fc_violation { GRDMA_H2_FC_CONN_OVERFLOW = 1, GRDMA_H2_FC_STREAM_OVERFLOW = 2, GRDMA_H2_FC_LOST = 4 };
@@ -904,6 +905,22 @@ int grdma_h2_pipe_attach_flow_control(grdma_h2_pipe* pipe, grdma_h2_fc* fc);
 int64_t grdma_h2_pipe_window_updates(grdma_h2_pipe* pipe, grdma_slice* slices_out, uint64_t cap, uint64_t out[8]);
 /* ... and its wire image: the number of bytes */
 int64_t grdma_h2_pipe_window_update_bytes(grdma_h2_pipe* pipe, void* bytes_out, uint64_t cap);
+/* grdma_h2_fc_account for n ledgers (1 .. GRDMA_H2_BATCH_MAX) in the same five launches (k_h2_links_fc_*): every ledger
+ * accounts the last standalone deframing of its OWN parser, exactly as the single call does, ordered behind it and behind
+ * every parser's last pipe step.  out: 8 result words per item, in item order.  What differs from the single call: an
+ * item's overflow (word 7: 1 = a cap, 2 = the call could not be accounted) is reported in its own words only and writes
+ * nothing for that item, the other items are exact; the return value is the number of items accounted without
+ * overflow, or a negative error.  -GRDMA_ERR_INVALID (nothing runs, grdma_last_error says why): n outside the range, a
+ * NULL ledger or one listed twice, a ledger attached to a pipe, a ledger whose parser is gone, has deframed nothing
+ * yet or whose last call is accounted already, null, zero or misaligned (16 bytes) targets. */
+typedef struct grdma_h2_fc_item {
+  grdma_h2_fc* fc;            /* distinct */
+  grdma_slice* d_slices_out;  /* device slice table of the item */
+  uint64_t slices_cap;
+  void* d_hdr_arena;          /* device header arena of the item, 32 bytes per slice */
+  uint64_t hdr_cap;
+} grdma_h2_fc_item;
+int grdma_h2_fc_account_batch(const grdma_h2_fc_item* items, uint32_t n, uint64_t* out);
 
 /* ---- HTTP/2 on several links of ONE job (the group pipe) ----
  * grdma_h2_pipe serves one link, and a job carries one set of kernels in front of and behind its rounds: a second
@@ -919,8 +936,8 @@ int64_t grdma_h2_pipe_window_update_bytes(grdma_h2_pipe* pipe, void* bytes_out, 
  * grdma_h2_group_pipe_sync's "slices parsed" word is that count.  (grdma_h2_pipe parses the recorded count.)
  * Create returns NULL (grdma_last_error says why) for: n == 0, a link index out of range or listed twice, a parser
  * listed twice, nmsgs 0 or above 4096, max_frame 0 or >= 2^24, a job that already carries such kernels (another pipe).
- * Not here (yet): the chunked deframer inside the batch (every transport is parsed sequentially), flow control (a
- * parser with a window ledger is refused) and HPACK. */
+ * Not here (yet): the chunked deframer inside the batch (every transport is parsed sequentially) and HPACK.  A parser
+ * that has a window ledger at create time is refused: ledgers come later, grdma_h2_group_pipe_attach_flow_control. */
 typedef struct grdma_h2_link_spec {
   uint32_t link;                 /* index into the job's links; distinct */
   const grdma_h2_msg* msgs;
@@ -952,6 +969,23 @@ int grdma_h2_group_pipe_attach_assemblers(grdma_h2_group_pipe* p, grdma_h2_asm* 
 /* the descriptors of spec i in the last synced step, as grdma_h2_pipe_messages: their number, -GRDMA_ERR_CAPACITY if
  * more than cap, -GRDMA_ERR_INVALID for a spec without assembler */
 int64_t grdma_h2_group_pipe_messages(grdma_h2_group_pipe* p, uint32_t i, grdma_h2_rx_msg* out, uint64_t cap);
+/* grdma_h2_pipe_attach_flow_control for the group pipe: every later step accounts the events of the listed links --
+ * five more kernels (k_h2_links_fc_*) however many links, behind the deframing and in attach order with the
+ * assemblers' six (grdma_job_hook_counts = (1, 6), (1, 12) with assemblers; with GRDMA_H2_PIPE_FUSED=0 enqueued behind
+ * the deframing).  n is the pipe's spec count; fcs[i] belongs to spec i's parser, NULL = that link stays without.  The
+ * pipe owns each listed link's window-update list (room for that ledger's max_updates frames).  ORDER: the create calls
+ * refuse a parser that already has a ledger, so create the pipe first, then grdma_h2_fc_create on the link's parser,
+ * then attach.  While attached, grdma_h2_fc_account, grdma_h2_fc_account_batch and grdma_h2_pipe_attach_flow_control
+ * refuse the ledger and grdma_h2_fc_destroy does nothing: destroy the pipe first (that detaches it).
+ * -GRDMA_ERR_INVALID (pipe and job as before): n other than the spec count, all entries NULL, a ledger of another
+ * parser than its spec's, one attached anywhere already, one listed twice, one whose parser is gone, a second attach, a
+ * group reply pipe (not built). */
+int grdma_h2_group_pipe_attach_flow_control(grdma_h2_group_pipe* p, grdma_h2_fc* const* fcs, uint32_t n);
+/* the window-update list of spec i in the last step, as grdma_h2_pipe_window_updates / _window_update_bytes;
+ * -GRDMA_ERR_INVALID for a spec without ledger */
+int64_t grdma_h2_group_pipe_window_updates(grdma_h2_group_pipe* p, uint32_t i, grdma_slice* slices_out, uint64_t cap,
+                                           uint64_t out[8]);
+int64_t grdma_h2_group_pipe_window_update_bytes(grdma_h2_group_pipe* p, uint32_t i, void* bytes_out, uint64_t cap);
 /* removes the kernels from the job's graph, detaches the assemblers, unbinds the replies of a group reply pipe; does
  * nothing while a reply pipe or group reply pipe reads one of this pipe's assemblers: destroy that one first */
 void grdma_h2_group_pipe_destroy(grdma_h2_group_pipe* p);
