@@ -1,4 +1,7 @@
 """Byte-level builders shared by the HTTP/2 deframing tests (CPU oracle and GPU parity)."""
+import json
+import os
+
 from oracle.pyorc import EV_MSG_BEGIN, EV_MSG_BYTES, EV_MSG_END
 
 PREFACE = b"PRI * HTTP/2.0\r\n\r\nSM\r\n\r\n"
@@ -27,3 +30,14 @@ def messages_of(events, data):
         elif k == EV_MSG_END:
             out.append((c, bytes(cur.pop(c))))
     return out
+
+
+def grpcio_capture():
+    """tests/golden/h2_grpcio_capture.json -> (the bytes a stock gRPC client put on the wire, the payloads that went in)"""
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "h2_grpcio_capture.json")
+    d = json.load(open(path))
+    data = bytes.fromhex(d["client_bytes_hex"])
+    from oracle import gen_h2_grpcio_capture
+    unary, stream = gen_h2_grpcio_capture.payloads()   # the payloads that went into the capture
+    assert [len(p) for p in unary + stream] == d["payload_lengths"]
+    return data, unary + stream

@@ -1,34 +1,15 @@
 """GPU parity for the HTTP/2 DATA framing (K6/K7) and deframing (K8/K9) kernels
 against the CPU oracle and the reference's own byte vectors."""
-import ctypes as C
-import json
-import os
 import random
 
 import pytest
 
 from oracle import pyorc
+from tests.h2_device_lib import (PADDED, UNPADDED, VEC, ParserPair, cut_mean, device_bytes, oracle_events, oracle_feed,
+                                 pack_slices, read_slices)
+from tests.h2_helpers import PREFACE, frame, grpc_msg, grpcio_capture, messages_of, unary_call
 
 pytestmark = pytest.mark.gpu
-
-VEC = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "h2_bad_client.json")))["vectors"]
-
-
-def read_slices(g, slices_buf, n):
-    raw = slices_buf.read(16 * n)
-    out = []
-    for i in range(n):
-        ptr = int.from_bytes(raw[16 * i:16 * i + 8], "little")
-        ln = int.from_bytes(raw[16 * i + 8:16 * i + 16], "little")
-        out.append((ptr, ln))
-    return out
-
-
-def device_bytes(g, ptr, n):
-    dst = C.create_string_buffer(max(1, n))
-    if n:
-        g._lib.check(g.load().grdma_copy_to_host(dst, ptr, n))
-    return dst.raw[:n]
 
 
 @pytest.mark.parametrize("lens,max_frame", [
@@ -63,30 +44,11 @@ def test_frame_messages_matches_oracle(gpu, lens, max_frame):
     assert wire == exp_wire and wire_bytes == len(exp_wire)
 
 
-def oracle_events(slices_bytes, prefix, max_frame=16384, streams=()):
-    p = pyorc.H2Parser(expect_client_prefix=prefix, max_frame_size=max_frame)
-    for sid in streams:
-        assert p.open_stream(sid) == 0
-    out = []
-    for i, s in enumerate(slices_bytes):
-        rc, ev = p.feed(s)
-        out += [(k, a, b, c, d, i) for k, a, b, c, d in ev]
-        if rc:
-            return rc, out
-    return 0, out
-
-
 def gpu_events(g, slices_bytes, prefix, max_frame=16384, gap_rng=None, streams=()):
     from grpc_rdma_amd import h2dev
-    arena, table, off = bytearray(), [], 0
-    for s in slices_bytes:
-        if gap_rng is not None:  # slices at arbitrary byte offsets, 0xEE filler between them
-            arena += b"\xee" * gap_rng.randrange(1, 16)
-            off = len(arena)
-        table.append((off, len(s)))
-        arena += s + (b"" if gap_rng is not None else bytes((-len(s)) % 16))
-        off = len(arena)
-    buf = g.DeviceBuffer(data=bytes(arena) + bytes(64))
+    # with a generator: slices at arbitrary byte offsets, 0xEE filler between them and nothing behind them
+    data, table = pack_slices(slices_bytes, UNPADDED if gap_rng is not None else PADDED, gap_rng)
+    buf = g.DeviceBuffer(data=data)
     p = h2dev.Parser(prefix, max_frame)
     if streams:
         assert p.open_streams(streams) == 0
@@ -177,25 +139,12 @@ def test_deframe_connection_errors(gpu):
 
 
 # ---- the stream map: every RPC is a new stream (parsing.cc:341-397, 566-680) ---------------------
-from h2_helpers import PREFACE, frame, grpc_msg, messages_of, unary_call  # noqa: E402
-
-
-def _chunk(data, rng, mean):
-    out, pos = [], 0
-    while pos < len(data):
-        n = max(1, int(rng.expovariate(1.0 / mean)))
-        out.append(data[pos:pos + n])
-        pos += n
-    return out
-
-
 def test_many_streams_on_one_connection_match_the_oracle(gpu):
     """>= 200 sequential unary streams, then 40 concurrent ones with interleaved DATA frames, on ONE
     server connection; the write side of finished calls is closed in batches as a server
     would after responding.  Events (incl. stream open / close), delivered messages and the
     number of live streams equal the oracle's at every step."""
     g = gpu
-    from grpc_rdma_amd import h2dev
     rng = random.Random(23)
     data = bytearray(PREFACE + frame(4, 0, 0))
     sid = 1
@@ -216,32 +165,15 @@ def test_many_streams_on_one_connection_match_the_oracle(gpu):
     data += frame(0, 0, 1, grpc_msg(b"late"))        # stream 1 left the map long ago: skipped
     data += frame(0, 0, 999999, grpc_msg(b"never"))  # never opened: skipped
     data = bytes(data)
-    chunks = _chunk(data, rng, 700)
-    po = pyorc.H2Parser(expect_client_prefix=True, max_concurrent_streams=100)
-    pg = h2dev.Parser(True, 16384, max_concurrent_streams=100, table_slots=256)
-    got_msgs, exp_msgs = [], []
+    chunks = cut_mean(data, rng, 700)
+    pp = ParserPair(g, True, orc_kw=dict(max_concurrent_streams=100), max_concurrent_streams=100, table_slots=256)
     for b0 in range(0, len(chunks), 9):              # one deframe call per batch of delivered slices
         batch = chunks[b0:b0 + 9]
-        ev_o = []
-        for i, c in enumerate(batch):
-            rc, ev = po.feed(c)
-            assert rc == 0
-            ev_o += [(k, a, b, c_, d, i) for k, a, b, c_, d in ev]
-        arena, table = bytearray(), []
-        for c in batch:
-            table.append((len(arena), len(c)))
-            arena += c + bytes((-len(c)) % 16)
-        buf = g.DeviceBuffer(data=bytes(arena) + bytes(64))
-        err, ev_g = pg.deframe(buf.ptr, table)
-        assert err == 0 and ev_g == ev_o
-        closed = [c_ for k, a, b, c_, d, i in ev_g if k == 7 and a == 0]
-        for c_ in closed:
-            assert po.close_writes(c_) == 0
-        assert pg.close_writes(closed) == 0
-        assert pg.live_streams() == po.live_streams() <= 100
-        buf.free()
-    assert po.live_streams() == 0
-    pg.close()
+        ev_g = pp.call(batch, cap=2 * sum(len(c) for c in batch) + 64)
+        pp.close_writes([c_ for k, a, b, c_, d, i in ev_g if k == 7 and a == 0])
+        assert pp.live() <= 100
+    assert pp.orc.live_streams() == 0
+    pp.close()
 
 
 def test_stream_map_rules_match_the_oracle(gpu):
@@ -265,7 +197,7 @@ def test_stream_map_rules_match_the_oracle(gpu):
     rng = random.Random(4)
     for prefix, data, streams in cases:
         for mean in (10000, 5, 1):
-            chunks = _chunk(data, rng, mean)
+            chunks = cut_mean(data, rng, mean)
             rc_o, ev_o = oracle_events(chunks, prefix, streams=streams)
             rc_g, ev_g = gpu_events(gpu, chunks, prefix, streams=streams)
             assert rc_g == rc_o
@@ -312,7 +244,7 @@ def test_malformed_control_frames_and_a_third_header_block_match_the_oracle(gpu)
         else:
             data = ok + b"".join(rng.sample(good, 6)) + blob + frame(0, 0, 1, grpc_msg(body))
         for mean in (10000, 7, 1):
-            chunks = _chunk(data, rng, mean)
+            chunks = cut_mean(data, rng, mean)
             rc_o, ev_o = oracle_events(chunks, True)
             rc_g, ev_g = gpu_events(gpu, chunks, True)
             assert rc_o == code, (code, rc_o)
@@ -321,7 +253,7 @@ def test_malformed_control_frames_and_a_third_header_block_match_the_oracle(gpu)
     # well-formed control frames of every kind in a row: no error, the same events
     data = ok + b"".join(good) + frame(0, 1, 1, grpc_msg(body))
     for mean in (10000, 3):
-        chunks = _chunk(data, rng, mean)
+        chunks = cut_mean(data, rng, mean)
         rc_o, ev_o = oracle_events(chunks, True)
         rc_g, ev_g = gpu_events(gpu, chunks, True)
         assert rc_o == 0 and rc_g == 0 and ev_g == ev_o
@@ -427,11 +359,8 @@ def test_h2_pipe_frame_job_deframe_matches_the_oracle(gpu):
         assert res["h2_error"] == 0 and res["framed"] == len(lens) and res["parsed"] == len(delivered)
         ds = job.delivered_slices(0)
         got = dst.read(dst_cap)
-        ev_o = []
-        for i, (o, n) in enumerate(ds):
-            rc, ev = po.feed(got[o:o + n])
-            assert rc == 0
-            ev_o += [(k, a, b, c, d, i) for k, a, b, c, d in ev]
+        rc, ev_o = oracle_feed(po, [got[o:o + n] for o, n in ds])
+        assert rc == 0
         assert res["event_list"] == ev_o, "step %d" % step
         # the bytes are the framed messages themselves
         stream = b"".join(got[o:o + n] for o, n in ds)
@@ -454,8 +383,7 @@ def test_deframe_real_grpc_client_bytes(gpu):
     tests/test_h2_oracle.py): k_h2_deframe, fed the bytes whole, in 16 KiB reads and cut at random
     points (aligned and unaligned), produces the oracle's events one for one and hands back the
     payloads that went into the calls."""
-    from test_h2_oracle import _grpcio_capture
-    data, exp = _grpcio_capture()
+    data, exp = grpcio_capture()
     for seed in range(5):
         rng = random.Random(seed)
         if seed == 0:
@@ -526,11 +454,8 @@ def test_two_alternating_h2_pipes_share_one_parser(gpu):
         job, dst = jobs[step % 2], dsts[step % 2]
         ds = job.delivered_slices(0)     # (every step of a job delivers the same slices)
         got = dst.read(dst_cap)
-        ev_o = []
-        for i, (o, n) in enumerate(ds):
-            rc, ev = po.feed(got[o:o + n])
-            assert rc == 0
-            ev_o += [(k, a, b, c, d, i) for k, a, b, c, d in ev]
+        rc, ev_o = oracle_feed(po, [got[o:o + n] for o, n in ds])
+        assert rc == 0
         per_step_events.append(ev_o)
     assert res[0]["event_list"] == per_step_events[4]   # pipe 0 ran steps 0, 2, 4
     assert res[1]["event_list"] == per_step_events[5]   # pipe 1 ran steps 1, 3, 5

@@ -15,7 +15,7 @@ import pytest
 
 from oracle import pyorc
 from tests.h2_helpers import PREFACE, frame
-from tests.test_h2_fast_host import receiver_slices, sender_slices
+from tests.h2_device_lib import receiver_slices, sender_slices
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLANG = "/opt/rocm/lib/llvm/bin/clang++"

@@ -9,6 +9,7 @@ import subprocess
 
 import pytest
 
+from tests.h2_device_lib import receiver_slices, sender_slices
 from tests.h2_helpers import PREFACE, frame, grpc_msg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,53 +48,6 @@ def parse(L, chunks, use_step, server=True, streams=(), max_frame=16384):
                                1 if use_step else 0, ev, cap, C.byref(nev), C.byref(steps))
     out = [tuple(ev[6 * i:6 * i + 6]) for i in range(nev.value)]
     return rc, out, steps.value
-
-
-def sender_slices(sizes, sid=1, end_stream=True, seed=0):
-    """Slices as chttp2 hands them to the endpoint: the message header rides in the inlined slice of the
-    first frame header (grpc_slice_buffer_add merge), payload slices by reference."""
-    out = []
-    for i, n in enumerate(sizes):
-        body = grpc_msg(bytes((j * 13 + i + seed) % 251 for j in range(n)))
-        off = 0
-        while off < len(body):
-            k = min(16384, len(body) - off)
-            last = end_stream and i == len(sizes) - 1 and off + k == len(body)
-            fh = k.to_bytes(3, "big") + bytes([0, 1 if last else 0]) + sid.to_bytes(4, "big")
-            if off == 0:
-                out.append(fh + body[:5])
-                if k > 5:
-                    out.append(body[5:k])
-            else:
-                out += [fh, body[off:off + k]]
-            off += k
-    return out
-
-
-def receiver_slices(tx, first=256):
-    """What endpoint reads deliver for those records (rdma_bp_posix.cc:180-326): a read sized to
-    max(256, first record) takes whole records and a piece of the next, the following read its rest."""
-    out, cur, room = [], b"", first
-    for rec in tx:
-        while rec:
-            if room == 0:
-                out.append(cur)
-                cur, room = b"", first
-            if not cur and len(rec) > first:
-                out.append(rec)  # a read sized to the record itself
-                rec = b""
-                continue
-            take = rec[:room]
-            cur += take
-            room -= len(take)
-            rec = rec[len(take):]
-            if room == 0 and rec:
-                out.append(cur)
-                out.append(rec)  # the next read is sized to what is left of the record
-                cur, room, rec = b"", first, b""
-    if cur:
-        out.append(cur)
-    return out
 
 
 PRE = [PREFACE + frame(4, 0, 0), frame(1, 4, 1, b"\x82")]

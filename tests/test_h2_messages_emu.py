@@ -46,9 +46,8 @@ def test_model_against_messages_of_on_the_capture():
     import random
     from oracle import pyorc
     from tests.h2_asm_model import AsmModel, OK, oracle_calls
-    from tests.h2_helpers import messages_of
-    from tests.test_h2_oracle import _grpcio_capture
-    data, exp = _grpcio_capture()
+    from tests.h2_helpers import grpcio_capture, messages_of
+    data, exp = grpcio_capture()
     _, ev = pyorc.H2Parser(expect_client_prefix=True).feed(data, cap=len(data) * 4)
     whole = messages_of([e[:5] for e in ev], data)
     assert [b for _, b in whole] == list(exp)

@@ -157,7 +157,7 @@ def test_oversized_frame_and_bad_prefix_are_connection_errors():
 # The stream map the DATA path reads (parsing.cc init_data_frame_parser / init_header_frame_parser,
 # chttp2_transport.cc grpc_chttp2_mark_stream_closed): lookup only, streams accepted from HEADERS on a
 # server, read-closed by END_STREAM, removed once both sides are closed.
-from h2_helpers import PREFACE, frame, grpc_msg, messages_of, unary_call  # noqa: E402
+from h2_helpers import PREFACE, frame, grpc_msg, grpcio_capture, messages_of, unary_call  # noqa: E402
 
 
 def test_two_hundred_sequential_unary_streams_and_forty_interleaved():
@@ -267,18 +267,6 @@ def test_continuation_and_first_frame_rules():
     assert rc == 0 and [(c, a) for k, a, b, c, d in ev if k == pyorc.EV_STREAM_CLOSED] == [(1, 0)]
 
 
-def _grpcio_capture():
-    import json
-    import os
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "h2_grpcio_capture.json")
-    d = json.load(open(path))
-    data = bytes.fromhex(d["client_bytes_hex"])
-    from oracle import gen_h2_grpcio_capture
-    unary, stream = gen_h2_grpcio_capture.payloads()   # the payloads that went into the capture
-    assert [len(p) for p in unary + stream] == d["payload_lengths"]
-    return data, unary + stream
-
-
 def test_oracle_deframes_what_a_real_grpc_client_sends():
     """tests/golden/h2_grpcio_capture.json holds every byte a stock gRPC C-core client (grpcio) put
     on the wire for four unary calls and one client-streaming call with known payloads
@@ -287,7 +275,7 @@ def test_oracle_deframes_what_a_real_grpc_client_sends():
     arbitrary points, must hand back exactly those payloads in order -- K8/K9 pinned against bytes
     produced by real chttp2 code, not by hand."""
     import random
-    data, exp = _grpcio_capture()
+    data, exp = grpcio_capture()
     assert data.startswith(PREFACE)
     for seed in range(6):
         rng = random.Random(seed)

@@ -6,36 +6,22 @@ import random
 
 import pytest
 
-from oracle import pyorc
-from tests.h2_helpers import PREFACE, frame, grpc_msg
-from tests.test_h2_fast_host import receiver_slices, sender_slices
+from tests.h2_device_lib import UNPADDED, oracle_feed, oracle_parser, pack_slices, receiver_slices, sender_slices
+from tests.h2_helpers import PREFACE, frame
 
 pytestmark = pytest.mark.gpu
 
 
-def oracle_events(chunks, prefix, streams=()):
-    p = pyorc.H2Parser(expect_client_prefix=prefix)
-    for sid in streams:
-        assert p.open_stream(sid) == 0
-    out = []
-    for i, s in enumerate(chunks):
-        rc, ev = p.feed(s)
-        out += [(k, a, b, c, d, i) for k, a, b, c, d in ev]
-        assert rc == 0
-    return out
+def expected_events(chunks, prefix, streams=()):
+    rc, ev = oracle_feed(oracle_parser(prefix, streams=streams), chunks)
+    assert rc == 0
+    return ev
 
 
 def gpu_events(g, chunks, prefix, step, gap_rng=None, streams=()):
     from grpc_rdma_amd import h2dev
-    arena, table = bytearray(), []
-    for s in chunks:
-        if gap_rng is not None:
-            arena += b"\xee" * gap_rng.randrange(1, 16)
-        else:
-            arena += bytes((-len(arena)) % 16)
-        table.append((len(arena), len(s)))
-        arena += s
-    buf = g.DeviceBuffer(data=bytes(arena) + bytes(64))
+    data, table = pack_slices(chunks, UNPADDED, gap_rng)
+    buf = g.DeviceBuffer(data=data)
     p = h2dev.Parser(prefix, boundary_step=step)
     if streams:
         assert p.open_streams(streams) == 0
@@ -55,7 +41,7 @@ def test_boundary_step_streaming_shapes(gpu, shape, gaps):
     sizes = [1 << 20, 16384 * 3 - 5, 40000, 16384 - 5, 7, 16384 * 70 + 123, 1, 300000, 5, 2, 16379, 16380]
     tx = sender_slices(sizes)
     chunks = PRE + (tx if shape == "sender" else receiver_slices(tx))
-    exp = oracle_events(chunks, True)
+    exp = expected_events(chunks, True)
     rng = random.Random(9)
     off, n_off = gpu_events(gpu, chunks, True, False, gap_rng=rng if gaps else None)
     on, n_on = gpu_events(gpu, chunks, True, True, gap_rng=rng if gaps else None)
@@ -70,7 +56,7 @@ def test_boundary_step_bench_shape(gpu):
     n = 24
     rx = receiver_slices(sender_slices([1 << 20] * n, end_stream=False))
     chunks = [frame(1, 4, 1, b"\x82")] + rx
-    exp = oracle_events(chunks, False, streams=(1,))
+    exp = expected_events(chunks, False, streams=(1,))
     on, steps = gpu_events(gpu, chunks, False, True, streams=(1,))
     assert on == exp
     assert steps == n
@@ -98,7 +84,7 @@ def test_boundary_step_random_streams_and_cuts(gpu):
                     cut.append(s_)
             body = cut
         chunks = parts + body
-        exp = oracle_events(chunks, True)
+        exp = expected_events(chunks, True)
         on, _ = gpu_events(gpu, chunks, True, True, gap_rng=rng if trial % 2 else None)
         assert on == exp, trial
 
@@ -121,13 +107,9 @@ def test_bulk_pairs_matches_the_oracle(gpu, shape, pairs):
             cut.append(s_)
     rng = random.Random(2)
     for chunks in (PRE + body, PRE + cut):
-        exp = oracle_events(chunks, True)
-        arena, table = bytearray(), []
-        for s_ in chunks:
-            arena += b"\xee" * rng.randrange(1, 16)
-            table.append((len(arena), len(s_)))
-            arena += s_
-        buf = gpu.DeviceBuffer(data=bytes(arena) + bytes(64))
+        exp = expected_events(chunks, True)
+        data, table = pack_slices(chunks, UNPADDED, rng)
+        buf = gpu.DeviceBuffer(data=data)
         p = h2dev.Parser(True, boundary_step=True, bulk_pairs=pairs)
         err, ev = p.deframe(buf.ptr, table, cap=8 * len(chunks) + 4096)
         p.close()

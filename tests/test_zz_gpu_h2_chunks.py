@@ -9,71 +9,10 @@ import numpy as np
 import pytest
 
 from oracle import pyorc
+from tests.h2_device_lib import Both, fast_sender_slices, oracle_feed, receiver_slices
 from tests.h2_helpers import PREFACE, frame, grpc_msg
-from tests.test_h2_fast_host import receiver_slices
 
 pytestmark = pytest.mark.gpu
-
-
-def fast_sender_slices(sizes, sid=1, seed=0, max_frame=16384):
-    """tests/test_h2_fast_host.py::sender_slices with numpy payloads (thousands of slices)."""
-    out = []
-    for i, n in enumerate(sizes):
-        pay = ((np.arange(n, dtype=np.uint32) * 13 + i + seed) % 251).astype(np.uint8).tobytes()
-        body = b"\x00" + n.to_bytes(4, "big") + pay
-        off = 0
-        while off < len(body):
-            k = min(max_frame, len(body) - off)
-            fh = k.to_bytes(3, "big") + bytes([0, 0]) + sid.to_bytes(4, "big")
-            if off == 0:
-                out.append(fh + body[:5])
-                if k > 5:
-                    out.append(body[5:k])
-            else:
-                out += [fh, body[off:off + k]]
-            off += k
-    return out
-
-
-class Both:
-    """The same calls on a device parser and on the oracle's."""
-
-    def __init__(self, g, prefix, streams=(), chunks=None, gap_seed=None):
-        from grpc_rdma_amd import h2dev
-        self.g = g
-        self.dev = h2dev.Parser(prefix, boundary_step=True, chunks=chunks)
-        self.orc = pyorc.H2Parser(expect_client_prefix=prefix)
-        if streams:
-            assert self.dev.open_streams(streams) == 0
-            for sid in streams:
-                assert self.orc.open_stream(sid) == 0
-        self.rng = random.Random(gap_seed) if gap_seed is not None else None
-
-    def call(self, slices):
-        arena, table = bytearray(), []
-        for s in slices:
-            if self.rng is not None:
-                arena += b"\xee" * self.rng.randrange(1, 16)
-            else:
-                arena += bytes((-len(arena)) % 16)
-            table.append((len(arena), len(s)))
-            arena += s
-        buf = self.g.DeviceBuffer(data=bytes(arena) + bytes(64))
-        err, ev = self.dev.deframe(buf.ptr, table, cap=8 * len(slices) + 4096)
-        exp = []
-        for i, s in enumerate(slices):
-            rc, e = self.orc.feed(s, cap=1024)
-            assert rc == 0
-            exp += [(k, a, b, c, d, i) for k, a, b, c, d in e]
-        assert err == 0
-        assert len(ev) == len(exp)
-        if ev != exp:
-            bad = next(i for i in range(len(ev)) if ev[i] != exp[i])
-            raise AssertionError("event %d: device %r, oracle %r" % (bad, ev[bad], exp[bad]))
-        return len(ev)
-
-    def close(self):
-        self.dev.close()
 
 
 @pytest.mark.parametrize("shape", ["sender", "receiver"])
@@ -251,11 +190,8 @@ def test_h2_pipe_at_the_bench_configuration_matches_the_oracle(gpu):
         ds = job.delivered_slices(0)
         assert res["parsed"] == len(ds)
         got = dst.read(dst_cap)
-        ev_o = []
-        for i, (o, n) in enumerate(ds):
-            rc, ev = po.feed(got[o:o + n], cap=1024)
-            assert rc == 0
-            ev_o += [(k, a, b, c, d, i) for k, a, b, c, d in ev]
+        rc, ev_o = oracle_feed(po, [got[o:o + n] for o, n in ds], cap=1024)
+        assert rc == 0
         assert len(res["event_list"]) == len(ev_o)
         assert res["event_list"] == ev_o, "step %d" % step
         if step == 0:

@@ -16,13 +16,11 @@ import os
 import pytest
 
 from oracle import pyorc
-from tests import test_zz_gpu_h2_links as links_mod
+from tests import h2_device_lib as links_mod
 from tests.h2_asm_model import OK
+from tests.h2_device_lib import (FH, FLOW_SIZES, SENTINEL, STEPPED, UNPADDED, RHarness, _interleaved, check_reply, device_bytes,
+                                 oracle_feed, oracle_parser, pack_slices, read_slices, receiver_slices, same)
 from tests.h2_helpers import frame
-from tests.test_gpu_h2 import device_bytes, read_slices
-from tests.test_h2_fast_host import receiver_slices
-from tests.test_zz_gpu_h2_flow import FH, SIZES as FLOW_SIZES, _interleaved
-from tests.test_zz_gpu_h2_reply import RHarness, check_reply
 
 pytestmark = pytest.mark.gpu
 
@@ -31,8 +29,7 @@ ID_A, ID_B, ID_C, ID_D, ID_E = 0x01020305, 0x7FFFFFFF, 0x00FF0001, 0x00010001, 0
 IDS = (ID_A, ID_B, ID_C, ID_D, ID_E)
 F16M = (1 << 24) - 1                       # the largest frame: 0xffffff on the wire
 L16M4, L16M7 = (1 << 24) + 4, (1 << 24) + 7  # message lengths with a non-zero top byte
-SENTINEL = 0x3C
-ERR_INVALID, ERR_CAPACITY = "error 2", "error 5"
+ERR_INVALID, ERR_CAPACITY = "error 2", "error 5"   # (as GrdmaError words them)
 
 _PAT = bytes((j * 13 + 7) % 251 for j in range(251 * 16))
 
@@ -144,9 +141,7 @@ class Framing:
                 parts.append(device_bytes(self.g, p, ln))
         wire = b"".join(parts)
         assert len(wire) == len(self.wire) == wire_bytes
-        if wire != self.wire:
-            bad = next(i for i in range(len(wire)) if wire[i] != self.wire[i])
-            raise AssertionError("wire byte %d: device %s, oracle %s" % (bad, wire[bad:bad + 16].hex(), self.wire[bad:bad + 16].hex()))
+        same(wire, self.wire, "wire")
         return got
 
     def arena_slices(self, got):
@@ -464,30 +459,20 @@ def deframe_case(case, shape):
     """-> (slices, the oracle's events for them)"""
     msgs, max_frame = DEFRAME_CASES[case]
     sl = slice_list(case, shape)
-    return sl, oracle_events(sl, streams_of(msgs), max_frame)
+    return sl, expected_events(sl, streams_of(msgs), max_frame)
 
 
-def oracle_events(slices, ids, max_frame, parser=None):
-    p = parser or pyorc.H2Parser(expect_client_prefix=False, max_frame_size=max_frame)
-    if parser is None:
-        for sid in ids:
-            assert p.open_stream(sid) == 0
-    out = []
-    for i, s in enumerate(slices):
-        rc, ev = p.feed(s, cap=min(2 * len(s) + 64, 4096))  # (the default is two events per byte: gigabytes at 16 MiB)
-        assert rc == 0
-        out += [(k, a, b, c, d, i) for k, a, b, c, d in ev]
-    return out
+def expected_events(slices, ids, max_frame, parser=None):
+    p = parser or oracle_parser(False, max_frame, ids)
+    # (the default cap is two events per byte: gigabytes at 16 MiB)
+    rc, ev = oracle_feed(p, slices, cap=lambda s: min(2 * len(s) + 64, 4096))
+    assert rc == 0
+    return ev
 
 
 def pack(slices, odd):
     """the slices in one arena, 16-byte packed or at odd offsets with filler between them -> (arena, [(offset, len)])"""
-    arena, table = bytearray(), []
-    for k, s in enumerate(slices):
-        arena += b"\xee" * (1 + (5 * k) % 15) if odd else bytes((-len(arena)) % 16)
-        table.append((len(arena), len(s)))
-        arena += s
-    return bytes(arena) + bytes(64), table
+    return pack_slices(slices, STEPPED if odd else UNPADDED)
 
 
 def device_events(g, buf, table, ids, max_frame, cap, **kw):
@@ -503,10 +488,7 @@ def device_events(g, buf, table, ids, max_frame, cap, **kw):
 
 
 def assert_events(got, exp):
-    assert len(got) == len(exp)
-    if got != exp:
-        bad = next(i for i in range(len(got)) if got[i] != exp[i])
-        raise AssertionError("event %d: device %r, oracle %r" % (bad, got[bad], exp[bad]))
+    same(got, exp, "events")
 
 
 PACKINGS = [False, True]
@@ -575,7 +557,7 @@ def test_deframe_chunked_and_merged(gpu, odd):
         _, wire, lens = oracle_framing(msgs, max_frame)
         sl = ([frame(1, 4, ID_B, b"\x82")] if k == 0 else []) + cut(wire, lens)
         assert k != 1 or len(sl) >= 2048
-        exp = oracle_events(sl, (), max_frame, parser=o)
+        exp = expected_events(sl, (), max_frame, parser=o)
         arena, table = pack(sl, odd)
         buf = gpu.DeviceBuffer(data=arena)
         err, ev = p.deframe(buf.ptr, table, cap=8 * len(sl) + 4096)
@@ -622,7 +604,7 @@ def test_reply_on_big_ids_at_64k_frames(gpu):
 
 
 def test_window_updates_carry_the_four_id_bytes(gpu):
-    """k_h2_fc_emit: WINDOW_UPDATE frames for big-id streams, against the model of tests/test_zz_gpu_h2_flow.py (FH.feed
+    """k_h2_fc_emit: WINDOW_UPDATE frames for big-id streams, against the model of tests/h2_flow_model.py (FH.feed
     compares slices, wire and counters exactly)."""
     ids = (ID_A, ID_B, ID_E, ID_C)
     h = FH(gpu, streams=ids, stream_window=1 << 20, conn_window=1 << 24, conn_threshold=0)
@@ -640,7 +622,7 @@ BIG_OF = {1: ID_A, 3: ID_B, 5: ID_E, 7: ID_C, 9: 0x40000001, 2: 0x01020304, 4: 0
 
 def test_group_pipe_step_on_big_ids(gpu, monkeypatch):
     """k_h2_frame_links and k_h2_deframe_links share the bodies above: one step of the four-link group pipe of
-    tests/test_zz_gpu_h2_links.py with the tables' stream ids replaced by big ones; slice tables, wire, delivered
+    tests/h2_device_lib.py (Links) with the tables' stream ids replaced by big ones; slice tables, wire, delivered
     bytes and events per link against the oracle."""
     from grpc_rdma_amd import h2dev
     monkeypatch.setenv("GRDMA_H2_PIPE_FUSED", "1")

@@ -1,10 +1,8 @@
 """Receive flow control on the device: the window ledger (grdma_h2_fc, csrc/grdma_h2_fc.h).
-The expected values come from the model below: the rules of include/grdma_amd.h applied to the ORACLE's event list
-(oracle/pyorc.H2Parser.feed), struct.pack for the frames and the 23-byte cut for the slices.  "Delivered to the
-stream's data parser" is what the deframer does (parsing.cc init_data_frame_parser): status 0 on a stream that is in
-the map and open for reads -- the model keeps that set itself, from the streams the test opened and the oracle's
-STREAM_OPEN / STREAM_CLOSED events.  Nothing of the library's own events or output goes into the model; every
-comparison is exact."""
+The expected values come from the Model of tests/h2_flow_model.py: the rules of include/grdma_amd.h applied to the
+ORACLE's event list (oracle/pyorc.H2Parser.feed), struct.pack for the frames and the 23-byte cut for the slices.
+Nothing of the library's own events or output goes into the model; every comparison is exact (FH of
+tests/h2_device_lib.py runs a call on the device and in the model and compares)."""
 import os
 import struct
 
@@ -12,163 +10,12 @@ import pytest
 
 from oracle import pyorc
 from oracle.pyorc import EV_FRAME, EV_STREAM_CLOSED, EV_STREAM_OPEN
-from tests.h2_asm_model import oracle_calls
-from tests.h2_helpers import PREFACE, frame, grpc_msg
-from tests.test_gpu_h2 import device_bytes, read_slices
+from tests.h2_device_lib import (FH, FLOW_SIZES as SIZES, Echo, _back_job, _interleaved, _pipe_setup, _server_call,
+                                 fast_sender_slices, pack_slices)
+from tests.h2_flow_model import CONN, LOST, STREAM, Model
+from tests.h2_helpers import frame, grpc_msg
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = 0x5A
-MAX_INC = (1 << 31) - 1
-CONN, STREAM, LOST = 1, 2, 4
-
-
-class Model:
-    def __init__(self, stream_window, conn_window, conn_threshold, max_updates, streams=()):
-        self.sw, self.cw, self.thr, self.maxu = stream_window, conn_window, conn_threshold, max_updates
-        self.live = set(streams)
-        self.announced = conn_window
-        self.lost = False
-        self.stats = dict(calls=0, conn_bytes=0, stream_bytes=0, frames=0, conn_overflows=0, stream_overflows=0)
-
-    def lost_call(self):
-        self.lost = True
-        return [], (0, 0, 0, 0, 0, LOST, 0, 2), b""
-
-    def call(self, events, err, slices_cap, hdr_cap):
-        """-> (slice lengths, result tuple, wire)"""
-        D, S, closed = 0, {}, set()
-        for e in events:
-            k, a, b, c, d = e[:5]
-            if k == EV_FRAME and a == 0:
-                D += d
-                if (b >> 8) == 0 and c in self.live:
-                    S[c] = S.get(c, 0) + d  # (insertion order: the order of the first counted frame)
-            elif k == EV_STREAM_OPEN:
-                self.live.add(c)
-            elif k == EV_STREAM_CLOSED:
-                self.live.discard(c)
-                closed.add(c)
-        viol = CONN if D > 0 and D > self.announced else 0
-        self.announced -= D
-        violators = [s for s, n in S.items() if n > self.sw]
-        if violators:
-            viol |= STREAM
-        frames = []
-        pending = self.cw - self.announced
-        if not err and pending > 0 and pending >= self.thr:
-            inc = min(pending, MAX_INC)
-            frames.append((0, inc))
-            self.announced += inc
-        if not err:
-            frames += [(s, min(n, MAX_INC)) for s, n in S.items() if n > 0 and s not in closed]
-        credited = sum(inc for s, inc in frames if s)
-        wire = b"".join(struct.pack(">BHBBII", 0, 4, 8, 0, s, inc) for s, inc in frames)
-        lens = [min(23, len(wire) - o) for o in range(0, len(wire), 23)]
-        over = len(frames) > self.maxu or len(lens) > slices_cap or 32 * len(lens) > hdr_cap
-        st = self.stats
-        st["calls"] += 1
-        st["conn_bytes"] += D
-        st["conn_overflows"] += 1 if viol & CONN else 0
-        st["stream_overflows"] += len(violators)
-        if not over:
-            st["stream_bytes"] += credited
-            st["frames"] += len(frames)
-        res = (len(frames), len(lens), len(wire), D, credited, viol | (LOST if self.lost else 0),
-               violators[0] if violators else 0, 1 if over else 0)
-        self.frames = frames
-        return lens, res, wire
-
-
-def _table(slices):
-    arena, table = bytearray(), []
-    for s in slices:
-        table.append((len(arena), len(s)))
-        arena += s + bytes((-len(s)) % 16)
-    return bytes(arena) + bytes(64), table
-
-
-class FH:
-    """a device parser with its ledger, the oracle's parser and the model beside them"""
-
-    def __init__(self, g, prefix=False, streams=(), stream_window=65535, conn_window=65535, conn_threshold=0,
-                 max_updates=64, cap=None, chunks=None, boundary_step=None, table_slots=0):
-        from grpc_rdma_amd import h2dev
-        self.g, self.h2dev = g, h2dev
-        self.parser = h2dev.Parser(prefix, chunks=chunks, boundary_step=boundary_step, table_slots=table_slots)
-        if streams:
-            assert self.parser.open_streams(streams) == 0
-        self.prefix, self.streams = prefix, tuple(streams)
-        self.fc = h2dev.FlowControl(self.parser, stream_window=stream_window, conn_window=conn_window,
-                                    conn_threshold=conn_threshold, max_updates=max_updates)
-        self.model = Model(stream_window, conn_window, conn_threshold, max_updates, streams)
-        self.cap = cap if cap is not None else (13 * max_updates + 22) // 23
-        self.calls = []
-        self.new_target()
-
-    def new_target(self):
-        self.slices = self.g.DeviceBuffer(data=bytes([SENTINEL]) * (16 * (self.cap + 4)))
-        self.hdr = self.g.DeviceBuffer(data=bytes([SENTINEL]) * (32 * (self.cap + 4)))
-
-    def deframe(self, slices, ev_cap=None):
-        data, table = _table(slices)
-        self.buf = self.g.DeviceBuffer(data=data)
-        self.calls.append(slices)
-        return self.parser.deframe(self.buf.ptr, table, cap=ev_cap or 8 * len(slices) + 4096)
-
-    def oracle(self):
-        return oracle_calls(self.calls, self.prefix, self.streams)[-1]
-
-    def account(self, cap=None, hdr_cap=None):
-        """account the last deframing on the device and in the model, compare, -> (result, wire)"""
-        cap = self.cap if cap is None else cap
-        hdr_cap = 32 * cap if hdr_cap is None else hdr_cap
-        err_o, ev_o = self.oracle()
-        lens, res, wire = self.model.call(ev_o, err_o, cap, hdr_cap)
-        if res[7]:
-            with pytest.raises(self.g.GrdmaError, match="error 5"):
-                self.fc.account(self.slices.ptr, cap, self.hdr.ptr, hdr_cap)
-            assert self.fc.last_result == res
-            # nothing was written
-            assert self.slices.read() == bytes([SENTINEL]) * self.slices.nbytes
-            assert self.hdr.read() == bytes([SENTINEL]) * self.hdr.nbytes
-        else:
-            sl, got, got_wire = self.fc.account(self.slices.ptr, cap, self.hdr.ptr, hdr_cap)
-            print("ledger: %r -> %r" % (res, got))
-            assert got == res
-            assert [n for _, n in sl] == lens
-            assert [p for p, _ in sl] == [self.hdr.ptr + 32 * k for k in range(len(sl))]
-            assert got_wire == wire
-            assert read_slices(self.g, self.slices, len(sl)) == sl
-        self.check_stats()
-        return res, wire
-
-    def check_stats(self):
-        st = self.fc.stats()
-        assert {k: st[k] for k in self.model.stats} == self.model.stats, st
-        assert st["announced"] == self.model.announced and st["lost"] == self.model.lost
-
-    def feed(self, slices, **kw):
-        err, ev = self.deframe(slices)
-        err_o, ev_o = self.oracle()
-        assert (err, ev) == (err_o, ev_o)
-        return self.account(**kw)
-
-    def close(self):
-        self.fc.close()
-        self.parser.close()
-
-
-def _interleaved(seed, sids, sizes):
-    """DATA frames of mixed sizes, the streams interleaved"""
-    out = []
-    for i, n in enumerate(sizes):
-        sid = sids[(i * 7 + seed) % len(sids)]
-        out.append(frame(0, 0, sid, bytes((i + j) % 251 for j in range(n))))
-    return out
-
-
-SIZES = [5, 1000, 16384, 0, 300, 9000, 1, 16384, 77, 4000, 0, 12000]
 
 
 def test_client_side_windows_never_binding(gpu):
@@ -199,20 +46,9 @@ def test_client_side_threshold_zero_and_half(gpu):
     h.close()
 
 
-def _server_open(sids):
-    return [PREFACE + frame(4, 0, 0)] + [frame(1, 4, s, b"\x82\x86") for s in sids]
-
-
 def test_server_side(gpu):
     h = FH(gpu, prefix=True, stream_window=1 << 20, conn_window=1 << 22, conn_threshold=0)
-    big = grpc_msg(b"q" * 9000)
-    res, _ = h.feed(_server_open((1, 3, 5)) + [
-        frame(0, 0, 1, grpc_msg(b"a" * 100)), frame(0, 0, 3, grpc_msg(b"b" * 3000)),
-        frame(0, 1, 1, grpc_msg(b"c" * 50)),                       # END_STREAM: no frame for 1, its bytes in the connection's
-        frame(0, 0, 5, big[:4000]), frame(3, 0, 5, (8).to_bytes(4, "big")),   # RST_STREAM mid-call
-        frame(0, 0, 5, b"x" * 10),                                 # ... and DATA behind it: connection only
-        frame(0, 0, 99, b"y" * 700),                               # an unknown stream: connection only
-        frame(0, 0, 3, b"")])
+    res, _ = h.feed(_server_call())
     assert h.model.frames == [(0, 105 + 3005 + 55 + 4000 + 10 + 700), (3, 3005)]
     # a DATA frame whose payload is split across two calls counts once, in the first
     whole = frame(0, 0, 3, grpc_msg(b"z" * 5000))
@@ -297,13 +133,13 @@ def test_round_trip(gpu):
     assert rc == 0 and [(e[1], e[3], e[4]) for e in ev if e[0] == EV_FRAME] == [(8, s, 4) for s in want]
     back = h2dev.Parser(False)
     assert back.open_streams([1, 3, 5]) == 0
-    data, table = _table([wire[:23], wire[23:46], wire[46:]])
+    data, table = pack_slices([wire[:23], wire[23:46], wire[46:]])
     buf = gpu.DeviceBuffer(data=data)
     err, ev = back.deframe(buf.ptr, table)
     assert err == 0 and [(e[1], e[3], e[4]) for e in ev if e[0] == EV_FRAME] == [(8, s, 4) for s in want]
     # the check looks at our bytes and not past them: a frame of length 5 is refused
     bad = struct.pack(">BHBBII", 0, 5, 8, 0, 1, 100)
-    data, table = _table([bad])
+    data, table = pack_slices([bad])
     buf = gpu.DeviceBuffer(data=data)
     err, _ = back.deframe(buf.ptr, table)
     assert err == 16
@@ -314,7 +150,7 @@ def test_round_trip(gpu):
 def test_with_the_assembler(gpu):
     from grpc_rdma_amd import h2dev
     slices = [frame(0, 0, 1, grpc_msg(b"a" * 3000)), frame(0, 0, 3, grpc_msg(b"b" * 10)), frame(0, 0, 1, grpc_msg(b""))]
-    data, table = _table(slices)
+    data, table = pack_slices(slices)
     buf = gpu.DeviceBuffer(data=data)
     runs = []
     for with_ledger in (False, True):
@@ -327,7 +163,7 @@ def test_with_the_assembler(gpu):
         err, msgs, ev = parser.deframe_messages(buf.ptr, table, a, want_events=True)
         runs.append((err, [tuple(m) for m in msgs], ev))
         if h:
-            h.calls.append(slices)
+            h.told(slices)
             res, _ = h.account()
             assert res[0] == 3 and res[3] == 3005 + 15 + 5
             with pytest.raises(gpu.GrdmaError, match="accounted already"):
@@ -344,7 +180,6 @@ def test_with_the_assembler(gpu):
 def test_in_a_pipe(gpu, fused):
     g = gpu
     from grpc_rdma_amd import h2dev, stream as gs
-    from tests.test_zz_gpu_h2_messages import _pipe_setup
     sizes = [70000, 1, 16379, 0, 20000, 5000]
     bodies = [bytes((j * 7 + i) % 251 for j in range(n)) for i, n in enumerate(sizes)]
     wire, _ = pyorc.h2_frame_batch(bodies, [1] * len(sizes), [0] * len(sizes), 16384)
@@ -412,7 +247,6 @@ def test_in_a_pipe(gpu, fused):
 
 
 def test_chunked_deframer_path(gpu):
-    from tests.test_zz_gpu_h2_chunks import fast_sender_slices
     warm = [frame(1, 4, 1, b"\x82")] + fast_sender_slices([100000] * 3)
     body = fast_sender_slices([100000] * 170, seed=1)
     assert len(body) >= 2048
@@ -439,7 +273,7 @@ def test_refusals_and_lifetime(gpu):
     t = g.DeviceBuffer(nbytes=1024)
     with pytest.raises(g.GrdmaError, match="deframed nothing yet"):
         fc.account(t.ptr, 4, t.ptr + 256, 128)
-    data, table = _table([frame(0, 0, 1, b"abc")])
+    data, table = pack_slices([frame(0, 0, 1, b"abc")])
     buf = g.DeviceBuffer(data=data)
     parser.deframe(buf.ptr, table)
     with pytest.raises(g.GrdmaError, match="misaligned"):
@@ -472,7 +306,6 @@ def test_refusals_and_lifetime(gpu):
 def test_group_pipes_refuse_a_ledger(gpu):
     g = gpu
     from grpc_rdma_amd import h2dev, stream as gs
-    from tests.test_zz_gpu_h2_messages import _pipe_setup
     parser = h2dev.Parser(False)
     assert parser.open_streams([1]) == 0
     (pipe,), (job,), keep = _pipe_setup(g, h2dev, gs, [100, 5000], 1, parser)
@@ -496,7 +329,6 @@ def test_group_pipes_refuse_a_ledger(gpu):
 def test_a_ledger_attached_elsewhere_is_refused(gpu):
     g = gpu
     from grpc_rdma_amd import h2dev, stream as gs
-    from tests.test_zz_gpu_h2_messages import _pipe_setup
     parser = h2dev.Parser(False)
     assert parser.open_streams([1]) == 0
     pipes, jobs, keep = _pipe_setup(g, h2dev, gs, [100, 5000], 2, parser)
@@ -521,8 +353,6 @@ def test_a_ledger_attached_elsewhere_is_refused(gpu):
 def test_a_reply_pipe_refuses_a_ledger(gpu):
     g = gpu
     from grpc_rdma_amd import h2dev, stream as gs
-    from tests.test_zz_gpu_h2_messages import _pipe_setup
-    from tests.test_zz_gpu_h2_reply import _back_job
     sizes = [3000, 0, 100]
     bodies = [bytes((j * 7 + i) % 251 for j in range(n)) for i, n in enumerate(sizes)]
     parser = h2dev.Parser(False)
@@ -556,7 +386,6 @@ def test_a_reply_pipe_refuses_a_ledger(gpu):
 
 def test_a_group_reply_pipe_refuses_a_ledger(gpu):
     from grpc_rdma_amd import h2dev
-    from tests.test_zz_gpu_h2_links_reply import Echo
     E = Echo(gpu)
     fc = h2dev.FlowControl(E.parsers_back[1])
     with pytest.raises(gpu.GrdmaError, match="ledger"):

@@ -1,5 +1,5 @@
 """Receive flow control on many links: grdma_h2_fc_account_batch (the five k_h2_links_fc_* kernels over a table of ledgers)
-and the group pipe with ledgers attached.  Expected values come from the Model of tests/test_zz_gpu_h2_flow.py -- the rules
+and the group pipe with ledgers attached.  Expected values come from the Model of tests/h2_flow_model.py -- the rules
 of include/grdma_amd.h applied to the ORACLE's event list -- with struct.pack for the frames and the 23-byte cut for the
 slices; nothing of the library's own events or output goes into it, and every comparison is exact.  The cases are small
 enough for the wave emulator (tests/test_h2_links_flow_emu.py)."""
@@ -8,11 +8,10 @@ import random
 import pytest
 
 from oracle import pyorc
+from tests.h2_device_lib import (FH, FLOW_SIZES as SIZES, Echo, LinkAsm, Links, _check_steps, _interleaved,  # noqa: F401
+                                 _pipe_setup, _server_call, fused, oracle_parser, pack_slices, read_slices, step_events)
+from tests.h2_flow_model import CONN, LOST, STREAM, Model
 from tests.h2_helpers import frame, grpc_msg
-from tests.test_gpu_h2 import read_slices
-from tests.test_zz_gpu_h2_flow import CONN, FH, LOST, SENTINEL, SIZES, STREAM, Model, _interleaved, _server_open
-from tests.test_zz_gpu_h2_links import TABLES, Links, _check_steps, fused  # noqa: F401  (fused is a fixture)
-from tests.test_zz_gpu_h2_links_messages import LinkAsm
 
 pytestmark = pytest.mark.gpu
 
@@ -46,36 +45,9 @@ def _batch(g, hs, order, lost=()):
         print("ledger %d: %r -> %r" % (i, res, got[k]))
         if res[7]:
             assert got[k] == (res, None), i
-            assert h.fc.last_result == res
-            # nothing of the item was written
-            assert h.slices.read() == bytes([SENTINEL]) * h.slices.nbytes, i
-            assert h.hdr.read() == bytes([SENTINEL]) * h.hdr.nbytes, i
-        else:
-            sl, r, w = got[k]
-            assert r == res, i
-            assert [n for _, n in sl] == lens, i
-            assert [p for p, _ in sl] == [h.hdr.ptr + 32 * j for j in range(len(sl))], i
-            assert w == wire, i
-            assert read_slices(g, h.slices, len(sl)) == sl, i
-        h.check_stats()
+        h.check_accounted((lens, res, wire), None if res[7] else got[k], "ledger %d" % i)
         out[i] = (res, wire)
     return out
-
-
-def _deframe_checked(h, slices, ev_cap=None):
-    err, ev = h.deframe(slices, ev_cap=ev_cap)
-    assert (err, ev) == h.oracle()
-    return err, ev
-
-
-def _server_call():
-    big = grpc_msg(b"q" * 9000)
-    return _server_open((1, 3, 5)) + [
-        frame(0, 0, 1, grpc_msg(b"a" * 100)), frame(0, 0, 3, grpc_msg(b"b" * 3000)),
-        frame(0, 1, 1, grpc_msg(b"c" * 50)),                                  # END_STREAM
-        frame(0, 0, 5, big[:4000]), frame(3, 0, 5, (8).to_bytes(4, "big")),   # RST_STREAM mid-call
-        frame(0, 0, 5, b"x" * 10), frame(0, 0, 99, b"y" * 700),               # behind it, and an unknown id: connection only
-        frame(0, 0, 3, b"")]
 
 
 NINE = [
@@ -119,7 +91,7 @@ def test_batch_equals_the_model_per_transport(gpu):
     outs = []
     for call in (0, 1):
         for h, slices in zip(hs, _nine_calls(call)):
-            _deframe_checked(h, slices)
+            h.deframe_checked(slices)
         outs.append(_batch(gpu, hs, order))
     first, second = outs
     assert hs[0].model.frames[0][0] == 0 and sorted(s for s, _ in hs[0].model.frames) == [0, 1, 3, 5]
@@ -169,12 +141,12 @@ def test_trouble_stays_with_its_link(gpu):
           FH(gpu, streams=(1, 3, 5), stream_window=1 << 20, conn_window=1 << 24)]                  # 4 nothing wrong
     with pytest.raises(gpu.GrdmaError, match="error 5"):
         hs[0].deframe([frame(0, 0, 1, b"b" * 10)] * 40, ev_cap=16)
-    err, _ = _deframe_checked(hs[1], [frame(0, 0, 1, b"a" * 500), frame(0, 0, 3, b"b" * 70), frame(6, 0, 0, b"short"),
+    err, _ = hs[1].deframe_checked([frame(0, 0, 1, b"a" * 500), frame(0, 0, 3, b"b" * 70), frame(6, 0, 0, b"short"),
                                       frame(0, 0, 1, b"never parsed")])
     assert err == 15
-    _deframe_checked(hs[2], four)
-    _deframe_checked(hs[3], [frame(0, 0, 3, b"c" * 100)] + [frame(0, 0, 1, b"a" * 16384)] * 5)
-    _deframe_checked(hs[4], _interleaved(0, (1, 3, 5), SIZES))
+    hs[2].deframe_checked(four)
+    hs[3].deframe_checked([frame(0, 0, 3, b"c" * 100)] + [frame(0, 0, 1, b"a" * 16384)] * 5)
+    hs[4].deframe_checked(_interleaved(0, (1, 3, 5), SIZES))
     out = _batch(gpu, hs, [3, 0, 4, 2, 1], lost={0})
     assert out[0][0] == (0, 0, 0, 0, 0, LOST, 0, 2)
     assert out[1][0] == (0, 0, 0, 570, 0, 0, 0, 0)
@@ -184,7 +156,7 @@ def test_trouble_stays_with_its_link(gpu):
     # a second call: the lost flag is sticky on its link alone, the cap overflow is gone, the others go on
     for h, slices in zip(hs, ([frame(0, 0, 1, b"d" * 9)], None, four[:2], [frame(0, 0, 3, b"e" * 50)], _interleaved(1, (1, 3, 5), SIZES[:5]))):
         if slices is not None:
-            _deframe_checked(h, slices)
+            h.deframe_checked(slices)
     ok = [0, 2, 3, 4]   # (the dead connection has deframed nothing new: it stays out)
     sub = [hs[i] for i in ok]
     out = _batch(gpu, sub, [2, 1, 3, 0])
@@ -205,9 +177,9 @@ def _three(gpu, middle_kw, slices, more_than):
     three = [frame(0, 0, 1, b"a" * 10), frame(0, 0, 3, b"b" * 20), frame(0, 0, 1, b"c" * 30)]
     hs = [FH(gpu, streams=(1, 3), stream_window=1 << 20, conn_window=1 << 20), FH(gpu, **middle_kw),
           FH(gpu, streams=(1, 3), stream_window=1 << 20, conn_window=1 << 20)]
-    _deframe_checked(hs[0], three)
-    _, ev = _deframe_checked(hs[1], slices, ev_cap=1 << 16)
-    _deframe_checked(hs[2], three)
+    hs[0].deframe_checked(three)
+    _, ev = hs[1].deframe_checked(slices, ev_cap=1 << 16)
+    hs[2].deframe_checked(three)
     assert len(hs[1].oracle()[1]) > more_than and len(ev) > more_than
     out = _batch(gpu, hs, [0, 1, 2])
     assert out[0] == out[2] and out[0][0][0] == 3 and out[0][0][3] == 60
@@ -221,7 +193,7 @@ def test_grid_stride_inside_a_share(gpu):
                      _small_frames(rng, WRAP8, 900), 8 * 256)
     assert out[1][0][0] == 9 and out[1][0][5] == 0 and out[1][0][7] == 0 and out[1][0][3] == out[1][0][4]
     # (the scratch table is cleared between calls)
-    _deframe_checked(hs[1], _small_frames(rng, WRAP8, 60))
+    hs[1].deframe_checked(_small_frames(rng, WRAP8, 60))
     assert _batch(gpu, hs[1:2], [0])[0][0][0] == 9
     for h in hs:
         h.close()
@@ -251,21 +223,15 @@ class LinkLedger:
     def __init__(self, L, li, parser):
         from grpc_rdma_amd import h2dev
         self.li, kw = li, LEDGERS[li]
-        sids = sorted({s for _, s, _ in TABLES[li]})
+        sids = L.streams(li)
         self.fc = h2dev.FlowControl(parser, **kw)
         self.model = Model(kw["stream_window"], kw["conn_window"], kw["conn_threshold"], kw["max_updates"], sids)
         self.cap = (13 * kw["max_updates"] + 22) // 23
-        self.orc = pyorc.H2Parser(expect_client_prefix=False, max_frame_size=L.max_frame)
-        for s in sids:
-            assert self.orc.open_stream(s) == 0
+        self.orc = oracle_parser(False, L.max_frame, sids)
 
     def check_step(self, L, got, what):
         """got = the group pipe's window_updates of this link for the step that just ended"""
-        ev = []
-        for s in L.delivered(self.li):
-            rc, e = self.orc.feed(s)
-            assert rc == 0
-            ev += e
+        ev = step_events(self.orc, L.delivered(self.li), what)
         lens, res, wire = self.model.call(ev, 0, self.cap, 32 * self.cap)
         sl, r, w = got
         print("link %d step %r: %r -> %r" % (self.li, what, res, r))
@@ -374,13 +340,10 @@ def test_group_pipe_with_ledgers_and_assemblers(gpu, fused, asm_first):
 def test_refusals_and_lifetime(gpu, monkeypatch):
     from grpc_rdma_amd import h2dev, stream as gs
     from grpc_rdma_amd._lib import GrdmaError
-    from tests.test_zz_gpu_h2_flow import _table
-    from tests.test_zz_gpu_h2_links_reply import Echo
-    from tests.test_zz_gpu_h2_messages import _pipe_setup
     monkeypatch.delenv("GRDMA_H2_PIPE_FUSED", raising=False)
     g = gpu
     t = g.DeviceBuffer(nbytes=4096)
-    data, table = _table([frame(0, 0, 1, b"abc")])
+    data, table = pack_slices([frame(0, 0, 1, b"abc")])
     buf = g.DeviceBuffer(data=data)
     lib = h2dev._bind()
 

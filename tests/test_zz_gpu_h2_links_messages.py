@@ -9,18 +9,17 @@ import pytest
 
 from oracle import pyorc
 from tests.h2_asm_model import AsmModel, OK, TOO_LARGE, NO_SPACE, TRUNCATED
+from tests.h2_device_lib import (ERR_CAPACITY, SENTINEL, LinkAsm, Links, Transport, _check_steps, _client_stream,  # noqa: F401
+                                 _eight_transports, cut_points, fused)
 from tests.h2_helpers import frame, grpc_msg
-from tests.test_zz_gpu_h2_links import (ERR_CAPACITY, TABLES, Links, Transport, _check_steps, _client_stream, _cut,  # noqa: F401
-                                        _eight_transports, fused)
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
 ALL = 1 << 63  # a release count above anything reported: everything
 
 
 class MT:
-    """a Transport of tests/test_zz_gpu_h2_links.py with a device assembler over an arena of its own and the model
+    """a Transport of tests/h2_device_lib.py with a device assembler over an arena of its own and the model
     beside it"""
 
     def __init__(self, g, t, arena_bytes=1 << 20, max_msg=4 << 20, max_pending=4096):
@@ -113,7 +112,7 @@ def test_batch_equals_the_single_call(gpu):
         (16385).to_bytes(3, "big") + bytes([0, 0]) + (1).to_bytes(4, "big") + bytes(100)
     wires = [_client_stream(21, [1], 4), bad, _client_stream(22, [1, 3], 5)]
     streams = [[1], [1], [1, 3]]
-    lists = [_cut(w, rng, k) for w, k in zip(wires, (6, 3, 9))]
+    lists = [cut_points(w, rng, k) for w, k in zip(wires, (6, 3, 9))]
     batch = [MT(gpu, Transport(gpu, "b%d" % i, False, l, streams=s)) for i, (l, s) in enumerate(zip(lists, streams))]
     single = [MT(gpu, Transport(gpu, "s%d" % i, False, l, streams=s)) for i, (l, s) in enumerate(zip(lists, streams))]
     got = _run(batch, lists)
@@ -138,7 +137,7 @@ def _trouble(g, tag):
     whole = lambda sid, b: frame(0, 0, sid, grpc_msg(b))  # noqa: E731
     rng = random.Random(9)
     return [
-        MT(g, Transport(g, "good" + tag, False, _cut(_client_stream(3, [1, 3], 7), rng, 9), streams=[1, 3])),
+        MT(g, Transport(g, "good" + tag, False, cut_points(_client_stream(3, [1, 3], 7), rng, 9), streams=[1, 3])),
         # 2 KiB of ring: the second message does not fit behind the first, nor does anything after it
         MT(g, Transport(g, "small-arena" + tag, False, [whole(1, b"x" * 1000), whole(1, b"y" * 1500), whole(1, b"z" * 10)],
                         streams=[1]), arena_bytes=2048),
@@ -149,7 +148,7 @@ def _trouble(g, tag):
         MT(g, Transport(g, "conn-error" + tag, False, [frame(0, 0, 7, m[:3000]),
                                                       (20000).to_bytes(3, "big") + bytes([0, 0]) + (7).to_bytes(4, "big")],
                         streams=[7])),
-        MT(g, Transport(g, "small-cap" + tag, False, _cut(_client_stream(4, [5], 5), rng, 3), streams=[5])),
+        MT(g, Transport(g, "small-cap" + tag, False, cut_points(_client_stream(4, [5], 5), rng, 3), streams=[5])),
     ]
 
 
@@ -161,7 +160,7 @@ def test_trouble_stays_with_its_link(gpu):
     for i, m in enumerate(mts):
         exp = m.expect(lists[i])
         if m.name == "small-cap":
-            assert len(exp[1]) > 3 and got[i][1] == ERR_CAPACITY and got[i][2] == ERR_CAPACITY
+            assert len(exp[1]) > 3 and got[i][1] == -ERR_CAPACITY and got[i][2] == -ERR_CAPACITY
             continue
         m.check(got[i], exp, m.name)
         seen |= {d[4] for d, _ in exp[2]}
@@ -208,40 +207,6 @@ def test_ring_pressure_over_many_calls(gpu):
 
 
 # ---- the group pipe with assemblers ----------------------------------------------------------------------------------
-class LinkAsm:
-    """per listed link: a device assembler, the model, an oracle parser of its own (the events the model is fed) and the
-    streams that have closed so far"""
-
-    def __init__(self, L, li, parser):
-        from grpc_rdma_amd import h2dev
-        self.li = li
-        self.arena = L.g.DeviceBuffer(data=bytes([SENTINEL]) * (1 << 20))
-        self.asm = h2dev.Assembler(parser, self.arena)
-        self.model = AsmModel(1 << 20)
-        self.orc = pyorc.H2Parser(expect_client_prefix=False, max_frame_size=L.max_frame)
-        for s in sorted({s for _, s, _ in TABLES[li]}):
-            assert self.orc.open_stream(s) == 0
-        self.closed = set()
-
-    def check_step(self, L, msgs, what):
-        """msgs = the group pipe's descriptors of this link for the step that just ended"""
-        got = L.delivered(self.li)
-        ev = []
-        for k, s in enumerate(got):
-            rc, e = self.orc.feed(s)
-            assert rc == 0
-            ev += [(kk, a, b, c, d, k) for kk, a, b, c, d in e]
-        self.model.release()   # (a step first releases everything reported before it)
-        exp = self.model.call(ev, got, 0)
-        assert [tuple(m) for m in msgs] == [d for d, _ in exp], what
-        assert all(m.status == OK for m in msgs), what
-        # the bodies that were framed, on the streams still open when the step began
-        framed = [(s, b) for (_, s, _), b in zip(TABLES[self.li], L.bodies[self.li]) if s not in self.closed]
-        assert [(m.stream_id, self.asm.view(m)) for m in msgs] == framed, what
-        assert [b for _, b in exp] == [b for _, b in framed], what
-        self.closed |= {e[3] for e in ev if e[0] == pyorc.EV_STREAM_CLOSED}
-
-
 def _group_case(gpu, fused, pipeline, with_asm, steps):
     from grpc_rdma_amd import h2dev
     from grpc_rdma_amd._lib import GrdmaError

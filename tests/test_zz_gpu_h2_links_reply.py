@@ -7,14 +7,10 @@ import ctypes as C
 
 import pytest
 
-from oracle import pyorc
-from tests.h2_asm_model import OK, oracle_calls
+from tests.h2_asm_model import OK
+from tests.h2_device_lib import (BATCHES, ERR_CAPACITY, SENTINEL, BackLinks, Echo, RHarness, Target, _batch, _dropped_slices, _pipe_setup,  # noqa: F401
+                                 check_framed, expected_reply, fused)
 from tests.h2_helpers import frame, grpc_msg
-from tests.test_gpu_h2 import device_bytes
-from tests.test_zz_gpu_h2_links import TABLES, Links, fused  # noqa: F401  (fused is a fixture)
-from tests.test_zz_gpu_h2_links_messages import LinkAsm
-from tests.test_zz_gpu_h2_messages import BATCHES, _batch, _pipe_setup, _slice_table
-from tests.test_zz_gpu_h2_reply import ERR_CAPACITY, SENTINEL, RHarness, Target, expected_reply
 
 pytestmark = pytest.mark.gpu
 
@@ -24,28 +20,16 @@ def _assemble(hs, lists, ev_caps=None):
     from grpc_rdma_amd import h2dev
     items = []
     for h, slices in zip(hs, lists):
-        data, table = _slice_table(slices)
-        buf = h.g.DeviceBuffer(data=data)
+        buf, table = h.pp.upload(slices)
         h.bufs = getattr(h, "bufs", []) + [buf]
         items.append((h.parser, h.asm, buf.ptr, table))
     got = h2dev.deframe_messages_batch(items, ev_caps=ev_caps)
     for h, slices, r in zip(hs, lists, got):
-        h.calls.append(slices)
-        err_o, ev_o = oracle_calls(h.calls, h.prefix, h.streams, h.max_frame)[-1]
-        exp = h.model.call(ev_o, slices, err_o)
-        if r[1] == ERR_CAPACITY:  # (a call the assembler skipped: the model is not asked)
+        _, _, exp = h.expect(slices)
+        if r[1] == -ERR_CAPACITY:  # (a call the assembler skipped: the model is not asked)
             continue
         assert [tuple(m) for m in r[1]] == [d for d, _ in exp]
     return got
-
-
-def _dropped_slices():
-    """the call of test_dropped_descriptors_change_the_layout: empty kept messages behind dropped ones"""
-    part = grpc_msg(b"t" * 800)[:500]
-    return [frame(0, 0, 1, grpc_msg(b"")), frame(0, 0, 1, grpc_msg(b"L" * 2000)), frame(0, 0, 1, grpc_msg(b"a" * 1000, 1)),
-            frame(0, 0, 3, part), frame(3, 0, 3, (8).to_bytes(4, "big")), frame(0, 0, 1, grpc_msg(b"")),
-            frame(0, 0, 1, grpc_msg(b"")), frame(0, 0, 1, grpc_msg(b"b" * 1100)), frame(0, 0, 1, grpc_msg(b"c" * 1000)),
-            frame(0, 0, 1, grpc_msg(b"d" * 10))]
 
 
 # (index into BATCHES or None = the dropped-descriptor call, reply max_frame, routes or None)
@@ -81,13 +65,9 @@ def _close(cases):
 
 
 def _check_item(g, t, n, st, h, mf, routes):
-    wire, lens, counters = expected_reply(h.last, mf, routes)
     print("reply item: %d descriptors -> kept %d, %d slices, %d wire bytes" % (len(h.last), st["kept"], n, st["wire_bytes"]))
     got_lens, got_wire, _ = t.wire(n)
-    assert n == len(lens) == st["slices"] and got_lens == lens
-    assert got_wire == wire and st["wire_bytes"] == len(wire)
-    assert {k: st[k] for k in counters} == counters
-    assert st["overflow"] == 0 and st["hdr_bytes"] <= 32 * n
+    check_framed(n, st, got_lens, got_wire, expected_reply(h.last, mf, routes), "reply item")
     # nothing behind what was framed, nothing behind the caps
     assert t.slices.read()[16 * n:] == bytes([SENTINEL]) * (16 * (t.cap + 4 - n))
     assert t.hdr.read()[32 * t.cap:] == bytes([SENTINEL]) * (32 * 4)
@@ -136,7 +116,7 @@ def test_trouble_stays_with_its_item(gpu):
     hs = [RHarness(gpu, 1 << 20, streams=[1]) for _ in specs]
     lists = [_batch(lens, 16384, 7 + i)[2] if lens is not None else [] for i, (_, lens, _) in enumerate(specs)]
     res = _assemble(hs, lists, ev_caps=[None, None, None, 3, None, None])
-    assert res[3][1] == ERR_CAPACITY and res[4][1] == []
+    assert res[3][1] == -ERR_CAPACITY and res[4][1] == []
     replies = [h2dev.Reply(h.asm, list(r.items()) if r else None, 16384, 3 if name == "max-messages" else 64)
                for h, (name, _, r) in zip(hs, specs)]
     need = [len(expected_reply(h.last, 16384, r)[1]) for h, (_, _, r) in zip(hs, specs)]
@@ -155,7 +135,7 @@ def test_trouble_stays_with_its_item(gpu):
         if name == "empty":
             assert n == 0 and st["overflow"] == 0 and st["kept"] == 0
         else:
-            assert n == ERR_CAPACITY and st["overflow"] == 1, name
+            assert n == -ERR_CAPACITY and st["overflow"] == 1, name
             if name == "slice-cap":
                 assert st["slices"] == need[1]
         assert t.slices.read() == bytes([SENTINEL]) * (16 * (t.cap + 4)), name
@@ -166,143 +146,7 @@ def test_trouble_stays_with_its_item(gpu):
         h.close()
 
 
-# ---- the group reply pipe --------------------------------------------------------------------------------------------
-ROUTES3 = {4: 44}   # link 3: stream 2 ends with its last message of the first step; only stream 4 is sent back
-
-
-class BackLinks:
-    """a MultiStreamJob of len(lens) links, each over a pair of its own, run once over slice lists of the lengths `lens`"""
-
-    def __init__(self, g, lens):
-        from grpc_rdma_amd import stream as gs
-        self.g, self.lens, self.pairs, self.dsts, self.keep, specs = g, lens, [], [], [], []
-        for li, ln in enumerate(lens):
-            a, b = g.Pair(1 << 18, 30), g.Pair(1 << 18, 30)
-            g.connect_pairs(a, b)
-            self.pairs += [a, b]
-            scratch = g.DeviceBuffer(data=bytes((j * 3 + li) % 249 for j in range(max(ln) + 64)))
-            N = sum(ln)
-            scap = 2 * len(ln) + 64 + N // 256
-            dcap = N + 16 * scap + 4096
-            dst = g.DeviceBuffer(nbytes=dcap)
-            specs.append((a, b, [(scratch.ptr, n) for n in ln], dst.ptr, dcap, scap))
-            self.dsts.append((dst, dcap))
-            self.keep.append(scratch)
-        self.job = gs.MultiStreamJob(specs, 256)
-        self.job.set_pipeline(False)
-        r = self.job.run(gs.RUN_EAGER)
-        assert r.done
-        self.job.set_rounds(int(max(r.tx_rounds, r.rx_rounds)) + 2)
-        r = self.job.run(gs.RUN_GRAPH)
-        assert r.done and r.bytes_delivered == sum(sum(x) for x in lens)
-        self.recorded = [len(self.job.delivered_slices(li)) for li in range(len(lens))]
-
-    def close(self):
-        self.job.close()
-        for p in self.pairs:
-            p.close()
-
-
-class Echo:
-    """forward: a Links job with a GroupPipe and an assembler on each of its four links; back: a job of four links with
-    a group reply pipe whose spec i frames what forward link i assembled, back parsers and back assemblers attached"""
-
-    def __init__(self, g):
-        from grpc_rdma_amd import h2dev
-        self.g = g
-        L = self.L = Links(g)
-        self.parsers = [L.parser(li) for li in range(4)]
-        self.gp = h2dev.GroupPipe(L.job, [L.spec(li, self.parsers[li][0]) for li in range(4)])
-        self.las = [LinkAsm(L, li, self.parsers[li][0]) for li in range(4)]
-        self.gp.attach_assemblers([la.asm for la in self.las])
-        self.routes = [None, None, None, ROUTES3]
-        self.replies = [h2dev.Reply(la.asm, list(r.items()) if r else None, 16384, 64) for la, r in zip(self.las, self.routes)]
-        # what comes back per link: the oracle's framing of the kept messages (compressed flag passed through)
-        self.back, self.wire, self.lens = [], [], []
-        for li, tab in enumerate(TABLES):
-            r = self.routes[li]
-            kept = [(b, r[s] if r else s, f & 1) for (_, s, f), b in zip(tab, L.bodies[li]) if r is None or s in r]
-            wire, lens = pyorc.h2_frame_batch([k[0] for k in kept], [k[1] for k in kept], [k[2] for k in kept], 16384)
-            self.back.append(kept)
-            self.wire.append(wire)
-            self.lens.append(lens)
-        assert len(self.back[3]) == 3 and all(len(k) == len(t) for k, t in zip(self.back[:3], TABLES))
-        self.B = BackLinks(g, self.lens)
-        self.parsers_back = []
-        for kept in self.back:
-            p = h2dev.Parser(False, 16384)
-            assert p.open_streams(sorted({s for _, s, _ in kept})) == 0
-            self.parsers_back.append(p)
-        self.rspecs = [(li, self.replies[li], self.parsers_back[li], self.B.recorded[li], 4 * len(self.lens[li]) + 256,
-                        sum(self.lens[li])) for li in range(4)]
-        self.arenas_back = [g.DeviceBuffer(nbytes=1 << 20) for _ in range(4)]
-        self.asms_back = [h2dev.Assembler(p, a) for p, a in zip(self.parsers_back, self.arenas_back)]
-        self.seq_back = [0] * 4
-        self.rp = None
-
-    def advance(self, li, delivered):
-        """link li's oracle parser and model take one step over `delivered` -> the model's descriptors"""
-        la, ev = self.las[li], []
-        for k, s in enumerate(delivered):
-            rc, e = la.orc.feed(s)
-            assert rc == 0
-            ev += [(kk, a, b, c, d, k) for kk, a, b, c, d in e]
-        la.model.release()   # (a step first releases everything reported before it)
-        return [d for d, _ in la.model.call(ev, delivered, 0)]
-
-    def forward_checked(self, what, overwritten=()):
-        """the forward step that was enqueued last has ended: per link the descriptors and bytes equal the model's
-        (overwritten: links whose assembler has taken another pipe's step since -- their models follow unchecked)"""
-        fr = self.gp.sync()
-        for li, la in enumerate(self.las):
-            assert fr[li]["h2_error"] == 0 and fr[li]["frame_overflow"] == 0, (what, li)
-            if li in overwritten:
-                self.advance(li, self.L.delivered(li))
-                continue
-            la.check_step(self.L, self.gp.messages(li), (what, li))
-            step_bytes = sum(((n + 255) // 256) * 256 for n, _, _ in TABLES[li])
-            assert la.asm.stats()["bytes_in_use"] <= step_bytes + max(n for n, _, _ in TABLES[li]), (what, li)
-
-    def back_checked(self, res, li, what):
-        """link li of the reply step that was synced as `res` delivered the forward bodies"""
-        r = res[li]
-        assert r["h2_error"] == 0 and r["frame_overflow"] == 0 and r["framed"] == len(self.lens[li]), (what, li, r)
-        got = self.rp.messages(li)
-        kept = self.back[li]
-        assert [(m.status, m.length, m.stream_id, m.flags) for m in got] == [(OK, len(b), s, f) for b, s, f in kept], (what, li)
-        assert [m.seq for m in got] == list(range(self.seq_back[li], self.seq_back[li] + len(kept))), (what, li)
-        self.seq_back[li] += len(kept)
-        assert [self.asms_back[li].view(m) for m in got] == [b for b, _, _ in kept], (what, li)
-        table = self.rp.slice_table(li)
-        assert [n for _, n in table] == self.lens[li], (what, li)
-        assert b"".join(device_bytes(self.g, p, n) for p, n in table) == self.wire[li], (what, li)
-        return table
-
-    def step(self, what):
-        self.gp.enqueue()
-        self.rp.enqueue()
-        res = self.rp.sync()
-        tables = [self.back_checked(res, li, what) for li in range(4)]
-        self.forward_checked(what)
-        return tables
-
-    def close(self):
-        from grpc_rdma_amd import h2dev
-        if self.rp:
-            self.rp.close()
-        self.gp.close()
-        assert self.gp.h is None
-        assert h2dev.job_hook_counts(self.B.job) == (0, 0) and h2dev.job_hook_counts(self.L.job) == (0, 0)
-        for r in self.replies:
-            r.close()
-        for a in self.asms_back + [la.asm for la in self.las]:
-            a.close()
-        for p in self.parsers_back + [p for p, _ in self.parsers]:
-            p.close()
-        self.B.close()
-        self.L.close()
-
-
+# ---- the group reply pipe (Echo and BackLinks: tests/h2_device_lib.py) ------------------------------------------------
 def test_group_reply_pipe(gpu, fused):
     """Four forward links and four back links, five echo steps; then link 0's parser takes a forward step of another
     shape through a second forward pipe: that spec alone reports frame overflow 2 and keeps its table; then the recorded

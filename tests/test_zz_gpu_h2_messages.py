@@ -8,84 +8,11 @@ import random
 import pytest
 
 from oracle import pyorc
-from tests.h2_asm_model import AsmModel, oracle_calls, OK, TOO_LARGE, NO_SPACE, TRUNCATED
-from tests.h2_helpers import PREFACE, frame, grpc_msg, messages_of
+from tests.h2_asm_model import OK, TOO_LARGE, NO_SPACE, TRUNCATED
+from tests.h2_device_lib import BATCHES, SENTINEL, Harness, _batch, _eight_streams, _pipe_setup, pack_slices
+from tests.h2_helpers import frame, grpc_msg, grpcio_capture, messages_of
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = 0xA5
-
-
-def _slice_table(slices, rng=None):
-    arena, table = bytearray(), []
-    for s in slices:
-        if rng is not None:
-            arena += b"\xee" * rng.randrange(1, 16)
-        table.append((len(arena), len(s)))
-        arena += s + bytes((-len(s)) % 16)
-    return bytes(arena) + bytes(64), table
-
-
-class Harness:
-    """one device parser + assembler and the model beside it; feed() runs one call on both and checks it"""
-
-    def __init__(self, g, arena_bytes, max_msg=4 << 20, max_pending=4096, prefix=False, streams=(), max_frame=16384,
-                 chunks=None, tensor=None, table_slots=0):
-        from grpc_rdma_amd import h2dev
-        self.g, self.h2dev = g, h2dev
-        self.parser = h2dev.Parser(prefix, max_frame, chunks=chunks, table_slots=table_slots)
-        if streams:
-            assert self.parser.open_streams(streams) == 0
-        self.arena = tensor if tensor is not None else g.DeviceBuffer(data=bytes([SENTINEL]) * arena_bytes)
-        self.asm = h2dev.Assembler(self.parser, self.arena, max_msg, max_pending)
-        self.model = AsmModel(arena_bytes, max_msg, max_pending)
-        self.prefix, self.streams, self.max_frame = prefix, streams, max_frame
-        self.calls = []
-
-    def feed(self, slices, rng=None, want_events=False):
-        data, table = _slice_table(slices, rng)
-        buf = self.g.DeviceBuffer(data=data)
-        r = self.parser.deframe_messages(buf.ptr, table, self.asm, want_events=want_events)
-        self.calls.append(slices)
-        err_o, ev_o = oracle_calls(self.calls, self.prefix, self.streams, self.max_frame)[-1]
-        exp = self.model.call(ev_o, slices, err_o)
-        err, got = r[0], r[1]
-        assert (err != 0) == (err_o != 0)
-        assert [tuple(m) for m in got] == [d for d, _ in exp]
-        for m, (_, body) in zip(got, exp):
-            if m.status == OK:
-                v = self.asm.view(m)
-                v = bytes(v.cpu().numpy().tobytes()) if hasattr(v, "cpu") else v
-                assert v == body, "message seq %d" % m.seq
-        if want_events:
-            return got, r[2], ev_o
-        return got
-
-    def release(self, n=None):
-        self.asm.release(n if n is not None else (1 << 63))
-        self.model.release(n)
-
-    def close(self):
-        self.asm.close()
-        self.parser.close()
-
-
-def _batch(lens, max_frame, seed):
-    rng = random.Random(seed)
-    bodies = [(bytes(rng.getrandbits(8) for _ in range(min(n, 4096))) * (n // 4096 + 1))[:n] for n in lens]
-    sids = [1] * len(lens)
-    flags = [rng.randrange(2) for _ in lens]
-    wire, slens = pyorc.h2_frame_batch(bodies, sids, flags, max_frame)
-    slices, o = [], 0
-    for n in slens:
-        slices.append(wire[o:o + n])
-        o += n
-    return bodies, wire, slices
-
-
-BATCHES = [([1 << 20], 16384), ([0], 16384), ([0, 0, 0, 5, 0, 0], 16384), ([3, 70000, 16379, 16380], 16384),
-           ([100, 0, 17], 3), ([9, 1, 0, 0], 1), ([5000] * 40, 1000), ([1048580] * 3, 16384),
-           ([0] * 300 + [7] * 10, 16384), ([20, 0, 21, 22, 0, 0, 23, 24], 5), ([7] * 4200 + [0, 9, 0, 0, 40000], 16384)]
 
 
 @pytest.mark.parametrize("lens,max_frame", BATCHES)
@@ -123,25 +50,6 @@ def test_every_cut_of_a_small_wire(gpu):
         got = h.feed([wire[:cut]]) + h.feed([wire[cut:]])
         assert [h.asm.view(m) for m in got] == bodies
         h.close()
-
-
-def _eight_streams(seed, nmsg=4, calls=5):
-    rng = random.Random(seed)
-    sids = list(range(1, 17, 2))
-    wire = bytearray(PREFACE + frame(4, 0, 0))
-    for s in sids:
-        wire += frame(1, 4, s, b"\x82\x86")
-    queues = {s: b"".join(grpc_msg(bytes(rng.getrandbits(8) for _ in range(rng.choice([0, 10, 3000, 40000]))))
-                          for _ in range(nmsg)) for s in sids}
-    while any(queues.values()):
-        s = rng.choice([s for s in sids if queues[s]])
-        n = rng.randrange(1, 16385)
-        part, queues[s] = queues[s][:n], queues[s][n:]
-        wire += frame(0, 1 if not queues[s] else 0, s, part)
-    wire = bytes(wire)
-    cuts = sorted(rng.sample(range(1, len(wire)), calls - 1))
-    bounds = [0] + cuts + [len(wire)]
-    return wire, [wire[a:b] for a, b in zip(bounds, bounds[1:])]
 
 
 def test_eight_interleaved_streams(gpu):
@@ -254,8 +162,7 @@ def test_random_ring_pressure(gpu):
 
 
 def test_stock_client_capture(gpu):
-    from test_h2_oracle import _grpcio_capture
-    data, exp = _grpcio_capture()
+    data, exp = grpcio_capture()
     for seed in range(3):
         rng = random.Random(seed)
         if seed == 0:
@@ -294,7 +201,7 @@ def test_events_out_equal_deframe(gpu):
     got, ev, _ = h.feed(slices, want_events=True)
     p = h2dev.Parser(False)
     assert p.open_streams([1]) == 0
-    data, table = _slice_table(slices)
+    data, table = pack_slices(slices)
     buf = gpu.DeviceBuffer(data=data)
     err, ev2 = p.deframe(buf.ptr, table)
     assert err == 0 and ev == ev2
@@ -309,13 +216,13 @@ torch.cuda.synchronize()
 sys.path.insert(0, sys.argv[1])
 import grpc_rdma_amd as g
 from grpc_rdma_amd import h2dev
-from tests.test_zz_gpu_h2_messages import _batch, _slice_table
+from tests.h2_device_lib import _batch, pack_slices
 g.init(0)
 bodies, wire, slices = _batch([1000, 0, 70000], 16384, 2)
 p = h2dev.Parser(False)
 assert p.open_streams([1]) == 0
 a = h2dev.Assembler(p, t, 4 << 20, 64)
-data, table = _slice_table(slices)
+data, table = pack_slices(slices)
 buf = g.DeviceBuffer(data=data)
 err, got = p.deframe_messages(buf.ptr, table, a)
 torch.cuda.synchronize()
@@ -377,35 +284,6 @@ def test_bad_arguments(gpu):
     a.close()
     p.close()
     other.close()
-
-
-def _pipe_setup(g, h2dev, gs, sizes, npipes, parser):
-    from grpc_rdma_amd import h2 as h2host
-    bufs = [g.DeviceBuffer(data=bytes((j * 7 + i) % 251 for j in range(n))) for i, n in enumerate(sizes)]
-    msgs = [(b.ptr, n, 1, 0) for b, n in zip(bufs, sizes)]
-    lens = []
-    for n in sizes:
-        lens += [len(it[1]) if it[0] == "inl" else it[1][1] for it in h2host.frame_message(n, 1, 16384)]
-    scratch = g.DeviceBuffer(nbytes=max(lens) + 64)
-    sge = [(scratch.ptr, n) for n in lens]
-    tx, rx = g.Pair(1 << 18, 30), g.Pair(1 << 18, 30)
-    g.connect_pairs(tx, rx)
-    N = sum(lens)
-    scap = 2 * len(lens) + 64 + N // 256
-    dst_cap = N + 16 * scap + 4096
-    keep = [bufs, scratch, tx, rx]
-    pipes, jobs = [], []
-    for _ in range(npipes):
-        dst = g.DeviceBuffer(nbytes=dst_cap)
-        job = gs.StreamJob(tx, rx, sge, dst.ptr, dst_cap, scap, 64)
-        r = job.run(gs.RUN_EAGER)
-        job.set_rounds(int(max(r.tx_rounds, r.rx_rounds)))
-        r = job.run(gs.RUN_GRAPH)
-        assert r.done and r.bytes_delivered == N
-        pipes.append(h2dev.Pipe(job, msgs, parser, len(job.delivered_slices(0)), 4 * len(lens) + 256))
-        jobs.append(job)
-        keep.append(dst)
-    return pipes, jobs, keep
 
 
 @pytest.mark.parametrize("fused", ["1", "0"])

@@ -9,79 +9,11 @@ import pytest
 
 from oracle import pyorc
 from tests.h2_asm_model import OK, TOO_LARGE, NO_SPACE, TRUNCATED
+from tests.h2_device_lib import (BATCHES, ERR_CAPACITY, ERR_INVALID, SENTINEL, RHarness, Target, _back_job, _batch, _dropped_slices, _eight_streams,
+                                 _pipe_setup, check_reply, device_bytes, expected_reply)
 from tests.h2_helpers import frame, grpc_msg
-from tests.test_gpu_h2 import device_bytes, read_slices
-from tests.test_zz_gpu_h2_messages import BATCHES, Harness, _batch, _eight_streams, _pipe_setup
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = 0xC3
-ERR_INVALID, ERR_CAPACITY = -2, -5
-
-
-class RHarness(Harness):
-    """Harness that keeps what the model reported for the last call: [((offset, length, seq, stream, status, flags),
-    body or None)]"""
-
-    def __init__(self, *a, **kw):
-        super().__init__(*a, **kw)
-        self.last = []
-        call = self.model.call
-
-        def keeping(events, slices, h2_error=0):
-            self.last = call(events, slices, h2_error)
-            return self.last
-
-        self.model.call = keeping
-
-
-def expected_reply(last, max_frame, routes=None):
-    """the oracle's framing of what the model kept -> (wire, slice lengths, counters)"""
-    kept, dropped, unrouted = [], 0, 0
-    for d, body in last:
-        if d[4] != OK:
-            dropped += 1
-        elif routes is not None and d[3] not in routes:
-            unrouted += 1
-        else:
-            kept.append((body, routes[d[3]] if routes is not None else d[3], d[5] & 1))
-    if kept:
-        wire, lens = pyorc.h2_frame_batch([k[0] for k in kept], [k[1] for k in kept], [k[2] for k in kept], max_frame)
-    else:
-        wire, lens = b"", []
-    return wire, lens, {"kept": len(kept), "dropped_status": dropped, "unrouted": unrouted}
-
-
-class Target:
-    """slice table and header arena for one framing, sentinel-filled, with room behind the caps"""
-
-    def __init__(self, g, cap):
-        self.g, self.cap = g, cap
-        self.slices = g.DeviceBuffer(data=bytes([SENTINEL]) * (16 * (cap + 4)))
-        self.hdr = g.DeviceBuffer(data=bytes([SENTINEL]) * (32 * (cap + 4)))
-
-    def frame(self, reply, cap=None, hdr_cap=None):
-        cap = self.cap if cap is None else cap
-        return reply.frame(self.slices.ptr, cap, self.hdr.ptr, 32 * cap if hdr_cap is None else hdr_cap)
-
-    def wire(self, n):
-        got = read_slices(self.g, self.slices, n)
-        return [ln for _, ln in got], b"".join(device_bytes(self.g, p, ln) for p, ln in got), got
-
-
-def check_reply(g, h, reply, max_frame, routes=None):
-    """frame the last call of h and compare with the oracle; -> (slices [(ptr, len)], wire)"""
-    wire, lens, counters = expected_reply(h.last, max_frame, routes)
-    t = h.target = Target(g, len(lens) + 1)  # (the header slices live in it: kept while the harness lives)
-    n, st = t.frame(reply)
-    got_lens, got_wire, got = t.wire(n)
-    print("reply: %d descriptors -> kept %d, %d slices, %d wire bytes, %d us" %
-          (len(h.last), st["kept"], n, st["wire_bytes"], st["frame_us"]))
-    assert n == len(lens) == st["slices"] and got_lens == lens
-    assert got_wire == wire and st["wire_bytes"] == len(wire)
-    assert {k: st[k] for k in counters} == counters
-    assert st["overflow"] == 0 and st["hdr_bytes"] <= 32 * n
-    return got, got_wire
 
 
 @pytest.mark.parametrize("reply_frame", ["same", "other"])
@@ -107,11 +39,7 @@ def test_dropped_descriptors_change_the_layout(gpu):
     test_truncation_and_reuse); a TOO_LARGE message sits between an empty kept message and a non-empty kept one, so the
     inlined-slice merge crosses the dropped descriptor."""
     from grpc_rdma_amd import h2dev
-    part = grpc_msg(b"t" * 800)[:500]
-    slices = [frame(0, 0, 1, grpc_msg(b"")), frame(0, 0, 1, grpc_msg(b"L" * 2000)), frame(0, 0, 1, grpc_msg(b"a" * 1000, 1)),
-              frame(0, 0, 3, part), frame(3, 0, 3, (8).to_bytes(4, "big")), frame(0, 0, 1, grpc_msg(b"")),
-              frame(0, 0, 1, grpc_msg(b"")), frame(0, 0, 1, grpc_msg(b"b" * 1100)), frame(0, 0, 1, grpc_msg(b"c" * 1000)),
-              frame(0, 0, 1, grpc_msg(b"d" * 10))]
+    slices = _dropped_slices()
     for max_frame in (16384, 7, 600):
         h = RHarness(gpu, 4096, max_msg=1200, streams=[1, 3])
         got = h.feed(slices)
@@ -202,10 +130,10 @@ def test_caps_and_arguments(gpu):
     out = (C.c_uint64 * 8)()
     t = Target(gpu, n)
     # one slice short, then one header slot short: nothing behind the caps is written
-    assert lib.grdma_h2_reply_frame(reply.h, t.slices.ptr, n - 1, t.hdr.ptr, 32 * n, out) == ERR_CAPACITY
+    assert lib.grdma_h2_reply_frame(reply.h, t.slices.ptr, n - 1, t.hdr.ptr, 32 * n, out) == -ERR_CAPACITY
     assert int(out[6]) == 1 and int(out[3]) == n
     hdr_need = 32 * sum(1 for ln in exp_lens if ln <= 23)
-    assert lib.grdma_h2_reply_frame(reply.h, t.slices.ptr, n, t.hdr.ptr, hdr_need - 1, out) == ERR_CAPACITY
+    assert lib.grdma_h2_reply_frame(reply.h, t.slices.ptr, n, t.hdr.ptr, hdr_need - 1, out) == -ERR_CAPACITY
     assert t.slices.read()[16 * (n - 1):] == bytes([SENTINEL]) * (16 * 5)
     assert t.hdr.read()[hdr_need - 32:] == bytes([SENTINEL]) * (32 * (n + 4) - hdr_need + 32)
     # exactly enough
@@ -216,25 +144,25 @@ def test_caps_and_arguments(gpu):
     assert t.hdr.read()[hdr_need:] == bytes([SENTINEL]) * (32 * (n + 4) - hdr_need)
     # more descriptors than max_messages
     small = h2dev.Reply(h.asm, None, 16384, 3)
-    assert lib.grdma_h2_reply_frame(small.h, t.slices.ptr, n, t.hdr.ptr, 32 * n, out) == ERR_CAPACITY
+    assert lib.grdma_h2_reply_frame(small.h, t.slices.ptr, n, t.hdr.ptr, 32 * n, out) == -ERR_CAPACITY
     small.close()
     # arguments
     f = lib.grdma_h2_reply_frame
-    assert f(None, t.slices.ptr, n, t.hdr.ptr, 32 * n, out) == ERR_INVALID
-    assert f(reply.h, None, n, t.hdr.ptr, 32 * n, out) == ERR_INVALID
-    assert f(reply.h, t.slices.ptr, 0, t.hdr.ptr, 32 * n, out) == ERR_INVALID
-    assert f(reply.h, t.slices.ptr, n, None, 32 * n, out) == ERR_INVALID
-    assert f(reply.h, t.slices.ptr, n, t.hdr.ptr, 0, out) == ERR_INVALID
-    assert f(reply.h, t.slices.ptr, n, t.hdr.ptr, 32 * n, None) == ERR_INVALID
-    assert f(reply.h, t.slices.ptr + 8, n, t.hdr.ptr, 32 * n, out) == ERR_INVALID
-    assert f(reply.h, t.slices.ptr, n, t.hdr.ptr + 4, 32 * n, out) == ERR_INVALID
+    assert f(None, t.slices.ptr, n, t.hdr.ptr, 32 * n, out) == -ERR_INVALID
+    assert f(reply.h, None, n, t.hdr.ptr, 32 * n, out) == -ERR_INVALID
+    assert f(reply.h, t.slices.ptr, 0, t.hdr.ptr, 32 * n, out) == -ERR_INVALID
+    assert f(reply.h, t.slices.ptr, n, None, 32 * n, out) == -ERR_INVALID
+    assert f(reply.h, t.slices.ptr, n, t.hdr.ptr, 0, out) == -ERR_INVALID
+    assert f(reply.h, t.slices.ptr, n, t.hdr.ptr, 32 * n, None) == -ERR_INVALID
+    assert f(reply.h, t.slices.ptr + 8, n, t.hdr.ptr, 32 * n, out) == -ERR_INVALID
+    assert f(reply.h, t.slices.ptr, n, t.hdr.ptr + 4, 32 * n, out) == -ERR_INVALID
     c = lib.grdma_h2_reply_create
     assert not c(None, None, 0, 16384, 64)
     assert not c(h.asm.h, None, 0, 0, 64)
     assert not c(h.asm.h, None, 0, 1 << 24, 64)
     assert not c(h.asm.h, None, 0, 16384, 0)
     assert not lib.grdma_h2_pipe_create_reply(None, 0, reply.h, h.parser.h, 1, 1, 1)
-    assert lib.grdma_h2_pipe_slice_table(None, None, 0) == ERR_INVALID
+    assert lib.grdma_h2_pipe_slice_table(None, None, 0) == -ERR_INVALID
     # the assembler is not destroyed under a reply that reads it
     lib.grdma_h2_asm_destroy(h.asm.h)
     assert f(reply.h, t.slices.ptr, n, t.hdr.ptr, 32 * n, out) == n
@@ -274,24 +202,6 @@ def test_end_to_end_standalone(gpu):
     reply.close()
     h1.close()
     h2.close()
-
-
-def _back_job(g, gs, lens):
-    """a job over a connection of its own whose recorded run carries slices of the lengths `lens`"""
-    scratch = g.DeviceBuffer(nbytes=max(lens) + 64)
-    sge = [(scratch.ptr, n) for n in lens]
-    tx, rx = g.Pair(1 << 18, 30), g.Pair(1 << 18, 30)
-    g.connect_pairs(tx, rx)
-    N = sum(lens)
-    scap = 2 * len(lens) + 64 + N // 256
-    dst_cap = N + 16 * scap + 4096
-    dst = g.DeviceBuffer(nbytes=dst_cap)
-    job = gs.StreamJob(tx, rx, sge, dst.ptr, dst_cap, scap, 64)
-    r = job.run(gs.RUN_EAGER)
-    job.set_rounds(int(max(r.tx_rounds, r.rx_rounds)))
-    r = job.run(gs.RUN_GRAPH)
-    assert r.done and r.bytes_delivered == N and r.bytes_sent == N
-    return job, lens, int(r.bytes_sent), [scratch, tx, rx, dst]
 
 
 @pytest.mark.parametrize("fused", ["1", "0"])

@@ -6,19 +6,18 @@ and probe linearly; the first two delete by backward shift.
 
 With table_slots=16 the mask is 15 and stream 2 * (h + 16 k) + 1 has home h: the ids below sit in clusters on homes
 14, 15, 0 and 1, so probing and shifting cross the end of the table.  References: the CPU oracle (pyorc.H2Parser), the
-sequential assembler model (tests/h2_asm_model.py) and the ledger's model (tests/test_zz_gpu_h2_flow.py, here with the
+sequential assembler model (tests/h2_asm_model.py) and the ledger's model (tests/h2_flow_model.py, here with the
 slot rule of rule 4).  Every comparison is exact."""
 import itertools
 import random
 
 import pytest
 
-from oracle import pyorc
 from oracle.pyorc import EV_FRAME, EV_STREAM_CLOSED, EV_STREAM_OPEN
 from tests.h2_asm_model import OK, TRUNCATED
+from tests.h2_device_lib import ERR_CAPACITY, FH, SENTINEL, Conn, Harness, cut_mean, fast_sender_slices, pack_slices
+from tests.h2_flow_model import LOST, STREAM, Model
 from tests.h2_helpers import PREFACE, frame, grpc_msg
-from tests.test_zz_gpu_h2_flow import FH, LOST, STREAM, Model
-from tests.test_zz_gpu_h2_messages import SENTINEL, Harness, _slice_table
 
 pytestmark = pytest.mark.gpu
 
@@ -28,19 +27,9 @@ HOME0 = tuple(32 * k + 1 for k in range(8))      # 1, 33, 65, ...: all on home 0
 WRAP4 = (31, 33, 63, 65)                         # homes 15 0 15 0 -> slots 15 0 1 2
 POOL24 = tuple(2 * (h + 16 * k) + 1 for k in range(6) for h in (14, 15, 0, 1))
 ERR_MAX_STREAMS = 9
-ERR_CAPACITY = 5
 RST = (8).to_bytes(4, "big")
 assert [(s >> 1) & 15 for s in WRAP8] == [14, 15, 0, 14, 15, 0, 14, 15] and all((s >> 1) & 15 == 0 for s in HOME0)
 assert [(s >> 1) & 15 for s in WRAP4] == [15, 0, 15, 0] and {(s >> 1) & 15 for s in POOL24} == {14, 15, 0, 1}
-
-
-def _cut(data, rng, mean=40):
-    out, pos = [], 0
-    while pos < len(data):
-        n = max(1, int(rng.expovariate(1.0 / mean)))
-        out.append(data[pos:pos + n])
-        pos += n
-    return out
 
 
 class Src:
@@ -67,68 +56,6 @@ class Src:
             if end <= self.pos:
                 out.append(m)
         return out
-
-
-class Conn:
-    """a device parser with a small stream map and the oracle's parser beside it: every call's events and the number
-    of live streams equal the oracle's; the messages are rebuilt from the DEVICE's events"""
-
-    def __init__(self, g, prefix, slots=SLOTS, **kw):
-        from grpc_rdma_amd import h2dev
-        self.g = g
-        self.dev = h2dev.Parser(prefix, table_slots=slots, **kw)
-        self.orc = pyorc.H2Parser(expect_client_prefix=prefix, max_concurrent_streams=slots // 2)
-        self.partial, self.done, self.ncalls = {}, [], 0
-
-    def open(self, ids):
-        assert self.dev.open_streams(ids) == 0
-        for s in ids:
-            assert self.orc.open_stream(s) == 0
-        self.live()
-
-    def close_writes(self, ids):
-        assert self.dev.close_writes(ids) == 0
-        for s in ids:
-            assert self.orc.close_writes(s) == 0
-        self.live()
-
-    def live(self):
-        n = self.dev.live_streams()
-        assert n == self.orc.live_streams(), "live streams after call %d" % self.ncalls
-        return n
-
-    def call(self, slices, want_err=0, cap=None):
-        data, table = _slice_table(slices)
-        buf = self.g.DeviceBuffer(data=data)
-        err, ev = self.dev.deframe(buf.ptr, table, cap=cap or 8 * len(slices) + 4096)
-        buf.free()
-        err_o, ev_o = 0, []
-        for i, s in enumerate(slices):
-            rc, e = self.orc.feed(s, cap=2 * len(s) + 64)
-            ev_o += [(k, a, b, c, d, i) for k, a, b, c, d in e]
-            if rc:
-                err_o = rc
-                break
-        self.ncalls += 1
-        assert err == err_o == want_err, "call %d" % self.ncalls
-        if ev != ev_o:
-            bad = next((i for i in range(min(len(ev), len(ev_o))) if ev[i] != ev_o[i]), min(len(ev), len(ev_o)))
-            raise AssertionError("call %d event %d of %d / %d: device %r, oracle %r" % (
-                self.ncalls, bad, len(ev), len(ev_o), ev[bad:bad + 1], ev_o[bad:bad + 1]))
-        self.live()
-        for k, a, b, c, d, i in ev:
-            if k == 3:
-                self.partial[c] = bytearray()
-            elif k == 4:
-                self.partial[c] += slices[i][a:a + b]
-            elif k == 5:
-                self.done.append((c, bytes(self.partial.pop(c))))
-            elif k == 7:
-                self.partial.pop(c, None)
-        return ev
-
-    def close(self):
-        self.dev.close()
 
 
 # ---- 1a. the parser's map: removal orders across the wrap ---------------------------------------------------------
@@ -158,12 +85,12 @@ def _removal_run(g, ids, order, n_rst, seed):
         data[i], data[i + 1] = data[i] + data[i + 1][:sh], data[i + 1][sh:]
     c = Conn(g, True)
     for d in data:
-        c.call(_cut(d, rng))
+        c.call(cut_mean(d, rng))
     assert c.live() == len(left)
     assert sorted(c.done) == sorted((s, src[s].msgs[0]) for s in left) and not c.partial
     for s in order[n_rst:]:
         c.close_writes([s])
-        c.call(_cut(b"".join(frame(0, 0, t, b"gone") for t in ids), rng))
+        c.call(cut_mean(b"".join(frame(0, 0, t, b"gone") for t in ids), rng))
     assert c.live() == 0 and len(c.done) == len(left)
     c.close()
 
@@ -250,7 +177,7 @@ def _client_sequence(g, seed, steps=25):
         for s in rng.sample(sorted(t for t in st if st[t]["reads"]), min(2, len([t for t in st if st[t]["reads"]]))):
             frames.append(frame(0, 0, s, st[s]["src"].take(rng.randrange(1, 31))))
         if frames:
-            c.call(_cut(b"".join(frames), rng, 12))
+            c.call(cut_mean(b"".join(frames), rng, 12))
     for s in list(st):
         leave(s)
     got = {s: [] for s in POOL24}
@@ -273,7 +200,7 @@ def test_parser_map_half_full_rule(gpu):
     nine = WRAP8 + (97,)
     # server: the ninth concurrent stream fails the connection
     c = Conn(gpu, True)
-    c.call(_cut(PREFACE + frame(4, 0, 0) + b"".join(frame(1, 4, s, b"\x82") for s in nine), rng), want_err=ERR_MAX_STREAMS)
+    c.call(cut_mean(PREFACE + frame(4, 0, 0) + b"".join(frame(1, 4, s, b"\x82") for s in nine), rng), want_err=ERR_MAX_STREAMS)
     assert c.dev.live_streams() == 8
     c.close()
     # client: the ninth id is refused, the eight before it stay usable
@@ -283,14 +210,13 @@ def test_parser_map_half_full_rule(gpu):
         assert c.orc.open_stream(s) == 0
     assert c.live() == 8
     body = {s: bytes([s]) * (s % 50) for s in nine}
-    c.call(_cut(b"".join(frame(0, 0, s, grpc_msg(body[s])) for s in nine), rng))
+    c.call(cut_mean(b"".join(frame(0, 0, s, grpc_msg(body[s])) for s in nine), rng))
     assert c.done == [(s, body[s]) for s in WRAP8]
     c.close()
 
 
 # ---- 1d. one chunked call on a stream that does not sit in its home slot, then on the shifted entry ------------------
 def test_parser_map_chunked_call_on_a_shifted_entry(gpu):
-    from tests.test_zz_gpu_h2_chunks import fast_sender_slices
     c = Conn(gpu, False, boundary_step=True)
     c.open([1, 33])                                   # both on home 0: 33 sits in slot 1
     c.call([frame(0, 1, 1, grpc_msg(b"first"))] + fast_sender_slices([3072] * 3, sid=33, max_frame=1024))
@@ -318,7 +244,7 @@ def _carry_run(g, ids, order, n_removed, seed):
     h = Harness(g, 64 << 10, streams=list(ids), table_slots=SLOTS)
     src = {s: Src(rng, [rng.randrange(300, 900)]) for s in ids}
     for call in range(rng.randrange(2, 4)):          # with the removal calls: partial over 3 to 5 calls and more
-        got = h.feed(_cut(b"".join(frame(0, 0, s, src[s].take(FIRST[(i + call) % 8] + 5 * call)) for i, s in enumerate(ids)), rng))
+        got = h.feed(cut_mean(b"".join(frame(0, 0, s, src[s].take(FIRST[(i + call) % 8] + 5 * call)) for i, s in enumerate(ids)), rng))
         assert got == []
     left, reopened = list(ids), None
     for n, r in enumerate(order[:n_removed]):
@@ -326,17 +252,16 @@ def _carry_run(g, ids, order, n_removed, seed):
         fr = [frame(0, 0, left[0], src[left[0]].take(rng.randrange(1, 30)))]
         fr.append(frame(3, 0, r, RST) if n % 2 == 0 else frame(0, 1, r, src[r].take(rng.randrange(0, 9))))
         fr += [frame(0, 0, s, src[s].take(rng.randrange(1, 30))) for s in left]
-        got = h.feed(_cut(b"".join(fr), rng))
+        got = h.feed(cut_mean(b"".join(fr), rng))
         assert [(m.stream_id, m.status) for m in got] == [(r, TRUNCATED)]
         if n == 0:
             # the id RST_STREAM freed starts a new call with a new message, partial as the others are
-            h.parser.open_streams([r])
-            h.calls.append(("open", [r]))
+            h.pp.open([r])
             reopened = r
             src[r] = Src(rng, [rng.randrange(300, 900)])
             left.append(r)
-            assert h.feed(_cut(frame(0, 0, r, src[r].take(rng.randrange(1, 200))), rng)) == []
-    got = h.feed(_cut(b"".join(frame(0, 0, s, src[s].rest()) for s in left), rng))
+            assert h.feed(cut_mean(frame(0, 0, r, src[r].take(rng.randrange(1, 200))), rng)) == []
+    got = h.feed(cut_mean(b"".join(frame(0, 0, s, src[s].rest()) for s in left), rng))
     assert [(m.stream_id, m.status) for m in got] == [(s, OK) for s in left] and reopened in left
     assert [h.asm.view(m) for m in got] == [src[s].msgs[0] for s in left]
     h.release()
@@ -392,7 +317,7 @@ def _assemble(g, ids, slots, seed, shuffled, ncalls, arena=256 << 10):
     h = Harness(g, arena, streams=list(ids), table_slots=slots)
     got = []
     for a, b in zip(bounds, bounds[1:]):
-        got += h.feed(_cut(wire[a:b], rng, 700))      # (descriptors and bytes against the model, call by call)
+        got += h.feed(cut_mean(wire[a:b], rng, 700))      # (descriptors and bytes against the model, call by call)
     by_stream = {s: [] for s in ids}
     for m in got:
         assert m.status == OK
@@ -430,11 +355,11 @@ def _one_byte_messages(n):
 def _failed_call(h, wire):
     """one call through the harness's parser and assembler that must fail with GRDMA_ERR_CAPACITY; the oracle's parser
     and the model are told"""
-    data, table = _slice_table([wire])
+    data, table = pack_slices([wire])
     buf = h.g.DeviceBuffer(data=data)
     with pytest.raises(h.g.GrdmaError, match="error %d" % ERR_CAPACITY):
         h.parser.deframe_messages(buf.ptr, table, h.asm)
-    h.calls.append([wire])
+    h.pp.expect([wire])
     h.model.failed_call()
 
 
@@ -488,7 +413,7 @@ def test_assembler_stream_limit_in_a_batch_of_two(gpu):
     asms = [h2dev.Assembler(p, a, 4 << 20, 4096) for p, a in zip(parsers, arenas)]
     items, keep = [], []
     for p, a, wire in zip(parsers, asms, (_one_byte_messages(n), ok_wire)):
-        data, table = _slice_table([wire])
+        data, table = pack_slices([wire])
         keep.append(gpu.DeviceBuffer(data=data))
         items.append((p, a, keep[-1].ptr, table))
     res = h2dev.deframe_messages_batch(items)
@@ -540,11 +465,8 @@ def _ledger(g, prefix, streams, stream_window=1 << 20, conn_window=1 << 24):
     return h
 
 
-def _account(h, slices, ev_cap=1 << 16):
-    err, ev = h.deframe(slices, ev_cap=ev_cap)
-    err_o, ev_o = h.oracle()
-    assert (err, ev) == (err_o, ev_o)
-    return h.account()
+def _account(h, slices):
+    return h.feed(slices, ev_cap=1 << 16)
 
 
 def _sources(rng, ids):
