@@ -32,6 +32,7 @@
 #include "grdma_h2_asm.h"
 #include "grdma_h2_reply.h"
 #include "grdma_h2_fc.h"
+#include "grdma_h2_sw.h"
 #include "grdma_h2_block.h"
 
 // --------------------------------------------------------------------- host API
@@ -63,6 +64,11 @@ struct grdma_h2_parser {
   // their number and the event capacity of the last one (its events stay in d_ev / d_res until the next call)
   struct grdma_h2_fc* fc = nullptr;
   uint64_t standalone_calls = 0, standalone_ev_cap = 0;
+  // send flow control (csrc/grdma_h2_sw.h): the parser's send windows, and what their intake reads of the last
+  // standalone deframing beside its events -- the receive arena and the length of the slice table (d_sl)
+  struct grdma_h2_sw* sw = nullptr;
+  const uint8_t* standalone_arena = nullptr;
+  uint64_t standalone_nsl = 0;
 };
 
 // How many chunks a parser created without saying so cuts a long list into: GRDMA_H2_CHUNKS (default and at most 256, 0 or 1 = the
@@ -237,6 +243,16 @@ static h2_stage h2_stage_fc_links(const h2fc_link* d_tab, uint32_t n) {
           h2_rec(k_h2_links_fc_sums, n * H2FC_LINK_GRID, H2FC_THREADS, d_tab, n),
           h2_rec(k_h2_links_fc_finish, n, H2FC_ONE_THREADS, d_tab),
           h2_rec(k_h2_links_fc_emit, n * H2FC_LINK_GRID, H2FC_THREADS, d_tab, n)};
+}
+
+// The intake of the send windows behind a deframing (csrc/grdma_h2_sw.h): it reads the events, the slice table and the
+// receive arena; and their framer: plan, then emit, as the reply's.
+static h2_stage h2_stage_sw_intake(h2sw_dev* d, const h2sw_call* d_call) {
+  return {h2_rec(k_h2_sw_clear, H2SW_GRID, H2SW_THREADS, d), h2_rec(k_h2_sw_take, H2SW_GRID, H2SW_THREADS, d, d_call),
+          h2_rec(k_h2_sw_finish, 1, H2SW_THREADS, d, d_call)};
+}
+static h2_stage h2_stage_sw_frame(h2sw_dev* d) {
+  return {h2_rec(k_h2_sw_plan, 1, H2SW_PLAN_THREADS, d), h2_rec(k_h2_sw_emit, H2SW_GRID, H2_EMIT_THREADS, d)};
 }
 
 // st goes behind the parser's last deframing by a pipe (the parser state is handed from one deframing to the next),

@@ -153,9 +153,11 @@ grdma_h2_parser* grdma_h2_parser_create(int expect_client_prefix, uint32_t max_f
 }
 
 static void h2_fc_parser_gone(struct grdma_h2_fc* f);
+static void h2_sw_parser_gone(struct grdma_h2_sw* s);
 void grdma_h2_parser_destroy(grdma_h2_parser* p) {
   if (!p) return;
   if (p->fc) h2_fc_parser_gone(p->fc);  // (the ledger outlives its parser as a husk: every call on it is refused)
+  if (p->sw) h2_sw_parser_gone(p->sw);  // (the send windows too)
   hipFree(p->d);
   hipFree(p->d_tab);
   hipFree(p->d_sl);
@@ -250,6 +252,8 @@ int64_t grdma_h2_deframe(grdma_h2_parser* p, const void* d_arena, const grdma_re
   if (h2_error) *h2_error = (int)h_res.error;
   p->standalone_calls++;
   p->standalone_ev_cap = cap;
+  p->standalone_arena = static_cast<const uint8_t*>(d_arena);
+  p->standalone_nsl = n;
   return h_res.overflow ? -GRDMA_ERR_CAPACITY : (int64_t)m;
 }
 
@@ -501,6 +505,8 @@ int64_t grdma_h2_deframe_messages(grdma_h2_parser* p, grdma_h2_asm* a, const voi
   a->copy_ms = c.ms[1];
   p->standalone_calls++;
   p->standalone_ev_cap = ev_cap;
+  p->standalone_arena = static_cast<const uint8_t*>(d_arena);
+  p->standalone_nsl = n;
   if (h2_error) *h2_error = (int)h_res.error;
   const uint64_t m = h_res.nevents < ev_cap ? h_res.nevents : ev_cap;
   if (events_out && m && !h2_read(events_out, p->d_ev, sizeof(grdma_h2_event) * m)) return -GRDMA_ERR_HIP;
@@ -933,6 +939,202 @@ int grdma_h2_fc_stats(grdma_h2_fc* f, uint64_t out[8]) {
   out[5] = h.st_stream_over | (h.lost ? 1ull << 63 : 0);
   out[6] = (uint64_t)h.announced;
   out[7] = (uint64_t)(f->last_ms * 1e6f);
+  return 0;
+}
+
+// ---- send flow control: the peer's windows and the framer under them (csrc/grdma_h2_sw.h) -------------------------------
+struct grdma_h2_sw {
+  grdma_h2_parser* parser = nullptr;
+  h2sw_dev* d = nullptr;
+  h2sw_dev h;                         // host copy of the configuration words
+  h2sw_call* d_call = nullptr;
+  grdma_h2_msg_dev* d_msgs = nullptr; // H2_FRAME_ONE_MAX
+  uint64_t* d_prog = nullptr;         // progress in [0, MAX), out [MAX, 2 MAX)
+  uint64_t taken = 0;                 // parser->standalone_calls of the last call taken in (at creation: of the calls before it)
+  float last_ms = 0;
+};
+
+// The parser of s is being destroyed: standalone calls on the stream of the calls have ended, and from now on s refuses
+// every call but destroy (its device block points into the parser's).
+static void h2_sw_parser_gone(grdma_h2_sw* s) {
+  h2_host_ctx* hc = h2_ctx();
+  if (hc) hipStreamSynchronize(hc->stream);
+  s->parser = nullptr;
+}
+
+static grdma_h2_sw* h2_sw_refuse(const char* why) {
+  grdma_fail_msg(GRDMA_ERR_INVALID, why);
+  return nullptr;
+}
+
+grdma_h2_sw* grdma_h2_sw_create(grdma_h2_parser* parser, uint32_t initial_window, uint32_t conn_window, uint32_t peer_max_frame) {
+  if (grdma_device_count() <= 0) return nullptr;
+  if (!parser) return h2_sw_refuse("h2 send windows: no parser");
+  if (parser->sw) return h2_sw_refuse("h2 send windows: the parser has send windows already");
+  if (initial_window > 0x7fffffffu || conn_window > 0x7fffffffu) return h2_sw_refuse("h2 send windows: a window above 2^31 - 1");
+  if (peer_max_frame < 16384 || peer_max_frame > 16777215) return h2_sw_refuse("h2 send windows: peer_max_frame outside 16384 .. 2^24 - 1");
+  grdma_h2_sw* s = new grdma_h2_sw();
+  s->parser = parser;
+  s->taken = parser->standalone_calls;
+  memset(&s->h, 0, sizeof(s->h));
+  h2sw_dev& h = s->h;
+  h.gp = parser->d;
+  h.tab_mask = parser->slots - 1;
+  h.conn = (long long)conn_window;
+  h.iws = initial_window;
+  h.pmf = peer_max_frame;
+  const size_t tab_bytes = sizeof(h2sw_slot) * parser->slots;
+  const bool ok = hipMalloc((void**)&s->d, sizeof(h2sw_dev)) == hipSuccess &&
+                  hipMalloc((void**)&h.tabs[0], tab_bytes) == hipSuccess && hipMalloc((void**)&h.tabs[1], tab_bytes) == hipSuccess &&
+                  hipMalloc((void**)&h.pieces, sizeof(h2sw_piece) * H2_FRAME_ONE_MAX) == hipSuccess &&
+                  hipMalloc((void**)&h.pos, sizeof(grdma_h2_msg_pos) * H2_FRAME_ONE_MAX) == hipSuccess &&
+                  hipMalloc((void**)&h.slot_of, sizeof(uint32_t) * H2_FRAME_ONE_MAX) == hipSuccess &&
+                  hipMalloc((void**)&s->d_msgs, sizeof(grdma_h2_msg_dev) * H2_FRAME_ONE_MAX) == hipSuccess &&
+                  hipMalloc((void**)&s->d_prog, sizeof(uint64_t) * 2 * H2_FRAME_ONE_MAX) == hipSuccess &&
+                  hipMalloc((void**)&s->d_call, sizeof(h2sw_call)) == hipSuccess &&
+                  hipMemset(h.tabs[0], 0, tab_bytes) == hipSuccess && hipMemset(h.tabs[1], 0, tab_bytes) == hipSuccess;
+  h.msgs = s->d_msgs;
+  h.prog_in = s->d_prog;
+  h.prog_out = s->d_prog ? s->d_prog + H2_FRAME_ONE_MAX : nullptr;
+  parser->sw = s;
+  if (!ok || hipMemcpy(s->d, &h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    grdma_h2_sw_destroy(s);
+    grdma_fail_msg(GRDMA_ERR_HIP, "h2 send windows: device allocation failed");
+    return nullptr;
+  }
+  return s;
+}
+
+void grdma_h2_sw_destroy(grdma_h2_sw* s) {
+  if (!s) return;
+  h2_host_ctx* hc = h2_ctx();
+  if (hc) hipStreamSynchronize(hc->stream);  // (standalone calls)
+  if (s->parser) s->parser->sw = nullptr;
+  hipFree(s->h.tabs[0]);
+  hipFree(s->h.tabs[1]);
+  hipFree(s->h.pieces);
+  hipFree(s->h.pos);
+  hipFree(s->h.slot_of);
+  hipFree(s->d_msgs);
+  hipFree(s->d_prog);
+  hipFree(s->d_call);
+  hipFree(s->d);
+  delete s;
+}
+
+int64_t grdma_h2_sw_intake(grdma_h2_sw* s, uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!s || !out) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: no send windows or no result array");
+  grdma_h2_parser* p = s->parser;
+  if (!p) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: the parser is gone");
+  if (p->standalone_calls == 0) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: the parser has deframed nothing yet");
+  if (s->taken == p->standalone_calls) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: this call is taken in already");
+  if (p->standalone_ev_cap >= 0xfffffff0ull) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: event positions are 32 bits");
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  // the stream of the standalone deframings: the call is ordered behind the one it reads, and behind the parser's last
+  // deframing by a pipe (the intake reads the stream map that step may change)
+  hipStream_t st = hc->stream;
+  if (!h2_wait_parser(st, p)) return -GRDMA_ERR_HIP;
+  const h2sw_call call{p->d_ev, p->d_res, p->d_sl, p->standalone_arena, p->standalone_ev_cap, p->standalone_nsl,
+                       p->standalone_calls > s->taken + 1 ? 1ull : 0ull};
+  const h2_stage intake = h2_stage_sw_intake(s->d, s->d_call);
+  uint64_t res[8];
+  h2_call c{"grdma_h2_sw_intake: a launch was rejected",
+            {{s->d_call, &call, sizeof(call)}}, {}, {h2_all(intake)},
+            {{res, reinterpret_cast<uint8_t*>(s->d) + offsetof(h2sw_dev, res), sizeof(res)}}};
+  if (int rc = h2_call_run(hc, &c)) return rc;
+  s->last_ms = c.ms[0];
+  s->taken = p->standalone_calls;
+  for (int i = 0; i < 8; i++) out[i] = res[i];
+  if (res[H2SW_I_OVERFLOW])
+    return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 send windows: the call's event list overflowed, its frames cannot be taken in");
+  return (int64_t)res[H2SW_I_UPDATES];
+}
+
+int64_t grdma_h2_sw_frame(grdma_h2_sw* s, const grdma_h2_msg* msgs, uint64_t* progress, uint64_t n, uint32_t max_frame,
+                          grdma_slice* d_slices_out, uint64_t slices_cap, void* d_hdr_arena, uint64_t hdr_cap, uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!s || !out || !msgs || !progress) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: no send windows, message table, progress or result array");
+  if (n == 0 || n > H2_FRAME_ONE_MAX) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: 1 .. 4096 messages a call");
+  if (max_frame == 0 || max_frame >= (1u << 24)) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: max_frame outside 1 .. 2^24 - 1");
+  if (!d_slices_out || !slices_cap || !d_hdr_arena || !hdr_cap || ((uintptr_t)d_slices_out & 15) || ((uintptr_t)d_hdr_arena & 15))
+    return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: a null, zero or misaligned slice table or header arena");
+  grdma_h2_parser* p = s->parser;
+  if (!p) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: the parser is gone");
+  for (uint64_t i = 0; i < n; i++) {
+    if (msgs[i].len >= (1ull << 32)) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: a message of 2^32 bytes or more");
+    if (progress[i] >= 5 + msgs[i].len) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: a message with nothing left to send");
+  }
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  hipStream_t st = hc->stream;
+  if (!h2_wait_parser(st, p)) return -GRDMA_ERR_HIP;  // (the plan looks streams up in the map)
+  const std::vector<grdma_h2_msg_dev> tmp = h2_msg_table(msgs, n);
+  h2sw_dev& h = s->h;
+  h.nmsgs = n;
+  h.max_frame = max_frame;
+  h.out = reinterpret_cast<grdma_sge*>(d_slices_out);
+  h.cap = slices_cap;
+  h.hdr = static_cast<uint8_t*>(d_hdr_arena);
+  h.hdr_cap = hdr_cap;
+  if (!h2_push_words(s->d, &h, offsetof(h2sw_dev, msgs), offsetof(h2sw_dev, conn), st)) return -GRDMA_ERR_HIP;
+  const h2_stage framing = h2_stage_sw_frame(s->d);
+  uint64_t res[8];
+  std::vector<uint64_t> after(n);
+  h2_call c{"grdma_h2_sw_frame: a launch was rejected",
+            {{s->d_msgs, tmp.data(), sizeof(grdma_h2_msg_dev) * n}, {s->d_prog, progress, sizeof(uint64_t) * n}}, {}, {h2_all(framing)},
+            {{res, reinterpret_cast<uint8_t*>(s->d) + offsetof(h2sw_dev, fres), sizeof(res)},
+             {after.data(), s->d_prog + H2_FRAME_ONE_MAX, sizeof(uint64_t) * n}}};
+  if (int rc = h2_call_run(hc, &c)) return rc;
+  s->last_ms = c.ms[0];
+  for (int i = 0; i < 8; i++) out[i] = res[i];
+  if (res[H2SW_F_OVERFLOW])  // (nothing was written, no window moved: progress stays as it is)
+    return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 send windows: a slice or header cap too small");
+  for (uint64_t i = 0; i < n; i++) progress[i] = after[i];
+  return (int64_t)res[H2SW_F_SLICES];
+}
+
+int grdma_h2_sw_windows(grdma_h2_sw* s, const uint32_t* ids, uint32_t n, int64_t* out) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!s || (n && (!ids || !out))) return -GRDMA_ERR_INVALID;
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  h2sw_dev h;
+  const uint32_t slots = s->h.tab_mask + 1;
+  std::vector<h2sw_slot> tab(slots);
+  if (!h2_read(&h, s->d, sizeof(h)) || !h2_read(tab.data(), h.tabs[h.cur & 1u], sizeof(h2sw_slot) * slots)) return -GRDMA_ERR_HIP;
+  for (uint32_t i = 0; i < n; i++) {
+    if (ids[i] == 0) {
+      out[i] = h.conn;
+      continue;
+    }
+    int64_t delta = 0;  // (a missing entry)
+    uint32_t t = (ids[i] >> 1) & h.tab_mask;
+    for (uint32_t probe = 0; probe < slots && tab[t].key != 0; probe++, t = (t + 1) & h.tab_mask)
+      if (tab[t].key == ids[i]) {
+        delta = tab[t].delta;
+        break;
+      }
+    out[i] = (int64_t)h.iws + delta;
+  }
+  return 0;
+}
+
+int grdma_h2_sw_stats(grdma_h2_sw* s, uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!s || !out) return -GRDMA_ERR_INVALID;
+  h2sw_dev h;
+  if (!h2_read(&h, s->d, sizeof(h))) return -GRDMA_ERR_HIP;
+  out[0] = h.st_intakes;
+  out[1] = h.st_updates;
+  out[2] = h.st_settings;
+  out[3] = h.st_violations | (h.lost ? 1ull << 63 : 0);
+  out[4] = h.st_frame_calls;
+  out[5] = h.st_sent;
+  out[6] = (uint64_t)h.iws | ((uint64_t)h.pmf << 32);
+  out[7] = (uint64_t)(s->last_ms * 1e6f);
   return 0;
 }
 

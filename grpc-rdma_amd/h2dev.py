@@ -207,6 +207,18 @@ def _bind():
         lib.grdma_h2_group_pipe_window_updates.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Slice), u64, C.POINTER(u64)]
         lib.grdma_h2_group_pipe_window_update_bytes.restype = C.c_int64
         lib.grdma_h2_group_pipe_window_update_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, u64]
+        lib.grdma_h2_sw_create.restype = C.c_void_p
+        lib.grdma_h2_sw_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+        lib.grdma_h2_sw_destroy.argtypes = [C.c_void_p]
+        lib.grdma_h2_sw_intake.restype = C.c_int64
+        lib.grdma_h2_sw_intake.argtypes = [C.c_void_p, C.POINTER(u64)]
+        lib.grdma_h2_sw_frame.restype = C.c_int64
+        lib.grdma_h2_sw_frame.argtypes = [C.c_void_p, C.POINTER(H2Msg), C.POINTER(u64), u64, C.c_uint32, C.c_void_p, u64,
+                                          C.c_void_p, u64, C.POINTER(u64)]
+        lib.grdma_h2_sw_windows.restype = C.c_int
+        lib.grdma_h2_sw_windows.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_int64)]
+        lib.grdma_h2_sw_stats.restype = C.c_int
+        lib.grdma_h2_sw_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
         lib.grdma_job_hook_counts.restype = C.c_int   # (not in include/grdma_amd.h: the job's side of the pipes)
         lib.grdma_job_hook_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         _bound = True
@@ -670,6 +682,75 @@ class FlowControl:
         """does nothing while a pipe has the ledger attached (close the pipe first)"""
         if self.h and not getattr(self, "_pipe", None):
             self.lib.grdma_h2_fc_destroy(self.h)
+            self.h = None
+
+
+class SendWindows:
+    """Send flow control of one transport on the device (grdma_h2_sw): the peer's windows, fed from the parser's
+    deframings (intake), and grdma_h2_frame_messages under them (frame).  One per parser."""
+
+    INTAKE = ("window_updates", "conn_credit", "stream_credit", "settings", "violations", "first_offender", "live_entries",
+              "overflow")
+    FRAME = ("completed", "held", "slices", "hdr_bytes", "wire_bytes", "granted", "stall", "overflow")
+    STATS = ("intakes", "window_updates", "settings", "violations", "frame_calls", "bytes_sent", "peer_settings", "kernel_us")
+    BAD_INCREMENT, WINDOW_OVERFLOW, BAD_SETTINGS, LOST = 1, 2, 4, 8
+
+    def __init__(self, parser, initial_window=65535, conn_window=65535, peer_max_frame=16384):
+        self.lib = _bind()
+        self.parser = parser  # (kept alive)
+        self.h = self.lib.grdma_h2_sw_create(parser.h, initial_window, conn_window, peer_max_frame)
+        if not self.h:
+            raise GrdmaError("h2 send windows: " + (self.lib.grdma_last_error() or b"creation failed").decode())
+        self.last_result = None
+
+    def intake(self):
+        """takes in the parser's last standalone deframing -> result tuple (INTAKE); raises GrdmaError on a refusal or a
+        lost call -- the result of the failed call stays in .last_result"""
+        out = (u64 * 8)()
+        n = self.lib.grdma_h2_sw_intake(self.h, out)
+        self.last_result = tuple(int(x) for x in out)
+        check(n)
+        return self.last_result
+
+    def frame(self, msgs, progress, max_frame, slices_ptr, cap, hdr_ptr, hdr_cap):
+        """msgs: [(payload device ptr, len, stream_id, flags), ...]; progress: flow-controlled bytes already sent per
+        message -> ([(ptr, len), ...], result tuple (FRAME), progress after the call); raises GrdmaError on a refusal or
+        a capacity overflow -- the result of the failed call stays in .last_result, nothing was sent"""
+        n = len(msgs)
+        prog = (u64 * max(1, n))(*progress)
+        out = (u64 * 8)()
+        k = self.lib.grdma_h2_sw_frame(self.h, _msg_array(msgs), prog, n, max_frame, slices_ptr, cap, hdr_ptr, hdr_cap, out)
+        self.last_result = tuple(int(x) for x in out)
+        k = check(k)
+        raw = C.create_string_buffer(max(1, 16 * k))
+        if k:
+            check(self.lib.grdma_copy_to_host(raw, slices_ptr, 16 * k))
+        sl = [(int.from_bytes(raw.raw[16 * i:16 * i + 8], "little"), int.from_bytes(raw.raw[16 * i + 8:16 * i + 16], "little"))
+              for i in range(k)]
+        return sl, self.last_result, [int(x) for x in prog[:n]]
+
+    def windows(self, ids):
+        """the windows as they are: id 0 is the connection's, another id its stream's (may be negative)"""
+        ids = list(ids)
+        arr = (C.c_uint32 * max(1, len(ids)))(*ids)
+        out = (C.c_int64 * max(1, len(ids)))()
+        check(self.lib.grdma_h2_sw_windows(self.h, arr, len(ids), out))
+        return [int(x) for x in out[:len(ids)]]
+
+    def stats(self):
+        """dict of STATS plus `lost` (the sticky flag), `initial_window` and `max_frame` (the peer's settings)"""
+        out = (u64 * 8)()
+        check(self.lib.grdma_h2_sw_stats(self.h, out))
+        r = dict(zip(SendWindows.STATS, [int(x) for x in out]))
+        r["kernel_us"] /= 1e3  # (the ABI word is nanoseconds)
+        r["lost"] = bool(r["violations"] >> 63)
+        r["violations"] &= (1 << 63) - 1
+        r["initial_window"], r["max_frame"] = r["peer_settings"] & 0xffffffff, r.pop("peer_settings") >> 32
+        return r
+
+    def close(self):
+        if self.h:
+            self.lib.grdma_h2_sw_destroy(self.h)
             self.h = None
 
 

@@ -617,8 +617,9 @@ typedef struct grdma_h2_parser grdma_h2_parser;
  * RST_STREAM closes both; a stream leaves the map once both sides are closed
  * (grpc_chttp2_mark_stream_closed, chttp2_transport.cc:2194-2244) -- the caller reports the write
  * side with grdma_h2_parser_close_writes.  HPACK, SETTINGS, PING, GOAWAY and WINDOW_UPDATE payloads
- * are control plane and are skipped here.  That holds for INCOMING WINDOW_UPDATE frames; our own -- the credit for the
- * DATA bytes received -- are produced on the device by the window ledger (grdma_h2_fc below).
+ * are control plane and are skipped here.  The deframer skips INCOMING WINDOW_UPDATE and SETTINGS payloads too; the send
+ * windows (grdma_h2_sw below) read them from the arena by the deframer's events.  Our own WINDOW_UPDATE frames -- the
+ * credit for the DATA bytes received -- are produced on the device by the window ledger (grdma_h2_fc below).
  * grdma_h2_parser_create(prefix, max) = create_ex(prefix ? SERVER | FIRST_FRAME : 0, max, 0xffffffff, 0).
  * table_slots: power of two >= 16 (0 = 4096); at most table_slots / 2 streams are live at once. */
 grdma_h2_parser* grdma_h2_parser_create(int expect_client_prefix, uint32_t max_frame_size);
@@ -872,8 +873,9 @@ int64_t grdma_h2_pipe_slice_table(grdma_h2_pipe* p, grdma_slice* out, uint64_t c
  * (GRDMA_H2_FC_*), first violating stream, overflow}.
  * Many links: grdma_h2_fc_account_batch and grdma_h2_group_pipe_attach_flow_control below.
  * Not here: ledgers in the batch deframers (grdma_h2_deframe_batch and grdma_h2_deframe_messages_batch refuse a parser
- * that has a ledger), the frames inside a reply pipe's slice table, and the send half (the framers do not look at the
- * peer's windows). */
+ * that has a ledger) and the frames inside a reply pipe's slice table.  The send half -- the peer's windows and a framer
+ * under them -- is grdma_h2_sw below; the other framers (grdma_h2_frame_messages, the pipes, grdma_h2_reply_*) still do
+ * not look at the peer's windows. */
 enum grdma_h2_fc_violation { GRDMA_H2_FC_CONN_OVERFLOW = 1, GRDMA_H2_FC_STREAM_OVERFLOW = 2, GRDMA_H2_FC_LOST = 4 };
 typedef struct grdma_h2_fc grdma_h2_fc;
 /* stream_window 1 .. 2^31-1 (what SETTINGS announced per stream), conn_window 65535 .. 2^31-1 (kept announced),
@@ -921,6 +923,76 @@ typedef struct grdma_h2_fc_item {
   uint64_t hdr_cap;
 } grdma_h2_fc_item;
 int grdma_h2_fc_account_batch(const grdma_h2_fc_item* items, uint32_t n, uint64_t* out);
+
+/* ---- Send flow control on the device: the peer's windows (csrc/grdma_h2_sw.h) ----
+ * The send half of RFC 7540 6.9 for one transport.  The peer's windows live in device memory, are fed from the
+ * deframer's events (the peer's WINDOW_UPDATE and SETTINGS frames arrive on the parser of the same transport), and
+ * grdma_h2_sw_frame never sends a byte the peer has not allowed and carries the rest over.  The sending rule is the
+ * reference's DataSendContext::max_outgoing (writing.cc): min(peer MAX_FRAME_SIZE, stream window, connection window),
+ * a stream's window being peer INITIAL_WINDOW_SIZE + delta (delta = credit received - bytes sent; a SETTINGS change is
+ * one scalar).  A fixed policy, not a port of flow_control.cc.
+ * INTAKE (grdma_h2_sw_intake) takes in the LAST standalone deframing of the parser (grdma_h2_deframe or
+ * grdma_h2_deframe_messages): its device event list, its slice table and its receive arena, which must still hold the
+ * call's bytes.  It is ordered behind that call on the device; call it before the stream map is changed from the host.
+ *  1. A frame's payload is the run of PAYLOAD events behind its FRAME event; PAYLOAD events in front of the call's
+ *     first FRAME event continue the frame the previous call's end cut (the carry: at most 3 bytes of a WINDOW_UPDATE
+ *     or 5 of a SETTINGS entry, plus the values of the unfinished SETTINGS frame).
+ *  2. WINDOW_UPDATE: the increment is the 4 payload bytes.  0, or bit 31 set: GRDMA_H2_SW_BAD_INCREMENT, nothing is
+ *     added.  Stream 0 adds to the connection's window; another id adds to its stream's delta iff the parser's map
+ *     holds the stream -- judged at the END of the call, not at the frame, which differs only for a stream that opens
+ *     or leaves inside the call; otherwise the frame is ignored, as the reference ignores a stream it cannot look up.
+ *     A window that would pass 2^31 - 1 stays there (GRDMA_H2_SW_WINDOW_OVERFLOW); the call's sum is judged, with the
+ *     INITIAL_WINDOW_SIZE the call leaves, for the connection and the streams that got credit in the call.
+ *  3. SETTINGS (not an ACK): entries of 6 bytes, id 4 = INITIAL_WINDOW_SIZE (above 2^31 - 1: GRDMA_H2_SW_BAD_SETTINGS,
+ *     not taken), id 5 = MAX_FRAME_SIZE (outside 16384 .. 2^24 - 1: the same), other ids ignored.  The values take effect
+ *     when the frame's LAST byte is in (a frame cut by a call's end: in the call that completes it); of several frames
+ *     the last wins, value by value.
+ *  4. An entry whose stream the map no longer holds at the end of the call is dropped (RST_STREAM, END_STREAM on both
+ *     sides, grdma_h2_parser_close_writes); the same id opened again starts at delta 0.
+ *  5. A call that ended with a connection error takes nothing in.  A call whose event list overflowed: the sticky
+ *     GRDMA_H2_SW_LOST flag, -GRDMA_ERR_CAPACITY, overflow word 2, the carry is dropped, nothing else changes.  A
+ *     standalone deframing that was never taken in sets the flag too and drops the carry; the windows keep what they
+ *     know and every later result block carries the flag.
+ *  Result block: {WINDOW_UPDATE frames applied, connection credit added, stream credit added, SETTINGS frames applied,
+ *  violations (GRDMA_H2_SW_*), first offending stream (by event order; 0: the connection or a SETTINGS frame), live
+ *  entries, overflow}.  Returns the number of WINDOW_UPDATE frames applied.
+ * FRAMING (grdma_h2_sw_frame) is grdma_h2_frame_messages under the windows, for 1 .. 4096 messages.  progress[i] (in/out,
+ * host) is how many of message i's 5 + len flow-controlled bytes earlier calls have sent; the caller submits unfinished
+ * messages again, the messages of one stream in their order.  r_i = 5 + len_i - progress_i (0 is refused), mf =
+ * min(max_frame, peer MAX_FRAME_SIZE).  In table order each message gets min(r_i, its stream's window, the connection's
+ * window), and nothing once an earlier message of its stream is unfinished; a stream the map does not hold gets
+ * nothing.  (Computed as a_i = min(r_i, max(0, W_s - sum of r_j over earlier messages of s)), g_i = min(a_i, max(0, C -
+ * sum of a_j over earlier messages)).)  Message i puts bytes [progress_i, progress_i + g_i) of [5-byte header | payload]
+ * into DATA frames of mf bytes, the last one shorter, END_STREAM only on the frame that completes a message flagged so,
+ * never a frame of size 0; the slice list is what grpc_slice_buffer_move_first_no_ref and grpc_slice_buffer_add make of
+ * it on ONE outbuf per call.  Then delta_s and the connection's window go down by what was granted.  A slice or header
+ * cap too small: -GRDMA_ERR_CAPACITY, overflow word 1, the totals in the result block -- and NOTHING is written, no window
+ * moves, progress stays (unlike the ledger: these bytes were not sent).  A stream a call names has an entry (delta 0)
+ * from then on.  Result block: {messages completed, messages cut or held, slices, header-arena bytes, wire bytes,
+ * flow-controlled bytes granted, stall bits (1 = the connection's window, 2 = a stream's, 4 = an unknown stream),
+ * overflow}.  Returns the slice count.
+ * -GRDMA_ERR_INVALID or NULL (grdma_last_error says why): a second grdma_h2_sw on a parser, windows above 2^31 - 1, intake
+ * with no call yet or of the same call twice, a parser that is gone (destroy still works), n = 0 or above 4096, r_i = 0,
+ * max_frame 0 or >= 2^24, null, zero or misaligned (16 bytes) targets.
+ * Not here: intake of a pipe's or group pipe's steps and the windowed framer as a pipe's framing stage (a job's graph
+ * carries a fixed slice count per step; a window-cut step has another shape), the many-link batch forms, the reply
+ * framer under windows, SETTINGS ACK and the other settings, HPACK. */
+enum grdma_h2_sw_violation { GRDMA_H2_SW_BAD_INCREMENT = 1, GRDMA_H2_SW_WINDOW_OVERFLOW = 2, GRDMA_H2_SW_BAD_SETTINGS = 4,
+                             GRDMA_H2_SW_LOST = 8 };
+typedef struct grdma_h2_sw grdma_h2_sw;
+/* initial_window, conn_window 0 .. 2^31-1 (RFC 7540: 65535 each until the peer says otherwise), peer_max_frame
+ * 16384 .. 2^24-1 (16384).  One per parser.  Standalone deframings in front of the creation are not its business. */
+grdma_h2_sw* grdma_h2_sw_create(grdma_h2_parser* parser, uint32_t initial_window, uint32_t conn_window, uint32_t peer_max_frame);
+void grdma_h2_sw_destroy(grdma_h2_sw* sw);
+int64_t grdma_h2_sw_intake(grdma_h2_sw* sw, uint64_t out[8]);
+int64_t grdma_h2_sw_frame(grdma_h2_sw* sw, const grdma_h2_msg* msgs, uint64_t* progress, uint64_t n, uint32_t max_frame,
+                          grdma_slice* d_slices_out, uint64_t slices_cap, void* d_hdr_arena, uint64_t hdr_cap, uint64_t out[8]);
+/* the windows as they are: ids[i] = 0 is the connection's, another id its stream's (INITIAL_WINDOW_SIZE + delta) */
+int grdma_h2_sw_windows(grdma_h2_sw* sw, const uint32_t* ids, uint32_t n, int64_t* out);
+/* {intakes, WINDOW_UPDATE frames applied, SETTINGS frames applied, violations (bit 63: the LOST flag), framing calls,
+ * flow-controlled bytes sent, peer INITIAL_WINDOW_SIZE | peer MAX_FRAME_SIZE << 32, kernel time of the last call in
+ * NANOseconds (HIP events)} */
+int grdma_h2_sw_stats(grdma_h2_sw* sw, uint64_t out[8]);
 
 /* ---- HTTP/2 on several links of ONE job (the group pipe) ----
  * grdma_h2_pipe serves one link, and a job carries one set of kernels in front of and behind its rounds: a second
