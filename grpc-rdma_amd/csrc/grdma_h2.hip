@@ -254,6 +254,16 @@ static h2_stage h2_stage_sw_intake(h2sw_dev* d, const h2sw_call* d_call) {
 static h2_stage h2_stage_sw_frame(h2sw_dev* d) {
   return {h2_rec(k_h2_sw_plan, 1, H2SW_PLAN_THREADS, d), h2_rec(k_h2_sw_emit, H2SW_GRID, H2_EMIT_THREADS, d)};
 }
+// ... of n links in the same three and two launches: every link a share of the grid, the one-workgroup stages side by side
+static_assert(H2SW_LINKS_MAX == GRDMA_H2_BATCH_MAX, "the send windows' link table is the batch's");
+static h2_stage h2_stage_sw_intake_links(const h2sw_link* d_tab, uint32_t n) {
+  return {h2_rec(k_h2_links_sw_clear, n * H2SW_LINK_GRID, H2SW_THREADS, d_tab, n),
+          h2_rec(k_h2_links_sw_take, n * H2SW_LINK_GRID, H2SW_THREADS, d_tab, n),
+          h2_rec(k_h2_links_sw_finish, n, H2SW_THREADS, d_tab)};
+}
+static h2_stage h2_stage_sw_frame_links(const h2sw_link* d_tab, uint32_t n) {
+  return {h2_rec(k_h2_links_sw_plan, n, H2SW_PLAN_THREADS, d_tab), h2_rec(k_h2_links_sw_emit, H2SW_GRID, H2_EMIT_THREADS, d_tab, n)};
+}
 
 // st goes behind the parser's last deframing by a pipe (the parser state is handed from one deframing to the next),
 // unless that one was enqueued on st itself.  (Only pipe steps leave last_deframed, on a job's or a deframe stream: for

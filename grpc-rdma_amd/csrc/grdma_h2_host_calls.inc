@@ -1138,6 +1138,137 @@ int grdma_h2_sw_stats(grdma_h2_sw* s, uint64_t out[8]) {
   return 0;
 }
 
+// ---- the send windows of many transports: an intake in three launches, a framing in two (h2_stage_sw_*_links) --------
+// The batch block of the process holds [table | one call block per item] (the ledger batch's shape; a framing has no
+// call blocks) and goes up in one copy.  An item's message table, progress and configuration words go up into its own
+// grdma_h2_sw's device memory, and its result words and progress come down from there.  One call at a time, as the other
+// batch calls.
+int grdma_h2_sw_intake_batch(grdma_h2_sw* const* sws, uint32_t n_items, uint64_t* out) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!sws || !out || n_items == 0 || n_items > GRDMA_H2_BATCH_MAX)
+    return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: 1 .. GRDMA_H2_BATCH_MAX items and a result array");
+  for (uint32_t i = 0; i < n_items; i++) {
+    const grdma_h2_sw* s = sws[i];
+    if (!s) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: an item without send windows");
+    for (uint32_t k = 0; k < i; k++)
+      if (sws[k] == s) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: the same send windows twice");
+    const grdma_h2_parser* p = s->parser;
+    if (!p) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a parser is gone");
+    if (p->standalone_calls == 0) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a parser has deframed nothing yet");
+    if (s->taken == p->standalone_calls) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a call is taken in already");
+    if (p->standalone_ev_cap >= 0xfffffff0ull) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: event positions are 32 bits");
+  }
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  hipStream_t st = hc->stream;
+  const h2_fc_block L = h2_fc_block_layout(sizeof(h2sw_link), sizeof(h2sw_call), n_items);
+  if (!h2_batch_reserve(L.total, st)) return -GRDMA_ERR_HIP;
+  uint8_t* const d = g_batch.d;
+  std::vector<uint8_t> up(L.end, 0);
+  auto* tab = reinterpret_cast<h2sw_link*>(up.data() + L.tab);
+  auto* calls = reinterpret_cast<h2sw_call*>(up.data() + L.calls);
+  const h2_stage intake = h2_stage_sw_intake_links(reinterpret_cast<const h2sw_link*>(d + L.tab), n_items);
+  h2_call c{"h2 send windows batch: a launch was rejected", {{d, up.data(), up.size()}}, {}, {h2_all(intake)}, {}};
+  for (uint32_t i = 0; i < n_items; i++) {
+    const grdma_h2_sw* s = sws[i];
+    const grdma_h2_parser* p = s->parser;
+    calls[i] = h2sw_call{p->d_ev, p->d_res, p->d_sl, p->standalone_arena, p->standalone_ev_cap, p->standalone_nsl,
+                         p->standalone_calls > s->taken + 1 ? 1ull : 0ull};
+    tab[i].F = s->d;
+    tab[i].call = reinterpret_cast<const h2sw_call*>(d + L.calls) + i;
+    c.down.push_back({out + 8 * (size_t)i, reinterpret_cast<const uint8_t*>(s->d) + offsetof(h2sw_dev, res), 8 * sizeof(uint64_t)});
+  }
+  // behind the standalone deframings (same stream) and each parser's last deframing by a pipe: the intake reads the
+  // stream map that step may change
+  for (uint32_t i = 0; i < n_items; i++)
+    if (!h2_wait_parser(st, sws[i]->parser)) return -GRDMA_ERR_HIP;
+  if (int rc = h2_call_run(hc, &c)) return rc;
+  int ok = 0;
+  for (uint32_t i = 0; i < n_items; i++) {
+    grdma_h2_sw* s = sws[i];
+    s->last_ms = c.ms[0];  // (the batch's, repeated)
+    s->taken = s->parser->standalone_calls;
+    ok += out[8 * (size_t)i + H2SW_I_OVERFLOW] == 0;
+  }
+  return ok;
+}
+
+int grdma_h2_sw_frame_batch(const grdma_h2_sw_frame_item* items, uint32_t n_items, uint64_t* out) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!items || !out || n_items == 0 || n_items > GRDMA_H2_BATCH_MAX)
+    return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: 1 .. GRDMA_H2_BATCH_MAX items and a result array");
+  uint64_t n_msgs = 0;
+  for (uint32_t i = 0; i < n_items; i++) {
+    const grdma_h2_sw_frame_item& it = items[i];
+    if (!it.sw || !it.msgs || !it.progress)
+      return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: an item without send windows, message table or progress");
+    for (uint32_t k = 0; k < i; k++)
+      if (items[k].sw == it.sw) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: the same send windows twice");
+    if (!it.sw->parser) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a parser is gone");
+    if (it.nmsgs == 0 || it.nmsgs > H2_FRAME_ONE_MAX) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: 1 .. 4096 messages an item");
+    if (it.max_frame == 0 || it.max_frame >= (1u << 24)) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: max_frame outside 1 .. 2^24 - 1");
+    if (!it.d_slices_out || !it.slices_cap || !it.d_hdr_arena || !it.hdr_cap || ((uintptr_t)it.d_slices_out & 15) ||
+        ((uintptr_t)it.d_hdr_arena & 15))
+      return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a null, zero or misaligned slice table or header arena");
+    for (uint64_t m = 0; m < it.nmsgs; m++) {
+      if (it.msgs[m].len >= (1ull << 32)) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a message of 2^32 bytes or more");
+      if (it.progress[m] >= 5 + it.msgs[m].len) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a message with nothing left to send");
+    }
+    n_msgs += it.nmsgs;
+  }
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  hipStream_t st = hc->stream;
+  const h2_fc_block L = h2_fc_block_layout(sizeof(h2sw_link), 0, n_items);  // (a framing has no call blocks)
+  if (!h2_batch_reserve(L.total, st)) return -GRDMA_ERR_HIP;
+  uint8_t* const d = g_batch.d;
+  std::vector<uint8_t> up(L.end, 0);
+  auto* tab = reinterpret_cast<h2sw_link*>(up.data() + L.tab);
+  // every item's message table in the device's form and its progress after the call: [at[i], at[i] + nmsgs)
+  std::vector<grdma_h2_msg_dev> tmp(n_msgs);
+  std::vector<uint64_t> after(n_msgs), at(n_items);
+  const h2_stage framing = h2_stage_sw_frame_links(reinterpret_cast<const h2sw_link*>(d + L.tab), n_items);
+  h2_call c{"h2 send windows batch: a launch was rejected", {{d, up.data(), up.size()}}, {}, {h2_all(framing)}, {}};
+  uint64_t off = 0;
+  for (uint32_t i = 0; i < n_items; i++) {
+    const grdma_h2_sw_frame_item& it = items[i];
+    grdma_h2_sw* s = it.sw;
+    at[i] = off;
+    for (uint64_t m = 0; m < it.nmsgs; m++)
+      tmp[off + m] = grdma_h2_msg_dev{static_cast<const uint8_t*>(it.msgs[m].payload), it.msgs[m].len, it.msgs[m].stream_id, it.msgs[m].flags};
+    tab[i].F = s->d;
+    tab[i].call = nullptr;
+    // the item's framing call: the words of h2sw_dev from `msgs` to the state, from the host mirror
+    h2sw_dev& h = s->h;
+    h.nmsgs = it.nmsgs;
+    h.max_frame = it.max_frame;
+    h.out = reinterpret_cast<grdma_sge*>(it.d_slices_out);
+    h.cap = it.slices_cap;
+    h.hdr = static_cast<uint8_t*>(it.d_hdr_arena);
+    h.hdr_cap = it.hdr_cap;
+    c.up.push_back({s->d_msgs, tmp.data() + off, sizeof(grdma_h2_msg_dev) * it.nmsgs});
+    c.up.push_back({s->d_prog, it.progress, sizeof(uint64_t) * it.nmsgs});
+    c.up.push_back({reinterpret_cast<uint8_t*>(s->d) + offsetof(h2sw_dev, msgs), reinterpret_cast<const uint8_t*>(&h) + offsetof(h2sw_dev, msgs),
+                    offsetof(h2sw_dev, conn) - offsetof(h2sw_dev, msgs)});
+    c.down.push_back({out + 8 * (size_t)i, reinterpret_cast<const uint8_t*>(s->d) + offsetof(h2sw_dev, fres), 8 * sizeof(uint64_t)});
+    c.down.push_back({after.data() + off, s->d_prog + H2_FRAME_ONE_MAX, sizeof(uint64_t) * it.nmsgs});
+    off += it.nmsgs;
+  }
+  // behind each parser's last deframing by a pipe: the plan looks streams up in the map
+  for (uint32_t i = 0; i < n_items; i++)
+    if (!h2_wait_parser(st, items[i].sw->parser)) return -GRDMA_ERR_HIP;
+  if (int rc = h2_call_run(hc, &c)) return rc;
+  int ok = 0;
+  for (uint32_t i = 0; i < n_items; i++) {
+    const grdma_h2_sw_frame_item& it = items[i];
+    it.sw->last_ms = c.ms[0];  // (the batch's, repeated)
+    if (out[8 * (size_t)i + H2SW_F_OVERFLOW]) continue;  // (nothing was written, no window moved: progress stays as it is)
+    for (uint64_t m = 0; m < it.nmsgs; m++) it.progress[m] = after[at[i] + m];
+    ok++;
+  }
+  return ok;
+}
+
 // ---- the message assembler on many links (h2_stage_asm_links, csrc/grdma_h2_asm.h) ---------------------------------
 namespace {
 // the pinned table of grdma_h2_asm_release_batch with the event of its last upload (the table is reused: the next call

@@ -33,6 +33,8 @@
 //                    only then the windows move.
 //   k_h2_sw_emit     fixed grid, one wave per piece by static grid-stride; writes nothing after an overflow
 // Kernel boundaries are the only agent-scope hand-over; inside the one-workgroup kernels barriers only.
+// The same five stages over a table of links (k_h2_links_sw_*: the send windows of many transports in the same three and
+// two launches) stand at the end of the file; both families include their bodies from csrc/grdma_h2_sw_stage.inc.
 #ifndef GRDMA_H2_SW_H
 #define GRDMA_H2_SW_H
 #include "grdma_h2_kernels.h"
@@ -223,129 +225,29 @@ __device__ __forceinline__ void h2sw_walk(h2sw_dev* F, const h2sw_call* call, h2
   F->carry_out = f;
 }
 
+// The stages' bodies are source text (csrc/grdma_h2_sw_stage.inc); the k_h2_links_sw_* kernels at the end of this file
+// include the same text over a table of links.
+#define H2SW_BLK blockIdx.x
+#define H2SW_NBLK gridDim.x
 __global__ __launch_bounds__(H2SW_THREADS) void k_h2_sw_clear(h2sw_dev* F) {
-  const uint64_t t0 = (uint64_t)blockIdx.x * H2SW_THREADS + threadIdx.x, step = (uint64_t)gridDim.x * H2SW_THREADS;
-  h2sw_slot* neu = F->tabs[F->cur ^ 1u];
-  const h2sw_slot empty = {0, H2SW_NONE, 0, 0, 0, 0};
-  for (uint64_t s = t0; s <= F->tab_mask; s += step) neu[s] = empty;
-  if (t0 == 0) {
-    F->c_conn = 0;
-    F->c_first = ~0ull;
-    F->c_iws = F->c_mfs = 0;
-    F->c_applied = F->c_nset = F->c_bad_inc = F->c_bad_set = F->c_full = 0;
-    F->c_conn_first = H2SW_NONE;
-    F->carry_out.type = 0;
-  }
+#define H2SW_STAGE 1
+#include "grdma_h2_sw_stage.inc"
+#undef H2SW_STAGE
 }
 
 __global__ __launch_bounds__(H2SW_THREADS) void k_h2_sw_take(h2sw_dev* F, const h2sw_call* call) {
-  if (!h2sw_taken(call)) return;  // (uniform) nothing is taken in
-  const uint64_t n = call->res->nevents;
-  const uint64_t t0 = (uint64_t)blockIdx.x * H2SW_THREADS + threadIdx.x, step = (uint64_t)gridDim.x * H2SW_THREADS;
-  const uint32_t m = F->tab_mask;
-  const h2sw_slot* old = F->tabs[F->cur];
-  h2sw_slot* neu = F->tabs[F->cur ^ 1u];
-  // the entries of the streams the map holds behind the call
-  for (uint64_t s = t0; s <= m; s += step) {
-    const h2sw_slot e = old[s];
-    if (e.key == 0 || tab_find(F->gp->tab, F->gp->tab_mask, e.key) < 0) continue;
-    const uint32_t t = h2sw_claim(neu, m, e.key);
-    if (t == H2SW_NONE) atomicExch(&F->c_full, 1u);
-    else atomicAdd(reinterpret_cast<unsigned long long*>(&neu[t].delta), (unsigned long long)e.delta);
-  }
-  // the carried frame goes on over the PAYLOAD events in front of the first FRAME event (position 0)
-  if (t0 == 0 && F->carry.type != 0 && !call->skipped) h2sw_walk(F, call, neu, F->carry, 0, n, 0);
-  // a frame per thread (position: its event index + 1)
-  for (uint64_t i = t0; i < n; i += step) {
-    const grdma_h2_event e = call->ev[i];
-    if (e.kind != EV_FRAME || (e.b >> 8) != 0) continue;
-    if (e.a != FT_WINDOW_UPDATE && !(e.a == FT_SETTINGS && !(e.b & 1u))) continue;
-    const h2sw_frame f = {e.a, e.c, 0, 0, 0, 0, 0};
-    h2sw_walk(F, call, neu, f, i + 1, n, (uint32_t)i + 1u);
-  }
+#define H2SW_STAGE 2
+#include "grdma_h2_sw_stage.inc"
+#undef H2SW_STAGE
 }
 
 __global__ __launch_bounds__(H2SW_THREADS) void k_h2_sw_finish(h2sw_dev* F, const h2sw_call* call) {
-  __shared__ uint64_t s_wave[H2SW_THREADS / 64];
-  __shared__ unsigned long long s_first;
-  __shared__ uint32_t s_over;
-  const uint32_t tid = threadIdx.x;
-  const bool lost = h2sw_lost(call), taken = h2sw_taken(call);
-  const bool full = taken && F->c_full != 0;  // (cannot be: the map holds at most half as many streams as the table has slots)
-  const bool apply = taken && !full;
-  const uint32_t iws = (apply && F->c_iws) ? (uint32_t)F->c_iws : F->iws;
-  if (tid == 0) {
-    s_first = F->c_first;
-    s_over = 0;
-  }
-  __syncthreads();
-  // ---- per slot of the table that is current behind the call: the credit, the clamp; how many entries live
-  h2sw_slot* T = F->tabs[apply ? (F->cur ^ 1u) : F->cur];
-  uint64_t live = 0, added = 0;
-  for (uint32_t t = tid; t <= F->tab_mask; t += H2SW_THREADS) {
-    h2sw_slot sl = T[t];
-    if (sl.key == 0) continue;
-    live++;
-    if (apply && sl.credit) {
-      const long long old = (long long)iws + sl.delta;
-      long long nw = old + (long long)sl.credit;
-      if (nw > H2SW_MAXW) {
-        nw = old > H2SW_MAXW ? old : H2SW_MAXW;
-        atomicAdd(&s_over, 1u);
-        atomicMin(&s_first, ((unsigned long long)sl.first << 32) | sl.key);
-      }
-      added += (uint64_t)(nw - old);
-      sl.delta = nw - (long long)iws;
-    }
-    if (apply) {
-      sl.credit = 0;
-      sl.first = H2SW_NONE;
-      T[t] = sl;
-    }
-  }
-  uint64_t n_live, n_added;
-  block_excl_scan(live, s_wave, &n_live);
-  block_excl_scan(added, s_wave, &n_added);
-  if (tid != 0) return;
-  if (call->skipped || lost || full) F->lost = 1;
-  if (call->skipped || lost) F->carry.type = 0;  // (its frame's end was not seen)
-  F->st_intakes++;
-  for (int k = 0; k < 8; k++) F->res[k] = 0;
-  F->res[H2SW_I_LIVE] = n_live;
-  F->res[H2SW_I_VIOLATIONS] = F->lost ? H2SW_V_LOST : 0;
-  if (lost || full) F->res[H2SW_I_OVERFLOW] = 2;
-  if (!apply) return;
-  // ---- the connection, the settings, the carry
-  uint64_t viol = 0, conn_added = 0, nviol = F->c_bad_inc + F->c_bad_set + s_over;
-  unsigned long long first = s_first;
-  if (F->c_conn) {
-    const long long old = F->conn;
-    long long nw = old + (long long)F->c_conn;  // (increments only add inside an intake: judging the call's sum is exact)
-    if (nw > H2SW_MAXW) {
-      nw = H2SW_MAXW;
-      nviol++;
-      viol |= H2SW_V_WINDOW;
-      const unsigned long long o = (unsigned long long)F->c_conn_first << 32;
-      if (o < first) first = o;
-    }
-    conn_added = (uint64_t)(nw - old);
-    F->conn = nw;
-  }
-  if (F->c_iws) F->iws = (uint32_t)F->c_iws;
-  if (F->c_mfs) F->pmf = (uint32_t)F->c_mfs;
-  F->carry = F->carry_out;
-  F->cur ^= 1u;
-  viol |= (F->c_bad_inc ? H2SW_V_INCREMENT : 0) | (F->c_bad_set ? H2SW_V_SETTINGS : 0) | (s_over ? H2SW_V_WINDOW : 0);
-  F->res[H2SW_I_UPDATES] = F->c_applied;
-  F->res[H2SW_I_CONN] = conn_added;
-  F->res[H2SW_I_STREAMS] = n_added;
-  F->res[H2SW_I_SETTINGS] = F->c_nset;
-  F->res[H2SW_I_VIOLATIONS] |= viol;
-  F->res[H2SW_I_FIRST] = first == ~0ull ? 0 : (uint32_t)first;
-  F->st_updates += F->c_applied;
-  F->st_settings += F->c_nset;
-  F->st_violations += nviol;
+#define H2SW_STAGE 3
+#include "grdma_h2_sw_stage.inc"
+#undef H2SW_STAGE
 }
+#undef H2SW_BLK
+#undef H2SW_NBLK
 
 // ---------------------------------------------------------------------------------------------------- the framer
 // The layout of a piece is the layout of a message (walk_message, h2_emit_message) started at an offset and ended by the
@@ -489,198 +391,125 @@ __device__ __forceinline__ uint64_t h2sw_block_scan(uint64_t v, uint64_t* ws, ui
 }
 
 __global__ __launch_bounds__(H2SW_PLAN_THREADS) void k_h2_sw_plan(h2sw_dev* F) {
-  __shared__ uint64_t s_wave[H2SW_PLAN_THREADS / 64];
-  // the tiles' aggregates of a block of messages: per wave the streams of its tile with their remaining bytes
-  __shared__ uint64_t s_agg[H2SW_PLAN_THREADS / 64][64];
-  __shared__ uint32_t s_key[H2SW_PLAN_THREADS / 64][64];
-  __shared__ uint32_t s_cnt[H2SW_PLAN_THREADS / 64];
-  __shared__ uint32_t s_stall[3];
-  const uint32_t tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  h2sw_slot* T = F->tabs[F->cur];
-  const uint32_t m = F->tab_mask;
-  const uint64_t n = F->nmsgs;
-  const uint32_t mf = (uint32_t)(F->max_frame < F->pmf ? F->max_frame : F->pmf);
-  const long long C = F->conn, iws = (long long)F->iws;
-  const grdma_h2_msg_dev* msgs = F->msgs;
-  h2sw_piece* pieces = F->pieces;
-  if (tid < 3) s_stall[tid] = 0;
-  __syncthreads();
-  // ---- the grant, the granted pieces compacted in table order
-  uint64_t base_a = 0, kept = 0, granted = 0, done = 0;
-  for (uint64_t m0 = 0; m0 < n; m0 += H2SW_PLAN_THREADS) {
-    const uint64_t i = m0 + tid;
-    grdma_h2_msg_dev msg{nullptr, 0, 0, 0};
-    uint64_t p = 0, r = 0;
-    uint32_t slot = H2SW_NONE;
-    if (i < n) {
-      msg = msgs[i];
-      p = F->prog_in[i];
-      r = 5 + msg.len - p;  // (the host has refused r == 0)
-    }
-    // Per distinct stream of my wave's tile (ballot, readlane, a masked scan, as k_h2_asm_tiles): ONE lane looks the
-    // stream up and claims its slot -- a stream the map does not hold gets nothing; one it holds has an entry from
-    // here on, delta 0 until it moves -- and the remaining bytes of the tile's earlier messages of the stream are summed.
-    uint64_t x = 0, agg = 0;
-    bool closes = false;  // the tile's last message of its stream
-    uint64_t rem = __ballot(msg.stream_id != 0);
-    while (rem) {
-      const int first = __builtin_ctzll(rem);
-      const uint32_t k = (uint32_t)__builtin_amdgcn_readlane((int)msg.stream_id, first);
-      const bool mem = msg.stream_id == k;
-      const uint64_t mm = __ballot(mem);
-      uint32_t sk = H2SW_NONE;
-      if (lane == first && tab_find(F->gp->tab, F->gp->tab_mask, k) >= 0) sk = h2sw_claim(T, m, k);
-      sk = (uint32_t)__builtin_amdgcn_readlane((int)sk, first);
-      if (sk != H2SW_NONE) {  // (uniform)
-        const uint64_t incl = wave_incl_scan(mem ? r : 0, lane);
-        if (mem) {
-          slot = sk;
-          x = incl - r;
-          if (lane == 63 - __builtin_clzll(mm)) {
-            closes = true;
-            agg = incl;
-          }
-        }
-      }
-      rem &= ~mm;
-    }
-    const uint32_t key = slot != H2SW_NONE ? msg.stream_id : 0;
-    if (i < n) F->slot_of[i] = closes ? (slot | 0x80000000u) : slot;  // (bit 31: the one that settles the tile's sum below)
-    // the stream's window, and the remaining bytes of its messages in the blocks in front (the slot carries them)
-    long long delta = 0;
-    uint64_t c = 0;
-    if (key) {
-      delta = T[slot].delta;
-      c = T[slot].run;
-    }
-    // ... and in the earlier tiles of the block: every tile lists its streams' sums in LDS
-    const uint64_t cm = __ballot(closes);
-    if (closes) {
-      const uint32_t at = (uint32_t)__builtin_popcountll(cm & ((1ull << lane) - 1ull));
-      s_key[wave][at] = key;
-      s_agg[wave][at] = agg;
-    }
-    if (lane == 0) s_cnt[wave] = (uint32_t)__builtin_popcountll(cm);
-    __syncthreads();
-    if (key) {
-      for (int w = 0; w < wave; w++) {
-        const uint32_t cnt = s_cnt[w];
-        for (uint32_t j = 0; j < cnt; j++)
-          if (s_key[w][j] == key) c += s_agg[w][j];
-      }
-      if (closes) {  // the block's last message of the stream hands the sum to the next block
-        bool later = false;
-        for (int w = wave + 1; w < H2SW_PLAN_THREADS / 64; w++) {
-          const uint32_t cnt = s_cnt[w];
-          for (uint32_t j = 0; j < cnt; j++) later = later || s_key[w][j] == key;
-        }
-        if (!later) T[slot].run = c + agg;
-      }
-    }
-    uint64_t a = 0;
-    if (key) {
-      const long long room = iws + delta - (long long)(c + x);
-      a = room <= 0 ? 0 : ((uint64_t)room < r ? (uint64_t)room : r);
-    }
-    uint64_t tot_a;
-    const uint64_t pre = base_a + h2sw_block_scan(a, s_wave, &tot_a);
-    base_a += tot_a;
-    const long long croom = C - (long long)pre;
-    const uint64_t g = croom <= 0 ? 0 : ((uint64_t)croom < a ? (uint64_t)croom : a);
-    if (i < n) {
-      if (!key) atomicAdd(&s_stall[2], 1u);
-      else if (a < r) atomicAdd(&s_stall[1], 1u);
-      if (g < a) atomicAdd(&s_stall[0], 1u);
-      F->prog_out[i] = p + g;
-    }
-    // what the tile grants per stream, added to the stream's slot by the tile's last message of the stream
-    uint64_t rem_g = __ballot(key != 0);
-    while (rem_g) {
-      const int first = __builtin_ctzll(rem_g);
-      const uint32_t k = (uint32_t)__builtin_amdgcn_readlane((int)key, first);
-      const bool mem = key == k;
-      const uint64_t mm = __ballot(mem);
-      const uint64_t incl = wave_incl_scan(mem ? g : 0, lane);
-      if (mem && closes && incl) atomicAdd(&T[slot].sent, (unsigned long long)incl);
-      rem_g &= ~mm;
-    }
-    uint64_t tot;
-    const uint64_t xk = h2sw_block_scan(g ? 1 : 0, s_wave, &tot);
-    if (g) pieces[kept + xk] = h2sw_piece{msg.payload, msg.len, msg.stream_id, msg.flags, p, g};
-    kept += tot;
-    h2sw_block_scan(g, s_wave, &tot);
-    granted += tot;
-    h2sw_block_scan((i < n && g == r) ? 1 : 0, s_wave, &tot);
-    done += tot;
-  }
-  __syncthreads();  // the piece table is complete: sizes look at a piece's neighbours
-  // ---- sizes and positions over the pieces (the loop of k_h2_frame_index)
-  uint64_t base_sl = 0, base_hdr = 0, base_wire = 0;
-  for (uint64_t k0 = 0; k0 < kept; k0 += H2SW_PLAN_THREADS) {
-    const uint64_t k = k0 + tid;
-    uint64_t n_sl = 0, n_hdr = 0, n_wire = 0;
-    uint32_t mode = 0;
-    if (k < kept) h2sw_piece_size(pieces, k, mf, &n_sl, &n_hdr, &n_wire, &mode);
-    uint64_t tot_sl, tot_hdr, tot_wire;
-    const uint64_t x_sl = h2sw_block_scan(n_sl, s_wave, &tot_sl);
-    const uint64_t x_hdr = h2sw_block_scan(n_hdr, s_wave, &tot_hdr);
-    h2sw_block_scan(n_wire, s_wave, &tot_wire);
-    if (k < kept) {
-      grdma_h2_msg_pos q;
-      q.sl = base_sl + x_sl;
-      q.hdr = base_hdr + x_hdr;
-      q.mode = mode;
-      q.pad = 0;
-      F->pos[k] = q;
-    }
-    base_sl += tot_sl;
-    base_hdr += tot_hdr;
-    base_wire += tot_wire;
-  }
-  const bool over = base_sl > F->cap || base_hdr > F->hdr_cap;  // (uniform: the totals are every thread's)
-  // ---- the windows move only when the bytes go out; the slots' scratch words go back to 0 either way.  Per tile and
-  // stream (the thread that added the tile's sum: its own word of the first pass), no sweep over the table: the first
-  // one to exchange a stream's sum for 0 moves the stream's window by it.
-  for (uint64_t i = tid; i < n; i += H2SW_PLAN_THREADS) {
-    const uint32_t v = F->slot_of[i];
-    if (v == H2SW_NONE || !(v >> 31)) continue;
-    const uint32_t slot = v & 0x7fffffffu;
-    T[slot].run = 0;
-    const unsigned long long sent = atomicExch(&T[slot].sent, 0ull);
-    if (!over && sent) atomicAdd(reinterpret_cast<unsigned long long*>(&T[slot].delta), 0ull - sent);
-  }
-  if (tid == 0) {
-    if (!over) {
-      F->conn = C - (long long)granted;
-      F->st_sent += granted;
-    }
-    F->st_frame_calls++;
-    F->npieces = kept;
-    F->fres[H2SW_F_DONE] = over ? 0 : done;
-    F->fres[H2SW_F_HELD] = over ? n : n - done;
-    F->fres[H2SW_F_SLICES] = base_sl;
-    F->fres[H2SW_F_HDR] = base_hdr;
-    F->fres[H2SW_F_WIRE] = base_wire;
-    F->fres[H2SW_F_GRANTED] = over ? 0 : granted;
-    F->fres[H2SW_F_STALL] = (s_stall[0] ? H2SW_STALL_CONN : 0) | (s_stall[1] ? H2SW_STALL_STREAM : 0) | (s_stall[2] ? H2SW_STALL_UNKNOWN : 0);
-    F->fres[H2SW_F_OVERFLOW] = over ? 1 : 0;
-  }
+#define H2SW_STAGE 4
+#include "grdma_h2_sw_stage.inc"
+#undef H2SW_STAGE
 }
 
 __global__ __launch_bounds__(H2_EMIT_THREADS) void k_h2_sw_emit(const h2sw_dev* F) {
-  if (F->fres[H2SW_F_OVERFLOW]) return;  // (nothing half-written)
-  const uint64_t n = F->npieces;
+#define H2SW_STAGE 5
+#include "grdma_h2_sw_stage.inc"
+#undef H2SW_STAGE
+}
+
+// ---- the five kernels over a table of L <= H2SW_LINKS_MAX links (the send windows of a batch): three launches an
+// intake and two a framing however many links.  Nothing is shared between the links -- every entry has its own h2sw_dev
+// (tables, piece and position scratch, accumulators, result blocks) and its own call block -- so every atomic stays on
+// the link's own h2sw_dev and tables, and a lost call, a connection error, a skipped deframing, a cap overflow or an empty
+// event list stay with their link.  The entry is loaded with a uniform index: it sits in scalar registers, as the single
+// kernels' parameters do.
+//   clear, take   link l owns the workgroups [l * H2SW_LINK_GRID, (l + 1) * H2SW_LINK_GRID): the single kernel's
+//                 grid-stride inside that share; the share's first thread clears the accumulators and continues the
+//                 carried frame
+//   finish, plan  grid L: workgroup l is the one workgroup of link l -- L finishes, L plans side by side
+//   emit          a fixed grid; the pieces of ALL links by one static grid-stride, so a stalled or overflowed link idles
+//                 nobody: every workgroup builds the exclusive prefix of the links' piece counts in LDS (one block scan,
+//                 one link per thread; a link whose result block reports an overflow contributes 0 and gets nothing
+//                 written), a wave finds the link of its piece by binary search over it (wave-uniform: the link's
+//                 pointers stay scalar) and lays the piece out with that link's tables and frame size.  A piece's run of
+//                 inlined slices (mode 2) ends with its link's last piece: npieces is the link's.
+// The kernel boundary is the only agent-scope hand-over; inside the finish and the plan barriers only.
+#define H2SW_LINKS_MAX 256  // (= GRDMA_H2_BATCH_MAX, include/grdma_amd.h; one thread per link in the emit's block scan)
+#ifdef GRDMA_WAVE_EMU
+#define H2SW_LINK_GRID 2
+#else
+#define H2SW_LINK_GRID 8    // 2048 threads per link: an event or a slot per thread up to 2048, grid-stride beyond
+#endif
+struct h2sw_link {
+  h2sw_dev* F;
+  const h2sw_call* call;  // (an intake's; a framing leaves it NULL)
+};
+static_assert(H2SW_LINKS_MAX <= H2_EMIT_THREADS, "k_h2_links_sw_emit scans one link per thread");
+// The table is written by the host in front of the launch and only read on the device, so it is read as constant
+// memory (as H2FC_ENTRY, csrc/grdma_h2_fc.h): pointers loaded from there are taken as global ones, and the link
+// kernels address as their single twins do.
+#ifdef GRDMA_WAVE_EMU
+#define H2SW_ENTRY(tab, l) ((tab)[l])
+#else
+#define H2SW_ENTRY(tab, l) (((const __attribute__((address_space(4))) h2sw_link*)(tab))[l])
+#endif
+
+// (a link's share of the grid)
+#define H2SW_BLK (blockIdx.x % H2SW_LINK_GRID)
+#define H2SW_NBLK H2SW_LINK_GRID
+__global__ __launch_bounds__(H2SW_THREADS) void k_h2_links_sw_clear(const h2sw_link* __restrict__ tab, uint32_t nlinks) {
+  const uint32_t l = blockIdx.x / H2SW_LINK_GRID;
+  if (l >= nlinks) return;
+  h2sw_dev* const F = H2SW_ENTRY(tab, l).F;
+#define H2SW_STAGE 1
+#include "grdma_h2_sw_stage.inc"
+#undef H2SW_STAGE
+}
+
+__global__ __launch_bounds__(H2SW_THREADS) void k_h2_links_sw_take(const h2sw_link* __restrict__ tab, uint32_t nlinks) {
+  const uint32_t l = blockIdx.x / H2SW_LINK_GRID;
+  if (l >= nlinks) return;
+  h2sw_dev* const F = H2SW_ENTRY(tab, l).F;
+  const h2sw_call* const call = H2SW_ENTRY(tab, l).call;
+#define H2SW_STAGE 2
+#include "grdma_h2_sw_stage.inc"
+#undef H2SW_STAGE
+}
+
+__global__ __launch_bounds__(H2SW_THREADS) void k_h2_links_sw_finish(const h2sw_link* __restrict__ tab) {
+  h2sw_dev* const F = H2SW_ENTRY(tab, blockIdx.x).F;
+  const h2sw_call* const call = H2SW_ENTRY(tab, blockIdx.x).call;
+#define H2SW_STAGE 3
+#include "grdma_h2_sw_stage.inc"
+#undef H2SW_STAGE
+}
+#undef H2SW_BLK
+#undef H2SW_NBLK
+
+__global__ __launch_bounds__(H2SW_PLAN_THREADS) void k_h2_links_sw_plan(const h2sw_link* __restrict__ tab) {
+  h2sw_dev* const F = H2SW_ENTRY(tab, blockIdx.x).F;
+#define H2SW_STAGE 4
+#include "grdma_h2_sw_stage.inc"
+#undef H2SW_STAGE
+}
+
+__global__ __launch_bounds__(H2_EMIT_THREADS) void k_h2_links_sw_emit(const h2sw_link* __restrict__ tab, uint32_t nlinks) {
+  __shared__ uint64_t s_pre[H2SW_LINKS_MAX + 1];  // exclusive prefix of the links' pieces; [nlinks]: the total
+  __shared__ uint64_t s_wave[H2_EMIT_THREADS / 64];
   const int lane = threadIdx.x & 63;
+  const uint32_t wv = uni32(threadIdx.x >> 6);
+  uint64_t mine = 0;
+  if (threadIdx.x < nlinks) {
+    const h2sw_dev* const F = tab[threadIdx.x].F;
+    if (!F->fres[H2SW_F_OVERFLOW]) mine = F->npieces;  // (nothing half-written)
+  }
+  const uint64_t incl = wave_incl_scan(mine, lane);
+  if (lane == 63) s_wave[wv] = incl;
+  __syncthreads();
+  uint64_t base = 0;
+  for (uint32_t w = 0; w < wv; w++) base += s_wave[w];
+  if (threadIdx.x == 0) s_pre[0] = 0;
+  s_pre[threadIdx.x + 1] = base + incl;
+  __syncthreads();
+  const uint64_t total = s_pre[nlinks];
   const uint64_t waves = (uint64_t)gridDim.x * (H2_EMIT_THREADS / 64);
-  const h2sw_piece* pieces = F->pieces;
-  const grdma_h2_msg_pos* pos = F->pos;
-  const uint32_t mf = (uint32_t)(F->max_frame < F->pmf ? F->max_frame : F->pmf);
-  grdma_sge* out = F->out;
-  uint8_t* hdr = F->hdr;
-  const uint64_t cap = F->cap, hdr_cap = F->hdr_cap;
-  for (uint64_t k = (uint64_t)blockIdx.x * (H2_EMIT_THREADS / 64) + (threadIdx.x >> 6); k < n; k += waves)
-    h2sw_emit_piece(pieces, k, n, mf, out, cap, hdr, hdr_cap, pos[k], lane);
+  for (uint64_t g = (uint64_t)blockIdx.x * (H2_EMIT_THREADS / 64) + wv; g < total; g += waves) {
+    uint32_t ll = 0, lh = nlinks;  // the last link whose prefix <= g (a link without pieces shares its prefix with the next)
+    while (lh - ll > 1) {
+      const uint32_t mid = (ll + lh) / 2;
+      if (uni64(s_pre[mid]) <= g) ll = mid;
+      else lh = mid;
+    }
+    const h2sw_dev* const F = H2SW_ENTRY(tab, ll).F;
+    const uint64_t k = g - uni64(s_pre[ll]);
+    const uint32_t mf = (uint32_t)(F->max_frame < F->pmf ? F->max_frame : F->pmf);
+    h2sw_emit_piece(F->pieces, k, F->npieces, mf, F->out, F->cap, F->hdr, F->hdr_cap, F->pos[k], lane);
+  }
 }
 
 }  // namespace

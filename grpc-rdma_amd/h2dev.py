@@ -54,6 +54,12 @@ class H2FcItem(C.Structure):
                 ("hdr_cap", u64)]
 
 
+class H2SwFrameItem(C.Structure):
+    _fields_ = [("sw", C.c_void_p), ("msgs", C.POINTER(H2Msg)), ("progress", C.POINTER(u64)), ("nmsgs", u64),
+                ("max_frame", C.c_uint32), ("pad", C.c_uint32), ("d_slices_out", C.c_void_p), ("slices_cap", u64),
+                ("d_hdr_arena", C.c_void_p), ("hdr_cap", u64)]
+
+
 MSG_OK, MSG_TOO_LARGE, MSG_NO_SPACE, MSG_TRUNCATED = 0, 1, 2, 3
 SYNC_KEYS = ("framed", "frame_overflow", "events", "deframe_overflow", "parsed", "h2_error", "frame_us", "deframe_us",
              "bulk_steps", "bulk_frames", "t_wait", "t_bulk", "t_total", "t_serial")
@@ -219,6 +225,10 @@ def _bind():
         lib.grdma_h2_sw_windows.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_int64)]
         lib.grdma_h2_sw_stats.restype = C.c_int
         lib.grdma_h2_sw_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
+        lib.grdma_h2_sw_intake_batch.restype = C.c_int
+        lib.grdma_h2_sw_intake_batch.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(u64)]
+        lib.grdma_h2_sw_frame_batch.restype = C.c_int
+        lib.grdma_h2_sw_frame_batch.argtypes = [C.POINTER(H2SwFrameItem), C.c_uint32, C.POINTER(u64)]
         lib.grdma_job_hook_counts.restype = C.c_int   # (not in include/grdma_amd.h: the job's side of the pipes)
         lib.grdma_job_hook_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         _bound = True
@@ -787,6 +797,63 @@ def account_batch(items):
             check(lib.grdma_copy_to_host(buf, ptr, ln))
             wire += buf.raw[:ln]
         res.append((sl, r, wire))
+    return res
+
+
+def intake_batch(sws):
+    """SendWindows.intake for many transports in three launches (grdma_h2_sw_intake_batch).  sws: distinct SendWindows;
+    each takes in the last standalone deframing of its own parser.  -> per item its result tuple (SendWindows.INTAKE);
+    an item whose call was lost reports for itself (overflow word 2, the LOST bit): its tuple is in the list, the
+    others are exact.  The result tuples also land in each object's .last_result.  Raises GrdmaError on a refusal."""
+    lib = _bind()
+    n = len(sws)
+    arr = (C.c_void_p * max(1, n))(*[s.h if s is not None else None for s in sws])
+    out = (u64 * (8 * max(1, n)))()
+    check(lib.grdma_h2_sw_intake_batch(arr, n, out))
+    res = []
+    for i, s in enumerate(sws):
+        s.last_result = tuple(int(x) for x in out[8 * i:8 * i + 8])
+        res.append(s.last_result)
+    return res
+
+
+def frame_windowed_batch(items):
+    """SendWindows.frame for many transports in two launches (grdma_h2_sw_frame_batch).  items: [(SendWindows, msgs,
+    progress, max_frame, slices device ptr, slices cap, header arena device ptr, header cap), ...] with distinct send
+    windows, msgs and progress as SendWindows.frame takes them.  -> per item ([(ptr, len), ...], result tuple
+    (SendWindows.FRAME), progress after the call); an item whose cap overflowed reports for itself: its result tuple and
+    None -- nothing of it was written, no window of it moved.  The result tuples also land in each object's
+    .last_result.  Raises GrdmaError on a refusal."""
+    lib = _bind()
+    n = len(items)
+    arr = (H2SwFrameItem * max(1, n))()
+    keep = []  # (the arrays the items point to)
+    for i, (sw, msgs, progress, max_frame, sl, cap, hdr, hdr_cap) in enumerate(items):
+        marr = _msg_array(msgs) if msgs is not None else None
+        prog = (u64 * max(1, len(progress)))(*progress) if progress is not None else None
+        keep.append((marr, prog))
+        arr[i].sw = sw.h if sw is not None else None
+        arr[i].msgs = marr
+        arr[i].progress = prog
+        arr[i].nmsgs = len(msgs) if msgs is not None else 0
+        arr[i].max_frame = max_frame
+        arr[i].d_slices_out, arr[i].slices_cap, arr[i].d_hdr_arena, arr[i].hdr_cap = sl, cap, hdr, hdr_cap
+    out = (u64 * (8 * max(1, n)))()
+    check(lib.grdma_h2_sw_frame_batch(arr, n, out))
+    res = []
+    for i, (sw, msgs, _, _, sl_ptr, _, _, _) in enumerate(items):
+        r = tuple(int(x) for x in out[8 * i:8 * i + 8])
+        sw.last_result = r
+        if r[7]:
+            res.append((r, None))
+            continue
+        k = r[2]
+        raw = C.create_string_buffer(max(1, 16 * k))
+        if k:
+            check(lib.grdma_copy_to_host(raw, sl_ptr, 16 * k))
+        sl = [(int.from_bytes(raw.raw[16 * j:16 * j + 8], "little"), int.from_bytes(raw.raw[16 * j + 8:16 * j + 16], "little"))
+              for j in range(k)]
+        res.append((sl, r, [int(x) for x in keep[i][1][:len(msgs)]]))
     return res
 
 

@@ -975,8 +975,8 @@ int grdma_h2_fc_account_batch(const grdma_h2_fc_item* items, uint32_t n, uint64_
  * with no call yet or of the same call twice, a parser that is gone (destroy still works), n = 0 or above 4096, r_i = 0,
  * max_frame 0 or >= 2^24, null, zero or misaligned (16 bytes) targets.
  * Not here: intake of a pipe's or group pipe's steps and the windowed framer as a pipe's framing stage (a job's graph
- * carries a fixed slice count per step; a window-cut step has another shape), the many-link batch forms, the reply
- * framer under windows, SETTINGS ACK and the other settings, HPACK. */
+ * carries a fixed slice count per step; a window-cut step has another shape), the reply framer under windows, SETTINGS
+ * ACK and the other settings, HPACK.  (The many-link batch forms: grdma_h2_sw_intake_batch / _frame_batch below.) */
 enum grdma_h2_sw_violation { GRDMA_H2_SW_BAD_INCREMENT = 1, GRDMA_H2_SW_WINDOW_OVERFLOW = 2, GRDMA_H2_SW_BAD_SETTINGS = 4,
                              GRDMA_H2_SW_LOST = 8 };
 typedef struct grdma_h2_sw grdma_h2_sw;
@@ -993,6 +993,38 @@ int grdma_h2_sw_windows(grdma_h2_sw* sw, const uint32_t* ids, uint32_t n, int64_
  * flow-controlled bytes sent, peer INITIAL_WINDOW_SIZE | peer MAX_FRAME_SIZE << 32, kernel time of the last call in
  * NANOseconds (HIP events)} */
 int grdma_h2_sw_stats(grdma_h2_sw* sw, uint64_t out[8]);
+/* grdma_h2_sw_intake for n send windows (1 .. GRDMA_H2_BATCH_MAX) in the same three launches (k_h2_links_sw_clear /
+ * _take / _finish): every sws[i] takes in the last standalone deframing of its OWN parser, exactly as the single call
+ * does (rules 1 .. 5 above, the skipped deframing judged per item), ordered behind it and behind every parser's last
+ * pipe step.  out: 8 result words per item, in item order.  What differs from the single call: an item's lost call
+ * (sticky GRDMA_H2_SW_LOST, overflow word 2, carry dropped) is reported in its own words only, the other items are
+ * exact; the return value is the number of items whose overflow word is 0, or a negative error.  -GRDMA_ERR_INVALID
+ * (nothing runs, nothing changes, grdma_last_error says why): n outside the range, a NULL array, a NULL item or one
+ * listed twice, an item whose parser is gone, has deframed nothing yet, whose last call is taken in already or whose
+ * event capacity is 0xfffffff0 or more (event positions are 32 bits). */
+int grdma_h2_sw_intake_batch(grdma_h2_sw* const* sws, uint32_t n, uint64_t* out);
+/* grdma_h2_sw_frame for n send windows (1 .. GRDMA_H2_BATCH_MAX) in the same two launches (k_h2_links_sw_plan / _emit):
+ * every item frames its own message table under its own windows into its own targets, exactly as the single call does.
+ * out: 8 result words per item, in item order.  What differs from the single call: an item whose slice or header cap is
+ * too small (overflow word 1) writes nothing, moves no window and keeps its progress, and the other items are framed;
+ * the return value is the number of items without overflow, or a negative error.  -GRDMA_ERR_INVALID (nothing runs,
+ * nothing changes): n outside the range, a NULL array, an item without send windows or with the same ones as another
+ * (two plans would share their tables), a parser that is gone, and per item what grdma_h2_sw_frame refuses: no message
+ * table or progress, nmsgs 0 or above 4096, max_frame 0 or >= 2^24, a message of 2^32 bytes or more, progress[i] >= 5 +
+ * len, null, zero or misaligned (16 bytes) targets. */
+typedef struct grdma_h2_sw_frame_item {
+  grdma_h2_sw* sw;            /* distinct */
+  const grdma_h2_msg* msgs;   /* host message table of the item */
+  uint64_t* progress;         /* in/out, host: as grdma_h2_sw_frame's */
+  uint64_t nmsgs;
+  uint32_t max_frame;
+  uint32_t pad;
+  grdma_slice* d_slices_out;  /* device slice table of the item */
+  uint64_t slices_cap;
+  void* d_hdr_arena;          /* device header arena of the item, 32 bytes per frame */
+  uint64_t hdr_cap;
+} grdma_h2_sw_frame_item;
+int grdma_h2_sw_frame_batch(const grdma_h2_sw_frame_item* items, uint32_t n, uint64_t* out);
 
 /* ---- HTTP/2 on several links of ONE job (the group pipe) ----
  * grdma_h2_pipe serves one link, and a job carries one set of kernels in front of and behind its rounds: a second
