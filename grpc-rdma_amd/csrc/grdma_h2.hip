@@ -33,6 +33,7 @@
 #include "grdma_h2_reply.h"
 #include "grdma_h2_fc.h"
 #include "grdma_h2_sw.h"
+#include "grdma_h2_ctl.h"
 #include "grdma_h2_block.h"
 
 // --------------------------------------------------------------------- host API
@@ -69,6 +70,8 @@ struct grdma_h2_parser {
   struct grdma_h2_sw* sw = nullptr;
   const uint8_t* standalone_arena = nullptr;
   uint64_t standalone_nsl = 0;
+  // control replies (csrc/grdma_h2_ctl.h): the parser's control-reply writer; it reads what the send windows read
+  struct grdma_h2_ctl* ctl = nullptr;
 };
 
 // How many chunks a parser created without saying so cuts a long list into: GRDMA_H2_CHUNKS (default and at most 256, 0 or 1 = the
@@ -263,6 +266,23 @@ static h2_stage h2_stage_sw_intake_links(const h2sw_link* d_tab, uint32_t n) {
 }
 static h2_stage h2_stage_sw_frame_links(const h2sw_link* d_tab, uint32_t n) {
   return {h2_rec(k_h2_links_sw_plan, n, H2SW_PLAN_THREADS, d_tab), h2_rec(k_h2_links_sw_emit, H2SW_GRID, H2_EMIT_THREADS, d_tab, n)};
+}
+
+// The control-reply writer behind a deframing (csrc/grdma_h2_ctl.h): it reads the events, the slice table and the
+// receive arena, as the intake of the send windows does.
+static h2_stage h2_stage_ctl(h2ctl_dev* d, const h2ctl_call* d_call) {
+  return {h2_rec(k_h2_ctl_last, H2CTL_GRID, H2CTL_THREADS, d, d_call), h2_rec(k_h2_ctl_mark, H2CTL_GRID, H2CTL_THREADS, d, d_call),
+          h2_rec(k_h2_ctl_scan, 1, H2CTL_THREADS, d, d_call), h2_rec(k_h2_ctl_emit, H2CTL_GRID, H2CTL_THREADS, d, d_call)};
+}
+// ... of n links in the same four launches: every link a share of the grid, the scans side by side
+static_assert(H2CTL_LINKS_MAX == GRDMA_H2_BATCH_MAX, "the control-reply writer's link table is the batch's");
+static_assert(H2CTL_GRID <= H2CTL_GRID_MAX && H2CTL_LINK_GRID <= H2CTL_GRID_MAX && H2CTL_GRID_MAX <= H2CTL_THREADS,
+              "the scan reads one workgroup's counts per thread");
+static h2_stage h2_stage_ctl_links(const h2ctl_link* d_tab, uint32_t n) {
+  return {h2_rec(k_h2_links_ctl_last, n * H2CTL_LINK_GRID, H2CTL_THREADS, d_tab, n),
+          h2_rec(k_h2_links_ctl_mark, n * H2CTL_LINK_GRID, H2CTL_THREADS, d_tab, n),
+          h2_rec(k_h2_links_ctl_scan, n, H2CTL_THREADS, d_tab),
+          h2_rec(k_h2_links_ctl_emit, n * H2CTL_LINK_GRID, H2CTL_THREADS, d_tab, n)};
 }
 
 // st goes behind the parser's last deframing by a pipe (the parser state is handed from one deframing to the next),

@@ -154,10 +154,12 @@ grdma_h2_parser* grdma_h2_parser_create(int expect_client_prefix, uint32_t max_f
 
 static void h2_fc_parser_gone(struct grdma_h2_fc* f);
 static void h2_sw_parser_gone(struct grdma_h2_sw* s);
+static void h2_ctl_parser_gone(struct grdma_h2_ctl* w);
 void grdma_h2_parser_destroy(grdma_h2_parser* p) {
   if (!p) return;
   if (p->fc) h2_fc_parser_gone(p->fc);  // (the ledger outlives its parser as a husk: every call on it is refused)
   if (p->sw) h2_sw_parser_gone(p->sw);  // (the send windows too)
+  if (p->ctl) h2_ctl_parser_gone(p->ctl);  // (and the control-reply writer)
   hipFree(p->d);
   hipFree(p->d_tab);
   hipFree(p->d_sl);
@@ -1265,6 +1267,182 @@ int grdma_h2_sw_frame_batch(const grdma_h2_sw_frame_item* items, uint32_t n_item
     if (out[8 * (size_t)i + H2SW_F_OVERFLOW]) continue;  // (nothing was written, no window moved: progress stays as it is)
     for (uint64_t m = 0; m < it.nmsgs; m++) it.progress[m] = after[at[i] + m];
     ok++;
+  }
+  return ok;
+}
+
+// ---- control replies: SETTINGS ACK, PING ACK, RST_STREAM from a deframing's events (csrc/grdma_h2_ctl.h) ---------------
+struct grdma_h2_ctl {
+  grdma_h2_parser* parser = nullptr;
+  h2ctl_dev* d = nullptr;
+  h2ctl_call* d_call = nullptr;
+  uint64_t taken = 0;  // parser->standalone_calls of the last call taken in (at creation: of the calls before it)
+  float last_ms = 0;
+};
+
+// The parser of w is being destroyed: from now on w refuses every call but destroy (its calls read the parser's buffers).
+static void h2_ctl_parser_gone(grdma_h2_ctl* w) {
+  h2_host_ctx* hc = h2_ctx();
+  if (hc) hipStreamSynchronize(hc->stream);
+  w->parser = nullptr;
+}
+
+static grdma_h2_ctl* h2_ctl_refuse(const char* why) {
+  grdma_fail_msg(GRDMA_ERR_INVALID, why);
+  return nullptr;
+}
+
+grdma_h2_ctl* grdma_h2_ctl_create(grdma_h2_parser* parser, uint32_t max_replies) {
+  if (grdma_device_count() <= 0) return nullptr;
+  if (!parser) return h2_ctl_refuse("h2 control replies: no parser");
+  if (parser->ctl) return h2_ctl_refuse("h2 control replies: the parser has a control-reply writer already");
+  if (max_replies == 0 || max_replies > (1u << 24)) return h2_ctl_refuse("h2 control replies: max_replies outside 1 .. 2^24");
+  grdma_h2_ctl* w = new grdma_h2_ctl();
+  w->parser = parser;
+  w->taken = parser->standalone_calls;
+  parser->ctl = w;
+  const uint64_t max64 = max_replies;
+  if (hipMalloc((void**)&w->d, sizeof(h2ctl_dev)) != hipSuccess || hipMalloc((void**)&w->d_call, sizeof(h2ctl_call)) != hipSuccess ||
+      hipMemset(w->d, 0, sizeof(h2ctl_dev)) != hipSuccess ||
+      hipMemcpy(reinterpret_cast<uint8_t*>(w->d) + offsetof(h2ctl_dev, max_replies), &max64, sizeof(max64), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    grdma_h2_ctl_destroy(w);
+    grdma_fail_msg(GRDMA_ERR_HIP, "h2 control replies: device allocation failed");
+    return nullptr;
+  }
+  return w;
+}
+
+void grdma_h2_ctl_destroy(grdma_h2_ctl* w) {
+  if (!w) return;
+  h2_host_ctx* hc = h2_ctx();
+  if (hc) hipStreamSynchronize(hc->stream);  // (standalone calls)
+  if (w->parser) w->parser->ctl = nullptr;
+  hipFree(w->d_call);
+  hipFree(w->d);
+  delete w;
+}
+
+// what a call on w into these targets would be refused for (nullptr: nothing); the single call and the batch share it
+static const char* h2_ctl_refusal(const grdma_h2_ctl* w, const void* d_slices_out, uint64_t slices_cap, const void* d_hdr_arena,
+                                  uint64_t hdr_cap) {
+  const grdma_h2_parser* p = w->parser;
+  if (!p) return "h2 control replies: the parser is gone";
+  if (p->standalone_calls == 0) return "h2 control replies: the parser has deframed nothing yet";
+  if (w->taken == p->standalone_calls) return "h2 control replies: this call is taken in already";
+  if (p->standalone_ev_cap >= 0xfffffff0ull) return "h2 control replies: event positions are 32 bits";
+  if (!d_slices_out || !slices_cap || !d_hdr_arena || !hdr_cap || ((uintptr_t)d_slices_out & 15) || ((uintptr_t)d_hdr_arena & 15))
+    return "h2 control replies: a null, zero or misaligned slice table or header arena";
+  return nullptr;
+}
+
+static h2ctl_call h2_ctl_call_of(const grdma_h2_ctl* w) {
+  const grdma_h2_parser* p = w->parser;
+  return h2ctl_call{p->d_ev, p->d_res, p->d_sl, p->standalone_arena, p->standalone_ev_cap, p->standalone_nsl,
+                    p->standalone_calls > w->taken + 1 ? 1ull : 0ull};
+}
+
+int64_t grdma_h2_ctl_reply(grdma_h2_ctl* w, grdma_slice* d_slices_out, uint64_t slices_cap, void* d_hdr_arena, uint64_t hdr_cap,
+                           uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!w || !out) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 control replies: no writer or no result array");
+  if (const char* why = h2_ctl_refusal(w, d_slices_out, slices_cap, d_hdr_arena, hdr_cap)) return grdma_fail_msg(GRDMA_ERR_INVALID, why);
+  grdma_h2_parser* p = w->parser;
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  // the stream of the standalone deframings: the call is ordered behind the one it reads
+  hipStream_t st = hc->stream;
+  if (!h2_wait_parser(st, p)) return -GRDMA_ERR_HIP;
+  const h2ctl_call call = h2_ctl_call_of(w);
+  struct { grdma_sge* out; uint64_t cap; uint8_t* hdr; uint64_t hdr_cap; } target{reinterpret_cast<grdma_sge*>(d_slices_out), slices_cap,
+                                                                                   static_cast<uint8_t*>(d_hdr_arena), hdr_cap};
+  static_assert(offsetof(h2ctl_dev, out) == 0 && offsetof(h2ctl_dev, max_replies) == sizeof(target), "a call's target leads the block");
+  const h2_stage stage = h2_stage_ctl(w->d, w->d_call);
+  uint64_t res[8];
+  h2_call c{"grdma_h2_ctl_reply: a launch was rejected",
+            {{w->d_call, &call, sizeof(call)}, {w->d, &target, sizeof(target)}}, {}, {h2_all(stage)},
+            {{res, reinterpret_cast<uint8_t*>(w->d) + offsetof(h2ctl_dev, res), sizeof(res)}}};
+  if (int rc = h2_call_run(hc, &c)) return rc;
+  w->last_ms = c.ms[0];
+  for (int i = 0; i < 8; i++) out[i] = res[i];
+  if (res[H2CTL_OVERFLOW] == 1)  // (nothing was written or committed, the call is not taken: it may be repeated)
+    return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 control replies: more replies than max_replies, or a slice or header cap too small");
+  w->taken = p->standalone_calls;
+  if (res[H2CTL_OVERFLOW])
+    return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 control replies: the call's event list overflowed, its frames cannot be answered");
+  return (int64_t)res[H2CTL_SLICES];
+}
+
+int grdma_h2_ctl_peer(grdma_h2_ctl* w, uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!w || !out) return -GRDMA_ERR_INVALID;
+  if (!h2_read(out, reinterpret_cast<const uint8_t*>(w->d) + offsetof(h2ctl_dev, peer), 8 * sizeof(uint64_t))) return -GRDMA_ERR_HIP;
+  return 0;
+}
+
+int grdma_h2_ctl_stats(grdma_h2_ctl* w, uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!w || !out) return -GRDMA_ERR_INVALID;
+  uint64_t st[5];
+  uint32_t lost[2];
+  if (!h2_read(st, reinterpret_cast<const uint8_t*>(w->d) + offsetof(h2ctl_dev, st_calls), sizeof(st)) ||
+      !h2_read(lost, reinterpret_cast<const uint8_t*>(w->d) + offsetof(h2ctl_dev, lost), sizeof(lost)))
+    return -GRDMA_ERR_HIP;
+  for (int i = 0; i < 5; i++) out[i] = st[i];  // calls, SETTINGS ACKs, PING ACKs, RST_STREAMs, wire bytes
+  out[5] = 0;
+  out[6] = lost[0] ? 1 : 0;
+  out[7] = (uint64_t)(w->last_ms * 1e6f);
+  return 0;
+}
+
+// The writers of many transports in the same four launches (h2_stage_ctl_links).  The batch block of the process holds
+// [table | one call block per item] (the ledger batch's shape) and goes up in one copy; an item's targets are the leading
+// words of its writer's own device block, its result words come down from there.  One call at a time, as the other batch
+// calls.
+int grdma_h2_ctl_reply_batch(const grdma_h2_ctl_item* items, uint32_t n_items, uint64_t* out) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!items || !out || n_items == 0 || n_items > GRDMA_H2_BATCH_MAX)
+    return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 control replies batch: 1 .. GRDMA_H2_BATCH_MAX items and a result array");
+  for (uint32_t i = 0; i < n_items; i++) {
+    const grdma_h2_ctl_item& it = items[i];
+    if (!it.ctl) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 control replies batch: an item without writer");
+    for (uint32_t k = 0; k < i; k++)
+      if (items[k].ctl == it.ctl) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 control replies batch: the same writer twice");
+    if (const char* why = h2_ctl_refusal(it.ctl, it.d_slices_out, it.slices_cap, it.d_hdr_arena, it.hdr_cap))
+      return grdma_fail_msg(GRDMA_ERR_INVALID, why);
+  }
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  hipStream_t st = hc->stream;
+  const h2_fc_block L = h2_fc_block_layout(sizeof(h2ctl_link), sizeof(h2ctl_call), n_items);
+  if (!h2_batch_reserve(L.total, st)) return -GRDMA_ERR_HIP;
+  uint8_t* const d = g_batch.d;
+  std::vector<uint8_t> up(L.end, 0);
+  auto* tab = reinterpret_cast<h2ctl_link*>(up.data() + L.tab);
+  auto* calls = reinterpret_cast<h2ctl_call*>(up.data() + L.calls);
+  struct target_words { grdma_sge* out; uint64_t cap; uint8_t* hdr; uint64_t hdr_cap; };
+  std::vector<target_words> targets(n_items);
+  const h2_stage stage = h2_stage_ctl_links(reinterpret_cast<const h2ctl_link*>(d + L.tab), n_items);
+  h2_call c{"h2 control replies batch: a launch was rejected", {{d, up.data(), up.size()}}, {}, {h2_all(stage)}, {}};
+  for (uint32_t i = 0; i < n_items; i++) {
+    const grdma_h2_ctl_item& it = items[i];
+    calls[i] = h2_ctl_call_of(it.ctl);
+    tab[i].F = it.ctl->d;
+    tab[i].call = reinterpret_cast<const h2ctl_call*>(d + L.calls) + i;
+    targets[i] = target_words{reinterpret_cast<grdma_sge*>(it.d_slices_out), it.slices_cap, static_cast<uint8_t*>(it.d_hdr_arena), it.hdr_cap};
+    c.up.push_back({it.ctl->d, &targets[i], sizeof(target_words)});
+    c.down.push_back({out + 8 * (size_t)i, reinterpret_cast<const uint8_t*>(it.ctl->d) + offsetof(h2ctl_dev, res), 8 * sizeof(uint64_t)});
+  }
+  for (uint32_t i = 0; i < n_items; i++)
+    if (!h2_wait_parser(st, items[i].ctl->parser)) return -GRDMA_ERR_HIP;
+  if (int rc = h2_call_run(hc, &c)) return rc;
+  int ok = 0;
+  for (uint32_t i = 0; i < n_items; i++) {
+    grdma_h2_ctl* w = items[i].ctl;
+    w->last_ms = c.ms[0];  // (the batch's, repeated)
+    const uint64_t over = out[8 * (size_t)i + H2CTL_OVERFLOW];
+    if (over != 1) w->taken = w->parser->standalone_calls;  // (a cap overflow leaves the call to be repeated)
+    ok += over == 0;
   }
   return ok;
 }

@@ -60,6 +60,11 @@ class H2SwFrameItem(C.Structure):
                 ("d_hdr_arena", C.c_void_p), ("hdr_cap", u64)]
 
 
+class H2CtlItem(C.Structure):
+    _fields_ = [("ctl", C.c_void_p), ("d_slices_out", C.c_void_p), ("slices_cap", u64), ("d_hdr_arena", C.c_void_p),
+                ("hdr_cap", u64)]
+
+
 MSG_OK, MSG_TOO_LARGE, MSG_NO_SPACE, MSG_TRUNCATED = 0, 1, 2, 3
 SYNC_KEYS = ("framed", "frame_overflow", "events", "deframe_overflow", "parsed", "h2_error", "frame_us", "deframe_us",
              "bulk_steps", "bulk_frames", "t_wait", "t_bulk", "t_total", "t_serial")
@@ -229,6 +234,17 @@ def _bind():
         lib.grdma_h2_sw_intake_batch.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(u64)]
         lib.grdma_h2_sw_frame_batch.restype = C.c_int
         lib.grdma_h2_sw_frame_batch.argtypes = [C.POINTER(H2SwFrameItem), C.c_uint32, C.POINTER(u64)]
+        lib.grdma_h2_ctl_create.restype = C.c_void_p
+        lib.grdma_h2_ctl_create.argtypes = [C.c_void_p, C.c_uint32]
+        lib.grdma_h2_ctl_destroy.argtypes = [C.c_void_p]
+        lib.grdma_h2_ctl_reply.restype = C.c_int64
+        lib.grdma_h2_ctl_reply.argtypes = [C.c_void_p, C.c_void_p, u64, C.c_void_p, u64, C.POINTER(u64)]
+        lib.grdma_h2_ctl_peer.restype = C.c_int
+        lib.grdma_h2_ctl_peer.argtypes = [C.c_void_p, C.POINTER(u64)]
+        lib.grdma_h2_ctl_stats.restype = C.c_int
+        lib.grdma_h2_ctl_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
+        lib.grdma_h2_ctl_reply_batch.restype = C.c_int
+        lib.grdma_h2_ctl_reply_batch.argtypes = [C.POINTER(H2CtlItem), C.c_uint32, C.POINTER(u64)]
         lib.grdma_job_hook_counts.restype = C.c_int   # (not in include/grdma_amd.h: the job's side of the pipes)
         lib.grdma_job_hook_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         _bound = True
@@ -762,6 +778,89 @@ class SendWindows:
         if self.h:
             self.lib.grdma_h2_sw_destroy(self.h)
             self.h = None
+
+
+def _read_slice_table(lib, slices_ptr, k):
+    raw = C.create_string_buffer(max(1, 16 * k))
+    if k:
+        check(lib.grdma_copy_to_host(raw, slices_ptr, 16 * k))
+    return [(int.from_bytes(raw.raw[16 * i:16 * i + 8], "little"), int.from_bytes(raw.raw[16 * i + 8:16 * i + 16], "little"))
+            for i in range(k)]
+
+
+class ControlReplies:
+    """The control replies of one transport on the device (grdma_h2_ctl): SETTINGS ACK, PING ACK and RST_STREAM written
+    from the parser's deframings, and the record of what the peer said.  One per parser; independent of FlowControl and
+    SendWindows, which may consume the same deframing."""
+
+    RESULT = ("frames", "slices", "wire_bytes", "settings_acks", "ping_acks", "rst_streams", "flags", "overflow")
+    PEER = ("settings_acks", "ping_acks", "last_ping_opaque", "goaways", "goaway_last_stream", "goaway_error", "goaway_call")
+    STATS = ("calls", "settings_acks", "ping_acks", "rst_streams", "wire_bytes", "reserved", "lost", "kernel_us")
+    LOST, GOAWAY = 1, 2
+
+    def __init__(self, parser, max_replies=4096):
+        self.lib = _bind()
+        self.parser = parser  # (kept alive)
+        self.h = self.lib.grdma_h2_ctl_create(parser.h, max_replies)
+        if not self.h:
+            raise GrdmaError("h2 control replies: " + (self.lib.grdma_last_error() or b"creation failed").decode())
+        self.last_result = None
+
+    def reply(self, slices_ptr, cap, hdr_ptr, hdr_cap):
+        """answers the parser's last standalone deframing -> ([(ptr, len), ...], result tuple (RESULT)); raises
+        GrdmaError on a refusal, a lost call or a capacity overflow -- the result of the failed call stays in
+        .last_result; after a capacity overflow (overflow word 1) the call may be repeated with larger targets"""
+        out = (u64 * 8)()
+        n = self.lib.grdma_h2_ctl_reply(self.h, slices_ptr, cap, hdr_ptr, hdr_cap, out)
+        self.last_result = tuple(int(x) for x in out)
+        n = check(n)
+        return _read_slice_table(self.lib, slices_ptr, n), self.last_result
+
+    def peer(self):
+        """dict of PEER: what the peer said so far"""
+        out = (u64 * 8)()
+        check(self.lib.grdma_h2_ctl_peer(self.h, out))
+        return dict(zip(ControlReplies.PEER, [int(x) for x in out]))
+
+    def stats(self):
+        """dict of STATS; `lost`: the sticky flag"""
+        out = (u64 * 8)()
+        check(self.lib.grdma_h2_ctl_stats(self.h, out))
+        r = dict(zip(ControlReplies.STATS, [int(x) for x in out]))
+        r.pop("reserved")
+        r["kernel_us"] /= 1e3  # (the ABI word is nanoseconds)
+        r["lost"] = bool(r["lost"])
+        return r
+
+    def close(self):
+        if self.h:
+            self.lib.grdma_h2_ctl_destroy(self.h)
+            self.h = None
+
+
+def control_batch(items):
+    """ControlReplies.reply for many transports in four launches (grdma_h2_ctl_reply_batch).  items: [(ControlReplies,
+    slices device ptr, slices cap, header arena device ptr, header cap), ...] with distinct writers; each answers the last
+    standalone deframing of its own parser.  -> per item ([(ptr, len), ...], result tuple (ControlReplies.RESULT)); an
+    item whose call was lost or overflowed a cap reports for itself: its result tuple and None, nothing of it was
+    written.  The result tuples also land in each writer's .last_result.  Raises GrdmaError on a refusal."""
+    lib = _bind()
+    n = len(items)
+    arr = (H2CtlItem * max(1, n))()
+    for i, item in enumerate(items):
+        if item is None:
+            continue
+        ctl, sl, cap, hdr, hdr_cap = item
+        arr[i].ctl = ctl.h if ctl is not None else None
+        arr[i].d_slices_out, arr[i].slices_cap, arr[i].d_hdr_arena, arr[i].hdr_cap = sl, cap, hdr, hdr_cap
+    out = (u64 * (8 * max(1, n)))()
+    check(lib.grdma_h2_ctl_reply_batch(arr, n, out))
+    res = []
+    for i, (ctl, sl_ptr, _, _, _) in enumerate(items):
+        r = tuple(int(x) for x in out[8 * i:8 * i + 8])
+        ctl.last_result = r
+        res.append((r, None) if r[7] else (_read_slice_table(lib, sl_ptr, r[1]), r))
+    return res
 
 
 def account_batch(items):

@@ -975,8 +975,8 @@ int grdma_h2_fc_account_batch(const grdma_h2_fc_item* items, uint32_t n, uint64_
  * with no call yet or of the same call twice, a parser that is gone (destroy still works), n = 0 or above 4096, r_i = 0,
  * max_frame 0 or >= 2^24, null, zero or misaligned (16 bytes) targets.
  * Not here: intake of a pipe's or group pipe's steps and the windowed framer as a pipe's framing stage (a job's graph
- * carries a fixed slice count per step; a window-cut step has another shape), the reply framer under windows, SETTINGS
- * ACK and the other settings, HPACK.  (The many-link batch forms: grdma_h2_sw_intake_batch / _frame_batch below.) */
+ * carries a fixed slice count per step; a window-cut step has another shape), the reply framer under windows, the
+ * other settings, HPACK (SETTINGS ACK: grdma_h2_ctl below).  (The many-link batch forms: grdma_h2_sw_intake_batch / _frame_batch below.) */
 enum grdma_h2_sw_violation { GRDMA_H2_SW_BAD_INCREMENT = 1, GRDMA_H2_SW_WINDOW_OVERFLOW = 2, GRDMA_H2_SW_BAD_SETTINGS = 4,
                              GRDMA_H2_SW_LOST = 8 };
 typedef struct grdma_h2_sw grdma_h2_sw;
@@ -1025,6 +1025,72 @@ typedef struct grdma_h2_sw_frame_item {
   uint64_t hdr_cap;
 } grdma_h2_sw_frame_item;
 int grdma_h2_sw_frame_batch(const grdma_h2_sw_frame_item* items, uint32_t n, uint64_t* out);
+
+/* ---- Control replies on the device: SETTINGS ACK, PING ACK, RST_STREAM (csrc/grdma_h2_ctl.h) ----
+ * The frames HTTP/2 obliges a transport to answer, written in device memory from a deframing's events, so that a
+ * connection stays alive with no host step between the deframer and the wire.  One control-reply writer per parser,
+ * independent of the ledger (grdma_h2_fc) and the send windows (grdma_h2_sw): all three may consume the same deframing
+ * in any order, each keeps its own count of the calls it has taken.  The sequential reference is
+ * tests/h2_control_model.py.
+ * 1. INPUT.  grdma_h2_ctl_reply takes in the LAST standalone deframing of the parser (grdma_h2_deframe or
+ *    grdma_h2_deframe_messages): its device event list, its slice table and its receive arena, which must still hold the
+ *    call's bytes; it is ordered behind that deframing on the device.  A frame's payload is the run of PAYLOAD events
+ *    behind its FRAME event; PAYLOAD events in front of the call's first FRAME event continue the frame the previous
+ *    call's end cut (the carry).  Every frame ends with a PAYLOAD event whose is_last is 1: the frame's completion.
+ * 2. REPLIES DUE.  SETTINGS without ACK: one SETTINGS ACK (00 00 00 04 01 00 00 00 00), in the call that completes the
+ *    frame.  PING without ACK: one PING ACK (00 00 08 06 01 00 00 00 00 + the 8 opaque bytes, read from the arena), in
+ *    the call that completes it.  A stream error -- a FRAME event whose status byte (b >> 8) is not 0, or a FRAME event
+ *    of type 0xff (stream in c) -- one RST_STREAM(stream, PROTOCOL_ERROR = 1) (00 00 04 03 00 + stream id + 00 00 00
+ *    01), in the call that holds the event.  The deframer reports each at most once; the writer does not deduplicate.
+ *    EVERY PING is answered: there is no ping-abuse policy, max_replies is the flood bound.
+ * 3. ORDER.  The PING ACKs first, in the order of their completions, then the SETTINGS ACKs and RST_STREAMs in the
+ *    order of their events.  RFC 7540 fixes no order between them: this is a fixed choice (the reference transport
+ *    flushes its ping acks in front of its queued control frames when it begins a write).
+ * 4. OUTPUT, in the ledger's form: the concatenated frames in a header arena, 32 bytes of arena per slice, cut into
+ *    23-byte inlined slices (the last one shorter), as grpc_slice_buffer_add makes of small inlined slices; the 9 bytes
+ *    behind a slice's 23 are not written.  The list is an outbuf of its own.  Result block: {frames, slices, wire bytes,
+ *    SETTINGS ACKs, PING ACKs, RST_STREAMs, flags (grdma_h2_ctl_flag), overflow}.  Returns the slice count.
+ * 5. WHAT THE PEER SAID (grdma_h2_ctl_peer): {SETTINGS ACKs received, PING ACKs received, the 8 opaque bytes of the last
+ *    PING ACK as a little-endian word of the wire bytes, GOAWAY frames received, last_stream_id of the last GOAWAY (bit
+ *    31 cleared), its error code, the number of the call (grdma_h2_ctl_stats word 0 behind it) that completed it, 0}.
+ *    "Last" is by completion within a call, by call order across calls.  GOAWAY debug data is skipped.
+ * 6. THE CARRY.  A call's end may cut one frame: its type and flags and, of a PING or GOAWAY, those of its first 8
+ *    payload bytes that are in.  Its reply or its record is due in the call that completes it.
+ * 7. ERRORS AND CAPS.  A call that ended with a connection error writes and records nothing, is taken, the carry goes.
+ *    A call whose event list overflowed sets the sticky flag GRDMA_H2_CTL_LOST, returns -GRDMA_ERR_CAPACITY with
+ *    overflow word 2, is taken, the carry goes, the record keeps what it knows.  A standalone deframing that was never
+ *    taken in (the send windows' "skipped" rule) sets the flag and drops the carry; the call itself is answered.  More
+ *    replies than max_replies, or a slice or header cap too small: overflow word 1, -GRDMA_ERR_CAPACITY, the result
+ *    block holds the totals, NOTHING is written and NOTHING is committed -- carry and record stay, the call is NOT taken
+ *    and may be repeated with larger targets while the deframing's buffers stand (unlike the ledger, whose bytes were
+ *    counted already: an unanswered PING must not be lost).
+ * -GRDMA_ERR_INVALID or NULL (grdma_last_error says why; nothing runs, nothing changes): a second writer on a parser,
+ * max_replies outside 1 .. 2^24, no call yet or a call taken in already, a parser that is gone (destroy still works),
+ * null, zero or misaligned (16 bytes) targets; in the batch n outside 1 .. GRDMA_H2_BATCH_MAX, a NULL item, the same
+ * writer twice.
+ * Not here: replies to a pipe's or group pipe's steps, the other settings, HPACK. */
+enum grdma_h2_ctl_flag { GRDMA_H2_CTL_LOST = 1, GRDMA_H2_CTL_GOAWAY = 2 /* a GOAWAY completed in this call */ };
+typedef struct grdma_h2_ctl grdma_h2_ctl;
+grdma_h2_ctl* grdma_h2_ctl_create(grdma_h2_parser* parser, uint32_t max_replies);  /* 1 .. 2^24; one per parser */
+void grdma_h2_ctl_destroy(grdma_h2_ctl* ctl);
+int64_t grdma_h2_ctl_reply(grdma_h2_ctl* ctl, grdma_slice* d_slices_out, uint64_t slices_cap, void* d_hdr_arena, uint64_t hdr_cap,
+                           uint64_t out[8]);
+int grdma_h2_ctl_peer(grdma_h2_ctl* ctl, uint64_t out[8]);
+/* {calls taken, SETTINGS ACKs written, PING ACKs written, RST_STREAMs written, wire bytes written, 0, the LOST flag,
+ * kernel time of the last call in NANOseconds (HIP events)} */
+int grdma_h2_ctl_stats(grdma_h2_ctl* ctl, uint64_t out[8]);
+/* grdma_h2_ctl_reply for n writers (1 .. GRDMA_H2_BATCH_MAX) in the same four launches (k_h2_links_ctl_*): every item
+ * answers the last standalone deframing of its OWN parser into its own targets, exactly as the single call does.  out: 8
+ * result words per item, in item order.  An item's overflow (word 1: not taken, may be repeated; word 2: lost) stays with
+ * the item, the other items are exact; the return value is the number of items without overflow, or a negative error. */
+typedef struct grdma_h2_ctl_item {
+  grdma_h2_ctl* ctl;          /* distinct */
+  grdma_slice* d_slices_out;  /* device slice table of the item */
+  uint64_t slices_cap;
+  void* d_hdr_arena;          /* device header arena of the item, 32 bytes per slice */
+  uint64_t hdr_cap;
+} grdma_h2_ctl_item;
+int grdma_h2_ctl_reply_batch(const grdma_h2_ctl_item* items, uint32_t n, uint64_t* out);
 
 /* ---- HTTP/2 on several links of ONE job (the group pipe) ----
  * grdma_h2_pipe serves one link, and a job carries one set of kernels in front of and behind its rounds: a second
