@@ -33,6 +33,7 @@
 #include "grdma_h2_reply.h"
 #include "grdma_h2_fc.h"
 #include "grdma_h2_sw.h"
+#include "grdma_h2_wr.h"
 #include "grdma_h2_ctl.h"
 #include "grdma_h2_block.h"
 
@@ -266,6 +267,19 @@ static h2_stage h2_stage_sw_intake_links(const h2sw_link* d_tab, uint32_t n) {
 }
 static h2_stage h2_stage_sw_frame_links(const h2sw_link* d_tab, uint32_t n) {
   return {h2_rec(k_h2_links_sw_plan, n, H2SW_PLAN_THREADS, d_tab), h2_rec(k_h2_links_sw_emit, H2SW_GRID, H2_EMIT_THREADS, d_tab, n)};
+}
+
+// The reply under the send windows (csrc/grdma_h2_wr.h): the queue stage builds the plan's table in device memory, the
+// send windows' framer runs unchanged over it, the commit keeps what the windows cut off.
+static h2_stage h2_stage_wr_frame(h2wr_dev* d, h2sw_dev* sw) {
+  return {h2_rec(k_h2_wr_queue, 1, H2WR_THREADS, d), h2_rec(k_h2_sw_plan, 1, H2SW_PLAN_THREADS, sw),
+          h2_rec(k_h2_sw_emit, H2SW_GRID, H2_EMIT_THREADS, sw), h2_rec(k_h2_wr_commit, 1, H2WR_THREADS, d)};
+}
+// ... of n links in the same four launches
+static_assert(H2WR_LINKS_MAX == GRDMA_H2_BATCH_MAX, "the windowed reply's link table is the batch's");
+static h2_stage h2_stage_wr_frame_links(const h2wr_link* d_tab, const h2sw_link* d_sw_tab, uint32_t n) {
+  return {h2_rec(k_h2_links_wr_queue, n, H2WR_THREADS, d_tab), h2_rec(k_h2_links_sw_plan, n, H2SW_PLAN_THREADS, d_sw_tab),
+          h2_rec(k_h2_links_sw_emit, H2SW_GRID, H2_EMIT_THREADS, d_sw_tab, n), h2_rec(k_h2_links_wr_commit, n, H2WR_THREADS, d_tab)};
 }
 
 // The control-reply writer behind a deframing (csrc/grdma_h2_ctl.h): it reads the events, the slice table and the

@@ -379,6 +379,7 @@ struct grdma_h2_asm {
   uint32_t replies = 0;            // reply framers that read its descriptors (grdma_h2_reply_create)
   uint32_t reply_pipes = 0;        // ... of which in a pipe: their jobs gather from the arena
   hipEvent_t last_read = nullptr;  // the gather of the last reply step enqueued: the next release waits for it
+  uint64_t calls = 0;              // standalone assembler calls, single and batch (the windowed reply takes each one once)
   float plan_ms = 0, copy_ms = 0;  // of the last standalone call
 };
 
@@ -505,6 +506,7 @@ int64_t grdma_h2_deframe_messages(grdma_h2_parser* p, grdma_h2_asm* a, const voi
   if (int rc = h2_call_run(hc, &c)) return rc;
   a->plan_ms = c.ms[0];
   a->copy_ms = c.ms[1];
+  a->calls++;
   p->standalone_calls++;
   p->standalone_ev_cap = ev_cap;
   p->standalone_arena = static_cast<const uint8_t*>(d_arena);
@@ -555,7 +557,15 @@ struct grdma_h2_reply {
   h2r_dev h;                        // host copy of the configuration words
   grdma_h2_route* d_routes = nullptr;
   h2_step_seq* seq = nullptr;       // the steps of the reply pipe, single or group, that frames through it (at most one: the scratch is one call's)
+  // replies under the peer's windows (csrc/grdma_h2_wr.h): the queue, once grdma_h2_reply_attach_windows has bound it
+  h2wr_dev* d_wr = nullptr;
+  h2wr_dev wr;                      // host copy of its configuration and call words
+  struct grdma_h2_sw* sw = nullptr; // the send windows the replies go out under; NULL once they are gone
+  uint64_t taken = 0;               // src->calls of the last source call taken (at the attachment: of the calls before it)
+  uint64_t attached_at = 0;         // src->calls at the attachment
+  uint64_t pending = 0;             // entries the last call left in the queue
 };
+static void h2_wr_free(grdma_h2_reply* r);
 
 // where the calls frame to, and (a pipe) the shape they must have: the words of h2r_dev from `out` to the result block
 static bool h2_reply_set_target(grdma_h2_reply* r, grdma_sge* out, uint64_t cap, uint8_t* hdr, uint64_t hdr_cap,
@@ -597,6 +607,7 @@ grdma_h2_reply* grdma_h2_reply_create(grdma_h2_asm* source, const grdma_h2_route
   r->src = source;
   source->replies++;
   memset(&r->h, 0, sizeof(r->h));
+  memset(&r->wr, 0, sizeof(r->wr));
   h2r_dev& h = r->h;
   h.src = source->d;
   h.n_routes = n_routes;
@@ -622,6 +633,7 @@ void grdma_h2_reply_destroy(grdma_h2_reply* r) {
   h2_host_ctx* hc = h2_ctx();
   if (hc) hipStreamSynchronize(hc->stream);  // (standalone calls)
   r->src->replies--;
+  h2_wr_free(r);
   hipFree(r->h.msgs);
   hipFree(r->h.pos);
   hipFree(r->d_routes);
@@ -635,6 +647,8 @@ int64_t grdma_h2_reply_frame(grdma_h2_reply* r, grdma_slice* d_slices_out, uint6
   if (!r || !d_slices_out || !slices_cap || !d_hdr_arena || !hdr_cap || !out || ((uintptr_t)d_slices_out & 15) ||
       ((uintptr_t)d_hdr_arena & 15) || r->seq || r->src->attached)
     return -GRDMA_ERR_INVALID;
+  if (r->d_wr)  // (one message could go out twice)
+    return grdma_fail_msg(GRDMA_ERR_INVALID, "grdma_h2_reply_frame: the reply frames under send windows (grdma_h2_reply_frame_windowed)");
   h2_host_ctx* hc = h2_ctx();
   if (!hc) return -GRDMA_ERR_HIP;
   // the stream of grdma_h2_deframe_messages: the call is ordered behind the one it reads
@@ -669,6 +683,7 @@ int grdma_h2_reply_frame_batch(grdma_h2_reply_item* items, uint32_t n_items) {
         ((uintptr_t)it.d_hdr_arena & 15))
       return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: a null, zero or misaligned slice table or header arena");
     if (it.reply->seq) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: a reply bound to a reply pipe");
+    if (it.reply->d_wr) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: a reply that frames under send windows");
     if (it.reply->src->attached)
       return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: a source assembler attached to a pipe or group pipe");
     for (uint32_t k = 0; k < i; k++) {
@@ -954,6 +969,8 @@ struct grdma_h2_sw {
   uint64_t* d_prog = nullptr;         // progress in [0, MAX), out [MAX, 2 MAX)
   uint64_t taken = 0;                 // parser->standalone_calls of the last call taken in (at creation: of the calls before it)
   float last_ms = 0;
+  struct grdma_h2_reply* reply = nullptr;  // the reply framer whose queue waits under these windows (csrc/grdma_h2_wr.h)
+  bool reply_gone = false;                 // ... has been destroyed: every call but destroy is refused
 };
 
 // The parser of s is being destroyed: standalone calls on the stream of the calls have ended, and from now on s refuses
@@ -1013,6 +1030,7 @@ void grdma_h2_sw_destroy(grdma_h2_sw* s) {
   h2_host_ctx* hc = h2_ctx();
   if (hc) hipStreamSynchronize(hc->stream);  // (standalone calls)
   if (s->parser) s->parser->sw = nullptr;
+  if (s->reply) s->reply->sw = nullptr;  // (the reply outlives its windows as a husk: every call on it is refused)
   hipFree(s->h.tabs[0]);
   hipFree(s->h.tabs[1]);
   hipFree(s->h.pieces);
@@ -1030,6 +1048,7 @@ int64_t grdma_h2_sw_intake(grdma_h2_sw* s, uint64_t out[8]) {
   if (!s || !out) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: no send windows or no result array");
   grdma_h2_parser* p = s->parser;
   if (!p) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: the parser is gone");
+  if (s->reply_gone) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: the reply framer whose queue waited under them is gone");
   if (p->standalone_calls == 0) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: the parser has deframed nothing yet");
   if (s->taken == p->standalone_calls) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: this call is taken in already");
   if (p->standalone_ev_cap >= 0xfffffff0ull) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: event positions are 32 bits");
@@ -1065,6 +1084,7 @@ int64_t grdma_h2_sw_frame(grdma_h2_sw* s, const grdma_h2_msg* msgs, uint64_t* pr
     return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: a null, zero or misaligned slice table or header arena");
   grdma_h2_parser* p = s->parser;
   if (!p) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: the parser is gone");
+  if (s->reply_gone) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: the reply framer whose queue waited under them is gone");
   for (uint64_t i = 0; i < n; i++) {
     if (msgs[i].len >= (1ull << 32)) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: a message of 2^32 bytes or more");
     if (progress[i] >= 5 + msgs[i].len) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: a message with nothing left to send");
@@ -1156,6 +1176,7 @@ int grdma_h2_sw_intake_batch(grdma_h2_sw* const* sws, uint32_t n_items, uint64_t
       if (sws[k] == s) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: the same send windows twice");
     const grdma_h2_parser* p = s->parser;
     if (!p) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a parser is gone");
+    if (s->reply_gone) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a reply framer whose queue waited under them is gone");
     if (p->standalone_calls == 0) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a parser has deframed nothing yet");
     if (s->taken == p->standalone_calls) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a call is taken in already");
     if (p->standalone_ev_cap >= 0xfffffff0ull) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: event positions are 32 bits");
@@ -1207,6 +1228,7 @@ int grdma_h2_sw_frame_batch(const grdma_h2_sw_frame_item* items, uint32_t n_item
     for (uint32_t k = 0; k < i; k++)
       if (items[k].sw == it.sw) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: the same send windows twice");
     if (!it.sw->parser) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a parser is gone");
+    if (it.sw->reply_gone) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a reply framer whose queue waited under them is gone");
     if (it.nmsgs == 0 || it.nmsgs > H2_FRAME_ONE_MAX) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: 1 .. 4096 messages an item");
     if (it.max_frame == 0 || it.max_frame >= (1u << 24)) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: max_frame outside 1 .. 2^24 - 1");
     if (!it.d_slices_out || !it.slices_cap || !it.d_hdr_arena || !it.hdr_cap || ((uintptr_t)it.d_slices_out & 15) ||
@@ -1267,6 +1289,228 @@ int grdma_h2_sw_frame_batch(const grdma_h2_sw_frame_item* items, uint32_t n_item
     if (out[8 * (size_t)i + H2SW_F_OVERFLOW]) continue;  // (nothing was written, no window moved: progress stays as it is)
     for (uint64_t m = 0; m < it.nmsgs; m++) it.progress[m] = after[at[i] + m];
     ok++;
+  }
+  return ok;
+}
+
+// ---- replies under the peer's windows: the queue in device memory, the windowed framer over it (csrc/grdma_h2_wr.h) -----
+// The queue's device block holds the call: the host pushes the three call words, and a LOCAL copy of the send windows'
+// framing words (targets, frame size) -- the mirror grdma_h2_sw_frame pushes from stays as that call left it.  Where the
+// plan's table lies and how many messages it holds is written on the device (k_h2_wr_queue).
+static void h2_wr_free(grdma_h2_reply* r) {
+  if (!r->wr.max_pending) return;  // (never attached)
+  if (r->sw) {
+    r->sw->reply = nullptr;
+    r->sw->reply_gone = true;  // (what waited in the queue is gone with it: the windows refuse every call but destroy)
+  }
+  for (int t = 0; t < 2; t++) {
+    hipFree(r->wr.msgs[t]);
+    hipFree(r->wr.prog[t]);
+    hipFree(r->wr.rank[t]);
+  }
+  hipFree(r->d_wr);
+  memset(&r->wr, 0, sizeof(r->wr));
+  r->d_wr = nullptr;
+  r->sw = nullptr;
+}
+
+int grdma_h2_reply_attach_windows(grdma_h2_reply* r, grdma_h2_sw* s, uint32_t max_pending) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!r || !s) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 windowed reply: a reply and send windows");
+  if (max_pending == 0 || max_pending > H2_FRAME_ONE_MAX) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 windowed reply: max_pending outside 1 .. 4096");
+  if (r->seq) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 windowed reply: the reply is bound to a reply pipe");
+  if (r->src->attached) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 windowed reply: the source assembler is attached to a pipe");
+  if (r->d_wr) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 windowed reply: the reply has send windows attached already");
+  if (s->reply || s->reply_gone) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 windowed reply: the send windows are attached to a reply already");
+  if (!s->parser) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 windowed reply: the send windows' parser is gone");
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc || hipStreamSynchronize(hc->stream) != hipSuccess) return -GRDMA_ERR_HIP;
+  h2wr_dev& w = r->wr;
+  memset(&w, 0, sizeof(w));
+  w.R = r->d;
+  w.F = s->d;
+  w.max_pending = max_pending;
+  bool ok = hipMalloc((void**)&r->d_wr, sizeof(h2wr_dev)) == hipSuccess;
+  for (int t = 0; t < 2 && ok; t++)
+    ok = hipMalloc((void**)&w.msgs[t], sizeof(grdma_h2_msg_dev) * max_pending) == hipSuccess &&
+         hipMalloc((void**)&w.prog[t], sizeof(uint64_t) * max_pending) == hipSuccess &&
+         hipMalloc((void**)&w.rank[t], sizeof(uint64_t) * max_pending) == hipSuccess;
+  ok = ok && hipMemcpy(r->d_wr, &w, sizeof(w), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    h2_wr_free(r);
+    return grdma_fail_msg(GRDMA_ERR_HIP, "h2 windowed reply: device allocation failed");
+  }
+  r->sw = s;
+  s->reply = r;
+  r->taken = r->attached_at = r->src->calls;
+  r->pending = 0;
+  return 0;
+}
+
+// what a call on r is refused for (NULL: nothing), the targets included
+static const char* h2_wr_refusal(const grdma_h2_reply* r, uint32_t flags, const void* d_slices_out, uint64_t slices_cap,
+                                 const void* d_hdr_arena, uint64_t hdr_cap) {
+  if (!r) return "h2 windowed reply: no reply";
+  if (!r->d_wr) return "h2 windowed reply: the reply has no send windows attached";
+  if (!r->sw) return "h2 windowed reply: the send windows are gone";
+  if (!r->sw->parser) return "h2 windowed reply: the send windows' parser is gone";
+  if (r->seq || r->src->attached) return "h2 windowed reply: a reply or source assembler bound to a pipe";
+  if (flags & ~(uint32_t)GRDMA_H2_WR_PENDING_ONLY) return "h2 windowed reply: unknown flags";
+  if (!d_slices_out || !slices_cap || !d_hdr_arena || !hdr_cap || ((uintptr_t)d_slices_out & 15) || ((uintptr_t)d_hdr_arena & 15))
+    return "h2 windowed reply: a null, zero or misaligned slice table or header arena";
+  if (r->src->calls == r->attached_at && r->pending == 0) return "h2 windowed reply: no source call yet and nothing waits";
+  return nullptr;
+}
+
+// the call words of r's queue for one call, in its host copy -> whether the source's last call is to be taken
+static bool h2_wr_call_words(grdma_h2_reply* r, uint32_t flags) {
+  const uint64_t calls = r->src->calls;
+  const bool is_new = calls > r->taken;
+  const bool take = is_new && !(flags & GRDMA_H2_WR_PENDING_ONLY);
+  r->wr.take = take ? 1 : 0;
+  r->wr.untaken = (is_new && !take) ? 1 : 0;
+  r->wr.lost_now = calls > r->taken + 1 ? 1 : 0;
+  return take;
+}
+
+// the send windows' framing words for a call of r, from a local copy of their mirror
+static h2sw_dev h2_wr_sw_words(const grdma_h2_reply* r, grdma_slice* d_slices_out, uint64_t slices_cap, void* d_hdr_arena, uint64_t hdr_cap) {
+  h2sw_dev h = r->sw->h;
+  h.msgs = r->wr.msgs[0];   // (k_h2_wr_queue names the table and the count)
+  h.prog_in = r->wr.prog[0];
+  h.nmsgs = 0;
+  h.max_frame = r->h.max_frame;
+  h.out = reinterpret_cast<grdma_sge*>(d_slices_out);
+  h.cap = slices_cap;
+  h.hdr = static_cast<uint8_t*>(d_hdr_arena);
+  h.hdr_cap = hdr_cap;
+  return h;
+}
+
+// behind a call of r that ran: what the host keeps of it
+static void h2_wr_ran(grdma_h2_reply* r, bool take, const uint64_t res[16], float ms) {
+  const uint64_t calls = r->src->calls;
+  if (calls > r->taken + 1) r->taken = calls - 1;  // (lost: the flag is the device's and sticky)
+  r->sw->last_ms = ms;
+  if (res[H2WR_OVERFLOW]) return;  // (the queue stands, the source call is not taken)
+  if (take) r->taken = calls;
+  r->pending = res[H2WR_PENDING];
+}
+
+int64_t grdma_h2_reply_frame_windowed(grdma_h2_reply* r, uint32_t flags, grdma_slice* d_slices_out, uint64_t slices_cap,
+                                      void* d_hdr_arena, uint64_t hdr_cap, uint64_t out[16]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!out) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 windowed reply: no result array");
+  if (const char* why = h2_wr_refusal(r, flags, d_slices_out, slices_cap, d_hdr_arena, hdr_cap)) return grdma_fail_msg(GRDMA_ERR_INVALID, why);
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  hipStream_t st = hc->stream;
+  grdma_h2_sw* s = r->sw;
+  // behind the source parser's last deframing (the descriptors) and the last one of the send windows' parser (the map)
+  if (!h2_wait_parser(st, r->src->parser) || !h2_wait_parser(st, s->parser)) return -GRDMA_ERR_HIP;
+  const bool take = h2_wr_call_words(r, flags);
+  const h2sw_dev h = h2_wr_sw_words(r, d_slices_out, slices_cap, d_hdr_arena, hdr_cap);
+  if (!h2_push_words(r->d_wr, &r->wr, offsetof(h2wr_dev, take), offsetof(h2wr_dev, n_tab), st) ||
+      !h2_push_words(s->d, &h, offsetof(h2sw_dev, msgs), offsetof(h2sw_dev, conn), st))
+    return -GRDMA_ERR_HIP;
+  const h2_stage framing = h2_stage_wr_frame(r->d_wr, s->d);
+  uint64_t res[16];
+  h2_call c{"grdma_h2_reply_frame_windowed: a launch was rejected", {}, {}, {h2_all(framing)},
+            {{res, reinterpret_cast<uint8_t*>(r->d_wr) + offsetof(h2wr_dev, res), sizeof(res)}}};
+  if (int rc = h2_call_run(hc, &c)) return rc;
+  h2_wr_ran(r, take, res, c.ms[0]);
+  for (int i = 0; i < 16; i++) out[i] = res[i];
+  out[H2WR_US] = (uint64_t)(c.ms[0] * 1e3f);
+  if (res[H2WR_OVERFLOW] == 2) return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 windowed reply: more entries than max_pending");
+  if (res[H2WR_OVERFLOW])
+    return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 windowed reply: a slice or header cap too small, a skipped source call or more descriptors than max_messages");
+  return (int64_t)res[H2WR_SLICES];
+}
+
+int64_t grdma_h2_reply_pending(grdma_h2_reply* r, uint64_t* out, uint64_t cap) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!r || !r->d_wr || (!out && cap)) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 windowed reply: no reply, no send windows attached or no array");
+  h2wr_dev w;
+  if (!h2_read(&w, r->d_wr, sizeof(w))) return -GRDMA_ERR_HIP;
+  const uint64_t n = w.nq < w.max_pending ? w.nq : w.max_pending;
+  std::vector<grdma_h2_msg_dev> msgs(n ? n : 1);
+  std::vector<uint64_t> prog(n ? n : 1);
+  if (n && (!h2_read(msgs.data(), w.msgs[w.cur & 1u], sizeof(grdma_h2_msg_dev) * n) || !h2_read(prog.data(), w.prog[w.cur & 1u], sizeof(uint64_t) * n)))
+    return -GRDMA_ERR_HIP;
+  uint64_t k = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    if (prog[i] >= 5 + msgs[i].len) continue;  // (finished: the next call's compaction drops it)
+    if (k < cap) {
+      out[3 * k] = msgs[i].stream_id;
+      out[3 * k + 1] = msgs[i].len;
+      out[3 * k + 2] = prog[i];
+    }
+    k++;
+  }
+  return (int64_t)k;
+}
+
+// ---- the windowed replies of many transports in four launches (h2_stage_wr_frame_links) -------------------------------
+// The batch block of the process holds [the queues' table | the send windows' table] (the ledger batch's layout: the
+// second table where that one has its call blocks) and goes up in one copy; an item's call words and framing words go up
+// into its own queue's and send windows' device memory, its result block comes down from its queue.
+int grdma_h2_reply_frame_windowed_batch(grdma_h2_wr_item* items, uint32_t n_items) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!items || n_items == 0 || n_items > GRDMA_H2_BATCH_MAX)
+    return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 windowed reply batch: 1 .. GRDMA_H2_BATCH_MAX items");
+  for (uint32_t i = 0; i < n_items; i++) {
+    const grdma_h2_wr_item& it = items[i];
+    if (const char* why = h2_wr_refusal(it.reply, it.flags, it.d_slices_out, it.slices_cap, it.d_hdr_arena, it.hdr_cap))
+      return grdma_fail_msg(GRDMA_ERR_INVALID, why);
+    for (uint32_t k = 0; k < i; k++) {
+      if (items[k].reply == it.reply) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 windowed reply batch: the same reply twice");
+      if (items[k].reply->src == it.reply->src)
+        return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 windowed reply batch: two replies of one source assembler");
+    }
+  }
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  hipStream_t st = hc->stream;
+  const h2_fc_block L = h2_fc_block_layout(sizeof(h2wr_link), sizeof(h2sw_link), n_items);
+  if (!h2_batch_reserve(L.total, st)) return -GRDMA_ERR_HIP;
+  uint8_t* const d = g_batch.d;
+  std::vector<uint8_t> up(L.end, 0);
+  auto* tab = reinterpret_cast<h2wr_link*>(up.data() + L.tab);
+  auto* sw_tab = reinterpret_cast<h2sw_link*>(up.data() + L.calls);
+  std::vector<h2sw_dev> words(n_items);
+  std::vector<uint64_t> res(16 * (size_t)n_items);
+  std::vector<char> take(n_items);
+  const h2_stage framing = h2_stage_wr_frame_links(reinterpret_cast<const h2wr_link*>(d + L.tab),
+                                                   reinterpret_cast<const h2sw_link*>(d + L.calls), n_items);
+  h2_call c{"h2 windowed reply batch: a launch was rejected", {{d, up.data(), up.size()}}, {}, {h2_all(framing)}, {}};
+  for (uint32_t i = 0; i < n_items; i++) {
+    const grdma_h2_wr_item& it = items[i];
+    grdma_h2_reply* r = it.reply;
+    take[i] = h2_wr_call_words(r, it.flags) ? 1 : 0;
+    words[i] = h2_wr_sw_words(r, it.d_slices_out, it.slices_cap, it.d_hdr_arena, it.hdr_cap);
+    tab[i].W = r->d_wr;
+    sw_tab[i].F = r->sw->d;
+    sw_tab[i].call = nullptr;
+    c.up.push_back({reinterpret_cast<uint8_t*>(r->d_wr) + offsetof(h2wr_dev, take), reinterpret_cast<const uint8_t*>(&r->wr) + offsetof(h2wr_dev, take),
+                    offsetof(h2wr_dev, n_tab) - offsetof(h2wr_dev, take)});
+    c.up.push_back({reinterpret_cast<uint8_t*>(r->sw->d) + offsetof(h2sw_dev, msgs), reinterpret_cast<const uint8_t*>(&words[i]) + offsetof(h2sw_dev, msgs),
+                    offsetof(h2sw_dev, conn) - offsetof(h2sw_dev, msgs)});
+    c.down.push_back({res.data() + 16 * (size_t)i, reinterpret_cast<const uint8_t*>(r->d_wr) + offsetof(h2wr_dev, res), 16 * sizeof(uint64_t)});
+  }
+  for (uint32_t i = 0; i < n_items; i++)
+    if (!h2_wait_parser(st, items[i].reply->src->parser) || !h2_wait_parser(st, items[i].reply->sw->parser)) return -GRDMA_ERR_HIP;
+  if (int rc = h2_call_run(hc, &c)) return rc;
+  g_h2_last_kernel_us = 1e3 * c.ms[0];
+  int ok = 0;
+  for (uint32_t i = 0; i < n_items; i++) {
+    grdma_h2_wr_item& it = items[i];
+    const uint64_t* rs = res.data() + 16 * (size_t)i;
+    h2_wr_ran(it.reply, take[i] != 0, rs, c.ms[0]);
+    for (int k = 0; k < 16; k++) it.out[k] = rs[k];
+    it.out[H2WR_US] = (uint64_t)(c.ms[0] * 1e3f);  // (the batch's, repeated)
+    it.n_slices = rs[H2WR_OVERFLOW] ? -(int64_t)GRDMA_ERR_CAPACITY : (int64_t)rs[H2WR_SLICES];
+    ok += rs[H2WR_OVERFLOW] == 0;
   }
   return ok;
 }
@@ -1531,6 +1775,7 @@ int grdma_h2_deframe_messages_batch(grdma_h2_messages_item* items, uint32_t n_it
     grdma_h2_messages_item& it = items[i];
     it.assembler->plan_ms = c.ms[1];  // (the batch's, repeated)
     it.assembler->copy_ms = c.ms[2];
+    it.assembler->calls++;
     it.n_msgs = it.n_events < 0 ? -(int64_t)GRDMA_ERR_CAPACITY : h2_asm_descriptors(hs[i], it.msgs_out, it.msgs_cap, st);
     if (it.n_msgs == -(int64_t)GRDMA_ERR_HIP) return -GRDMA_ERR_HIP;
     more = more || it.n_msgs > 0;

@@ -73,7 +73,7 @@ static bool h2_seq_install(h2_step_seq* s, const h2_stage& pre, const h2_stage& 
 // shape the job's graph was recorded for.  The source of a reply pipe assembles in forward pipes.
 static bool h2_seq_bind_reply(h2_step_seq* s, grdma_h2_reply* r, grdma_sge* d_sges, uint64_t count, uint8_t* d_hdr,
                               uint64_t hdr_cap, uint64_t recorded_wire_bytes) {
-  if (r->seq || !r->src->attached) return false;
+  if (r->seq || !r->src->attached || r->d_wr) return false;  // (a reply under send windows frames standalone only)
   if (!h2_reply_set_target(r, d_sges, count, d_hdr, hdr_cap, 1, count, recorded_wire_bytes, nullptr)) return false;
   r->seq = s;
   r->src->reply_pipes++;

@@ -60,6 +60,12 @@ class H2SwFrameItem(C.Structure):
                 ("d_hdr_arena", C.c_void_p), ("hdr_cap", u64)]
 
 
+class H2WrItem(C.Structure):
+    _fields_ = [("reply", C.c_void_p), ("flags", C.c_uint32), ("pad", C.c_uint32), ("d_slices_out", C.c_void_p),
+                ("slices_cap", u64), ("d_hdr_arena", C.c_void_p), ("hdr_cap", u64), ("n_slices", C.c_int64),
+                ("out", u64 * 16)]
+
+
 class H2CtlItem(C.Structure):
     _fields_ = [("ctl", C.c_void_p), ("d_slices_out", C.c_void_p), ("slices_cap", u64), ("d_hdr_arena", C.c_void_p),
                 ("hdr_cap", u64)]
@@ -234,6 +240,14 @@ def _bind():
         lib.grdma_h2_sw_intake_batch.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(u64)]
         lib.grdma_h2_sw_frame_batch.restype = C.c_int
         lib.grdma_h2_sw_frame_batch.argtypes = [C.POINTER(H2SwFrameItem), C.c_uint32, C.POINTER(u64)]
+        lib.grdma_h2_reply_attach_windows.restype = C.c_int
+        lib.grdma_h2_reply_attach_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        lib.grdma_h2_reply_frame_windowed.restype = C.c_int64
+        lib.grdma_h2_reply_frame_windowed.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, u64, C.c_void_p, u64, C.POINTER(u64)]
+        lib.grdma_h2_reply_pending.restype = C.c_int64
+        lib.grdma_h2_reply_pending.argtypes = [C.c_void_p, C.POINTER(u64), u64]
+        lib.grdma_h2_reply_frame_windowed_batch.restype = C.c_int
+        lib.grdma_h2_reply_frame_windowed_batch.argtypes = [C.POINTER(H2WrItem), C.c_uint32]
         lib.grdma_h2_ctl_create.restype = C.c_void_p
         lib.grdma_h2_ctl_create.argtypes = [C.c_void_p, C.c_uint32]
         lib.grdma_h2_ctl_destroy.argtypes = [C.c_void_p]
@@ -649,10 +663,72 @@ class Reply:
         self.last_stats = dict(zip(Reply.REPLY_STATS, [int(x) for x in out]))
         return check(n), self.last_stats
 
+    # ---- under the peer's windows (grdma_h2_reply_attach_windows / _frame_windowed) -----------------------------------
+    WINDOWED = ("finished", "pending", "slices", "hdr_bytes", "wire_bytes", "granted", "stall", "overflow", "taken_new",
+                "dropped_status", "unrouted", "dropped_closed", "releasable", "flags", "frame_us", "spare")
+    PENDING_ONLY, LOST = 1, 1
+
+    def attach_windows(self, sw, max_pending=4096):
+        """binds the reply to the SendWindows of the transport its replies go out on and allocates the queue of what the
+        windows cut off; from then on frame_windowed frames, frame is refused"""
+        rc = self.lib.grdma_h2_reply_attach_windows(self.h, sw.h if sw is not None else None, max_pending)
+        if rc < 0:
+            raise GrdmaError("h2 windowed reply: " + (self.lib.grdma_last_error() or b"attach failed").decode())
+        self.send_windows = sw  # (kept alive)
+
+    def frame_windowed(self, slices_ptr, cap, hdr_ptr, hdr_cap, pending_only=False):
+        """what waited, then (unless pending_only) what the assembler's last call brought, under the windows ->
+        ([(ptr, len), ...], dict of WINDOWED); raises GrdmaError on a refusal or an overflow -- the result of the failed
+        call stays in .last_windowed, nothing was sent, the queue stands"""
+        out = (u64 * 16)()
+        n = self.lib.grdma_h2_reply_frame_windowed(self.h, Reply.PENDING_ONLY if pending_only else 0, slices_ptr, cap,
+                                                   hdr_ptr, hdr_cap, out)
+        self.last_windowed = dict(zip(Reply.WINDOWED, [int(x) for x in out]))
+        n = check(n)
+        return _read_slice_table(self.lib, slices_ptr, n), self.last_windowed
+
+    def pending(self):
+        """the queue as it is: [(outgoing stream, message length, flow-controlled bytes sent), ...] in its order"""
+        n = check(self.lib.grdma_h2_reply_pending(self.h, None, 0))
+        out = (u64 * max(1, 3 * n))()
+        n = check(self.lib.grdma_h2_reply_pending(self.h, out, n))
+        return [(int(out[3 * i]), int(out[3 * i + 1]), int(out[3 * i + 2])) for i in range(n)]
+
     def close(self):
         if self.h:
             self.lib.grdma_h2_reply_destroy(self.h)
             self.h = None
+
+
+def _read_slice_table(lib, slices_ptr, n):
+    raw = C.create_string_buffer(max(1, 16 * n))
+    if n:
+        check(lib.grdma_copy_to_host(raw, slices_ptr, 16 * n))
+    return [(int.from_bytes(raw.raw[16 * i:16 * i + 8], "little"), int.from_bytes(raw.raw[16 * i + 8:16 * i + 16], "little"))
+            for i in range(n)]
+
+
+def reply_frame_windowed_batch(items):
+    """Reply.frame_windowed for many transports in four launches (grdma_h2_reply_frame_windowed_batch).  items: [(Reply,
+    slices device ptr, slices cap, header arena device ptr, header cap, pending_only), ...] with distinct replies of
+    distinct source assemblers, each attached to its own SendWindows.  -> per item (slice list, or the integer
+    -GRDMA_ERR_CAPACITY (-5) where that item overflowed and nothing of it was written; dict of Reply.WINDOWED).  frame_us
+    is the batch's, repeated.  The results also land in each Reply's .last_windowed."""
+    lib = _bind()
+    n = len(items)
+    arr = (H2WrItem * max(1, n))()
+    for i, (reply, sl, cap, hdr, hdr_cap, pending_only) in enumerate(items):
+        arr[i].reply = reply.h if reply is not None else None
+        arr[i].flags = Reply.PENDING_ONLY if pending_only else 0
+        arr[i].d_slices_out, arr[i].slices_cap, arr[i].d_hdr_arena, arr[i].hdr_cap = sl, cap, hdr, hdr_cap
+    check(lib.grdma_h2_reply_frame_windowed_batch(arr, n))
+    res = []
+    for i in range(n):
+        st = dict(zip(Reply.WINDOWED, [int(x) for x in arr[i].out]))
+        items[i][0].last_windowed = st
+        k = int(arr[i].n_slices)
+        res.append((_read_slice_table(lib, items[i][1], k) if k >= 0 else k, st))
+    return res
 
 
 FC_CONN_OVERFLOW, FC_STREAM_OVERFLOW, FC_LOST = 1, 2, 4

@@ -975,8 +975,8 @@ int grdma_h2_fc_account_batch(const grdma_h2_fc_item* items, uint32_t n, uint64_
  * with no call yet or of the same call twice, a parser that is gone (destroy still works), n = 0 or above 4096, r_i = 0,
  * max_frame 0 or >= 2^24, null, zero or misaligned (16 bytes) targets.
  * Not here: intake of a pipe's or group pipe's steps and the windowed framer as a pipe's framing stage (a job's graph
- * carries a fixed slice count per step; a window-cut step has another shape), the reply framer under windows, the
- * other settings, HPACK (SETTINGS ACK: grdma_h2_ctl below).  (The many-link batch forms: grdma_h2_sw_intake_batch / _frame_batch below.) */
+ * carries a fixed slice count per step; a window-cut step has another shape), the
+ * other settings, HPACK (the reply framer under these windows: grdma_h2_reply_frame_windowed below) (SETTINGS ACK: grdma_h2_ctl below).  (The many-link batch forms: grdma_h2_sw_intake_batch / _frame_batch below.) */
 enum grdma_h2_sw_violation { GRDMA_H2_SW_BAD_INCREMENT = 1, GRDMA_H2_SW_WINDOW_OVERFLOW = 2, GRDMA_H2_SW_BAD_SETTINGS = 4,
                              GRDMA_H2_SW_LOST = 8 };
 typedef struct grdma_h2_sw grdma_h2_sw;
@@ -1025,6 +1025,81 @@ typedef struct grdma_h2_sw_frame_item {
   uint64_t hdr_cap;
 } grdma_h2_sw_frame_item;
 int grdma_h2_sw_frame_batch(const grdma_h2_sw_frame_item* items, uint32_t n, uint64_t* out);
+
+/* ---- Replies under the peer's windows (csrc/grdma_h2_wr.h) ----
+ * grdma_h2_reply_frame under a grdma_h2_sw: the device-resident reply path (deframer, assembler, reply, wire) against a
+ * peer that holds it to its windows.  What the windows cut off waits in a queue in DEVICE memory -- a reply has no host
+ * table -- and its bytes stay unreleased in the source assembler's ring until they are sent.
+ * BINDING.  grdma_h2_reply_attach_windows(reply, sw, max_pending) binds a reply framer to the send windows of the
+ *  transport its replies go OUT on: for an echo the send windows of the source assembler's own parser, for a proxy
+ *  another transport's.  It allocates the queue, max_pending = 1 .. 4096 entries (the windowed plan's limit).  One
+ *  attachment per reply and one per sw.  Source calls in front of the attachment are not the queue's business.
+ *  -GRDMA_ERR_INVALID: a reply bound to a reply pipe, a source assembler attached to a pipe, a second attachment of either,
+ *  a sw whose parser is gone.  grdma_h2_reply_destroy and grdma_h2_sw_destroy work in either order; after the other is
+ *  gone every call on the survivor but destroy is refused (the queue held what the windows had promised).
+ *  grdma_h2_reply_frame on an attached reply is refused: one message could go out twice.
+ * THE CALL.  grdma_h2_reply_frame_windowed frames ONE message table: [the queue's entries, in their order | the kept
+ *  descriptors of the source assembler's last call, in reported order].  The second part is there only if that call has
+ *  not been taken yet and flags lacks GRDMA_H2_WR_PENDING_ONLY.  Kept and routed as grdma_h2_reply_frame keeps and
+ *  routes: status OK, the route table, the compressed flag passed through, never END_STREAM.  The table is framed as
+ *  grdma_h2_sw_frame frames a host table with the same messages and progress (the grant, the piece layout, mf =
+ *  min(the reply's max_frame, peer MAX_FRAME_SIZE), the slice merge rules); new entries start at progress 0.  An entry
+ *  that finishes leaves the queue, the others stay in order with their new progress: per-stream order is the queue's
+ *  order, and the grant gives nothing once an earlier message of the stream is unfinished.
+ * CLOSED STREAMS.  Before the grant every entry, old or new, is looked up in the map of the sw's parser.  An entry whose
+ *  outgoing stream the map does not hold is dropped -- even one that is partly sent -- and counted in `dropped closed`:
+ *  the peer has reset or finished that stream, and a message that can never be granted must not pin the ring.  So the
+ *  stall bits never carry 4 (an unknown stream).
+ * TAKING THE SOURCE'S CALLS.  The assembler counts its standalone calls (grdma_h2_deframe_messages and _batch).  A
+ *  call taken already and no flag: the queue alone is framed.  No source call since the attachment and an empty queue:
+ *  -GRDMA_ERR_INVALID.  A source call that was never taken because the count ran ahead by more than one: the sticky
+ *  GRDMA_H2_WR_LOST in the flags word; the call itself is answered.  A call the assembler skipped, or more descriptors
+ *  than the reply's max_messages: overflow word 1.
+ * OVERFLOW.  A slice or header cap too small: overflow word 1, the totals in their words.  More entries than
+ *  max_pending: overflow word 2, their count in the `still pending` word.  Both: -GRDMA_ERR_CAPACITY, NOTHING is
+ *  written, no window moves, the queue and its progress stand, the source call is NOT taken, the words 8 .. 11 are 0.
+ *  Repeat the call with larger targets, or with GRDMA_H2_WR_PENDING_ONLY once credit has come in.
+ * RELEASE.  Payload goes by reference into the assembler's arena.  `releasable` says how many of the oldest
+ *  reported-and-unreleased messages no queue entry refers to after this call, in the unit grdma_h2_asm_release counts
+ *  in (every reported descriptor is one, NO_SPACE ones too): messages finished in this call, dropped by status,
+ *  unrouted, dropped as closed, of a lost call.  A source call that is new but was not taken is not covered.  Release
+ *  them behind the send that gathers this call's slices.
+ * RESULT BLOCK out[16]: {0 finished, 1 still pending, 2 slices, 3 header-arena bytes, 4 wire bytes, 5 flow-controlled
+ *  bytes granted, 6 stall bits (1 = the connection's window, 2 = a stream's), 7 overflow, 8 taken new (descriptors
+ *  appended to the queue), 9 dropped by status, 10 unrouted, 11 dropped closed, 12 releasable, 13 flags (GRDMA_H2_WR_LOST),
+ *  14 framing time in us (HIP events, the four launches), 15 spare: 0}.  Returns the slice count.
+ * MIXING.  grdma_h2_sw_frame and grdma_h2_sw_intake on the same sw between windowed replies are allowed and consistent:
+ *  the windows are one state, and the queue owns its progress words.
+ * -GRDMA_ERR_INVALID (grdma_last_error says why): no attachment, send windows or parser gone, null, zero or misaligned
+ *  (16 bytes) targets, unknown flags.
+ * Not here: the windowed reply inside a pipe or group pipe (a job's graph carries a fixed slice count per step). */
+enum { GRDMA_H2_WR_PENDING_ONLY = 1 };  /* flags of a call */
+enum { GRDMA_H2_WR_LOST = 1 };          /* flags word of the result block */
+int grdma_h2_reply_attach_windows(grdma_h2_reply* reply, grdma_h2_sw* sw, uint32_t max_pending);
+int64_t grdma_h2_reply_frame_windowed(grdma_h2_reply* reply, uint32_t flags, grdma_slice* d_slices_out, uint64_t slices_cap,
+                                      void* d_hdr_arena, uint64_t hdr_cap, uint64_t out[16]);
+/* the queue as it is, unfinished entries in order: per entry {outgoing stream, message length, flow-controlled bytes
+ * sent} in out[3 i .. 3 i + 2], at most cap entries written; returns their number */
+int64_t grdma_h2_reply_pending(grdma_h2_reply* reply, uint64_t* out, uint64_t cap);
+/* grdma_h2_reply_frame_windowed for n replies (1 .. GRDMA_H2_BATCH_MAX) in the same four launches (k_h2_links_wr_queue,
+ * k_h2_links_sw_plan, k_h2_links_sw_emit, k_h2_links_wr_commit): every item frames its own queue and source call under
+ * its own windows into its own targets, exactly as the single call does.  An item's overflow (1 or 2) and its LOST flag
+ * stay with the item: n_slices is -GRDMA_ERR_CAPACITY there and the other items are exact.  Returns the number of items
+ * without overflow, or a negative error.  -GRDMA_ERR_INVALID (nothing runs, nothing changes): n outside the range, a NULL
+ * array, an item without reply, the same reply, source assembler or send windows twice, and per item what the single
+ * call refuses. */
+typedef struct grdma_h2_wr_item {
+  grdma_h2_reply* reply;      /* distinct, attached to distinct send windows, of distinct source assemblers */
+  uint32_t flags;             /* GRDMA_H2_WR_PENDING_ONLY */
+  uint32_t pad;
+  grdma_slice* d_slices_out;  /* device slice table of the item */
+  uint64_t slices_cap;
+  void* d_hdr_arena;          /* device header arena of the item, 32 bytes per frame */
+  uint64_t hdr_cap;
+  int64_t n_slices;           /* out: the single call's return value */
+  uint64_t out[16];           /* out: the single call's result block; out[14] is the batch's time, repeated */
+} grdma_h2_wr_item;
+int grdma_h2_reply_frame_windowed_batch(grdma_h2_wr_item* items, uint32_t n);
 
 /* ---- Control replies on the device: SETTINGS ACK, PING ACK, RST_STREAM (csrc/grdma_h2_ctl.h) ----
  * The frames HTTP/2 obliges a transport to answer, written in device memory from a deframing's events, so that a
