@@ -306,15 +306,18 @@ static bool h2_wait_parser(hipStream_t st, const grdma_h2_parser* p) {
   return !p->last_deframed || p->last_stream == st || hipStreamWaitEvent(st, p->last_deframed, 0) == hipSuccess;
 }
 
-// a host message table in the device's form
-static std::vector<grdma_h2_msg_dev> h2_msg_table(const grdma_h2_msg* msgs, uint64_t n) {
-  std::vector<grdma_h2_msg_dev> tab(n);
+// a host message table in the device's form: into tab, or as a table of its own
+static void h2_msg_rows(const grdma_h2_msg* msgs, uint64_t n, grdma_h2_msg_dev* tab) {
   for (uint64_t i = 0; i < n; i++) {
     tab[i].payload = static_cast<const uint8_t*>(msgs[i].payload);
     tab[i].len = msgs[i].len;
     tab[i].stream_id = msgs[i].stream_id;
     tab[i].flags = msgs[i].flags;
   }
+}
+static std::vector<grdma_h2_msg_dev> h2_msg_table(const grdma_h2_msg* msgs, uint64_t n) {
+  std::vector<grdma_h2_msg_dev> tab(n);
+  h2_msg_rows(msgs, n, tab.data());
   return tab;
 }
 // ... uploaded to a device table of its own (a pipe's: the caller frees it)

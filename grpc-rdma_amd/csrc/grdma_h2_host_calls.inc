@@ -66,6 +66,83 @@ static bool h2_push_words(void* dev, const void* host, size_t off_begin, size_t 
   const size_t len = off_end - off_begin;
   return (st ? hipMemcpyAsync(dst, src, len, hipMemcpyHostToDevice, st) : hipMemcpy(dst, src, len, hipMemcpyHostToDevice)) == hipSuccess;
 }
+// ... as an upload of a call
+static h2_xfer h2_words(void* dev, const void* host, size_t off_begin, size_t off_end) {
+  return {static_cast<uint8_t*>(dev) + off_begin, static_cast<const uint8_t*>(host) + off_begin, off_end - off_begin};
+}
+// the n result words at off of a device block, as a download of a call
+static h2_xfer h2_result(uint64_t* dst, const void* dev, size_t off, size_t n = 8) {
+  return {dst, static_cast<const uint8_t*>(dev) + off, n * sizeof(uint64_t)};
+}
+
+// ---- what a facility's single call and its batch share ---------------------------------------------------------------------
+// The rules of a facility stand once, in static functions over ONE item: a refusal (a reason without the facility's
+// name, NULL when there is none), the call block or words, the target words, and what the host keeps behind a call that
+// ran.  The single entry point is those steps around its own stage; the batch is the same steps in a loop around the
+// links stage, inside an h2_batch (below).
+static int h2_invalid(const char* who, const char* why) {
+  char msg[256];
+  snprintf(msg, sizeof(msg), "%s: %s", who, why);
+  return grdma_fail_msg(GRDMA_ERR_INVALID, msg);  // (copies it)
+}
+// a refused creation
+static std::nullptr_t h2_no(const char* why) {
+  grdma_fail_msg(GRDMA_ERR_INVALID, why);
+  return nullptr;
+}
+
+// where a call writes frames: a slice table and a header arena in device memory
+static const char* h2_bad_target(const void* d_slices_out, uint64_t slices_cap, const void* d_hdr_arena, uint64_t hdr_cap) {
+  if (!d_slices_out || !slices_cap || !d_hdr_arena || !hdr_cap || ((uintptr_t)d_slices_out & 15) || ((uintptr_t)d_hdr_arena & 15))
+    return "a null, zero or misaligned slice table or header arena";
+  return nullptr;
+}
+
+// A follower of a parser's standalone deframings: the ledger, the send windows and the control-reply writer each read
+// what the last grdma_h2_deframe / grdma_h2_deframe_messages left in the parser's buffers, every call once.
+struct h2_follow {
+  grdma_h2_parser* parser = nullptr;  // NULL once the parser is gone: the follower's device block points into the parser's
+  uint64_t taken = 0;                 // parser->standalone_calls of the last call taken
+  float last_ms = 0;                  // of the last call's stage
+};
+// The parser of f is being destroyed: standalone calls on the stream of the calls have ended, and from now on f refuses
+// every call but destroy.  (A ledger attached to a pipe stays with the pipe, whose parser must outlive it.)
+static void h2_follow_parser_gone(h2_follow* f) {
+  h2_host_ctx* hc = h2_ctx();
+  if (hc) hipStreamSynchronize(hc->stream);
+  f->parser = nullptr;
+}
+// positions32: the facility keeps event positions in 32 bits
+static const char* h2_follow_refusal(const h2_follow& f, const char* taken_already, bool positions32) {
+  const grdma_h2_parser* p = f.parser;
+  if (!p) return "the parser is gone";
+  if (p->standalone_calls == 0) return "the parser has deframed nothing yet";
+  if (f.taken == p->standalone_calls) return taken_already;
+  if (positions32 && p->standalone_ev_cap >= 0xfffffff0ull) return "event positions are 32 bits";
+  return nullptr;
+}
+// The parser's last standalone deframing as f's call block names it; each facility's block takes the members it has.
+struct h2_deframed {
+  const grdma_h2_event* ev;
+  const grdma_h2_deframe_result* res;
+  const grdma_slice_out* sl;
+  const uint8_t* arena;
+  uint64_t ev_cap, nsl;
+  uint64_t skipped;  // a deframing in front of this one was never taken
+  operator h2fc_call() const { return {ev, res, ev_cap}; }
+  operator h2sw_call() const { return {ev, res, sl, arena, ev_cap, nsl, skipped}; }
+  operator h2ctl_call() const { return {ev, res, sl, arena, ev_cap, nsl, skipped}; }
+};
+static h2_deframed h2_follow_deframed(const h2_follow& f) {
+  const grdma_h2_parser* p = f.parser;
+  return {p->d_ev, p->d_res, p->d_sl, p->standalone_arena, p->standalone_ev_cap, p->standalone_nsl,
+          p->standalone_calls > f.taken + 1 ? 1ull : 0ull};
+}
+// behind a call of f that ran
+static void h2_follow_ran(h2_follow* f, float ms, bool taken = true) {
+  f->last_ms = ms;
+  if (taken) f->taken = f->parser->standalone_calls;
+}
 
 static double g_h2_last_kernel_us = 0;
 static uint64_t g_h2_last_boundary_steps = 0;
@@ -152,14 +229,10 @@ grdma_h2_parser* grdma_h2_parser_create(int expect_client_prefix, uint32_t max_f
                                    max_frame_size, 0xffffffffu, 0);
 }
 
-static void h2_fc_parser_gone(struct grdma_h2_fc* f);
-static void h2_sw_parser_gone(struct grdma_h2_sw* s);
-static void h2_ctl_parser_gone(struct grdma_h2_ctl* w);
+static void h2_followers_parser_gone(grdma_h2_parser* p);
 void grdma_h2_parser_destroy(grdma_h2_parser* p) {
   if (!p) return;
-  if (p->fc) h2_fc_parser_gone(p->fc);  // (the ledger outlives its parser as a husk: every call on it is refused)
-  if (p->sw) h2_sw_parser_gone(p->sw);  // (the send windows too)
-  if (p->ctl) h2_ctl_parser_gone(p->ctl);  // (and the control-reply writer)
+  h2_followers_parser_gone(p);  // (the ledger, the send windows and the control-reply writer outlive it as husks)
   hipFree(p->d);
   hipFree(p->d_tab);
   hipFree(p->d_sl);
@@ -285,6 +358,64 @@ bool h2_batch_reserve(uint64_t total, hipStream_t st) {
 }
 }  // namespace
 
+// The scaffold of a batch call whose block is [table | one block per item] (the ledgers', the send windows', the
+// writers', the windowed replies' and the replies'): begin, item for each item, open, the facility's per-item steps
+// (which fill the image and add each item's own uploads, downloads and parsers to wait for), run.
+struct h2_batch {
+  const char* who;   // "h2 ... batch": leads every refusal
+  const char* noun;  // what an item names
+  const char* launch_refused;  // grdma_last_error when the runtime refuses a launch
+  h2_host_ctx* hc = nullptr;
+  uint8_t* d = nullptr;      // the block in device memory: the table at d, and behind open() the items' blocks at d + blocks
+  uint64_t blocks = 0;
+  std::vector<uint8_t> up;   // its host image, zeroed (a result block never reports another call's)
+  std::vector<const void*> seen;
+  std::vector<const grdma_h2_parser*> behind;  // the call goes behind each one's last deframing by a pipe (another stream)
+  h2_call c{};
+
+  int begin(bool arrays, uint32_t n_items) {
+    if (!arrays || n_items == 0 || n_items > GRDMA_H2_BATCH_MAX) return h2_invalid(who, "1 .. GRDMA_H2_BATCH_MAX items");
+    seen.reserve(n_items);
+    behind.reserve(2 * (size_t)n_items);
+    return 0;
+  }
+  // one item per object; why: what the facility's own rules refuse the item for (an item without object among them)
+  int item(const void* obj, const char* why) {
+    for (const void* s : seen)
+      if (obj && s == obj) {
+        char twice[96];
+        snprintf(twice, sizeof(twice), "the same %s twice", noun);
+        return h2_invalid(who, twice);
+      }
+    seen.push_back(obj);
+    return why ? h2_invalid(who, why) : 0;
+  }
+  // a block of `total` bytes whose first `end` go up (a layout of the caller's own)
+  int reserve(uint64_t end, uint64_t total) {
+    hc = h2_ctx();
+    if (!hc || !h2_batch_reserve(total, hc->stream)) return -GRDMA_ERR_HIP;
+    d = g_batch.d;
+    up.assign(end, 0);
+    c.up.reserve(1 + 3 * seen.size());
+    c.down.reserve(1 + 2 * seen.size());
+    c.up.push_back({d, up.data(), up.size()});
+    return 0;
+  }
+  int open(uint64_t link_bytes, uint64_t block_bytes, uint32_t n_items) {
+    const h2_fc_block L = h2_fc_block_layout(link_bytes, block_bytes, n_items);
+    blocks = L.calls;
+    return reserve(L.end, L.total);
+  }
+  // 0, or what h2_call_run returns; c.ms: what the timed sections took
+  int run(std::vector<h2_span> timed) {
+    for (const grdma_h2_parser* p : behind)
+      if (!h2_wait_parser(hc->stream, p)) return -GRDMA_ERR_HIP;
+    c.refused = launch_refused;
+    c.timed = std::move(timed);
+    return h2_call_run(hc, &c);
+  }
+};
+
 static_assert(sizeof(grdma_read_slice) == sizeof(grdma_slice_out) && sizeof(grdma_slice_out) % 16 == 0, "layout");
 static h2_deframe_block h2_deframe_batch_layout(uint32_t n_items, uint64_t n_sl, uint64_t n_ev, bool assembled) {
   return h2_deframe_block_layout({sizeof(grdma_h2_link_deframe), sizeof(grdma_slice_out), sizeof(grdma_h2_deframe_result),
@@ -336,35 +467,28 @@ static void h2_batch_hand_back(Item* items, uint32_t n_items, const h2_deframe_b
 
 int grdma_h2_deframe_batch(grdma_h2_deframe_item* items, uint32_t n_items) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!items || n_items == 0 || n_items > GRDMA_H2_BATCH_MAX) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 batch: 1 .. GRDMA_H2_BATCH_MAX items");
+  h2_batch b{"h2 batch", "parser", "h2 batch: a launch was rejected"};
+  if (int rc = b.begin(items, n_items)) return rc;
   uint64_t n_sl = 0, n_ev = 0;
   for (uint32_t i = 0; i < n_items; i++) {
     const grdma_h2_deframe_item& it = items[i];
-    if (!it.parser || !it.d_arena || (!it.slices && it.n) || (!it.events_out && it.cap))
-      return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 batch: an item without parser, arena, slices or event array");
-    if (it.parser->asm_attached) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 batch: a parser whose assembler is attached to a pipe");
-    if (it.parser->fc) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 batch: a parser with a flow-control ledger (single transport only)");
-    for (uint32_t k = 0; k < i; k++)
-      if (items[k].parser == it.parser) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 batch: the same parser twice");
+    const char* why = nullptr;
+    if (!it.parser || !it.d_arena || (!it.slices && it.n) || (!it.events_out && it.cap)) why = "an item without parser, arena, slices or event array";
+    else if (it.parser->asm_attached) why = "a parser whose assembler is attached to a pipe";
+    else if (it.parser->fc) why = "a parser with a flow-control ledger (single transport only)";
+    if (int rc = b.item(it.parser, why)) return rc;
     n_sl += it.n;
     n_ev += it.cap;
   }
-  h2_host_ctx* hc = h2_ctx();
-  if (!hc) return -GRDMA_ERR_HIP;
   const h2_deframe_block L = h2_deframe_batch_layout(n_items, n_sl, n_ev, false);
-  if (!h2_batch_reserve(L.total, hc->stream)) return -GRDMA_ERR_HIP;
-  uint8_t* const d = g_batch.d;
-  std::vector<uint8_t> up(L.events, 0), down(L.total - L.results);  // (the result blocks go up zeroed: a call never reports another's)
-  h2_batch_pack(items, n_items, L, up.data(), d);
-  // behind each parser's previous deframing (a pipe step on another stream)
-  for (uint32_t i = 0; i < n_items; i++)
-    if (!h2_wait_parser(hc->stream, items[i].parser)) return -GRDMA_ERR_HIP;
-  const h2_stage deframing = h2_stage_deframe_links(reinterpret_cast<const grdma_h2_link_deframe*>(d + L.tab), n_items);
-  h2_call c{"h2 batch: the launch of k_h2_deframe_links was rejected",
-            {{d, up.data(), up.size()}}, {}, {h2_all(deframing)},
-            {{down.data(), d + L.results, down.size()}}};
-  if (int rc = h2_call_run(hc, &c)) return rc;
-  g_h2_last_kernel_us = 1e3 * c.ms[0];
+  if (int rc = b.reserve(L.events, L.total)) return rc;  // ([0, events) goes up)
+  std::vector<uint8_t> down(L.total - L.results);
+  h2_batch_pack(items, n_items, L, b.up.data(), b.d);
+  for (uint32_t i = 0; i < n_items; i++) b.behind.push_back(items[i].parser);
+  b.c.down.push_back({down.data(), b.d + L.results, down.size()});
+  const h2_stage deframing = h2_stage_deframe_links(reinterpret_cast<const grdma_h2_link_deframe*>(b.d + L.tab), n_items);
+  if (int rc = b.run({h2_all(deframing)})) return rc;
+  g_h2_last_kernel_us = 1e3 * b.c.ms[0];
   h2_batch_hand_back(items, n_items, L, down.data());
   return 0;
 }
@@ -567,18 +691,22 @@ struct grdma_h2_reply {
 };
 static void h2_wr_free(grdma_h2_reply* r);
 
-// where the calls frame to, and (a pipe) the shape they must have: the words of h2r_dev from `out` to the result block
+// where a call frames to, and (a pipe) the shape it must have: the words of an h2r_dev from `out` to the result block
+static void h2_reply_target(h2r_dev* h, grdma_sge* out, uint64_t cap, uint8_t* hdr, uint64_t hdr_cap, uint64_t check_shape,
+                            uint64_t want_slices, uint64_t want_wire) {
+  h->out = out;
+  h->cap = cap;
+  h->hdr = hdr;
+  h->hdr_cap = hdr_cap;
+  h->check_shape = check_shape;
+  h->want_slices = want_slices;
+  h->want_wire = want_wire;
+}
+// ... in r's host copy, and uploaded (a pipe's)
 static bool h2_reply_set_target(grdma_h2_reply* r, grdma_sge* out, uint64_t cap, uint8_t* hdr, uint64_t hdr_cap,
                                 uint64_t check_shape, uint64_t want_slices, uint64_t want_wire, hipStream_t st) {
-  h2r_dev& h = r->h;
-  h.out = out;
-  h.cap = cap;
-  h.hdr = hdr;
-  h.hdr_cap = hdr_cap;
-  h.check_shape = check_shape;
-  h.want_slices = want_slices;
-  h.want_wire = want_wire;
-  return h2_push_words(r->d, &h, offsetof(h2r_dev, out), offsetof(h2r_dev, res), st);
+  h2_reply_target(&r->h, out, cap, hdr, hdr_cap, check_shape, want_slices, want_wire);
+  return h2_push_words(r->d, &r->h, offsetof(h2r_dev, out), offsetof(h2r_dev, res), st);
 }
 
 // (a pipe's reader, behind the pipe's own wait: a blocking copy, not a copy and a synchronise on the stream of the calls --
@@ -641,119 +769,85 @@ void grdma_h2_reply_destroy(grdma_h2_reply* r) {
   delete r;
 }
 
+// what a call on r into these targets is refused for
+static const char* h2_reply_refusal(const grdma_h2_reply* r, const void* d_slices_out, uint64_t slices_cap, const void* d_hdr_arena,
+                                    uint64_t hdr_cap) {
+  if (!r) return "no reply";
+  if (const char* why = h2_bad_target(d_slices_out, slices_cap, d_hdr_arena, hdr_cap)) return why;
+  if (r->seq) return "the reply is bound to a reply pipe";
+  if (r->d_wr) return "the reply frames under send windows (grdma_h2_reply_frame_windowed)";  // (one message could go out twice)
+  if (r->src->attached) return "the source assembler is attached to a pipe or group pipe";
+  return nullptr;
+}
+// a call's result words res and what its stage took, to the caller -> the slice count, -GRDMA_ERR_CAPACITY after an overflow
+static int64_t h2_reply_ran(const uint64_t res[8], float ms, uint64_t out[8]) {
+  for (int i = 0; i < 7; i++) out[i] = res[i];
+  out[7] = (uint64_t)(ms * 1e3f);
+  return res[H2R_OVERFLOW] ? -(int64_t)GRDMA_ERR_CAPACITY : (int64_t)res[H2R_SLICES];
+}
+
 int64_t grdma_h2_reply_frame(grdma_h2_reply* r, grdma_slice* d_slices_out, uint64_t slices_cap, void* d_hdr_arena,
                              uint64_t hdr_cap, uint64_t out[8]) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!r || !d_slices_out || !slices_cap || !d_hdr_arena || !hdr_cap || !out || ((uintptr_t)d_slices_out & 15) ||
-      ((uintptr_t)d_hdr_arena & 15) || r->seq || r->src->attached)
-    return -GRDMA_ERR_INVALID;
-  if (r->d_wr)  // (one message could go out twice)
-    return grdma_fail_msg(GRDMA_ERR_INVALID, "grdma_h2_reply_frame: the reply frames under send windows (grdma_h2_reply_frame_windowed)");
+  if (!out) return h2_invalid("grdma_h2_reply_frame", "no result array");
+  if (const char* why = h2_reply_refusal(r, d_slices_out, slices_cap, d_hdr_arena, hdr_cap)) return h2_invalid("grdma_h2_reply_frame", why);
   h2_host_ctx* hc = h2_ctx();
   if (!hc) return -GRDMA_ERR_HIP;
   // the stream of grdma_h2_deframe_messages: the call is ordered behind the one it reads
-  hipStream_t st = hc->stream;
-  if (!h2_reply_set_target(r, reinterpret_cast<grdma_sge*>(d_slices_out), slices_cap, static_cast<uint8_t*>(d_hdr_arena),
-                           hdr_cap, 0, 0, 0, st))
-    return -GRDMA_ERR_HIP;
+  h2_reply_target(&r->h, reinterpret_cast<grdma_sge*>(d_slices_out), slices_cap, static_cast<uint8_t*>(d_hdr_arena), hdr_cap, 0, 0, 0);
   const h2_stage framing = h2_stage_reply(r->d);
   uint64_t res[8];
-  h2_call c{"grdma_h2_reply_frame: a launch was rejected", {}, {}, {h2_all(framing)},
-            {{res, reinterpret_cast<uint8_t*>(r->d) + offsetof(h2r_dev, res), sizeof(res)}}};
+  h2_call c{"grdma_h2_reply_frame: a launch was rejected", {h2_words(r->d, &r->h, offsetof(h2r_dev, out), offsetof(h2r_dev, res))}, {},
+            {h2_all(framing)}, {h2_result(res, r->d, offsetof(h2r_dev, res))}};
   if (int rc = h2_call_run(hc, &c)) return rc;
-  for (int i = 0; i < 7; i++) out[i] = res[i];
-  out[7] = (uint64_t)(c.ms[0] * 1e3f);
-  if (res[H2R_OVERFLOW]) return -GRDMA_ERR_CAPACITY;
-  return (int64_t)res[H2R_SLICES];
+  return h2_reply_ran(res, c.ms[0], out);
 }
 
 // ---- the replies of many transports in two launches (h2_stage_reply_links) ------------------------------------------
 // The batch block of the process holds the call: [table | one h2r_dev per item] goes up in one copy -- the item's
 // framer with the item's targets and a zeroed result block; scratch, routes and source stay the reply's own -- and the
 // h2r_dev blocks come down in one copy.  One call at a time, as the other batch calls.
-
 int grdma_h2_reply_frame_batch(grdma_h2_reply_item* items, uint32_t n_items) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!items || n_items == 0 || n_items > GRDMA_H2_BATCH_MAX)
-    return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: 1 .. GRDMA_H2_BATCH_MAX items");
+  h2_batch b{"h2 reply batch", "reply", "h2 reply batch: a launch was rejected"};
+  if (int rc = b.begin(items, n_items)) return rc;
   for (uint32_t i = 0; i < n_items; i++) {
     const grdma_h2_reply_item& it = items[i];
-    if (!it.reply) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: an item without reply");
-    if (!it.d_slices_out || !it.slices_cap || !it.d_hdr_arena || !it.hdr_cap || ((uintptr_t)it.d_slices_out & 15) ||
-        ((uintptr_t)it.d_hdr_arena & 15))
-      return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: a null, zero or misaligned slice table or header arena");
-    if (it.reply->seq) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: a reply bound to a reply pipe");
-    if (it.reply->d_wr) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: a reply that frames under send windows");
-    if (it.reply->src->attached)
-      return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: a source assembler attached to a pipe or group pipe");
-    for (uint32_t k = 0; k < i; k++) {
-      if (items[k].reply == it.reply) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: the same reply twice");
-      // (each reply has scratch of its own, so two of one source could run side by side; the rule is one item per
-      // transport, as in the other batch calls)
-      if (items[k].reply->src == it.reply->src)
-        return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 reply batch: two replies of one source assembler");
-    }
+    if (int rc = b.item(it.reply, h2_reply_refusal(it.reply, it.d_slices_out, it.slices_cap, it.d_hdr_arena, it.hdr_cap))) return rc;
+    // (each reply has scratch of its own, so two of one source could run side by side; the rule is one item per
+    // transport, as in the other batch calls)
+    for (uint32_t k = 0; k < i; k++)
+      if (items[k].reply->src == it.reply->src) return h2_invalid(b.who, "two replies of one source assembler");
   }
-  h2_host_ctx* hc = h2_ctx();
-  if (!hc) return -GRDMA_ERR_HIP;
   const h2_reply_block L = h2_reply_block_layout(sizeof(h2r_link), sizeof(h2r_dev), n_items);
-  if (!h2_batch_reserve(L.total, hc->stream)) return -GRDMA_ERR_HIP;
-  uint8_t* const d = g_batch.d;
-  std::vector<uint8_t> up(L.end, 0);
+  if (int rc = b.reserve(L.end, L.total)) return rc;
   std::vector<h2r_dev> down(n_items);
-  auto* tab = reinterpret_cast<h2r_link*>(up.data() + L.tab);
-  auto* devs = reinterpret_cast<h2r_dev*>(up.data() + L.devs);
+  auto* tab = reinterpret_cast<h2r_link*>(b.up.data());
+  auto* devs = reinterpret_cast<h2r_dev*>(b.up.data() + L.devs);
   for (uint32_t i = 0; i < n_items; i++) {
     const grdma_h2_reply_item& it = items[i];
-    h2r_dev h = it.reply->h;
-    h.out = reinterpret_cast<grdma_sge*>(it.d_slices_out);
-    h.cap = it.slices_cap;
-    h.hdr = static_cast<uint8_t*>(it.d_hdr_arena);
-    h.hdr_cap = it.hdr_cap;
-    h.check_shape = h.want_slices = h.want_wire = 0;
-    memset(h.res, 0, sizeof(h.res));
-    devs[i] = h;
-    tab[i].R = reinterpret_cast<h2r_dev*>(d + L.devs) + i;
+    devs[i] = it.reply->h;  // (a copy: the reply's own keeps the targets of its single calls)
+    h2_reply_target(&devs[i], reinterpret_cast<grdma_sge*>(it.d_slices_out), it.slices_cap, static_cast<uint8_t*>(it.d_hdr_arena), it.hdr_cap, 0, 0, 0);
+    memset(devs[i].res, 0, sizeof(devs[i].res));
+    tab[i].R = reinterpret_cast<h2r_dev*>(b.d + L.devs) + i;
+    // behind each source parser's last deframing (a pipe step on another stream; the standalone calls share this stream)
+    b.behind.push_back(it.reply->src->parser);
   }
-  // behind each source parser's last deframing (a pipe step on another stream; the standalone calls share this stream)
-  for (uint32_t i = 0; i < n_items; i++)
-    if (!h2_wait_parser(hc->stream, items[i].reply->src->parser)) return -GRDMA_ERR_HIP;
-  const h2_stage framing = h2_stage_reply_links(reinterpret_cast<const h2r_link*>(d + L.tab), n_items);
-  h2_call c{"h2 reply batch: a launch was rejected",
-            {{d, up.data(), up.size()}}, {}, {h2_all(framing)},
-            {{down.data(), d + L.devs, sizeof(h2r_dev) * n_items}}};
-  if (int rc = h2_call_run(hc, &c)) return rc;
-  const uint64_t us = (uint64_t)(c.ms[0] * 1e3f);
-  g_h2_last_kernel_us = 1e3 * c.ms[0];
-  for (uint32_t i = 0; i < n_items; i++) {
-    grdma_h2_reply_item& it = items[i];
-    const uint64_t* res = down[i].res;
-    for (int k = 0; k < 7; k++) it.out[k] = res[k];
-    it.out[7] = us;  // (the batch's, repeated)
-    it.n_slices = res[H2R_OVERFLOW] ? -(int64_t)GRDMA_ERR_CAPACITY : (int64_t)res[H2R_SLICES];
-  }
+  b.c.down.push_back({down.data(), b.d + L.devs, sizeof(h2r_dev) * n_items});
+  const h2_stage framing = h2_stage_reply_links(reinterpret_cast<const h2r_link*>(b.d), n_items);
+  if (int rc = b.run({h2_all(framing)})) return rc;
+  g_h2_last_kernel_us = 1e3 * b.c.ms[0];
+  for (uint32_t i = 0; i < n_items; i++) items[i].n_slices = h2_reply_ran(down[i].res, b.c.ms[0], items[i].out);  // (the time: the batch's, repeated)
   return 0;
 }
 
 // ---- receive flow control: the window ledger (csrc/grdma_h2_fc.h) -------------------------------------------------
-struct grdma_h2_fc {
-  grdma_h2_parser* parser = nullptr;
+struct grdma_h2_fc : h2_follow {     // (taken: the last call accounted)
   h2fc_dev* d = nullptr;
   h2fc_dev h;                      // host copy of the configuration words
   h2fc_call* d_call = nullptr;     // standalone calls
   h2_step_seq* seq = nullptr;      // the steps of the pipe, single or group, that account through it
-  uint64_t accounted = 0;          // parser->standalone_calls of the last call accounted
-  float last_ms = 0;
 };
-
-// The parser of f is being destroyed: standalone calls on f's stream have ended, and from now on f refuses every call
-// but destroy (its device block points into the parser's).  A ledger attached to a pipe stays with the pipe, whose
-// parser must outlive it as it must without a ledger.
-static void h2_fc_parser_gone(grdma_h2_fc* f) {
-  h2_host_ctx* hc = h2_ctx();
-  if (hc) hipStreamSynchronize(hc->stream);
-  f->parser = nullptr;
-}
 
 // the bit words of calls of up to ev_cap events (a resize drains the device: setup, not a hot path)
 static bool h2_fc_prepare(grdma_h2_fc* f, uint64_t ev_cap) {
@@ -774,30 +868,30 @@ static bool h2_fc_prepare(grdma_h2_fc* f, uint64_t ev_cap) {
   return h2_push_words(f->d, &h, offsetof(h2fc_dev, scratch_ev), offsetof(h2fc_dev, out), nullptr) && ok;
 }
 
-// where the calls write: the words of h2fc_dev from `out` to the state
-static bool h2_fc_set_target(grdma_h2_fc* f, grdma_sge* out, uint64_t cap, uint8_t* hdr, uint64_t hdr_cap, hipStream_t st) {
+// where the calls write: the words of h2fc_dev from `out` to the state, in the host copy -> their upload
+static h2_xfer h2_fc_target(grdma_h2_fc* f, grdma_sge* out, uint64_t cap, uint8_t* hdr, uint64_t hdr_cap) {
   h2fc_dev& h = f->h;
   h.out = out;
   h.cap = cap;
   h.hdr = hdr;
   h.hdr_cap = hdr_cap;
-  return h2_push_words(f->d, &h, offsetof(h2fc_dev, out), offsetof(h2fc_dev, announced), st);
+  return h2_words(f->d, &h, offsetof(h2fc_dev, out), offsetof(h2fc_dev, announced));
 }
-
-static grdma_h2_fc* h2_fc_refuse(const char* why) {
-  grdma_fail_msg(GRDMA_ERR_INVALID, why);
-  return nullptr;
+// ... uploaded at once (a pipe's)
+static bool h2_fc_set_target(grdma_h2_fc* f, grdma_sge* out, uint64_t cap, uint8_t* hdr, uint64_t hdr_cap, hipStream_t st) {
+  h2_fc_target(f, out, cap, hdr, hdr_cap);
+  return h2_push_words(f->d, &f->h, offsetof(h2fc_dev, out), offsetof(h2fc_dev, announced), st);
 }
 
 grdma_h2_fc* grdma_h2_fc_create(grdma_h2_parser* parser, uint32_t stream_window, uint32_t conn_window, uint32_t conn_threshold,
                                 uint32_t max_updates) {
   if (grdma_device_count() <= 0) return nullptr;
-  if (!parser) return h2_fc_refuse("h2 flow control: no parser");
-  if (parser->fc) return h2_fc_refuse("h2 flow control: the parser has a ledger already");
-  if (stream_window == 0 || stream_window > 0x7fffffffu) return h2_fc_refuse("h2 flow control: stream_window outside 1 .. 2^31 - 1");
-  if (conn_window < 65535 || conn_window > 0x7fffffffu) return h2_fc_refuse("h2 flow control: conn_window outside 65535 .. 2^31 - 1");
-  if (conn_threshold > conn_window) return h2_fc_refuse("h2 flow control: conn_threshold above conn_window");
-  if (max_updates == 0 || max_updates > (1u << 24)) return h2_fc_refuse("h2 flow control: max_updates outside 1 .. 2^24");
+  if (!parser) return h2_no("h2 flow control: no parser");
+  if (parser->fc) return h2_no("h2 flow control: the parser has a ledger already");
+  if (stream_window == 0 || stream_window > 0x7fffffffu) return h2_no("h2 flow control: stream_window outside 1 .. 2^31 - 1");
+  if (conn_window < 65535 || conn_window > 0x7fffffffu) return h2_no("h2 flow control: conn_window outside 65535 .. 2^31 - 1");
+  if (conn_threshold > conn_window) return h2_no("h2 flow control: conn_threshold above conn_window");
+  if (max_updates == 0 || max_updates > (1u << 24)) return h2_no("h2 flow control: max_updates outside 1 .. 2^24");
   grdma_h2_fc* f = new grdma_h2_fc();
   f->parser = parser;
   memset(&f->h, 0, sizeof(f->h));
@@ -838,40 +932,37 @@ void grdma_h2_fc_destroy(grdma_h2_fc* f) {
   delete f;
 }
 
+// what a call on f into these targets is refused for
+static const char* h2_fc_refusal(const grdma_h2_fc* f, const void* d_slices_out, uint64_t slices_cap, const void* d_hdr_arena, uint64_t hdr_cap) {
+  if (!f) return "a call without ledger";
+  if (f->seq) return "the ledger is attached to a pipe (its steps account)";
+  if (const char* why = h2_follow_refusal(*f, "this call is accounted already", false)) return why;
+  return h2_bad_target(d_slices_out, slices_cap, d_hdr_arena, hdr_cap);
+}
+
 int64_t grdma_h2_fc_account(grdma_h2_fc* f, grdma_slice* d_slices_out, uint64_t slices_cap, void* d_hdr_arena, uint64_t hdr_cap,
                             uint64_t out[8]) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!f || !out) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control: no ledger or no result array");
-  if (!d_slices_out || !slices_cap || !d_hdr_arena || !hdr_cap || ((uintptr_t)d_slices_out & 15) || ((uintptr_t)d_hdr_arena & 15))
-    return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control: a null, zero or misaligned slice table or header arena");
-  if (f->seq) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control: the ledger is attached to a pipe (its steps account)");
-  grdma_h2_parser* p = f->parser;
-  if (!p) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control: the ledger's parser is gone");
-  if (p->standalone_calls == 0) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control: the parser has deframed nothing yet");
-  if (f->accounted == p->standalone_calls) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control: this call is accounted already");
+  if (!out) return h2_invalid("h2 flow control", "no result array");
+  if (const char* why = h2_fc_refusal(f, d_slices_out, slices_cap, d_hdr_arena, hdr_cap)) return h2_invalid("h2 flow control", why);
   h2_host_ctx* hc = h2_ctx();
   if (!hc) return -GRDMA_ERR_HIP;
-  if (!h2_fc_prepare(f, p->standalone_ev_cap)) return -GRDMA_ERR_HIP;
+  if (!h2_fc_prepare(f, f->parser->standalone_ev_cap)) return -GRDMA_ERR_HIP;
   // the stream of the standalone deframings: the call is ordered behind the one it reads
   // ... and behind the parser's last deframing by a pipe: k_h2_fc_finish reads the stream map that step may change
-  hipStream_t st = hc->stream;
-  if (!h2_wait_parser(st, p)) return -GRDMA_ERR_HIP;
-  const h2fc_call call{p->d_ev, p->d_res, p->standalone_ev_cap};
-  if (!h2_fc_set_target(f, reinterpret_cast<grdma_sge*>(d_slices_out), slices_cap, static_cast<uint8_t*>(d_hdr_arena), hdr_cap, st))
-    return -GRDMA_ERR_HIP;
+  if (!h2_wait_parser(hc->stream, f->parser)) return -GRDMA_ERR_HIP;
+  const h2fc_call call = h2_follow_deframed(*f);
   const h2_stage ledger = h2_stage_fc(f->d, f->d_call);
-  uint64_t res[8];
   h2_call c{"grdma_h2_fc_account: a launch was rejected",
-            {{f->d_call, &call, sizeof(call)}}, {}, {h2_all(ledger)},
-            {{res, reinterpret_cast<uint8_t*>(f->d) + offsetof(h2fc_dev, res), sizeof(res)}}};
+            {h2_fc_target(f, reinterpret_cast<grdma_sge*>(d_slices_out), slices_cap, static_cast<uint8_t*>(d_hdr_arena), hdr_cap),
+             {f->d_call, &call, sizeof(call)}},
+            {}, {h2_all(ledger)}, {h2_result(out, f->d, offsetof(h2fc_dev, res))}};
   if (int rc = h2_call_run(hc, &c)) return rc;
-  f->last_ms = c.ms[0];
-  f->accounted = p->standalone_calls;
-  for (int i = 0; i < 8; i++) out[i] = res[i];
-  if (res[H2FC_OVERFLOW] == 2)
+  h2_follow_ran(f, c.ms[0]);
+  if (out[H2FC_OVERFLOW] == 2)
     return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 flow control: the call's event list overflowed, its bytes cannot be accounted");
-  if (res[H2FC_OVERFLOW]) return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 flow control: more frames than max_updates, or a slice or header cap too small");
-  return (int64_t)res[H2FC_SLICES];
+  if (out[H2FC_OVERFLOW]) return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 flow control: more frames than max_updates, or a slice or header cap too small");
+  return (int64_t)out[H2FC_SLICES];
 }
 
 // ---- the ledgers of many transports in five launches (h2_stage_fc_links) ---------------------------------------------
@@ -880,62 +971,31 @@ int64_t grdma_h2_fc_account(grdma_h2_fc* f, grdma_slice* d_slices_out, uint64_t 
 // bytes down per item behind the stage).  One call at a time, as the other batch calls.
 int grdma_h2_fc_account_batch(const grdma_h2_fc_item* items, uint32_t n_items, uint64_t* out) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!items || !out || n_items == 0 || n_items > GRDMA_H2_BATCH_MAX)
-    return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control batch: 1 .. GRDMA_H2_BATCH_MAX items and a result array");
+  h2_batch b{"h2 flow control batch", "ledger", "h2 flow control batch: a launch was rejected"};
+  if (int rc = b.begin(items && out, n_items)) return rc;
   for (uint32_t i = 0; i < n_items; i++) {
     const grdma_h2_fc_item& it = items[i];
-    const grdma_h2_fc* f = it.fc;
-    if (!f) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control batch: an item without ledger");
-    for (uint32_t k = 0; k < i; k++)
-      if (items[k].fc == f) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control batch: the same ledger twice");
-    if (f->seq) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control batch: a ledger attached to a pipe (its steps account)");
-    const grdma_h2_parser* p = f->parser;
-    if (!p) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control batch: a ledger's parser is gone");
-    if (p->standalone_calls == 0) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control batch: a parser has deframed nothing yet");
-    if (f->accounted == p->standalone_calls) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control batch: a call is accounted already");
-    if (!it.d_slices_out || !it.slices_cap || !it.d_hdr_arena || !it.hdr_cap || ((uintptr_t)it.d_slices_out & 15) ||
-        ((uintptr_t)it.d_hdr_arena & 15))
-      return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 flow control batch: a null, zero or misaligned slice table or header arena");
+    if (int rc = b.item(it.fc, h2_fc_refusal(it.fc, it.d_slices_out, it.slices_cap, it.d_hdr_arena, it.hdr_cap))) return rc;
   }
-  h2_host_ctx* hc = h2_ctx();
-  if (!hc) return -GRDMA_ERR_HIP;
-  hipStream_t st = hc->stream;
   for (uint32_t i = 0; i < n_items; i++)
     if (!h2_fc_prepare(items[i].fc, items[i].fc->parser->standalone_ev_cap)) return -GRDMA_ERR_HIP;
-  const h2_fc_block L = h2_fc_block_layout(sizeof(h2fc_link), sizeof(h2fc_call), n_items);
-  if (!h2_batch_reserve(L.total, st)) return -GRDMA_ERR_HIP;
-  uint8_t* const d = g_batch.d;
-  std::vector<uint8_t> up(L.end, 0);
-  auto* tab = reinterpret_cast<h2fc_link*>(up.data() + L.tab);
-  auto* calls = reinterpret_cast<h2fc_call*>(up.data() + L.calls);
-  const h2_stage ledgers = h2_stage_fc_links(reinterpret_cast<const h2fc_link*>(d + L.tab), n_items);
-  h2_call c{"h2 flow control batch: a launch was rejected", {{d, up.data(), up.size()}}, {}, {h2_all(ledgers)}, {}};
+  if (int rc = b.open(sizeof(h2fc_link), sizeof(h2fc_call), n_items)) return rc;
+  auto* tab = reinterpret_cast<h2fc_link*>(b.up.data());
+  auto* calls = reinterpret_cast<h2fc_call*>(b.up.data() + b.blocks);
   for (uint32_t i = 0; i < n_items; i++) {
     const grdma_h2_fc_item& it = items[i];
     grdma_h2_fc* f = it.fc;
-    const grdma_h2_parser* p = f->parser;
-    calls[i] = h2fc_call{p->d_ev, p->d_res, p->standalone_ev_cap};
-    tab[i].F = f->d;
-    tab[i].call = reinterpret_cast<const h2fc_call*>(d + L.calls) + i;
-    // where the item's call writes: the words of h2fc_dev from `out` to the state, from the host mirror
-    f->h.out = reinterpret_cast<grdma_sge*>(it.d_slices_out);
-    f->h.cap = it.slices_cap;
-    f->h.hdr = static_cast<uint8_t*>(it.d_hdr_arena);
-    f->h.hdr_cap = it.hdr_cap;
-    c.up.push_back({reinterpret_cast<uint8_t*>(f->d) + offsetof(h2fc_dev, out), reinterpret_cast<const uint8_t*>(&f->h) + offsetof(h2fc_dev, out),
-                    offsetof(h2fc_dev, announced) - offsetof(h2fc_dev, out)});
-    c.down.push_back({out + 8 * (size_t)i, reinterpret_cast<const uint8_t*>(f->d) + offsetof(h2fc_dev, res), 8 * sizeof(uint64_t)});
+    calls[i] = h2_follow_deframed(*f);
+    tab[i] = {f->d, reinterpret_cast<const h2fc_call*>(b.d + b.blocks) + i};
+    b.c.up.push_back(h2_fc_target(f, reinterpret_cast<grdma_sge*>(it.d_slices_out), it.slices_cap, static_cast<uint8_t*>(it.d_hdr_arena), it.hdr_cap));
+    b.c.down.push_back(h2_result(out + 8 * (size_t)i, f->d, offsetof(h2fc_dev, res)));
+    b.behind.push_back(f->parser);  // (the finish reads the stream map a pipe's deframing may change)
   }
-  // behind the standalone deframings (same stream) and each parser's last deframing by a pipe: the finish reads the
-  // stream map that step may change
-  for (uint32_t i = 0; i < n_items; i++)
-    if (!h2_wait_parser(st, items[i].fc->parser)) return -GRDMA_ERR_HIP;
-  if (int rc = h2_call_run(hc, &c)) return rc;
+  const h2_stage ledgers = h2_stage_fc_links(reinterpret_cast<const h2fc_link*>(b.d), n_items);
+  if (int rc = b.run({h2_all(ledgers)})) return rc;
   int ok = 0;
   for (uint32_t i = 0; i < n_items; i++) {
-    grdma_h2_fc* f = items[i].fc;
-    f->last_ms = c.ms[0];  // (the batch's, repeated)
-    f->accounted = f->parser->standalone_calls;
+    h2_follow_ran(items[i].fc, b.c.ms[0]);  // (the time: the batch's, repeated)
     ok += out[8 * (size_t)i + H2FC_OVERFLOW] == 0;
   }
   return ok;
@@ -960,38 +1020,22 @@ int grdma_h2_fc_stats(grdma_h2_fc* f, uint64_t out[8]) {
 }
 
 // ---- send flow control: the peer's windows and the framer under them (csrc/grdma_h2_sw.h) -------------------------------
-struct grdma_h2_sw {
-  grdma_h2_parser* parser = nullptr;
+struct grdma_h2_sw : h2_follow {        // (taken: the last call taken in; at creation: the calls before it)
   h2sw_dev* d = nullptr;
   h2sw_dev h;                         // host copy of the configuration words
   h2sw_call* d_call = nullptr;
   grdma_h2_msg_dev* d_msgs = nullptr; // H2_FRAME_ONE_MAX
   uint64_t* d_prog = nullptr;         // progress in [0, MAX), out [MAX, 2 MAX)
-  uint64_t taken = 0;                 // parser->standalone_calls of the last call taken in (at creation: of the calls before it)
-  float last_ms = 0;
   struct grdma_h2_reply* reply = nullptr;  // the reply framer whose queue waits under these windows (csrc/grdma_h2_wr.h)
   bool reply_gone = false;                 // ... has been destroyed: every call but destroy is refused
 };
 
-// The parser of s is being destroyed: standalone calls on the stream of the calls have ended, and from now on s refuses
-// every call but destroy (its device block points into the parser's).
-static void h2_sw_parser_gone(grdma_h2_sw* s) {
-  h2_host_ctx* hc = h2_ctx();
-  if (hc) hipStreamSynchronize(hc->stream);
-  s->parser = nullptr;
-}
-
-static grdma_h2_sw* h2_sw_refuse(const char* why) {
-  grdma_fail_msg(GRDMA_ERR_INVALID, why);
-  return nullptr;
-}
-
 grdma_h2_sw* grdma_h2_sw_create(grdma_h2_parser* parser, uint32_t initial_window, uint32_t conn_window, uint32_t peer_max_frame) {
   if (grdma_device_count() <= 0) return nullptr;
-  if (!parser) return h2_sw_refuse("h2 send windows: no parser");
-  if (parser->sw) return h2_sw_refuse("h2 send windows: the parser has send windows already");
-  if (initial_window > 0x7fffffffu || conn_window > 0x7fffffffu) return h2_sw_refuse("h2 send windows: a window above 2^31 - 1");
-  if (peer_max_frame < 16384 || peer_max_frame > 16777215) return h2_sw_refuse("h2 send windows: peer_max_frame outside 16384 .. 2^24 - 1");
+  if (!parser) return h2_no("h2 send windows: no parser");
+  if (parser->sw) return h2_no("h2 send windows: the parser has send windows already");
+  if (initial_window > 0x7fffffffu || conn_window > 0x7fffffffu) return h2_no("h2 send windows: a window above 2^31 - 1");
+  if (peer_max_frame < 16384 || peer_max_frame > 16777215) return h2_no("h2 send windows: peer_max_frame outside 16384 .. 2^24 - 1");
   grdma_h2_sw* s = new grdma_h2_sw();
   s->parser = parser;
   s->taken = parser->standalone_calls;
@@ -1043,79 +1087,93 @@ void grdma_h2_sw_destroy(grdma_h2_sw* s) {
   delete s;
 }
 
+// what every call on s but destroy is refused for
+static const char* h2_sw_gone(const grdma_h2_sw* s) {
+  if (!s) return "a call without send windows";
+  if (!s->parser) return "the parser is gone";
+  if (s->reply_gone) return "the reply framer whose queue waited under them is gone";
+  return nullptr;
+}
+static const char* h2_sw_intake_refusal(const grdma_h2_sw* s) {
+  if (const char* why = h2_sw_gone(s)) return why;
+  return h2_follow_refusal(*s, "this call is taken in already", true);
+}
+// (the single call's arguments are an item of the batch)
+static const char* h2_sw_frame_refusal(const grdma_h2_sw_frame_item& it) {
+  if (const char* why = h2_sw_gone(it.sw)) return why;
+  if (!it.msgs || !it.progress) return "no message table or progress";
+  if (it.nmsgs == 0 || it.nmsgs > H2_FRAME_ONE_MAX) return "1 .. 4096 messages a call";
+  if (it.max_frame == 0 || it.max_frame >= (1u << 24)) return "max_frame outside 1 .. 2^24 - 1";
+  if (const char* why = h2_bad_target(it.d_slices_out, it.slices_cap, it.d_hdr_arena, it.hdr_cap)) return why;
+  for (uint64_t m = 0; m < it.nmsgs; m++) {
+    if (it.msgs[m].len >= (1ull << 32)) return "a message of 2^32 bytes or more";
+    if (it.progress[m] >= 5 + it.msgs[m].len) return "a message with nothing left to send";
+  }
+  return nullptr;
+}
+// The framing call of an item: the words of h2sw_dev from `msgs` to the state in the host copy, and its transfers added
+// to c -- the table (tab: it.msgs in the device's form), the progress and the words up into the send windows' own device
+// memory, the result words (to res) and the progress behind the call (to after) down from there.
+static void h2_sw_frame_transfers(h2_call* c, const grdma_h2_sw_frame_item& it, const grdma_h2_msg_dev* tab, uint64_t* res, uint64_t* after) {
+  grdma_h2_sw* s = it.sw;
+  h2sw_dev& h = s->h;
+  h.nmsgs = it.nmsgs;
+  h.max_frame = it.max_frame;
+  h.out = reinterpret_cast<grdma_sge*>(it.d_slices_out);
+  h.cap = it.slices_cap;
+  h.hdr = static_cast<uint8_t*>(it.d_hdr_arena);
+  h.hdr_cap = it.hdr_cap;
+  c->up.push_back({s->d_msgs, tab, sizeof(grdma_h2_msg_dev) * it.nmsgs});
+  c->up.push_back({s->d_prog, it.progress, sizeof(uint64_t) * it.nmsgs});
+  c->up.push_back(h2_words(s->d, &h, offsetof(h2sw_dev, msgs), offsetof(h2sw_dev, conn)));
+  c->down.push_back(h2_result(res, s->d, offsetof(h2sw_dev, fres)));
+  c->down.push_back({after, s->d_prog + H2_FRAME_ONE_MAX, sizeof(uint64_t) * it.nmsgs});
+}
+// behind a framing call that ran -> whether the item's frames stand
+static bool h2_sw_frame_ran(const grdma_h2_sw_frame_item& it, float ms, const uint64_t* res, const uint64_t* after) {
+  it.sw->last_ms = ms;
+  if (res[H2SW_F_OVERFLOW]) return false;  // (nothing was written, no window moved: progress stays as it is)
+  for (uint64_t m = 0; m < it.nmsgs; m++) it.progress[m] = after[m];
+  return true;
+}
+
 int64_t grdma_h2_sw_intake(grdma_h2_sw* s, uint64_t out[8]) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!s || !out) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: no send windows or no result array");
-  grdma_h2_parser* p = s->parser;
-  if (!p) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: the parser is gone");
-  if (s->reply_gone) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: the reply framer whose queue waited under them is gone");
-  if (p->standalone_calls == 0) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: the parser has deframed nothing yet");
-  if (s->taken == p->standalone_calls) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: this call is taken in already");
-  if (p->standalone_ev_cap >= 0xfffffff0ull) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: event positions are 32 bits");
+  if (!out) return h2_invalid("h2 send windows", "no result array");
+  if (const char* why = h2_sw_intake_refusal(s)) return h2_invalid("h2 send windows", why);
   h2_host_ctx* hc = h2_ctx();
   if (!hc) return -GRDMA_ERR_HIP;
   // the stream of the standalone deframings: the call is ordered behind the one it reads, and behind the parser's last
   // deframing by a pipe (the intake reads the stream map that step may change)
-  hipStream_t st = hc->stream;
-  if (!h2_wait_parser(st, p)) return -GRDMA_ERR_HIP;
-  const h2sw_call call{p->d_ev, p->d_res, p->d_sl, p->standalone_arena, p->standalone_ev_cap, p->standalone_nsl,
-                       p->standalone_calls > s->taken + 1 ? 1ull : 0ull};
+  if (!h2_wait_parser(hc->stream, s->parser)) return -GRDMA_ERR_HIP;
+  const h2sw_call call = h2_follow_deframed(*s);
   const h2_stage intake = h2_stage_sw_intake(s->d, s->d_call);
-  uint64_t res[8];
   h2_call c{"grdma_h2_sw_intake: a launch was rejected",
-            {{s->d_call, &call, sizeof(call)}}, {}, {h2_all(intake)},
-            {{res, reinterpret_cast<uint8_t*>(s->d) + offsetof(h2sw_dev, res), sizeof(res)}}};
+            {{s->d_call, &call, sizeof(call)}}, {}, {h2_all(intake)}, {h2_result(out, s->d, offsetof(h2sw_dev, res))}};
   if (int rc = h2_call_run(hc, &c)) return rc;
-  s->last_ms = c.ms[0];
-  s->taken = p->standalone_calls;
-  for (int i = 0; i < 8; i++) out[i] = res[i];
-  if (res[H2SW_I_OVERFLOW])
+  h2_follow_ran(s, c.ms[0]);
+  if (out[H2SW_I_OVERFLOW])
     return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 send windows: the call's event list overflowed, its frames cannot be taken in");
-  return (int64_t)res[H2SW_I_UPDATES];
+  return (int64_t)out[H2SW_I_UPDATES];
 }
 
 int64_t grdma_h2_sw_frame(grdma_h2_sw* s, const grdma_h2_msg* msgs, uint64_t* progress, uint64_t n, uint32_t max_frame,
                           grdma_slice* d_slices_out, uint64_t slices_cap, void* d_hdr_arena, uint64_t hdr_cap, uint64_t out[8]) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!s || !out || !msgs || !progress) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: no send windows, message table, progress or result array");
-  if (n == 0 || n > H2_FRAME_ONE_MAX) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: 1 .. 4096 messages a call");
-  if (max_frame == 0 || max_frame >= (1u << 24)) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: max_frame outside 1 .. 2^24 - 1");
-  if (!d_slices_out || !slices_cap || !d_hdr_arena || !hdr_cap || ((uintptr_t)d_slices_out & 15) || ((uintptr_t)d_hdr_arena & 15))
-    return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: a null, zero or misaligned slice table or header arena");
-  grdma_h2_parser* p = s->parser;
-  if (!p) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: the parser is gone");
-  if (s->reply_gone) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: the reply framer whose queue waited under them is gone");
-  for (uint64_t i = 0; i < n; i++) {
-    if (msgs[i].len >= (1ull << 32)) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: a message of 2^32 bytes or more");
-    if (progress[i] >= 5 + msgs[i].len) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows: a message with nothing left to send");
-  }
+  if (!out) return h2_invalid("h2 send windows", "no result array");
+  const grdma_h2_sw_frame_item it{s, msgs, progress, n, max_frame, 0, d_slices_out, slices_cap, d_hdr_arena, hdr_cap};
+  if (const char* why = h2_sw_frame_refusal(it)) return h2_invalid("h2 send windows", why);
   h2_host_ctx* hc = h2_ctx();
   if (!hc) return -GRDMA_ERR_HIP;
-  hipStream_t st = hc->stream;
-  if (!h2_wait_parser(st, p)) return -GRDMA_ERR_HIP;  // (the plan looks streams up in the map)
-  const std::vector<grdma_h2_msg_dev> tmp = h2_msg_table(msgs, n);
-  h2sw_dev& h = s->h;
-  h.nmsgs = n;
-  h.max_frame = max_frame;
-  h.out = reinterpret_cast<grdma_sge*>(d_slices_out);
-  h.cap = slices_cap;
-  h.hdr = static_cast<uint8_t*>(d_hdr_arena);
-  h.hdr_cap = hdr_cap;
-  if (!h2_push_words(s->d, &h, offsetof(h2sw_dev, msgs), offsetof(h2sw_dev, conn), st)) return -GRDMA_ERR_HIP;
+  if (!h2_wait_parser(hc->stream, s->parser)) return -GRDMA_ERR_HIP;  // (the plan looks streams up in the map)
+  const std::vector<grdma_h2_msg_dev> tab = h2_msg_table(msgs, n);
   const h2_stage framing = h2_stage_sw_frame(s->d);
-  uint64_t res[8];
   std::vector<uint64_t> after(n);
-  h2_call c{"grdma_h2_sw_frame: a launch was rejected",
-            {{s->d_msgs, tmp.data(), sizeof(grdma_h2_msg_dev) * n}, {s->d_prog, progress, sizeof(uint64_t) * n}}, {}, {h2_all(framing)},
-            {{res, reinterpret_cast<uint8_t*>(s->d) + offsetof(h2sw_dev, fres), sizeof(res)},
-             {after.data(), s->d_prog + H2_FRAME_ONE_MAX, sizeof(uint64_t) * n}}};
+  h2_call c{"grdma_h2_sw_frame: a launch was rejected", {}, {}, {h2_all(framing)}, {}};
+  h2_sw_frame_transfers(&c, it, tab.data(), out, after.data());
   if (int rc = h2_call_run(hc, &c)) return rc;
-  s->last_ms = c.ms[0];
-  for (int i = 0; i < 8; i++) out[i] = res[i];
-  if (res[H2SW_F_OVERFLOW])  // (nothing was written, no window moved: progress stays as it is)
-    return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 send windows: a slice or header cap too small");
-  for (uint64_t i = 0; i < n; i++) progress[i] = after[i];
-  return (int64_t)res[H2SW_F_SLICES];
+  if (!h2_sw_frame_ran(it, c.ms[0], out, after.data())) return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 send windows: a slice or header cap too small");
+  return (int64_t)out[H2SW_F_SLICES];
 }
 
 int grdma_h2_sw_windows(grdma_h2_sw* s, const uint32_t* ids, uint32_t n, int64_t* out) {
@@ -1167,50 +1225,25 @@ int grdma_h2_sw_stats(grdma_h2_sw* s, uint64_t out[8]) {
 // batch calls.
 int grdma_h2_sw_intake_batch(grdma_h2_sw* const* sws, uint32_t n_items, uint64_t* out) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!sws || !out || n_items == 0 || n_items > GRDMA_H2_BATCH_MAX)
-    return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: 1 .. GRDMA_H2_BATCH_MAX items and a result array");
-  for (uint32_t i = 0; i < n_items; i++) {
-    const grdma_h2_sw* s = sws[i];
-    if (!s) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: an item without send windows");
-    for (uint32_t k = 0; k < i; k++)
-      if (sws[k] == s) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: the same send windows twice");
-    const grdma_h2_parser* p = s->parser;
-    if (!p) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a parser is gone");
-    if (s->reply_gone) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a reply framer whose queue waited under them is gone");
-    if (p->standalone_calls == 0) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a parser has deframed nothing yet");
-    if (s->taken == p->standalone_calls) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a call is taken in already");
-    if (p->standalone_ev_cap >= 0xfffffff0ull) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: event positions are 32 bits");
-  }
-  h2_host_ctx* hc = h2_ctx();
-  if (!hc) return -GRDMA_ERR_HIP;
-  hipStream_t st = hc->stream;
-  const h2_fc_block L = h2_fc_block_layout(sizeof(h2sw_link), sizeof(h2sw_call), n_items);
-  if (!h2_batch_reserve(L.total, st)) return -GRDMA_ERR_HIP;
-  uint8_t* const d = g_batch.d;
-  std::vector<uint8_t> up(L.end, 0);
-  auto* tab = reinterpret_cast<h2sw_link*>(up.data() + L.tab);
-  auto* calls = reinterpret_cast<h2sw_call*>(up.data() + L.calls);
-  const h2_stage intake = h2_stage_sw_intake_links(reinterpret_cast<const h2sw_link*>(d + L.tab), n_items);
-  h2_call c{"h2 send windows batch: a launch was rejected", {{d, up.data(), up.size()}}, {}, {h2_all(intake)}, {}};
-  for (uint32_t i = 0; i < n_items; i++) {
-    const grdma_h2_sw* s = sws[i];
-    const grdma_h2_parser* p = s->parser;
-    calls[i] = h2sw_call{p->d_ev, p->d_res, p->d_sl, p->standalone_arena, p->standalone_ev_cap, p->standalone_nsl,
-                         p->standalone_calls > s->taken + 1 ? 1ull : 0ull};
-    tab[i].F = s->d;
-    tab[i].call = reinterpret_cast<const h2sw_call*>(d + L.calls) + i;
-    c.down.push_back({out + 8 * (size_t)i, reinterpret_cast<const uint8_t*>(s->d) + offsetof(h2sw_dev, res), 8 * sizeof(uint64_t)});
-  }
-  // behind the standalone deframings (same stream) and each parser's last deframing by a pipe: the intake reads the
-  // stream map that step may change
+  h2_batch b{"h2 send windows batch", "send windows", "h2 send windows batch: a launch was rejected"};
+  if (int rc = b.begin(sws && out, n_items)) return rc;
   for (uint32_t i = 0; i < n_items; i++)
-    if (!h2_wait_parser(st, sws[i]->parser)) return -GRDMA_ERR_HIP;
-  if (int rc = h2_call_run(hc, &c)) return rc;
+    if (int rc = b.item(sws[i], h2_sw_intake_refusal(sws[i]))) return rc;
+  if (int rc = b.open(sizeof(h2sw_link), sizeof(h2sw_call), n_items)) return rc;
+  auto* tab = reinterpret_cast<h2sw_link*>(b.up.data());
+  auto* calls = reinterpret_cast<h2sw_call*>(b.up.data() + b.blocks);
+  for (uint32_t i = 0; i < n_items; i++) {
+    const grdma_h2_sw* s = sws[i];
+    calls[i] = h2_follow_deframed(*s);
+    tab[i] = {s->d, reinterpret_cast<const h2sw_call*>(b.d + b.blocks) + i};
+    b.c.down.push_back(h2_result(out + 8 * (size_t)i, s->d, offsetof(h2sw_dev, res)));
+    b.behind.push_back(s->parser);  // (the intake reads the stream map a pipe's deframing may change)
+  }
+  const h2_stage intake = h2_stage_sw_intake_links(reinterpret_cast<const h2sw_link*>(b.d), n_items);
+  if (int rc = b.run({h2_all(intake)})) return rc;
   int ok = 0;
   for (uint32_t i = 0; i < n_items; i++) {
-    grdma_h2_sw* s = sws[i];
-    s->last_ms = c.ms[0];  // (the batch's, repeated)
-    s->taken = s->parser->standalone_calls;
+    h2_follow_ran(sws[i], b.c.ms[0]);  // (the time: the batch's, repeated)
     ok += out[8 * (size_t)i + H2SW_I_OVERFLOW] == 0;
   }
   return ok;
@@ -1218,78 +1251,32 @@ int grdma_h2_sw_intake_batch(grdma_h2_sw* const* sws, uint32_t n_items, uint64_t
 
 int grdma_h2_sw_frame_batch(const grdma_h2_sw_frame_item* items, uint32_t n_items, uint64_t* out) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!items || !out || n_items == 0 || n_items > GRDMA_H2_BATCH_MAX)
-    return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: 1 .. GRDMA_H2_BATCH_MAX items and a result array");
+  h2_batch b{"h2 send windows batch", "send windows", "h2 send windows batch: a launch was rejected"};
+  if (int rc = b.begin(items && out, n_items)) return rc;
   uint64_t n_msgs = 0;
   for (uint32_t i = 0; i < n_items; i++) {
-    const grdma_h2_sw_frame_item& it = items[i];
-    if (!it.sw || !it.msgs || !it.progress)
-      return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: an item without send windows, message table or progress");
-    for (uint32_t k = 0; k < i; k++)
-      if (items[k].sw == it.sw) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: the same send windows twice");
-    if (!it.sw->parser) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a parser is gone");
-    if (it.sw->reply_gone) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a reply framer whose queue waited under them is gone");
-    if (it.nmsgs == 0 || it.nmsgs > H2_FRAME_ONE_MAX) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: 1 .. 4096 messages an item");
-    if (it.max_frame == 0 || it.max_frame >= (1u << 24)) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: max_frame outside 1 .. 2^24 - 1");
-    if (!it.d_slices_out || !it.slices_cap || !it.d_hdr_arena || !it.hdr_cap || ((uintptr_t)it.d_slices_out & 15) ||
-        ((uintptr_t)it.d_hdr_arena & 15))
-      return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a null, zero or misaligned slice table or header arena");
-    for (uint64_t m = 0; m < it.nmsgs; m++) {
-      if (it.msgs[m].len >= (1ull << 32)) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a message of 2^32 bytes or more");
-      if (it.progress[m] >= 5 + it.msgs[m].len) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 send windows batch: a message with nothing left to send");
-    }
-    n_msgs += it.nmsgs;
+    if (int rc = b.item(items[i].sw, h2_sw_frame_refusal(items[i]))) return rc;
+    n_msgs += items[i].nmsgs;
   }
-  h2_host_ctx* hc = h2_ctx();
-  if (!hc) return -GRDMA_ERR_HIP;
-  hipStream_t st = hc->stream;
-  const h2_fc_block L = h2_fc_block_layout(sizeof(h2sw_link), 0, n_items);  // (a framing has no call blocks)
-  if (!h2_batch_reserve(L.total, st)) return -GRDMA_ERR_HIP;
-  uint8_t* const d = g_batch.d;
-  std::vector<uint8_t> up(L.end, 0);
-  auto* tab = reinterpret_cast<h2sw_link*>(up.data() + L.tab);
-  // every item's message table in the device's form and its progress after the call: [at[i], at[i] + nmsgs)
-  std::vector<grdma_h2_msg_dev> tmp(n_msgs);
+  if (int rc = b.open(sizeof(h2sw_link), 0, n_items)) return rc;  // (a framing has no call blocks)
+  auto* tab = reinterpret_cast<h2sw_link*>(b.up.data());
+  // every item's message table in the device's form and its progress behind the call: [at[i], at[i] + nmsgs)
+  std::vector<grdma_h2_msg_dev> msgs(n_msgs);
   std::vector<uint64_t> after(n_msgs), at(n_items);
-  const h2_stage framing = h2_stage_sw_frame_links(reinterpret_cast<const h2sw_link*>(d + L.tab), n_items);
-  h2_call c{"h2 send windows batch: a launch was rejected", {{d, up.data(), up.size()}}, {}, {h2_all(framing)}, {}};
   uint64_t off = 0;
   for (uint32_t i = 0; i < n_items; i++) {
     const grdma_h2_sw_frame_item& it = items[i];
-    grdma_h2_sw* s = it.sw;
     at[i] = off;
-    for (uint64_t m = 0; m < it.nmsgs; m++)
-      tmp[off + m] = grdma_h2_msg_dev{static_cast<const uint8_t*>(it.msgs[m].payload), it.msgs[m].len, it.msgs[m].stream_id, it.msgs[m].flags};
-    tab[i].F = s->d;
-    tab[i].call = nullptr;
-    // the item's framing call: the words of h2sw_dev from `msgs` to the state, from the host mirror
-    h2sw_dev& h = s->h;
-    h.nmsgs = it.nmsgs;
-    h.max_frame = it.max_frame;
-    h.out = reinterpret_cast<grdma_sge*>(it.d_slices_out);
-    h.cap = it.slices_cap;
-    h.hdr = static_cast<uint8_t*>(it.d_hdr_arena);
-    h.hdr_cap = it.hdr_cap;
-    c.up.push_back({s->d_msgs, tmp.data() + off, sizeof(grdma_h2_msg_dev) * it.nmsgs});
-    c.up.push_back({s->d_prog, it.progress, sizeof(uint64_t) * it.nmsgs});
-    c.up.push_back({reinterpret_cast<uint8_t*>(s->d) + offsetof(h2sw_dev, msgs), reinterpret_cast<const uint8_t*>(&h) + offsetof(h2sw_dev, msgs),
-                    offsetof(h2sw_dev, conn) - offsetof(h2sw_dev, msgs)});
-    c.down.push_back({out + 8 * (size_t)i, reinterpret_cast<const uint8_t*>(s->d) + offsetof(h2sw_dev, fres), 8 * sizeof(uint64_t)});
-    c.down.push_back({after.data() + off, s->d_prog + H2_FRAME_ONE_MAX, sizeof(uint64_t) * it.nmsgs});
+    h2_msg_rows(it.msgs, it.nmsgs, msgs.data() + off);
+    tab[i] = {it.sw->d, nullptr};
+    h2_sw_frame_transfers(&b.c, it, msgs.data() + off, out + 8 * (size_t)i, after.data() + off);
+    b.behind.push_back(it.sw->parser);  // (the plan looks streams up in the map)
     off += it.nmsgs;
   }
-  // behind each parser's last deframing by a pipe: the plan looks streams up in the map
-  for (uint32_t i = 0; i < n_items; i++)
-    if (!h2_wait_parser(st, items[i].sw->parser)) return -GRDMA_ERR_HIP;
-  if (int rc = h2_call_run(hc, &c)) return rc;
+  const h2_stage framing = h2_stage_sw_frame_links(reinterpret_cast<const h2sw_link*>(b.d), n_items);
+  if (int rc = b.run({h2_all(framing)})) return rc;
   int ok = 0;
-  for (uint32_t i = 0; i < n_items; i++) {
-    const grdma_h2_sw_frame_item& it = items[i];
-    it.sw->last_ms = c.ms[0];  // (the batch's, repeated)
-    if (out[8 * (size_t)i + H2SW_F_OVERFLOW]) continue;  // (nothing was written, no window moved: progress stays as it is)
-    for (uint64_t m = 0; m < it.nmsgs; m++) it.progress[m] = after[at[i] + m];
-    ok++;
-  }
+  for (uint32_t i = 0; i < n_items; i++) ok += h2_sw_frame_ran(items[i], b.c.ms[0], out + 8 * (size_t)i, after.data() + at[i]);  // (the time: the batch's, repeated)
   return ok;
 }
 
@@ -1348,18 +1335,17 @@ int grdma_h2_reply_attach_windows(grdma_h2_reply* r, grdma_h2_sw* s, uint32_t ma
   return 0;
 }
 
-// what a call on r is refused for (NULL: nothing), the targets included
+// what a call on r is refused for, the targets included
 static const char* h2_wr_refusal(const grdma_h2_reply* r, uint32_t flags, const void* d_slices_out, uint64_t slices_cap,
                                  const void* d_hdr_arena, uint64_t hdr_cap) {
-  if (!r) return "h2 windowed reply: no reply";
-  if (!r->d_wr) return "h2 windowed reply: the reply has no send windows attached";
-  if (!r->sw) return "h2 windowed reply: the send windows are gone";
-  if (!r->sw->parser) return "h2 windowed reply: the send windows' parser is gone";
-  if (r->seq || r->src->attached) return "h2 windowed reply: a reply or source assembler bound to a pipe";
-  if (flags & ~(uint32_t)GRDMA_H2_WR_PENDING_ONLY) return "h2 windowed reply: unknown flags";
-  if (!d_slices_out || !slices_cap || !d_hdr_arena || !hdr_cap || ((uintptr_t)d_slices_out & 15) || ((uintptr_t)d_hdr_arena & 15))
-    return "h2 windowed reply: a null, zero or misaligned slice table or header arena";
-  if (r->src->calls == r->attached_at && r->pending == 0) return "h2 windowed reply: no source call yet and nothing waits";
+  if (!r) return "no reply";
+  if (!r->d_wr) return "the reply has no send windows attached";
+  if (!r->sw) return "the send windows are gone";
+  if (!r->sw->parser) return "the send windows' parser is gone";
+  if (r->seq || r->src->attached) return "a reply or source assembler bound to a pipe";
+  if (flags & ~(uint32_t)GRDMA_H2_WR_PENDING_ONLY) return "unknown flags";
+  if (const char* why = h2_bad_target(d_slices_out, slices_cap, d_hdr_arena, hdr_cap)) return why;
+  if (r->src->calls == r->attached_at && r->pending == 0) return "no source call yet and nothing waits";
   return nullptr;
 }
 
@@ -1374,9 +1360,13 @@ static bool h2_wr_call_words(grdma_h2_reply* r, uint32_t flags) {
   return take;
 }
 
-// the send windows' framing words for a call of r, from a local copy of their mirror
-static h2sw_dev h2_wr_sw_words(const grdma_h2_reply* r, grdma_slice* d_slices_out, uint64_t slices_cap, void* d_hdr_arena, uint64_t hdr_cap) {
-  h2sw_dev h = r->sw->h;
+// A call of r, its transfers added to c: the call words up into the queue, the send windows' framing words up from
+// *words -- a LOCAL copy of their mirror with the call's targets -- and the queue's result block down to res.
+// -> whether the source's last call is to be taken
+static bool h2_wr_transfers(h2_call* c, grdma_h2_reply* r, uint32_t flags, grdma_slice* d_slices_out, uint64_t slices_cap, void* d_hdr_arena,
+                            uint64_t hdr_cap, h2sw_dev* words, uint64_t* res) {
+  const bool take = h2_wr_call_words(r, flags);
+  h2sw_dev& h = *words = r->sw->h;
   h.msgs = r->wr.msgs[0];   // (k_h2_wr_queue names the table and the count)
   h.prog_in = r->wr.prog[0];
   h.nmsgs = 0;
@@ -1385,47 +1375,43 @@ static h2sw_dev h2_wr_sw_words(const grdma_h2_reply* r, grdma_slice* d_slices_ou
   h.cap = slices_cap;
   h.hdr = static_cast<uint8_t*>(d_hdr_arena);
   h.hdr_cap = hdr_cap;
-  return h;
+  c->up.push_back(h2_words(r->d_wr, &r->wr, offsetof(h2wr_dev, take), offsetof(h2wr_dev, n_tab)));
+  c->up.push_back(h2_words(r->sw->d, words, offsetof(h2sw_dev, msgs), offsetof(h2sw_dev, conn)));
+  c->down.push_back(h2_result(res, r->d_wr, offsetof(h2wr_dev, res), 16));
+  return take;
 }
 
-// behind a call of r that ran: what the host keeps of it
-static void h2_wr_ran(grdma_h2_reply* r, bool take, const uint64_t res[16], float ms) {
+// behind a call of r that ran: what the host keeps of it, and its result block to the caller -> whether it stands
+static bool h2_wr_ran(grdma_h2_reply* r, bool take, const uint64_t res[16], float ms, uint64_t out[16]) {
+  for (int i = 0; i < 16; i++) out[i] = res[i];
+  out[H2WR_US] = (uint64_t)(ms * 1e3f);
   const uint64_t calls = r->src->calls;
   if (calls > r->taken + 1) r->taken = calls - 1;  // (lost: the flag is the device's and sticky)
   r->sw->last_ms = ms;
-  if (res[H2WR_OVERFLOW]) return;  // (the queue stands, the source call is not taken)
+  if (res[H2WR_OVERFLOW]) return false;  // (the queue stands, the source call is not taken)
   if (take) r->taken = calls;
   r->pending = res[H2WR_PENDING];
+  return true;
 }
 
 int64_t grdma_h2_reply_frame_windowed(grdma_h2_reply* r, uint32_t flags, grdma_slice* d_slices_out, uint64_t slices_cap,
                                       void* d_hdr_arena, uint64_t hdr_cap, uint64_t out[16]) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!out) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 windowed reply: no result array");
-  if (const char* why = h2_wr_refusal(r, flags, d_slices_out, slices_cap, d_hdr_arena, hdr_cap)) return grdma_fail_msg(GRDMA_ERR_INVALID, why);
+  if (!out) return h2_invalid("h2 windowed reply", "no result array");
+  if (const char* why = h2_wr_refusal(r, flags, d_slices_out, slices_cap, d_hdr_arena, hdr_cap)) return h2_invalid("h2 windowed reply", why);
   h2_host_ctx* hc = h2_ctx();
   if (!hc) return -GRDMA_ERR_HIP;
-  hipStream_t st = hc->stream;
-  grdma_h2_sw* s = r->sw;
   // behind the source parser's last deframing (the descriptors) and the last one of the send windows' parser (the map)
-  if (!h2_wait_parser(st, r->src->parser) || !h2_wait_parser(st, s->parser)) return -GRDMA_ERR_HIP;
-  const bool take = h2_wr_call_words(r, flags);
-  const h2sw_dev h = h2_wr_sw_words(r, d_slices_out, slices_cap, d_hdr_arena, hdr_cap);
-  if (!h2_push_words(r->d_wr, &r->wr, offsetof(h2wr_dev, take), offsetof(h2wr_dev, n_tab), st) ||
-      !h2_push_words(s->d, &h, offsetof(h2sw_dev, msgs), offsetof(h2sw_dev, conn), st))
-    return -GRDMA_ERR_HIP;
-  const h2_stage framing = h2_stage_wr_frame(r->d_wr, s->d);
+  if (!h2_wait_parser(hc->stream, r->src->parser) || !h2_wait_parser(hc->stream, r->sw->parser)) return -GRDMA_ERR_HIP;
+  const h2_stage framing = h2_stage_wr_frame(r->d_wr, r->sw->d);
+  h2sw_dev words;
   uint64_t res[16];
-  h2_call c{"grdma_h2_reply_frame_windowed: a launch was rejected", {}, {}, {h2_all(framing)},
-            {{res, reinterpret_cast<uint8_t*>(r->d_wr) + offsetof(h2wr_dev, res), sizeof(res)}}};
+  h2_call c{"grdma_h2_reply_frame_windowed: a launch was rejected", {}, {}, {h2_all(framing)}, {}};
+  const bool take = h2_wr_transfers(&c, r, flags, d_slices_out, slices_cap, d_hdr_arena, hdr_cap, &words, res);
   if (int rc = h2_call_run(hc, &c)) return rc;
-  h2_wr_ran(r, take, res, c.ms[0]);
-  for (int i = 0; i < 16; i++) out[i] = res[i];
-  out[H2WR_US] = (uint64_t)(c.ms[0] * 1e3f);
+  if (h2_wr_ran(r, take, res, c.ms[0], out)) return (int64_t)res[H2WR_SLICES];
   if (res[H2WR_OVERFLOW] == 2) return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 windowed reply: more entries than max_pending");
-  if (res[H2WR_OVERFLOW])
-    return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 windowed reply: a slice or header cap too small, a skipped source call or more descriptors than max_messages");
-  return (int64_t)res[H2WR_SLICES];
+  return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 windowed reply: a slice or header cap too small, a skipped source call or more descriptors than max_messages");
 }
 
 int64_t grdma_h2_reply_pending(grdma_h2_reply* r, uint64_t* out, uint64_t cap) {
@@ -1457,90 +1443,60 @@ int64_t grdma_h2_reply_pending(grdma_h2_reply* r, uint64_t* out, uint64_t cap) {
 // into its own queue's and send windows' device memory, its result block comes down from its queue.
 int grdma_h2_reply_frame_windowed_batch(grdma_h2_wr_item* items, uint32_t n_items) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!items || n_items == 0 || n_items > GRDMA_H2_BATCH_MAX)
-    return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 windowed reply batch: 1 .. GRDMA_H2_BATCH_MAX items");
+  h2_batch b{"h2 windowed reply batch", "reply", "h2 windowed reply batch: a launch was rejected"};
+  if (int rc = b.begin(items, n_items)) return rc;
   for (uint32_t i = 0; i < n_items; i++) {
     const grdma_h2_wr_item& it = items[i];
-    if (const char* why = h2_wr_refusal(it.reply, it.flags, it.d_slices_out, it.slices_cap, it.d_hdr_arena, it.hdr_cap))
-      return grdma_fail_msg(GRDMA_ERR_INVALID, why);
-    for (uint32_t k = 0; k < i; k++) {
-      if (items[k].reply == it.reply) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 windowed reply batch: the same reply twice");
-      if (items[k].reply->src == it.reply->src)
-        return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 windowed reply batch: two replies of one source assembler");
-    }
+    if (int rc = b.item(it.reply, h2_wr_refusal(it.reply, it.flags, it.d_slices_out, it.slices_cap, it.d_hdr_arena, it.hdr_cap))) return rc;
+    for (uint32_t k = 0; k < i; k++)
+      if (items[k].reply->src == it.reply->src) return h2_invalid(b.who, "two replies of one source assembler");
   }
-  h2_host_ctx* hc = h2_ctx();
-  if (!hc) return -GRDMA_ERR_HIP;
-  hipStream_t st = hc->stream;
-  const h2_fc_block L = h2_fc_block_layout(sizeof(h2wr_link), sizeof(h2sw_link), n_items);
-  if (!h2_batch_reserve(L.total, st)) return -GRDMA_ERR_HIP;
-  uint8_t* const d = g_batch.d;
-  std::vector<uint8_t> up(L.end, 0);
-  auto* tab = reinterpret_cast<h2wr_link*>(up.data() + L.tab);
-  auto* sw_tab = reinterpret_cast<h2sw_link*>(up.data() + L.calls);
+  if (int rc = b.open(sizeof(h2wr_link), sizeof(h2sw_link), n_items)) return rc;
+  auto* tab = reinterpret_cast<h2wr_link*>(b.up.data());
+  auto* sw_tab = reinterpret_cast<h2sw_link*>(b.up.data() + b.blocks);
   std::vector<h2sw_dev> words(n_items);
   std::vector<uint64_t> res(16 * (size_t)n_items);
   std::vector<char> take(n_items);
-  const h2_stage framing = h2_stage_wr_frame_links(reinterpret_cast<const h2wr_link*>(d + L.tab),
-                                                   reinterpret_cast<const h2sw_link*>(d + L.calls), n_items);
-  h2_call c{"h2 windowed reply batch: a launch was rejected", {{d, up.data(), up.size()}}, {}, {h2_all(framing)}, {}};
   for (uint32_t i = 0; i < n_items; i++) {
     const grdma_h2_wr_item& it = items[i];
     grdma_h2_reply* r = it.reply;
-    take[i] = h2_wr_call_words(r, it.flags) ? 1 : 0;
-    words[i] = h2_wr_sw_words(r, it.d_slices_out, it.slices_cap, it.d_hdr_arena, it.hdr_cap);
+    take[i] = h2_wr_transfers(&b.c, r, it.flags, it.d_slices_out, it.slices_cap, it.d_hdr_arena, it.hdr_cap, &words[i], res.data() + 16 * (size_t)i);
     tab[i].W = r->d_wr;
-    sw_tab[i].F = r->sw->d;
-    sw_tab[i].call = nullptr;
-    c.up.push_back({reinterpret_cast<uint8_t*>(r->d_wr) + offsetof(h2wr_dev, take), reinterpret_cast<const uint8_t*>(&r->wr) + offsetof(h2wr_dev, take),
-                    offsetof(h2wr_dev, n_tab) - offsetof(h2wr_dev, take)});
-    c.up.push_back({reinterpret_cast<uint8_t*>(r->sw->d) + offsetof(h2sw_dev, msgs), reinterpret_cast<const uint8_t*>(&words[i]) + offsetof(h2sw_dev, msgs),
-                    offsetof(h2sw_dev, conn) - offsetof(h2sw_dev, msgs)});
-    c.down.push_back({res.data() + 16 * (size_t)i, reinterpret_cast<const uint8_t*>(r->d_wr) + offsetof(h2wr_dev, res), 16 * sizeof(uint64_t)});
+    sw_tab[i] = {r->sw->d, nullptr};
+    b.behind.push_back(r->src->parser);  // (the descriptors)
+    b.behind.push_back(r->sw->parser);   // (the map)
   }
-  for (uint32_t i = 0; i < n_items; i++)
-    if (!h2_wait_parser(st, items[i].reply->src->parser) || !h2_wait_parser(st, items[i].reply->sw->parser)) return -GRDMA_ERR_HIP;
-  if (int rc = h2_call_run(hc, &c)) return rc;
-  g_h2_last_kernel_us = 1e3 * c.ms[0];
+  const h2_stage framing = h2_stage_wr_frame_links(reinterpret_cast<const h2wr_link*>(b.d), reinterpret_cast<const h2sw_link*>(b.d + b.blocks), n_items);
+  if (int rc = b.run({h2_all(framing)})) return rc;
+  g_h2_last_kernel_us = 1e3 * b.c.ms[0];
   int ok = 0;
   for (uint32_t i = 0; i < n_items; i++) {
     grdma_h2_wr_item& it = items[i];
     const uint64_t* rs = res.data() + 16 * (size_t)i;
-    h2_wr_ran(it.reply, take[i] != 0, rs, c.ms[0]);
-    for (int k = 0; k < 16; k++) it.out[k] = rs[k];
-    it.out[H2WR_US] = (uint64_t)(c.ms[0] * 1e3f);  // (the batch's, repeated)
-    it.n_slices = rs[H2WR_OVERFLOW] ? -(int64_t)GRDMA_ERR_CAPACITY : (int64_t)rs[H2WR_SLICES];
-    ok += rs[H2WR_OVERFLOW] == 0;
+    const bool stands = h2_wr_ran(it.reply, take[i] != 0, rs, b.c.ms[0], it.out);  // (the time: the batch's, repeated)
+    it.n_slices = stands ? (int64_t)rs[H2WR_SLICES] : -(int64_t)GRDMA_ERR_CAPACITY;
+    ok += stands;
   }
   return ok;
 }
 
 // ---- control replies: SETTINGS ACK, PING ACK, RST_STREAM from a deframing's events (csrc/grdma_h2_ctl.h) ---------------
-struct grdma_h2_ctl {
-  grdma_h2_parser* parser = nullptr;
+struct grdma_h2_ctl : h2_follow {  // (taken: the last call taken in; at creation: the calls before it)
   h2ctl_dev* d = nullptr;
   h2ctl_call* d_call = nullptr;
-  uint64_t taken = 0;  // parser->standalone_calls of the last call taken in (at creation: of the calls before it)
-  float last_ms = 0;
 };
 
-// The parser of w is being destroyed: from now on w refuses every call but destroy (its calls read the parser's buffers).
-static void h2_ctl_parser_gone(grdma_h2_ctl* w) {
-  h2_host_ctx* hc = h2_ctx();
-  if (hc) hipStreamSynchronize(hc->stream);
-  w->parser = nullptr;
-}
-
-static grdma_h2_ctl* h2_ctl_refuse(const char* why) {
-  grdma_fail_msg(GRDMA_ERR_INVALID, why);
-  return nullptr;
+static void h2_followers_parser_gone(grdma_h2_parser* p) {
+  h2_follow* const followers[3] = {p->fc, p->sw, p->ctl};
+  for (h2_follow* f : followers)
+    if (f) h2_follow_parser_gone(f);
 }
 
 grdma_h2_ctl* grdma_h2_ctl_create(grdma_h2_parser* parser, uint32_t max_replies) {
   if (grdma_device_count() <= 0) return nullptr;
-  if (!parser) return h2_ctl_refuse("h2 control replies: no parser");
-  if (parser->ctl) return h2_ctl_refuse("h2 control replies: the parser has a control-reply writer already");
-  if (max_replies == 0 || max_replies > (1u << 24)) return h2_ctl_refuse("h2 control replies: max_replies outside 1 .. 2^24");
+  if (!parser) return h2_no("h2 control replies: no parser");
+  if (parser->ctl) return h2_no("h2 control replies: the parser has a control-reply writer already");
+  if (max_replies == 0 || max_replies > (1u << 24)) return h2_no("h2 control replies: max_replies outside 1 .. 2^24");
   grdma_h2_ctl* w = new grdma_h2_ctl();
   w->parser = parser;
   w->taken = parser->standalone_calls;
@@ -1567,54 +1523,46 @@ void grdma_h2_ctl_destroy(grdma_h2_ctl* w) {
   delete w;
 }
 
-// what a call on w into these targets would be refused for (nullptr: nothing); the single call and the batch share it
-static const char* h2_ctl_refusal(const grdma_h2_ctl* w, const void* d_slices_out, uint64_t slices_cap, const void* d_hdr_arena,
-                                  uint64_t hdr_cap) {
-  const grdma_h2_parser* p = w->parser;
-  if (!p) return "h2 control replies: the parser is gone";
-  if (p->standalone_calls == 0) return "h2 control replies: the parser has deframed nothing yet";
-  if (w->taken == p->standalone_calls) return "h2 control replies: this call is taken in already";
-  if (p->standalone_ev_cap >= 0xfffffff0ull) return "h2 control replies: event positions are 32 bits";
-  if (!d_slices_out || !slices_cap || !d_hdr_arena || !hdr_cap || ((uintptr_t)d_slices_out & 15) || ((uintptr_t)d_hdr_arena & 15))
-    return "h2 control replies: a null, zero or misaligned slice table or header arena";
-  return nullptr;
+// what a call of an item (the single call's arguments are one) is refused for
+static const char* h2_ctl_refusal(const grdma_h2_ctl_item& it) {
+  if (!it.ctl) return "a call without writer";
+  if (const char* why = h2_follow_refusal(*it.ctl, "this call is taken in already", true)) return why;
+  return h2_bad_target(it.d_slices_out, it.slices_cap, it.d_hdr_arena, it.hdr_cap);
 }
-
-static h2ctl_call h2_ctl_call_of(const grdma_h2_ctl* w) {
-  const grdma_h2_parser* p = w->parser;
-  return h2ctl_call{p->d_ev, p->d_res, p->d_sl, p->standalone_arena, p->standalone_ev_cap, p->standalone_nsl,
-                    p->standalone_calls > w->taken + 1 ? 1ull : 0ull};
+// where an item's call writes: the leading words of its writer's device block
+struct h2ctl_target { grdma_sge* out; uint64_t cap; uint8_t* hdr; uint64_t hdr_cap; };
+static_assert(offsetof(h2ctl_dev, out) == 0 && offsetof(h2ctl_dev, max_replies) == sizeof(h2ctl_target), "a call's target leads the block");
+static h2ctl_target h2_ctl_target(const grdma_h2_ctl_item& it) {
+  return {reinterpret_cast<grdma_sge*>(it.d_slices_out), it.slices_cap, static_cast<uint8_t*>(it.d_hdr_arena), it.hdr_cap};
+}
+// behind a call of w that ran, res its result words -> whether its frames stand
+static bool h2_ctl_ran(grdma_h2_ctl* w, float ms, const uint64_t* res) {
+  // (a cap overflow, 1: nothing was written or committed, the call is not taken and may be repeated)
+  h2_follow_ran(w, ms, res[H2CTL_OVERFLOW] != 1);
+  return res[H2CTL_OVERFLOW] == 0;
 }
 
 int64_t grdma_h2_ctl_reply(grdma_h2_ctl* w, grdma_slice* d_slices_out, uint64_t slices_cap, void* d_hdr_arena, uint64_t hdr_cap,
                            uint64_t out[8]) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!w || !out) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 control replies: no writer or no result array");
-  if (const char* why = h2_ctl_refusal(w, d_slices_out, slices_cap, d_hdr_arena, hdr_cap)) return grdma_fail_msg(GRDMA_ERR_INVALID, why);
-  grdma_h2_parser* p = w->parser;
+  if (!out) return h2_invalid("h2 control replies", "no result array");
+  const grdma_h2_ctl_item it{w, d_slices_out, slices_cap, d_hdr_arena, hdr_cap};
+  if (const char* why = h2_ctl_refusal(it)) return h2_invalid("h2 control replies", why);
   h2_host_ctx* hc = h2_ctx();
   if (!hc) return -GRDMA_ERR_HIP;
   // the stream of the standalone deframings: the call is ordered behind the one it reads
-  hipStream_t st = hc->stream;
-  if (!h2_wait_parser(st, p)) return -GRDMA_ERR_HIP;
-  const h2ctl_call call = h2_ctl_call_of(w);
-  struct { grdma_sge* out; uint64_t cap; uint8_t* hdr; uint64_t hdr_cap; } target{reinterpret_cast<grdma_sge*>(d_slices_out), slices_cap,
-                                                                                   static_cast<uint8_t*>(d_hdr_arena), hdr_cap};
-  static_assert(offsetof(h2ctl_dev, out) == 0 && offsetof(h2ctl_dev, max_replies) == sizeof(target), "a call's target leads the block");
+  if (!h2_wait_parser(hc->stream, w->parser)) return -GRDMA_ERR_HIP;
+  const h2ctl_call call = h2_follow_deframed(*w);
+  const h2ctl_target target = h2_ctl_target(it);
   const h2_stage stage = h2_stage_ctl(w->d, w->d_call);
-  uint64_t res[8];
   h2_call c{"grdma_h2_ctl_reply: a launch was rejected",
             {{w->d_call, &call, sizeof(call)}, {w->d, &target, sizeof(target)}}, {}, {h2_all(stage)},
-            {{res, reinterpret_cast<uint8_t*>(w->d) + offsetof(h2ctl_dev, res), sizeof(res)}}};
+            {h2_result(out, w->d, offsetof(h2ctl_dev, res))}};
   if (int rc = h2_call_run(hc, &c)) return rc;
-  w->last_ms = c.ms[0];
-  for (int i = 0; i < 8; i++) out[i] = res[i];
-  if (res[H2CTL_OVERFLOW] == 1)  // (nothing was written or committed, the call is not taken: it may be repeated)
+  if (h2_ctl_ran(w, c.ms[0], out)) return (int64_t)out[H2CTL_SLICES];
+  if (out[H2CTL_OVERFLOW] == 1)
     return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 control replies: more replies than max_replies, or a slice or header cap too small");
-  w->taken = p->standalone_calls;
-  if (res[H2CTL_OVERFLOW])
-    return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 control replies: the call's event list overflowed, its frames cannot be answered");
-  return (int64_t)res[H2CTL_SLICES];
+  return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 control replies: the call's event list overflowed, its frames cannot be answered");
 }
 
 int grdma_h2_ctl_peer(grdma_h2_ctl* w, uint64_t out[8]) {
@@ -1645,49 +1593,27 @@ int grdma_h2_ctl_stats(grdma_h2_ctl* w, uint64_t out[8]) {
 // calls.
 int grdma_h2_ctl_reply_batch(const grdma_h2_ctl_item* items, uint32_t n_items, uint64_t* out) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!items || !out || n_items == 0 || n_items > GRDMA_H2_BATCH_MAX)
-    return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 control replies batch: 1 .. GRDMA_H2_BATCH_MAX items and a result array");
-  for (uint32_t i = 0; i < n_items; i++) {
-    const grdma_h2_ctl_item& it = items[i];
-    if (!it.ctl) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 control replies batch: an item without writer");
-    for (uint32_t k = 0; k < i; k++)
-      if (items[k].ctl == it.ctl) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 control replies batch: the same writer twice");
-    if (const char* why = h2_ctl_refusal(it.ctl, it.d_slices_out, it.slices_cap, it.d_hdr_arena, it.hdr_cap))
-      return grdma_fail_msg(GRDMA_ERR_INVALID, why);
-  }
-  h2_host_ctx* hc = h2_ctx();
-  if (!hc) return -GRDMA_ERR_HIP;
-  hipStream_t st = hc->stream;
-  const h2_fc_block L = h2_fc_block_layout(sizeof(h2ctl_link), sizeof(h2ctl_call), n_items);
-  if (!h2_batch_reserve(L.total, st)) return -GRDMA_ERR_HIP;
-  uint8_t* const d = g_batch.d;
-  std::vector<uint8_t> up(L.end, 0);
-  auto* tab = reinterpret_cast<h2ctl_link*>(up.data() + L.tab);
-  auto* calls = reinterpret_cast<h2ctl_call*>(up.data() + L.calls);
-  struct target_words { grdma_sge* out; uint64_t cap; uint8_t* hdr; uint64_t hdr_cap; };
-  std::vector<target_words> targets(n_items);
-  const h2_stage stage = h2_stage_ctl_links(reinterpret_cast<const h2ctl_link*>(d + L.tab), n_items);
-  h2_call c{"h2 control replies batch: a launch was rejected", {{d, up.data(), up.size()}}, {}, {h2_all(stage)}, {}};
-  for (uint32_t i = 0; i < n_items; i++) {
-    const grdma_h2_ctl_item& it = items[i];
-    calls[i] = h2_ctl_call_of(it.ctl);
-    tab[i].F = it.ctl->d;
-    tab[i].call = reinterpret_cast<const h2ctl_call*>(d + L.calls) + i;
-    targets[i] = target_words{reinterpret_cast<grdma_sge*>(it.d_slices_out), it.slices_cap, static_cast<uint8_t*>(it.d_hdr_arena), it.hdr_cap};
-    c.up.push_back({it.ctl->d, &targets[i], sizeof(target_words)});
-    c.down.push_back({out + 8 * (size_t)i, reinterpret_cast<const uint8_t*>(it.ctl->d) + offsetof(h2ctl_dev, res), 8 * sizeof(uint64_t)});
-  }
+  h2_batch b{"h2 control replies batch", "writer", "h2 control replies batch: a launch was rejected"};
+  if (int rc = b.begin(items && out, n_items)) return rc;
   for (uint32_t i = 0; i < n_items; i++)
-    if (!h2_wait_parser(st, items[i].ctl->parser)) return -GRDMA_ERR_HIP;
-  if (int rc = h2_call_run(hc, &c)) return rc;
-  int ok = 0;
+    if (int rc = b.item(items[i].ctl, h2_ctl_refusal(items[i]))) return rc;
+  if (int rc = b.open(sizeof(h2ctl_link), sizeof(h2ctl_call), n_items)) return rc;
+  auto* tab = reinterpret_cast<h2ctl_link*>(b.up.data());
+  auto* calls = reinterpret_cast<h2ctl_call*>(b.up.data() + b.blocks);
+  std::vector<h2ctl_target> targets(n_items);
   for (uint32_t i = 0; i < n_items; i++) {
-    grdma_h2_ctl* w = items[i].ctl;
-    w->last_ms = c.ms[0];  // (the batch's, repeated)
-    const uint64_t over = out[8 * (size_t)i + H2CTL_OVERFLOW];
-    if (over != 1) w->taken = w->parser->standalone_calls;  // (a cap overflow leaves the call to be repeated)
-    ok += over == 0;
+    const grdma_h2_ctl* w = items[i].ctl;
+    calls[i] = h2_follow_deframed(*w);
+    tab[i] = {w->d, reinterpret_cast<const h2ctl_call*>(b.d + b.blocks) + i};
+    targets[i] = h2_ctl_target(items[i]);
+    b.c.up.push_back({w->d, &targets[i], sizeof(h2ctl_target)});
+    b.c.down.push_back(h2_result(out + 8 * (size_t)i, w->d, offsetof(h2ctl_dev, res)));
+    b.behind.push_back(w->parser);
   }
+  const h2_stage stage = h2_stage_ctl_links(reinterpret_cast<const h2ctl_link*>(b.d), n_items);
+  if (int rc = b.run({h2_all(stage)})) return rc;
+  int ok = 0;
+  for (uint32_t i = 0; i < n_items; i++) ok += h2_ctl_ran(items[i].ctl, b.c.ms[0], out + 8 * (size_t)i);  // (the time: the batch's, repeated)
   return ok;
 }
 
@@ -1712,62 +1638,54 @@ h2_links_ctx* h2_links() {
 
 int grdma_h2_deframe_messages_batch(grdma_h2_messages_item* items, uint32_t n_items) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
-  if (!items || n_items == 0 || n_items > GRDMA_H2_BATCH_MAX)
-    return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 messages batch: 1 .. GRDMA_H2_BATCH_MAX items");
+  h2_batch b{"h2 messages batch", "parser", "h2 messages batch: a launch was rejected"};
+  if (int rc = b.begin(items, n_items)) return rc;
   uint64_t n_sl = 0, n_ev = 0;
   bool want_events = false;
   for (uint32_t i = 0; i < n_items; i++) {
     const grdma_h2_messages_item& it = items[i];
+    const char* why = nullptr;
     if (!it.parser || !it.d_arena || (!it.slices && it.n) || it.cap == 0 || (!it.msgs_out && it.msgs_cap))
-      return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 messages batch: an item without parser, arena, slices, event capacity or descriptor array");
-    if (!it.assembler) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 messages batch: an item without assembler");
-    if (it.assembler->parser != it.parser) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 messages batch: an assembler of another parser");
-    if (it.parser->fc) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 messages batch: a parser with a flow-control ledger (single transport only)");
-    if (it.assembler->attached || it.parser->asm_attached)
-      return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 messages batch: an assembler attached to a pipe");
-    for (uint32_t k = 0; k < i; k++) {
-      if (items[k].parser == it.parser) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 messages batch: the same parser twice");
-      if (items[k].assembler == it.assembler) return grdma_fail_msg(GRDMA_ERR_INVALID, "h2 messages batch: the same assembler twice");
-    }
+      why = "an item without parser, arena, slices, event capacity or descriptor array";
+    else if (!it.assembler) why = "an item without assembler";
+    else if (it.assembler->parser != it.parser) why = "an assembler of another parser";
+    else if (it.parser->fc) why = "a parser with a flow-control ledger (single transport only)";
+    else if (it.assembler->attached || it.parser->asm_attached) why = "an assembler attached to a pipe";
+    if (int rc = b.item(it.parser, why)) return rc;  // (an assembler has one parser: its items are distinct with their parsers)
     n_sl += it.n;
     n_ev += it.cap;
     want_events = want_events || it.events_out;
   }
-  h2_host_ctx* hc = h2_ctx();
-  if (!hc) return -GRDMA_ERR_HIP;
-  hipStream_t st = hc->stream;
   for (uint32_t i = 0; i < n_items; i++)
     if (!h2_asm_prepare(items[i].assembler, items[i].cap)) return -GRDMA_ERR_HIP;
   const h2_deframe_block L = h2_deframe_batch_layout(n_items, n_sl, n_ev, true);
-  if (!h2_batch_reserve(L.total, st)) return -GRDMA_ERR_HIP;
-  uint8_t* const d = g_batch.d;
-  // (the result blocks go up zeroed; the events come down only when an item asks for them)
-  std::vector<uint8_t> up(L.events, 0), down((want_events ? L.total : L.events) - L.results);
-  h2_batch_pack(items, n_items, L, up.data(), d);
+  if (int rc = b.reserve(L.events, L.total)) return rc;  // ([0, events) goes up)
+  hipStream_t st = b.hc->stream;
+  uint8_t* const d = b.d;
+  // (the events come down only when an item asks for them)
+  std::vector<uint8_t> down((want_events ? L.total : L.events) - L.results);
+  h2_batch_pack(items, n_items, L, b.up.data(), d);
   // on top of the deframe table: every assembler with a call block that names what its item's deframer leaves
-  const auto* dtab = reinterpret_cast<const grdma_h2_link_deframe*>(up.data() + L.tab);
-  auto* atab = reinterpret_cast<h2a_link*>(up.data() + L.asm_tab);
-  auto* calls = reinterpret_cast<h2a_call*>(up.data() + L.asm_calls);
+  const auto* dtab = reinterpret_cast<const grdma_h2_link_deframe*>(b.up.data() + L.tab);
+  auto* atab = reinterpret_cast<h2a_link*>(b.up.data() + L.asm_tab);
+  auto* calls = reinterpret_cast<h2a_call*>(b.up.data() + L.asm_calls);
   for (uint32_t i = 0; i < n_items; i++) {
     const grdma_h2_link_deframe& q = dtab[i];
     calls[i] = h2a_call{q.ev, q.res, q.slices, q.arena, q.ev_cap, 0};
     atab[i].A = items[i].assembler->d;
     atab[i].call = reinterpret_cast<const h2a_call*>(d + L.asm_calls) + i;
+    b.behind.push_back(items[i].parser);
   }
-  // behind each parser's previous deframing (a pipe step on another stream)
-  for (uint32_t i = 0; i < n_items; i++)
-    if (!h2_wait_parser(st, items[i].parser)) return -GRDMA_ERR_HIP;
   // the deframing; then the assembly: the plan and the copy, timed apart.  One download of the results (and the events);
   // then every assembler's block, and below the descriptors from where each assembler keeps them (its own buffer: the
   // kernels are the single call's, which reports from there)
   const h2_stage deframing = h2_stage_deframe_links(reinterpret_cast<const grdma_h2_link_deframe*>(d + L.tab), n_items);
   const h2_stage assembly = h2_stage_asm_links(reinterpret_cast<const h2a_link*>(d + L.asm_tab), n_items);
   std::vector<h2a_dev> hs(n_items);
-  h2_call c{"h2 messages batch: a launch was rejected",
-            {{d, up.data(), up.size()}}, {}, {h2_all(deframing), h2_asm_plan(assembly), h2_asm_copy(assembly)},
-            {{down.data(), d + L.results, down.size()}}};
-  for (uint32_t i = 0; i < n_items; i++) c.down.push_back({&hs[i], items[i].assembler->d, sizeof(h2a_dev)});
-  if (int rc = h2_call_run(hc, &c)) return rc;
+  b.c.down.push_back({down.data(), d + L.results, down.size()});
+  for (uint32_t i = 0; i < n_items; i++) b.c.down.push_back({&hs[i], items[i].assembler->d, sizeof(h2a_dev)});
+  if (int rc = b.run({h2_all(deframing), h2_asm_plan(assembly), h2_asm_copy(assembly)})) return rc;
+  const h2_call& c = b.c;
   g_h2_last_kernel_us = 1e3 * c.ms[0];
   h2_batch_hand_back(items, n_items, L, down.data());
   bool more = false;

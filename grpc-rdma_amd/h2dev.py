@@ -118,6 +118,38 @@ def _events(arr, m):
     return [(e.kind, e.a, e.b, e.c, e.d, e.slice) for e in arr[:m]]
 
 
+def _read_slice_table(lib, slices_ptr, n):
+    """the first n rows of a slice table in device memory -> [(ptr, len), ...]"""
+    raw = C.create_string_buffer(max(1, 16 * n))
+    if n:
+        check(lib.grdma_copy_to_host(raw, slices_ptr, 16 * n))
+    return [(int.from_bytes(raw.raw[16 * i:16 * i + 8], "little"), int.from_bytes(raw.raw[16 * i + 8:16 * i + 16], "little"))
+            for i in range(n)]
+
+
+def _read_wire(lib, slices):
+    """the bytes the slices [(device ptr, len), ...] point to, in their order"""
+    wire = b""
+    for ptr, ln in slices:
+        buf = C.create_string_buffer(max(1, ln))
+        check(lib.grdma_copy_to_host(buf, ptr, ln))
+        wire += buf.raw[:ln]
+    return wire
+
+
+def _set_target(item, target):
+    """the target fields of a batch item from (slices device ptr, slices cap, header arena device ptr, header cap)"""
+    item.d_slices_out, item.slices_cap, item.d_hdr_arena, item.hdr_cap = target
+
+
+def _results(out, objs, words=8):
+    """the result words `out` of a call cut into one tuple per object, each also left in its object's .last_result"""
+    res = [tuple(int(x) for x in out[words * i:words * i + words]) for i in range(len(objs))]
+    for o, r in zip(objs, res):
+        o.last_result = r
+    return res
+
+
 _bound = False
 
 
@@ -439,9 +471,9 @@ def reply_frame_batch(items):
     lib = _bind()
     n = len(items)
     arr = (H2ReplyItem * max(1, n))()
-    for i, (reply, sl, cap, hdr, hdr_cap) in enumerate(items):
+    for i, (reply, *target) in enumerate(items):
         arr[i].reply = reply.h if reply is not None else None
-        arr[i].d_slices_out, arr[i].slices_cap, arr[i].d_hdr_arena, arr[i].hdr_cap = sl, cap, hdr, hdr_cap
+        _set_target(arr[i], target)
     check(lib.grdma_h2_reply_frame_batch(arr, n))
     res = []
     for i in range(n):
@@ -700,14 +732,6 @@ class Reply:
             self.h = None
 
 
-def _read_slice_table(lib, slices_ptr, n):
-    raw = C.create_string_buffer(max(1, 16 * n))
-    if n:
-        check(lib.grdma_copy_to_host(raw, slices_ptr, 16 * n))
-    return [(int.from_bytes(raw.raw[16 * i:16 * i + 8], "little"), int.from_bytes(raw.raw[16 * i + 8:16 * i + 16], "little"))
-            for i in range(n)]
-
-
 def reply_frame_windowed_batch(items):
     """Reply.frame_windowed for many transports in four launches (grdma_h2_reply_frame_windowed_batch).  items: [(Reply,
     slices device ptr, slices cap, header arena device ptr, header cap, pending_only), ...] with distinct replies of
@@ -717,10 +741,10 @@ def reply_frame_windowed_batch(items):
     lib = _bind()
     n = len(items)
     arr = (H2WrItem * max(1, n))()
-    for i, (reply, sl, cap, hdr, hdr_cap, pending_only) in enumerate(items):
+    for i, (reply, *target, pending_only) in enumerate(items):
         arr[i].reply = reply.h if reply is not None else None
         arr[i].flags = Reply.PENDING_ONLY if pending_only else 0
-        arr[i].d_slices_out, arr[i].slices_cap, arr[i].d_hdr_arena, arr[i].hdr_cap = sl, cap, hdr, hdr_cap
+        _set_target(arr[i], target)
     check(lib.grdma_h2_reply_frame_windowed_batch(arr, n))
     res = []
     for i in range(n):
@@ -755,19 +779,9 @@ class FlowControl:
         raises GrdmaError on a refusal or a capacity overflow -- the result of the failed call stays in .last_result"""
         out = (u64 * 8)()
         n = self.lib.grdma_h2_fc_account(self.h, slices_ptr, cap, hdr_ptr, hdr_cap, out)
-        self.last_result = tuple(int(x) for x in out)
-        n = check(n)
-        raw = C.create_string_buffer(max(1, 16 * n))
-        if n:
-            check(self.lib.grdma_copy_to_host(raw, slices_ptr, 16 * n))
-        sl = [(int.from_bytes(raw.raw[16 * i:16 * i + 8], "little"), int.from_bytes(raw.raw[16 * i + 8:16 * i + 16], "little"))
-              for i in range(n)]
-        wire = b""
-        for ptr, ln in sl:
-            buf = C.create_string_buffer(max(1, ln))
-            check(self.lib.grdma_copy_to_host(buf, ptr, ln))
-            wire += buf.raw[:ln]
-        return sl, self.last_result, wire
+        _results(out, [self])
+        sl = _read_slice_table(self.lib, slices_ptr, check(n))
+        return sl, self.last_result, _read_wire(self.lib, sl)
 
     def stats(self):
         """dict of STATS; `lost`: the sticky flag; announced: the connection window the peer knows (may be negative)"""
@@ -810,7 +824,7 @@ class SendWindows:
         lost call -- the result of the failed call stays in .last_result"""
         out = (u64 * 8)()
         n = self.lib.grdma_h2_sw_intake(self.h, out)
-        self.last_result = tuple(int(x) for x in out)
+        _results(out, [self])
         check(n)
         return self.last_result
 
@@ -822,14 +836,8 @@ class SendWindows:
         prog = (u64 * max(1, n))(*progress)
         out = (u64 * 8)()
         k = self.lib.grdma_h2_sw_frame(self.h, _msg_array(msgs), prog, n, max_frame, slices_ptr, cap, hdr_ptr, hdr_cap, out)
-        self.last_result = tuple(int(x) for x in out)
-        k = check(k)
-        raw = C.create_string_buffer(max(1, 16 * k))
-        if k:
-            check(self.lib.grdma_copy_to_host(raw, slices_ptr, 16 * k))
-        sl = [(int.from_bytes(raw.raw[16 * i:16 * i + 8], "little"), int.from_bytes(raw.raw[16 * i + 8:16 * i + 16], "little"))
-              for i in range(k)]
-        return sl, self.last_result, [int(x) for x in prog[:n]]
+        _results(out, [self])
+        return _read_slice_table(self.lib, slices_ptr, check(k)), self.last_result, [int(x) for x in prog[:n]]
 
     def windows(self, ids):
         """the windows as they are: id 0 is the connection's, another id its stream's (may be negative)"""
@@ -856,14 +864,6 @@ class SendWindows:
             self.h = None
 
 
-def _read_slice_table(lib, slices_ptr, k):
-    raw = C.create_string_buffer(max(1, 16 * k))
-    if k:
-        check(lib.grdma_copy_to_host(raw, slices_ptr, 16 * k))
-    return [(int.from_bytes(raw.raw[16 * i:16 * i + 8], "little"), int.from_bytes(raw.raw[16 * i + 8:16 * i + 16], "little"))
-            for i in range(k)]
-
-
 class ControlReplies:
     """The control replies of one transport on the device (grdma_h2_ctl): SETTINGS ACK, PING ACK and RST_STREAM written
     from the parser's deframings, and the record of what the peer said.  One per parser; independent of FlowControl and
@@ -888,9 +888,8 @@ class ControlReplies:
         .last_result; after a capacity overflow (overflow word 1) the call may be repeated with larger targets"""
         out = (u64 * 8)()
         n = self.lib.grdma_h2_ctl_reply(self.h, slices_ptr, cap, hdr_ptr, hdr_cap, out)
-        self.last_result = tuple(int(x) for x in out)
-        n = check(n)
-        return _read_slice_table(self.lib, slices_ptr, n), self.last_result
+        _results(out, [self])
+        return _read_slice_table(self.lib, slices_ptr, check(n)), self.last_result
 
     def peer(self):
         """dict of PEER: what the peer said so far"""
@@ -926,17 +925,13 @@ def control_batch(items):
     for i, item in enumerate(items):
         if item is None:
             continue
-        ctl, sl, cap, hdr, hdr_cap = item
+        ctl, *target = item
         arr[i].ctl = ctl.h if ctl is not None else None
-        arr[i].d_slices_out, arr[i].slices_cap, arr[i].d_hdr_arena, arr[i].hdr_cap = sl, cap, hdr, hdr_cap
+        _set_target(arr[i], target)
     out = (u64 * (8 * max(1, n)))()
     check(lib.grdma_h2_ctl_reply_batch(arr, n, out))
-    res = []
-    for i, (ctl, sl_ptr, _, _, _) in enumerate(items):
-        r = tuple(int(x) for x in out[8 * i:8 * i + 8])
-        ctl.last_result = r
-        res.append((r, None) if r[7] else (_read_slice_table(lib, sl_ptr, r[1]), r))
-    return res
+    return [(r, None) if r[7] else (_read_slice_table(lib, item[1], r[1]), r)
+            for item, r in zip(items, _results(out, [item[0] for item in items]))]
 
 
 def account_batch(items):
@@ -948,30 +943,18 @@ def account_batch(items):
     lib = _bind()
     n = len(items)
     arr = (H2FcItem * max(1, n))()
-    for i, (fc, sl, cap, hdr, hdr_cap) in enumerate(items):
+    for i, (fc, *target) in enumerate(items):
         arr[i].fc = fc.h if fc is not None else None
-        arr[i].d_slices_out, arr[i].slices_cap, arr[i].d_hdr_arena, arr[i].hdr_cap = sl, cap, hdr, hdr_cap
+        _set_target(arr[i], target)
     out = (u64 * (8 * max(1, n)))()
     check(lib.grdma_h2_fc_account_batch(arr, n, out))
     res = []
-    for i, (fc, sl_ptr, _, _, _) in enumerate(items):
-        r = tuple(int(x) for x in out[8 * i:8 * i + 8])
-        fc.last_result = r
+    for item, r in zip(items, _results(out, [item[0] for item in items])):
         if r[7]:
             res.append((r, None))
             continue
-        k = r[1]
-        raw = C.create_string_buffer(max(1, 16 * k))
-        if k:
-            check(lib.grdma_copy_to_host(raw, sl_ptr, 16 * k))
-        sl = [(int.from_bytes(raw.raw[16 * j:16 * j + 8], "little"), int.from_bytes(raw.raw[16 * j + 8:16 * j + 16], "little"))
-              for j in range(k)]
-        wire = b""
-        for ptr, ln in sl:
-            buf = C.create_string_buffer(max(1, ln))
-            check(lib.grdma_copy_to_host(buf, ptr, ln))
-            wire += buf.raw[:ln]
-        res.append((sl, r, wire))
+        sl = _read_slice_table(lib, item[1], r[1])
+        res.append((sl, r, _read_wire(lib, sl)))
     return res
 
 
@@ -985,11 +968,7 @@ def intake_batch(sws):
     arr = (C.c_void_p * max(1, n))(*[s.h if s is not None else None for s in sws])
     out = (u64 * (8 * max(1, n)))()
     check(lib.grdma_h2_sw_intake_batch(arr, n, out))
-    res = []
-    for i, s in enumerate(sws):
-        s.last_result = tuple(int(x) for x in out[8 * i:8 * i + 8])
-        res.append(s.last_result)
-    return res
+    return _results(out, sws)
 
 
 def frame_windowed_batch(items):
@@ -1003,7 +982,7 @@ def frame_windowed_batch(items):
     n = len(items)
     arr = (H2SwFrameItem * max(1, n))()
     keep = []  # (the arrays the items point to)
-    for i, (sw, msgs, progress, max_frame, sl, cap, hdr, hdr_cap) in enumerate(items):
+    for i, (sw, msgs, progress, max_frame, *target) in enumerate(items):
         marr = _msg_array(msgs) if msgs is not None else None
         prog = (u64 * max(1, len(progress)))(*progress) if progress is not None else None
         keep.append((marr, prog))
@@ -1012,24 +991,11 @@ def frame_windowed_batch(items):
         arr[i].progress = prog
         arr[i].nmsgs = len(msgs) if msgs is not None else 0
         arr[i].max_frame = max_frame
-        arr[i].d_slices_out, arr[i].slices_cap, arr[i].d_hdr_arena, arr[i].hdr_cap = sl, cap, hdr, hdr_cap
+        _set_target(arr[i], target)
     out = (u64 * (8 * max(1, n)))()
     check(lib.grdma_h2_sw_frame_batch(arr, n, out))
-    res = []
-    for i, (sw, msgs, _, _, sl_ptr, _, _, _) in enumerate(items):
-        r = tuple(int(x) for x in out[8 * i:8 * i + 8])
-        sw.last_result = r
-        if r[7]:
-            res.append((r, None))
-            continue
-        k = r[2]
-        raw = C.create_string_buffer(max(1, 16 * k))
-        if k:
-            check(lib.grdma_copy_to_host(raw, sl_ptr, 16 * k))
-        sl = [(int.from_bytes(raw.raw[16 * j:16 * j + 8], "little"), int.from_bytes(raw.raw[16 * j + 8:16 * j + 16], "little"))
-              for j in range(k)]
-        res.append((sl, r, [int(x) for x in keep[i][1][:len(msgs)]]))
-    return res
+    return [(r, None) if r[7] else (_read_slice_table(lib, item[4], r[2]), r, [int(x) for x in prog[:len(item[1])]])
+            for item, (_, prog), r in zip(items, keep, _results(out, [item[0] for item in items]))]
 
 
 class Pipe:
