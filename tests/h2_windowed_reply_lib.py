@@ -5,10 +5,6 @@ tests/h2_windowed_reply_model.py beside them.  Every call runs on the device and
 slice list, whole slice table and header arena with the fill outside the written part, result block, windows, the
 queue's progress, the assembler's bytes in use.  pytest rewrites no `assert` in a helper module, so every check here goes
 through `same`."""
-import os
-import re
-import subprocess
-
 import pytest
 
 from oracle import pyorc
@@ -224,35 +220,3 @@ def frame_batch(hs, kw=None):
         same(sl == -5, bool(h.expected[2][7]), "item %d: -GRDMA_ERR_CAPACITY where the model overflows" % i)
         out.append(h.check(None if sl == -5 else sl, st, "batch item %d" % i))
     return out
-
-
-# ---- the kernels' resources (the two emulator files share this) ---------------------------------------------------------
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-
-STAGES = ("queue", "commit")
-FIELDS = {"ScratchSize [bytes/lane]": "scratch", "VGPRs Spill": "vspill", "SGPRs Spill": "sspill", "VGPRs": "vgprs",
-          "LDS Size [bytes/block]": "lds"}
-
-
-def wr_kernel_resources(tmp_path):
-    """-Rpass-analysis=kernel-resource-usage of csrc/grdma_h2.hip for gfx950 -> {kernel: {field: value}} of the kernels
-    whose names begin with k_h2_wr_ or k_h2_links_wr_"""
-    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "grpc-rdma_amd", "csrc", "grdma_h2.hip")
-    p = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-c", src,
-                        "-o", str(tmp_path / "h2.o"), "-Rpass-analysis=kernel-resource-usage"],
-                       capture_output=True, text=True, timeout=600)
-    same(p.returncode, 0, "hipcc: " + p.stderr[-2000:])
-    cur, seen = None, {}
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            k = re.search(r"k_h2_(?:links_)?wr_[a-z]+?(?=E)", m.group(1))
-            cur = k.group(0) if k else None
-            if cur:
-                seen[cur] = {}
-            continue
-        if cur:
-            m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|VGPRs|LDS Size \[bytes/block\]): (\d+)", line)
-            if m:
-                seen[cur][FIELDS[m.group(1)]] = int(m.group(2))
-    return seen

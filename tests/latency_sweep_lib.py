@@ -22,6 +22,7 @@ import tempfile
 import time
 
 from oracle import pyorc
+from tests.pair_lib import STATE_KEYS, mk_link
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "grpc-rdma_amd", "csrc")
@@ -402,7 +403,6 @@ def run_on_device(g, seq, fast, count_exact=True):
     """The sequence on a connection a -> b whose reads a watcher of the latency engine carries out; every drain's reads
     against the oracle's, then counters, state, rings and b's record-size history.  `fast`: GRDMA_WATCH_FAST as the
     caller has set it (read when the engine starts)."""
-    from tests.test_gpu_pair_parity import STATE_KEYS, mk_link
     lib = g.load()
     F = seq.final
     lib.grdma_watch_fast_drains.restype = C.c_uint64

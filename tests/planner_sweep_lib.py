@@ -23,7 +23,7 @@ import ctypes as C
 import random
 
 from oracle import pyorc
-from tests.test_gpu_stream_job import PASSES, _advance, _fast_counts, _run_job, _table_cache_stats, check_rx_state, rx_state_of
+from tests.stream_job_lib import PASSES, _advance, _fast_counts, _run_job, _table_cache_stats, check_rx_state, rx_state_of
 
 MINRD, RESET, LOOKBACK, PMAX, PER, CHUNK = 256, 512, 192, 512, 4, 256
 NONE = None   # (a witness that is absent: no such record in the drain)

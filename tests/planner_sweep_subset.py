@@ -3,7 +3,7 @@ case (planner_sweep_lib.emu_subset).  Not collected by name: the hardware suite 
 tests/test_zz_gpu_planner_sweep.py and needs none of them twice."""
 import pytest
 
-import planner_sweep_lib as L
+from tests import planner_sweep_lib as L
 
 pytestmark = pytest.mark.gpu
 

@@ -31,6 +31,7 @@ import time
 import zlib
 
 from oracle import pyorc
+from tests.pair_lib import _mask_pads, _ring_eq, check_state, mk_link
 
 RESERVED = 24           # ring_buffer.h:52
 THREADS = 256           # PLAN_THREADS
@@ -419,7 +420,6 @@ WRITE_DEADLINE = 30.0   # seconds one burst may take before the test fails
 
 def run_on_device(g, script, wire, tag=""):
     """The finished script on a connected pair a -> b: after every step what the oracle showed after the same step."""
-    from tests.test_gpu_pair_parity import _mask_pads, _ring_eq, check_state, mk_link
     lib = g.load()
     _declare(lib)
     flags = WIRES[wire]

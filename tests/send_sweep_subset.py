@@ -3,7 +3,7 @@ case (send_sweep_lib.emu_subset).  Not collected by name: the hardware suite run
 tests/test_zz_gpu_send_sweep.py and needs none of them twice."""
 import pytest
 
-import send_sweep_lib as L
+from tests import send_sweep_lib as L
 
 pytestmark = pytest.mark.gpu
 

@@ -17,7 +17,7 @@ import random
 import pytest
 
 from oracle import pyorc
-from h2_helpers import PREFACE, frame, messages_of
+from tests.h2_helpers import PREFACE, frame, messages_of
 
 MAX_SIZE = (4 << 20) - 1024
 

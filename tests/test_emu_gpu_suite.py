@@ -13,41 +13,12 @@ tests/test_gpu_stream_job.py -m gpu -k r256k.
 This checks kernel LOGIC when no GPU is at hand; the GPU runs stay the reference."""
 import os
 import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
-EMU_SO = os.path.join(ROOT, "oracle", "_build", "libgrdma_emu.so")
+from tests.emu_harness import CLANG, ROOT, emu_lib, run_gpu_tests  # noqa: F401  (emu_lib is a fixture)
 
 pytestmark = pytest.mark.skipif(not os.path.exists(CLANG), reason="needs the ROCm clang++ as host compiler")
-
-
-@pytest.fixture(scope="module")
-def emu_lib(built):
-    srcs = []
-    for d in (os.path.join(ROOT, "grpc-rdma_amd", "csrc"), os.path.join(ROOT, "tests", "cc"), os.path.join(ROOT, "include")):
-        srcs += [os.path.join(d, f) for f in os.listdir(d) if f.endswith((".hip", ".cc", ".h", ".hpp", ".sh", ".inc"))]
-    if not os.path.exists(EMU_SO) or any(os.path.getmtime(s) > os.path.getmtime(EMU_SO) for s in srcs):
-        subprocess.check_call(["bash", os.path.join(ROOT, "tests", "cc", "build_emu.sh")], stdout=subprocess.DEVNULL,
-                              stderr=subprocess.DEVNULL)
-    return EMU_SO
-
-
-def run_gpu_tests(emu_lib, args, min_passed):
-    env = dict(os.environ, GRDMA_LIB_PATH=emu_lib, GRDMA_TEST_NEW="1", GRDMA_TEST_ALLOW_EMU="1")
-    cmd = [sys.executable, "-m", "pytest", "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider", "--timeout", "600"] + args
-    last = ""
-    for attempt in range(2):  # (the staging waves of the deframer are real threads: one retry on a scheduling hiccup)
-        p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
-        last = (p.stdout + p.stderr)[-3000:]
-        if p.returncode == 0:
-            tail = p.stdout.strip().splitlines()[-1]
-            n = int(tail.split(" passed")[0].split()[-1])
-            assert n >= min_passed, tail
-            return
-    raise AssertionError(last)
 
 
 def test_deframer_gpu_tests_under_the_emulator(emu_lib):

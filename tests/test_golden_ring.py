@@ -3,54 +3,15 @@
 recorded value.  Unlike test_oracle_vs_ref.py this needs neither /root/reference
 nor oracle/_ref: the vectors are committed."""
 import glob
-import hashlib
 import json
 import os
-import random
 
 import pytest
 
 from oracle import pyorc
+from tests.pair_lib import payload, replay, sha
 
 GOLDEN = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "ring_*.json")))
-
-
-def payload(seed, n):
-    rng = random.Random(seed)
-    return bytes(rng.getrandbits(8) for _ in range(n))
-
-
-def sha(b):
-    return hashlib.sha256(b).hexdigest()
-
-
-def replay(doc, link, ring_exact=True, mask=None):
-    for i, st in enumerate(doc["steps"]):
-        if st["op"] == "send":
-            sl = [payload(s, n) for s, n in st["slices"]]
-            assert link.send(0, sl, st.get("byte_idx", 0)) == st["sent"], (doc["name"], i)
-            assert [list(w) for w in link.last_wrs(0)] == st["wrs"]
-            if ring_exact:
-                assert sha(link.staging_mem(0)) == st["staging_sha256"]
-        elif st["op"] == "recv":
-            got = link.recv(1, st["cap"])
-            assert len(got) == st["got_len"] and sha(got) == st["got_sha256"]
-        else:
-            got, alloc = link.endpoint_read(1)
-            assert len(got) == st["got_len"] and sha(got) == st["got_sha256"]
-            assert alloc == st["alloc"]
-        if ring_exact:
-            assert sha(link.ring_mem(1)) == st["ring_sha256"], (doc["name"], i)
-        elif "ring_hex" in st:
-            assert mask(link.ring_mem(1), bytes.fromhex(st["ring_hex"])), (doc["name"], i)
-        rx, tx = link.state(1), link.state(0)
-        for k, v in st["rx_state"].items():
-            assert rx[k] == v, (doc["name"], i, "rx", k)
-        for k, v in st["tx_state"].items():
-            assert tx[k] == v, (doc["name"], i, "tx", k)
-        assert link.readable(1) == st["readable"]
-        assert link.has_message(1) == st["has_message"]
-        assert link.writable(0) == st["writable"]
 
 
 @pytest.mark.parametrize("path", GOLDEN, ids=[os.path.basename(p) for p in GOLDEN])

@@ -11,25 +11,11 @@ import random
 import pytest
 
 from oracle import pyorc
+from tests.stream_job_lib import framed
 
 pytestmark = pytest.mark.gpu
 
 PASSES = 3
-
-
-def framed(n_msgs, msg_len, seed, max_frame=16384):
-    """-> (wire bytes, slice lengths) of n_msgs framed messages as chttp2 hands them to the endpoint;
-    message i is a rotation of one random block, so every message differs."""
-    rng = random.Random(seed)
-    block = bytes(rng.getrandbits(8) for _ in range(4099))
-    wire, lens = bytearray(), []
-    for i in range(n_msgs):
-        rot = (i * 131) % len(block)
-        body = (block[rot:] + block[:rot]) * (msg_len // len(block) + 1)
-        w, l = pyorc.h2_frame_message(body[:msg_len], stream_id=2 * i + 1, max_frame=max_frame)
-        wire += w
-        lens += l
-    return bytes(wire), lens
 
 
 def mixed(n_msgs, seed, lo=1, hi=(4 << 20) - 1024):

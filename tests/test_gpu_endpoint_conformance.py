@@ -6,18 +6,9 @@ import subprocess
 
 import pytest
 
+from tests.endpoint_conformance_lib import ROOT, run
+
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HARNESS = os.path.join(ROOT, "tests", "cc", "endpoint_conformance")
-
-
-def run(*args, env=None):
-    e = dict(os.environ)
-    e.update(env or {})
-    p = subprocess.run([HARNESS] + [str(a) for a in args], capture_output=True, text=True, timeout=900, env=e)
-    assert p.returncode == 0, p.stdout + p.stderr
-    return p.stdout
 
 
 def test_multiple_shutdown_and_half_close(gpu):

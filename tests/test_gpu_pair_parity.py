@@ -11,29 +11,12 @@ import random
 import pytest
 
 from oracle import pyorc
+from tests.pair_lib import STATE_KEYS, _mask_pads, _ring_eq, check_state, mk_link, replay
 
 pytestmark = pytest.mark.gpu
 
-STATE_KEYS = ["head", "moving_head", "remain", "remote_tail", "remote_head",
-              "internal_read_size", "credit_msgs", "partial_write"]
-
-
-def mk_link(g, R, sge, flags=0):
-    a, b = g.Pair(R, sge, flags), g.Pair(R, sge, flags)
-    g.connect_pairs(a, b)
-    return a, b
-
-
 def dev_slices(g, slices, rng):
     return [g.DeviceBuffer(data=s, offset=rng.randrange(16)) for s in slices]
-
-
-def check_state(a, b, o):
-    sa, sb = a.state(), b.state()
-    oa, ob = o.state(0), o.state(1)
-    for k in STATE_KEYS:
-        assert sa[k] == oa[k], ("side0", k, sa, oa)
-        assert sb[k] == ob[k], ("side1", k, sb, ob)
 
 
 @pytest.mark.parametrize("flags", [0, 2, 4, 6], ids=["staged", "direct", "staged-finegrained", "direct-finegrained"])
@@ -78,46 +61,6 @@ def test_random_ops_match_oracle(gpu, seed, flags):
         assert b.HasMessage() == o.has_message(1)
         assert a.GetWritableSize() == o.writable(0)
     a.close(); b.close(); o.close()
-
-
-def _records(buf):
-    """Yield (offset, payload_len) of back-to-back records in a staging image."""
-    off = 0
-    while off + 16 <= len(buf):
-        n = int.from_bytes(buf[off:off + 8], "little")
-        if n == 0:
-            break
-        yield off, n
-        off += 16 + ((n + 7) & ~7)
-
-
-def _mask_pads(buf):
-    out = bytearray(buf)
-    for off, n in _records(buf):
-        for q in range(off + 8 + n, off + 8 + ((n + 7) & ~7)):
-            out[q] = 0
-    return bytes(out)
-
-
-def _ring_eq(x, y):
-    # Oracle staging starts zeroed and both sides see the same send history, but
-    # the oracle's pad bytes can hold stale bytes of an earlier, longer record.
-    # Compare everything except pad bytes, which are located from the record tags
-    # still in the ring (both images must agree on every tag word).
-    if x == y:
-        return True
-    R = len(x)
-    diff = [i for i in range(R) if x[i] != y[i]]
-    # every differing byte must be a pad byte: the HIP side holds 0 there
-    for i in diff:
-        if x[i] != 0:
-            return False
-        w = i & ~7
-        # pad bytes live in the last payload word of a record: the next word is the footer
-        nxt = (w + 8) % R
-        if x[nxt:nxt + 8] != b"\xff" * 8 or y[nxt:nxt + 8] != b"\xff" * 8:
-            return False
-    return True
 
 
 def test_streaming_one_mib_messages(gpu):
@@ -319,7 +262,6 @@ def test_golden_reference_traces_on_gpu(gpu):
     vector carries it (pad bytes excepted: the reference leaves stale staging bytes
     there, the HIP encoder writes zeros)."""
     import glob, json, os
-    from tests.test_golden_ring import replay
     for path in sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "ring_*.json"))):
         doc = json.load(open(path))
         link = _GpuLinkAdapter(gpu, doc["ring_size"], doc["max_sge"])

@@ -1,18 +1,13 @@
 """CPU suite for send flow control on many links (k_h2_links_sw_*, grdma_h2_sw_intake_batch, grdma_h2_sw_frame_batch):
 its GPU tests under the wave emulator and the kernels' resources for gfx950."""
 import os
-import re
-import subprocess
 
 import pytest
 
-from tests.test_emu_gpu_suite import CLANG, ROOT, emu_lib, run_gpu_tests  # noqa: F401  (emu_lib is a fixture)
-
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from tests.emu_harness import CLANG, emu_lib, run_gpu_tests  # noqa: F401  (emu_lib is a fixture)
+from tests.kernel_resources import kernels_of, needs_hipcc
 
 STAGES = ("clear", "take", "finish", "plan", "emit")
-FIELDS = {"ScratchSize [bytes/lane]": "scratch", "VGPRs Spill": "vspill", "SGPRs Spill": "sspill", "VGPRs": "vgprs",
-          "LDS Size [bytes/block]": "lds"}
 
 
 @pytest.mark.skipif(not os.path.exists(CLANG), reason="needs the ROCm clang++ as host compiler")
@@ -23,33 +18,15 @@ def test_links_send_window_gpu_tests_under_the_emulator(emu_lib):  # noqa: F811
     run_gpu_tests(emu_lib, ["tests/test_zz_gpu_h2_links_send_window.py", "-n", "4"], 10)
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_link_send_window_kernels_resources(tmp_path):
+@needs_hipcc
+def test_link_send_window_kernels_resources():
     """The five many-link kernels exist beside their single-transport twins, none uses scratch or spills, and clear,
     take, finish and plan take no more VGPRs or LDS than the kernel they share their source text with, in the same
     compile.  (k_h2_links_sw_emit carries the links' prefix in LDS and a search over it: its counts stand in
     docs/h2_deframer.md beside k_h2_sw_emit's and are not bounded by them.)"""
-    src = os.path.join(ROOT, "grpc-rdma_amd", "csrc", "grdma_h2.hip")
-    p = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-c", src,
-                        "-o", str(tmp_path / "h2.o"), "-Rpass-analysis=kernel-resource-usage"],
-                       capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    cur, seen = None, {}
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            k = re.search(r"k_h2_(?:links_)?sw_[a-z]+?(?=E)", m.group(1))
-            cur = k.group(0) if k else None
-            if cur:
-                seen[cur] = {}
-            continue
-        if cur:
-            m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|VGPRs|LDS Size \[bytes/block\]): (\d+)", line)
-            if m:
-                seen[cur][FIELDS[m.group(1)]] = int(m.group(2))
+    seen = kernels_of("grdma_h2.hip", "k_h2_sw_", "k_h2_links_sw_")
     assert set(seen) == {"k_h2_sw_" + s for s in STAGES} | {"k_h2_links_sw_" + s for s in STAGES}, sorted(seen)
     for k, v in seen.items():
-        assert set(v) == set(FIELDS.values()), (k, v)
         assert (v["scratch"], v["vspill"], v["sspill"]) == (0, 0, 0), (k, v)
     for s in STAGES[:4]:
         one, many = seen["k_h2_sw_" + s], seen["k_h2_links_sw_" + s]

@@ -5,8 +5,10 @@ import os
 
 import pytest
 
-from tests.h2_windowed_reply_lib import HIPCC, STAGES, wr_kernel_resources
-from tests.test_emu_gpu_suite import CLANG, emu_lib, run_gpu_tests  # noqa: F401  (emu_lib is a fixture)
+from tests.emu_harness import CLANG, emu_lib, run_gpu_tests  # noqa: F401  (emu_lib is a fixture)
+from tests.kernel_resources import kernels_of, needs_hipcc
+
+STAGES = ("queue", "commit")
 
 
 @pytest.mark.skipif(not os.path.exists(CLANG), reason="needs the ROCm clang++ as host compiler")
@@ -16,11 +18,11 @@ def test_links_windowed_reply_gpu_tests_under_the_emulator(emu_lib):  # noqa: F8
     run_gpu_tests(emu_lib, ["tests/test_zz_gpu_h2_links_windowed_reply.py", "-n", "4"], 5)
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_link_windowed_reply_kernels_resources(tmp_path):
+@needs_hipcc
+def test_link_windowed_reply_kernels_resources():
     """Both many-link kernels exist beside their twins and take no more VGPRs or LDS than the kernel they share their
     source text with, in the same compile."""
-    seen = wr_kernel_resources(tmp_path)
+    seen = kernels_of("grdma_h2.hip", "k_h2_wr_", "k_h2_links_wr_")
     for s in STAGES:
         one, many = seen["k_h2_wr_" + s], seen["k_h2_links_wr_" + s]
         assert (many["scratch"], many["vspill"], many["sspill"]) == (0, 0, 0), (s, many)

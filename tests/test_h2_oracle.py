@@ -157,7 +157,7 @@ def test_oversized_frame_and_bad_prefix_are_connection_errors():
 # The stream map the DATA path reads (parsing.cc init_data_frame_parser / init_header_frame_parser,
 # chttp2_transport.cc grpc_chttp2_mark_stream_closed): lookup only, streams accepted from HEADERS on a
 # server, read-closed by END_STREAM, removed once both sides are closed.
-from h2_helpers import PREFACE, frame, grpc_msg, grpcio_capture, messages_of, unary_call  # noqa: E402
+from tests.h2_helpers import PREFACE, frame, grpc_msg, grpcio_capture, messages_of, unary_call  # noqa: E402
 
 
 def test_two_hundred_sequential_unary_streams_and_forty_interleaved():

@@ -1,14 +1,11 @@
 """CPU suite for send flow control on the device (the peer's windows and the framer under them: k_h2_sw_*,
 grdma_h2_sw_*): its GPU tests under the wave emulator and the kernels' resources for gfx950."""
 import os
-import re
-import subprocess
 
 import pytest
 
-from tests.test_emu_gpu_suite import CLANG, ROOT, emu_lib, run_gpu_tests  # noqa: F401  (emu_lib is a fixture)
-
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from tests.emu_harness import CLANG, emu_lib, run_gpu_tests  # noqa: F401  (emu_lib is a fixture)
+from tests.kernel_resources import kernels_of, needs_hipcc
 
 KERNELS = ("k_h2_sw_clear", "k_h2_sw_take", "k_h2_sw_finish", "k_h2_sw_plan", "k_h2_sw_emit")
 
@@ -21,27 +18,10 @@ def test_send_window_gpu_tests_under_the_emulator(emu_lib):  # noqa: F811
     run_gpu_tests(emu_lib, ["tests/test_zz_gpu_h2_send_window.py", "-n", "4"], 70)
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_send_window_kernels_resources(tmp_path):
+@needs_hipcc
+def test_send_window_kernels_resources():
     """The five kernels exist and use no scratch and spill nothing."""
-    src = os.path.join(ROOT, "grpc-rdma_amd", "csrc", "grdma_h2.hip")
-    p = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-c", src,
-                        "-o", str(tmp_path / "h2.o"), "-Rpass-analysis=kernel-resource-usage"],
-                       capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    cur, seen = None, {}
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            k = re.search(r"k_h2_sw_[a-z_]+?(?=E)", m.group(1))
-            cur = k.group(0) if k else None
-            if cur:
-                seen[cur] = {}
-            continue
-        if cur:
-            m = re.search(r"(ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill): (\d+)", line)
-            if m:
-                seen[cur][m.group(1)] = int(m.group(2))
+    seen = kernels_of("grdma_h2.hip", "k_h2_sw_")
     assert set(seen) == set(KERNELS), sorted(seen)
     for k, v in seen.items():
-        assert v == {"ScratchSize [bytes/lane]": 0, "VGPRs Spill": 0, "SGPRs Spill": 0}, (k, v)
+        assert (v["scratch"], v["vspill"], v["sspill"]) == (0, 0, 0), (k, v)

@@ -6,7 +6,7 @@ import os
 
 import pytest
 
-from tests.test_emu_gpu_suite import CLANG, emu_lib, run_gpu_tests  # noqa: F401  (emu_lib is a fixture)
+from tests.emu_harness import CLANG, emu_lib, run_gpu_tests  # noqa: F401  (emu_lib is a fixture)
 
 
 @pytest.mark.skipif(not os.path.exists(CLANG), reason="needs the ROCm clang++ as host compiler")

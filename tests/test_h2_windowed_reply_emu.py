@@ -4,8 +4,10 @@ import os
 
 import pytest
 
-from tests.h2_windowed_reply_lib import FIELDS, HIPCC, STAGES, wr_kernel_resources
-from tests.test_emu_gpu_suite import CLANG, emu_lib, run_gpu_tests  # noqa: F401  (emu_lib is a fixture)
+from tests.emu_harness import CLANG, emu_lib, run_gpu_tests  # noqa: F401  (emu_lib is a fixture)
+from tests.kernel_resources import kernels_of, needs_hipcc
+
+STAGES = ("queue", "commit")
 
 
 @pytest.mark.skipif(not os.path.exists(CLANG), reason="needs the ROCm clang++ as host compiler")
@@ -17,11 +19,10 @@ def test_windowed_reply_gpu_tests_under_the_emulator(emu_lib):  # noqa: F811
     run_gpu_tests(emu_lib, ["tests/test_zz_gpu_h2_windowed_reply.py", "-n", "4"], 20)
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_windowed_reply_kernels_resources(tmp_path):
+@needs_hipcc
+def test_windowed_reply_kernels_resources():
     """Exactly the four new kernels exist under the new prefixes, and none uses scratch or spills."""
-    seen = wr_kernel_resources(tmp_path)
+    seen = kernels_of("grdma_h2.hip", "k_h2_wr_", "k_h2_links_wr_")
     assert set(seen) == {"k_h2_wr_" + s for s in STAGES} | {"k_h2_links_wr_" + s for s in STAGES}, sorted(seen)
     for k, v in seen.items():
-        assert set(v) == set(FIELDS.values()), (k, v)
         assert (v["scratch"], v["vspill"], v["sspill"]) == (0, 0, 0), (k, v)

@@ -13,8 +13,8 @@ import os
 
 import pytest
 
-import job_schedule_trace as T
-from tests.test_emu_gpu_suite import CLANG, emu_lib  # noqa: F401  (emu_lib is a fixture)
+from tests import job_schedule_trace as T
+from tests.emu_harness import CLANG, emu_lib  # noqa: F401  (emu_lib is a fixture)
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "job_schedules.json")
 

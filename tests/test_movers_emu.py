@@ -18,7 +18,7 @@ import subprocess
 
 import pytest
 
-import mover_sweep_lib as M
+from tests import mover_sweep_lib as M
 
 pytestmark = pytest.mark.skipif(not os.path.exists(M.CLANG), reason="needs the ROCm clang++ as host compiler")
 

@@ -10,8 +10,8 @@ import os
 
 import pytest
 
-import planner_sweep_lib as L
-from tests.test_emu_gpu_suite import CLANG, emu_lib, run_gpu_tests  # noqa: F401  (emu_lib is a fixture)
+from tests import planner_sweep_lib as L
+from tests.emu_harness import CLANG, emu_lib, run_gpu_tests  # noqa: F401  (emu_lib is a fixture)
 
 
 def test_every_case_of_the_sweep_shows_its_witnesses():

@@ -9,8 +9,8 @@ import os
 
 import pytest
 
-import send_sweep_lib as L
-from tests.test_emu_gpu_suite import CLANG, emu_lib, run_gpu_tests  # noqa: F401  (emu_lib is a fixture)
+from tests import send_sweep_lib as L
+from tests.emu_harness import CLANG, emu_lib, run_gpu_tests  # noqa: F401  (emu_lib is a fixture)
 
 PER_FAMILY = {"A": 33, "B": 461, "C": 8, "D": 28, "E": 30, "F": 5, "G": 20, "H": 1, "I": 6, "J": 24}
 

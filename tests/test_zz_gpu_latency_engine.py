@@ -5,7 +5,7 @@ runs in a thread of its own: tests/test_emu_gpu_suite.py; the file sorts last.)"
 import pytest
 
 from oracle import pyorc
-from tests.test_gpu_pair_parity import STATE_KEYS, mk_link
+from tests.pair_lib import STATE_KEYS, mk_link
 
 pytestmark = pytest.mark.gpu
 

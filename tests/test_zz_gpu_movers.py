@@ -11,7 +11,7 @@ compared whole, byte for byte, so a byte written outside [dst, dst + n) or clear
 No tolerance.  The case lists and the reference live in tests/mover_sweep_lib.py."""
 import pytest
 
-import mover_sweep_lib as M
+from tests import mover_sweep_lib as M
 
 pytestmark = pytest.mark.gpu
 

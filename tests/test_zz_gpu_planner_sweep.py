@@ -8,7 +8,7 @@ Every case's witnesses are checked from the oracle alone when this module is imp
 edge it is there for fails the collection, on any machine, before anything runs on a device."""
 import pytest
 
-import planner_sweep_lib as L
+from tests import planner_sweep_lib as L
 
 pytestmark = pytest.mark.gpu
 

@@ -2,7 +2,7 @@
 conformance harness with GRDMA_PROFILE=1).  Host-side statistics are covered by tests/test_stats_time.py."""
 import pytest
 
-from tests.test_gpu_endpoint_conformance import run
+from tests.endpoint_conformance_lib import run
 
 pytestmark = pytest.mark.gpu
 

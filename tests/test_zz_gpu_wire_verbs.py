@@ -27,7 +27,7 @@ import numpy as np
 import pytest
 
 from oracle import pyorc
-from tests.test_gpu_pair_parity import _ring_eq   # (equal up to the pad bytes: the reference leaves stale staging bytes there)
+from tests.pair_lib import _ring_eq   # (equal up to the pad bytes: the reference leaves stale staging bytes there)
 
 pytestmark = pytest.mark.gpu
 

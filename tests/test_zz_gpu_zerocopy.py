@@ -13,7 +13,7 @@ import random
 import pytest
 
 from oracle import pyorc
-from tests.test_gpu_pair_parity import _ring_eq, check_state, mk_link
+from tests.pair_lib import _ring_eq, check_state, mk_link, payload
 
 pytestmark = pytest.mark.gpu
 
@@ -179,7 +179,6 @@ def test_zero_copy_golden_traces_on_gpu(gpu):
     device writes zeros there)."""
     import glob
     import json
-    from tests.test_golden_ring import payload
     g = gpu
     here = os.path.dirname(os.path.abspath(__file__))
     for path in sorted(glob.glob(os.path.join(here, "golden", "zc_*.json"))):

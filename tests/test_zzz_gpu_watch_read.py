@@ -15,7 +15,7 @@ import time
 import pytest
 
 from oracle import pyorc
-from tests.test_gpu_pair_parity import STATE_KEYS, mk_link
+from tests.pair_lib import STATE_KEYS, mk_link
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(300, method="thread")]
 

@@ -5,7 +5,7 @@ ROOT=os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.inser
 import grpc_rdma_amd as g
 from grpc_rdma_amd import stream as gs
 from oracle import pyorc
-import test_gpu_stream_job as T
+from tests import stream_job_lib as T
 g.init(0)
 R, max_sge, sends, n_msgs, msg_len = 1 << 20, 64, 2, 12, 200000
 rng = random.Random(R % 73 + sends)
