@@ -241,3 +241,84 @@ class SendModel:
         self.stats["bytes_sent"] += sum(g)
         return (lens, bytes(wire), (done, len(msgs) - done, len(lens), hdr, len(wire), sum(g), stall, 0),
                 [p + x for p, x in zip(progress, g)])
+
+
+# ---- where a call's grant lies: what the witnesses of the send-plan sweep read (tests/h2_send_plan_sweep_lib.py) -----------
+TILE, BLOCK = 64, 512  # a wave's tile of the plan, the plan's workgroup (H2SW_PLAN_THREADS)
+
+
+def plan_facts(model, msgs, progress, max_frame, live):
+    """what model.frame would decide, without moving anything: per message the remaining bytes, the stream-allowed bytes
+    a and the grant g, and the granted pieces [(message index, p, g)] in table order"""
+    rem = [5 + len(b) - p for (b, _, _), p in zip(msgs, progress)]
+    streams = [s for _, s, _ in msgs]
+    windows = {s: (model.window(s) if s in live else None) for s in streams}
+    a, g = grant_prefix(rem, streams, windows, model.conn)
+    return dict(n=len(msgs), msgs=msgs, p=list(progress), rem=rem, streams=streams, windows=windows, conn=model.conn,
+                mf=min(max_frame, model.pmf), a=a, g=g, pieces=[(i, progress[i], x) for i, x in enumerate(g) if x])
+
+
+def known(f, i):
+    return f["windows"][f["streams"][i]] is not None
+
+
+def tile_lists(f):
+    """per tile of 64 messages the streams the map holds, in the order of their last message in the tile: the order of
+    the plan's per-tile lists"""
+    out = []
+    for t0 in range(0, f["n"], TILE):
+        last = {}
+        for i in range(t0, min(t0 + TILE, f["n"])):
+            if known(f, i):
+                last[f["streams"][i]] = i
+        out.append(sorted(last, key=last.get))
+    return out
+
+
+def stream_end(f, s):
+    """-> (i, cut): the window of stream s ends in message i at byte cut of [header | body] (cut == 5 + len: exactly at
+    its end, so the stream's next message gets nothing); None where the call's messages do not reach the window's end"""
+    left = f["windows"][s]
+    for i in range(f["n"]):
+        if f["streams"][i] == s:
+            if left <= f["rem"][i]:
+                return i, f["p"][i] + max(left, 0)
+            left -= f["rem"][i]
+    return None
+
+
+def conn_end(f):
+    """the same for the connection's window over the stream-allowed bytes"""
+    left = f["conn"]
+    for i in range(f["n"]):
+        if f["a"][i] and left <= f["a"][i]:
+            return i, f["p"][i] + max(left, 0)
+        left -= f["a"][i]
+    return None
+
+
+def tail_inlined(piece):
+    return piece[1] + piece[2] <= 5
+
+
+def run_before(f, k):
+    """how many header-only pieces stand directly in front of piece k"""
+    j = k
+    while j > 0 and tail_inlined(f["pieces"][j - 1]):
+        j -= 1
+    return k - j
+
+
+def back_fill(f, k):
+    """the bytes in the outbuf's back slice when piece k begins, 0 where that slice is no inlined one: the run in front
+    of the piece through sb_add"""
+    sb = []
+    for i, p, g in f["pieces"][k - run_before(f, k):k]:
+        body, s, fl = f["msgs"][i]
+        frame_piece(sb, bytearray(), body, s, fl, f["mf"], p, g)
+    return sb[-1][0] if sb and sb[-1][1] else 0
+
+
+def frames_of(f, k):
+    """DATA frames of piece k"""
+    return -(-f["pieces"][k][2] // f["mf"])
