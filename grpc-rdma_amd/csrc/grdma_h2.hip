@@ -35,6 +35,7 @@
 #include "grdma_h2_sw.h"
 #include "grdma_h2_wr.h"
 #include "grdma_h2_ctl.h"
+#include "grdma_h2_hpack.h"
 #include "grdma_h2_block.h"
 
 // --------------------------------------------------------------------- host API
@@ -73,6 +74,8 @@ struct grdma_h2_parser {
   uint64_t standalone_nsl = 0;
   // control replies (csrc/grdma_h2_ctl.h): the parser's control-reply writer; it reads what the send windows read
   struct grdma_h2_ctl* ctl = nullptr;
+  // header blocks (csrc/grdma_h2_hpack.h): the parser's header decoder; it reads what the control-reply writer reads
+  struct grdma_h2_hpack* hpack = nullptr;
 };
 
 // How many chunks a parser created without saying so cuts a long list into: GRDMA_H2_CHUNKS (default and at most 256, 0 or 1 = the
@@ -298,6 +301,18 @@ static h2_stage h2_stage_ctl_links(const h2ctl_link* d_tab, uint32_t n) {
           h2_rec(k_h2_links_ctl_scan, n, H2CTL_THREADS, d_tab),
           h2_rec(k_h2_links_ctl_emit, n * H2CTL_LINK_GRID, H2CTL_THREADS, d_tab, n)};
 }
+
+// The header decoder behind a deframing (csrc/grdma_h2_hpack.h): the gather, whose totals the host sizes the scratch of the
+// other stages by, and those stages.
+static h2_stage h2_stage_hpack_gather(h2hp_dev* d, const h2hp_call* d_call) {
+  return {h2_rec(k_h2_hpack_gather, 1, H2HP_THREADS, d, d_call)};
+}
+static h2_stage h2_stage_hpack_decode(h2hp_dev* d, const h2hp_call* d_call) {
+  return {h2_rec(k_h2_hpack_copy, H2HP_GRID, H2HP_THREADS, d, d_call), h2_rec(k_h2_hpack_split, H2HP_GRID, H2HP_THREADS, d, d_call),
+          h2_rec(k_h2_hpack_walk, 1, H2HP_THREADS, d, d_call), h2_rec(k_h2_hpack_emit, H2HP_GRID, H2HP_THREADS, d, d_call),
+          h2_rec(k_h2_hpack_commit, H2HP_GRID, H2HP_THREADS, d, d_call)};
+}
+static h2_stage h2_stage_hpack_resize(h2hp_dev* d) { return {h2_rec(k_h2_hpack_resize, 1, 64, d)}; }
 
 // st goes behind the parser's last deframing by a pipe (the parser state is handed from one deframing to the next),
 // unless that one was enqueued on st itself.  (Only pipe steps leave last_deframed, on a job's or a deframe stream: for

@@ -132,6 +132,7 @@ struct h2_deframed {
   operator h2fc_call() const { return {ev, res, ev_cap}; }
   operator h2sw_call() const { return {ev, res, sl, arena, ev_cap, nsl, skipped}; }
   operator h2ctl_call() const { return {ev, res, sl, arena, ev_cap, nsl, skipped}; }
+  operator h2hp_call() const { return {ev, res, sl, arena, ev_cap, nsl, skipped}; }
 };
 static h2_deframed h2_follow_deframed(const h2_follow& f) {
   const grdma_h2_parser* p = f.parser;
@@ -1486,8 +1487,25 @@ struct grdma_h2_ctl : h2_follow {  // (taken: the last call taken in; at creatio
   h2ctl_call* d_call = nullptr;
 };
 
+struct grdma_h2_hpack : h2_follow {  // (csrc/grdma_h2_hpack.h; its calls stand behind the control replies')
+  h2hp_dev* d = nullptr;
+  h2hp_call* d_call = nullptr;
+  uint8_t* d_carry = nullptr;
+  // a call's scratch, grown between the call's two steps
+  uint8_t* d_stage = nullptr;
+  uint64_t stage_cap = 0;
+  h2hp_rec* d_recs = nullptr;
+  uint64_t recs_cap = 0;
+  h2hp_rec* d_outs = nullptr;
+  uint64_t outs_cap = 0;
+  h2hp_item* d_items = nullptr;
+  uint64_t items_cap = 0;
+  h2hp_blk* d_blks = nullptr;
+  uint64_t blks_cap = 0;
+};
+
 static void h2_followers_parser_gone(grdma_h2_parser* p) {
-  h2_follow* const followers[3] = {p->fc, p->sw, p->ctl};
+  h2_follow* const followers[4] = {p->fc, p->sw, p->ctl, p->hpack};
   for (h2_follow* f : followers)
     if (f) h2_follow_parser_gone(f);
 }
@@ -1615,6 +1633,173 @@ int grdma_h2_ctl_reply_batch(const grdma_h2_ctl_item* items, uint32_t n_items, u
   int ok = 0;
   for (uint32_t i = 0; i < n_items; i++) ok += h2_ctl_ran(items[i].ctl, b.c.ms[0], out + 8 * (size_t)i);  // (the time: the batch's, repeated)
   return ok;
+}
+
+// ---- header blocks: HPACK on the device (csrc/grdma_h2_hpack.h) ----------------------------------------------------------
+// The decoder follows the parser's standalone deframings as the control-reply writer does.  A call has two steps on the
+// stream of the calls: the gather, whose totals come down, and -- the staging buffer and the record tables sized by
+// them -- the other stages.
+struct h2hp_target { h2hp_block_out* blocks; uint64_t blocks_cap; h2hp_field_out* fields; uint64_t fields_cap; uint8_t* strings; uint64_t strings_cap; };
+struct h2hp_scratch { uint8_t* stage; uint64_t stage_cap; h2hp_rec* recs; uint64_t recs_cap; h2hp_rec* outs; uint64_t outs_cap;
+                      h2hp_item* items; h2hp_blk* blks; uint64_t items_cap; };
+struct h2hp_config { uint8_t* carry_buf; uint64_t max_block; uint32_t setting, pad0; };
+static_assert(offsetof(h2hp_dev, blocks) == 0 && offsetof(h2hp_dev, stage) == sizeof(h2hp_target) &&
+              offsetof(h2hp_dev, carry_buf) == sizeof(h2hp_target) + sizeof(h2hp_scratch) &&
+              offsetof(h2hp_dev, carry) == offsetof(h2hp_dev, carry_buf) + sizeof(h2hp_config),
+              "a call's target, its scratch and the configuration lead the block");
+static_assert(sizeof(h2hp_block_out) == sizeof(grdma_h2_header_block) && sizeof(h2hp_field_out) == sizeof(grdma_h2_header_field), "layout");
+static_assert(H2HP_F_FAILED == GRDMA_H2_HPACK_FAILED && H2HP_F_LOST == GRDMA_H2_HPACK_LOST && H2HP_F_OPEN == GRDMA_H2_HPACK_OPEN, "flags");
+static_assert(H2HP_E_PADDING == GRDMA_H2_HPACK_ERR_PADDING && H2HP_E_DEFRAMER == GRDMA_H2_HPACK_ERR_DEFRAMER, "error codes");
+static_assert(sizeof(h2hp_huff_table) == sizeof(((h2hp_dev*)0)->huff) && sizeof(h2hp_static_off) == sizeof(((h2hp_dev*)0)->st_off) &&
+              sizeof(h2hp_static_bytes) == sizeof(((h2hp_dev*)0)->st_bytes), "the tables as they are uploaded");
+
+grdma_h2_hpack* grdma_h2_hpack_create(grdma_h2_parser* parser, uint32_t max_table_size, uint32_t max_block_bytes) {
+  if (grdma_device_count() <= 0) return nullptr;
+  if (!parser) return h2_no("h2 header decoder: no parser");
+  if (parser->hpack) return h2_no("h2 header decoder: the parser has a header decoder already");
+  if (max_table_size > H2HP_MAX_TABLE) return h2_no("h2 header decoder: max_table_size above 65536");
+  if (max_block_bytes < 64 || max_block_bytes > (1u << 20)) return h2_no("h2 header decoder: max_block_bytes outside 64 .. 2^20");
+  grdma_h2_hpack* w = new grdma_h2_hpack();
+  w->parser = parser;
+  w->taken = parser->standalone_calls;
+  parser->hpack = w;
+  bool ok = hipMalloc((void**)&w->d, sizeof(h2hp_dev)) == hipSuccess && hipMalloc((void**)&w->d_call, sizeof(h2hp_call)) == hipSuccess &&
+            hipMalloc((void**)&w->d_carry, max_block_bytes) == hipSuccess && hipMemset(w->d, 0, sizeof(h2hp_dev)) == hipSuccess;
+  if (ok) {
+    uint8_t* d = reinterpret_cast<uint8_t*>(w->d);
+    const h2hp_config cfg = {w->d_carry, max_block_bytes, max_table_size, 0};
+    const uint32_t cur_max = max_table_size < 4096u ? max_table_size : 4096u;  // (RFC 7541 4.2: where the peer's encoder starts)
+    ok = hipMemcpy(d + offsetof(h2hp_dev, carry_buf), &cfg, sizeof(cfg), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + offsetof(h2hp_dev, cur_max), &cur_max, sizeof(cur_max), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + offsetof(h2hp_dev, huff), h2hp_huff_table, sizeof(h2hp_huff_table), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + offsetof(h2hp_dev, st_off), h2hp_static_off, sizeof(h2hp_static_off), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + offsetof(h2hp_dev, st_bytes), h2hp_static_bytes, sizeof(h2hp_static_bytes), hipMemcpyHostToDevice) == hipSuccess;
+  }
+  if (!ok) {
+    (void)hipGetLastError();
+    grdma_h2_hpack_destroy(w);
+    grdma_fail_msg(GRDMA_ERR_HIP, "h2 header decoder: device allocation failed");
+    return nullptr;
+  }
+  return w;
+}
+
+void grdma_h2_hpack_destroy(grdma_h2_hpack* w) {
+  if (!w) return;
+  h2_host_ctx* hc = h2_ctx();
+  if (hc) hipStreamSynchronize(hc->stream);  // (standalone calls)
+  if (w->parser) w->parser->hpack = nullptr;
+  hipFree(w->d_blks);
+  hipFree(w->d_items);
+  hipFree(w->d_outs);
+  hipFree(w->d_recs);
+  hipFree(w->d_stage);
+  hipFree(w->d_carry);
+  hipFree(w->d_call);
+  hipFree(w->d);
+  delete w;
+}
+
+int grdma_h2_hpack_set_max_table_size(grdma_h2_hpack* w, uint32_t max_table_size) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!w) return h2_invalid("h2 header decoder", "no decoder");
+  if (!w->parser) return h2_invalid("h2 header decoder", "the parser is gone");
+  if (max_table_size > H2HP_MAX_TABLE) return h2_invalid("h2 header decoder", "max_table_size above 65536");
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  const h2_stage stage = h2_stage_hpack_resize(w->d);
+  h2_call c{"grdma_h2_hpack_set_max_table_size: a launch was rejected",
+            {{reinterpret_cast<uint8_t*>(w->d) + offsetof(h2hp_dev, setting), &max_table_size, sizeof(max_table_size)}}, h2_all(stage), {}, {}};
+  return h2_call_run(hc, &c);
+}
+
+int64_t grdma_h2_hpack_decode(grdma_h2_hpack* w, grdma_h2_header_block* d_blocks, uint64_t blocks_cap, grdma_h2_header_field* d_fields,
+                              uint64_t fields_cap, void* d_strings, uint64_t strings_cap, uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!out) return h2_invalid("h2 header decoder", "no result array");
+  if (!w) return h2_invalid("h2 header decoder", "a call without decoder");
+  if (const char* why = h2_follow_refusal(*w, "this call is taken in already", true)) return h2_invalid("h2 header decoder", why);
+  if (!d_blocks || !blocks_cap || !d_fields || !fields_cap || !d_strings || !strings_cap || ((uintptr_t)d_blocks & 15) ||
+      ((uintptr_t)d_fields & 15) || ((uintptr_t)d_strings & 15))
+    return h2_invalid("h2 header decoder", "a null, zero or misaligned block table, field table or string arena");
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  // the stream of the standalone deframings: the call is ordered behind the one it reads
+  if (!h2_wait_parser(hc->stream, w->parser)) return -GRDMA_ERR_HIP;
+  const uint64_t nitems = w->parser->standalone_ev_cap + 2;  // (an item per event and the carried one; as many blocks at most)
+  if (!h2_grow(&w->d_items, &w->items_cap, nitems) || !h2_grow(&w->d_blks, &w->blks_cap, nitems)) return -GRDMA_ERR_HIP;
+  const h2hp_call call = h2_follow_deframed(*w);
+  const h2hp_target target = {reinterpret_cast<h2hp_block_out*>(d_blocks), blocks_cap, reinterpret_cast<h2hp_field_out*>(d_fields), fields_cap,
+                              static_cast<uint8_t*>(d_strings), strings_cap};
+  h2hp_scratch scratch = {w->d_stage, w->stage_cap, w->d_recs, w->recs_cap, w->d_outs, w->outs_cap, w->d_items, w->d_blks,
+                          std::min(w->items_cap, w->blks_cap)};
+  uint8_t* const d = reinterpret_cast<uint8_t*>(w->d);
+  uint64_t pre[4] = {0, 0, 0, 0};
+  const h2_stage gather = h2_stage_hpack_gather(w->d, w->d_call);
+  h2_call c1{"grdma_h2_hpack_decode: a launch was rejected",
+             {{w->d_call, &call, sizeof(call)}, {d, &target, sizeof(target)}, {d + offsetof(h2hp_dev, stage), &scratch, sizeof(scratch)}}, {},
+             {h2_all(gather)}, {h2_result(pre, w->d, offsetof(h2hp_dev, pre), 4)}};
+  if (int rc = h2_call_run(hc, &c1)) return rc;
+  if (pre[0] > (1ull << 30)) return h2_invalid("h2 header decoder", "more than 2^30 bytes of header blocks in one call");
+  const uint64_t nouts = std::min<uint64_t>(fields_cap, pre[0]) + 1;
+  if (!h2_grow(&w->d_stage, &w->stage_cap, pre[0] + 16) || !h2_grow(&w->d_recs, &w->recs_cap, pre[0] + 1) ||
+      !h2_grow(&w->d_outs, &w->outs_cap, nouts))
+    return -GRDMA_ERR_HIP;
+  scratch = {w->d_stage, w->stage_cap, w->d_recs, w->recs_cap, w->d_outs, w->outs_cap, w->d_items, w->d_blks, std::min(w->items_cap, w->blks_cap)};
+  const h2_stage stage = h2_stage_hpack_decode(w->d, w->d_call);
+  h2_call c2{"grdma_h2_hpack_decode: a launch was rejected", {{d + offsetof(h2hp_dev, stage), &scratch, sizeof(scratch)}}, {}, {h2_all(stage)},
+             {h2_result(out, w->d, offsetof(h2hp_dev, res))}};
+  if (int rc = h2_call_run(hc, &c2)) return rc;
+  // (a cap overflow, 1: nothing was written or committed, the call is not taken and may be repeated)
+  h2_follow_ran(w, c1.ms[0] + c2.ms[0], out[H2HP_OVERFLOW] != 1);
+  if (out[H2HP_OVERFLOW] == 0) return (int64_t)out[H2HP_BLOCKS];
+  if (out[H2HP_OVERFLOW] == 1)
+    return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 header decoder: more blocks, fields or string bytes than the targets hold");
+  return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 header decoder: the call's event list overflowed, its header blocks are lost");
+}
+
+int grdma_h2_hpack_table(grdma_h2_hpack* w, void* host_buf, uint64_t cap, uint64_t out[4]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!w || !out || (!host_buf && cap)) return -GRDMA_ERR_INVALID;
+  uint32_t st[4];  // size limit, bytes, entries, insertions
+  std::vector<h2hp_entry> ring(H2HP_RING);
+  std::vector<uint8_t> bytes(H2HP_BYTES);
+  const uint8_t* d = reinterpret_cast<const uint8_t*>(w->d);
+  if (!h2_read(st, d + offsetof(h2hp_dev, cur_max), sizeof(st)) || !h2_read(ring.data(), d + offsetof(h2hp_dev, ring), sizeof(h2hp_entry) * H2HP_RING) ||
+      !h2_read(bytes.data(), d + offsetof(h2hp_dev, bytes), H2HP_BYTES))
+    return -GRDMA_ERR_HIP;
+  const uint32_t cnt = st[2] < H2HP_RING ? st[2] : H2HP_RING;
+  uint64_t need = 0;
+  for (uint32_t q = 0; q < cnt; q++) {
+    const h2hp_entry& e = ring[(st[3] - 1u - q) & (H2HP_RING - 1u)];
+    need += 8ull + e.name_len + e.value_len;
+  }
+  out[0] = cnt;
+  out[1] = need;
+  out[2] = st[1];
+  out[3] = st[0];
+  if (need > cap) return -GRDMA_ERR_CAPACITY;
+  uint8_t* o = static_cast<uint8_t*>(host_buf);
+  for (uint32_t q = 0; q < cnt; q++) {  // newest first: name length, value length, name, value
+    const h2hp_entry& e = ring[(st[3] - 1u - q) & (H2HP_RING - 1u)];
+    memcpy(o, &e.name_len, 4);
+    memcpy(o + 4, &e.value_len, 4);
+    o += 8;
+    for (uint32_t k = 0; k < e.name_len; k++) *o++ = bytes[((e.name_src & 0x3fffffffu) + k) & (H2HP_BYTES - 1u)];
+    for (uint32_t k = 0; k < e.value_len; k++) *o++ = bytes[((e.value_src & 0x3fffffffu) + k) & (H2HP_BYTES - 1u)];
+  }
+  return 0;
+}
+
+int grdma_h2_hpack_stats(grdma_h2_hpack* w, uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!w || !out) return -GRDMA_ERR_INVALID;
+  uint64_t st[7];  // sticky word, then the six counters
+  if (!h2_read(st, reinterpret_cast<const uint8_t*>(w->d) + offsetof(h2hp_dev, sticky), sizeof(st))) return -GRDMA_ERR_HIP;
+  for (int i = 0; i < 6; i++) out[i] = st[i + 1];  // calls, blocks, fields, string bytes, inserts, evictions
+  out[6] = st[0];
+  out[7] = (uint64_t)(w->last_ms * 1e6f);
+  return 0;
 }
 
 // ---- the message assembler on many links (h2_stage_asm_links, csrc/grdma_h2_asm.h) ---------------------------------

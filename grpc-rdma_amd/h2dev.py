@@ -291,6 +291,17 @@ def _bind():
         lib.grdma_h2_ctl_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
         lib.grdma_h2_ctl_reply_batch.restype = C.c_int
         lib.grdma_h2_ctl_reply_batch.argtypes = [C.POINTER(H2CtlItem), C.c_uint32, C.POINTER(u64)]
+        lib.grdma_h2_hpack_create.restype = C.c_void_p
+        lib.grdma_h2_hpack_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        lib.grdma_h2_hpack_destroy.argtypes = [C.c_void_p]
+        lib.grdma_h2_hpack_set_max_table_size.restype = C.c_int
+        lib.grdma_h2_hpack_set_max_table_size.argtypes = [C.c_void_p, C.c_uint32]
+        lib.grdma_h2_hpack_decode.restype = C.c_int64
+        lib.grdma_h2_hpack_decode.argtypes = [C.c_void_p, C.c_void_p, u64, C.c_void_p, u64, C.c_void_p, u64, C.POINTER(u64)]
+        lib.grdma_h2_hpack_table.restype = C.c_int
+        lib.grdma_h2_hpack_table.argtypes = [C.c_void_p, C.c_void_p, u64, C.POINTER(u64)]
+        lib.grdma_h2_hpack_stats.restype = C.c_int
+        lib.grdma_h2_hpack_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
         lib.grdma_job_hook_counts.restype = C.c_int   # (not in include/grdma_amd.h: the job's side of the pipes)
         lib.grdma_job_hook_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         _bound = True
@@ -910,6 +921,67 @@ class ControlReplies:
     def close(self):
         if self.h:
             self.lib.grdma_h2_ctl_destroy(self.h)
+            self.h = None
+
+
+class HeaderDecoder:
+    """The header blocks of one transport decoded on the device (grdma_h2_hpack): the HPACK blocks of the parser's
+    deframings as a block table, a field table and a string arena in device memory.  One per parser; independent of
+    FlowControl, SendWindows and ControlReplies, which may consume the same deframing."""
+
+    RESULT = ("blocks", "fields", "string_bytes", "inserted", "evicted", "table_bytes", "flags", "overflow")
+    STATS = ("calls", "blocks", "fields", "string_bytes", "inserted", "evicted", "flags", "kernel_us")
+    FAILED, LOST, OPEN = 1, 2, 4
+    ERRORS = (None, "padding", "block too large", "integer", "truncated", "huffman", "index", "size update", "deframer")
+
+    def __init__(self, parser, max_table_size=4096, max_block_bytes=65536):
+        self.lib = _bind()
+        self.parser = parser  # (kept alive)
+        self.h = self.lib.grdma_h2_hpack_create(parser.h, max_table_size, max_block_bytes)
+        if not self.h:
+            raise GrdmaError("h2 header decoder: " + (self.lib.grdma_last_error() or b"creation failed").decode())
+        self.last_result = None
+
+    def set_max_table_size(self, n):
+        """our SETTINGS_HEADER_TABLE_SIZE from now on: the bound of the peer's size updates; a lowered one evicts at once"""
+        check(self.lib.grdma_h2_hpack_set_max_table_size(self.h, n))
+
+    def decode(self, blocks_ptr, blocks_cap, fields_ptr, fields_cap, strings_ptr, strings_cap):
+        """decodes the header blocks of the parser's last standalone deframing into the three device targets -> (block
+        count, result tuple (RESULT)); raises GrdmaError on a refusal, a lost call or a capacity overflow -- the result
+        of the failed call stays in .last_result; after a capacity overflow (overflow word 1) the call may be repeated
+        with larger targets.  flags: FAILED | LOST | OPEN, the error in bits 8..15, the failing stream from bit 32"""
+        out = (u64 * 8)()
+        n = self.lib.grdma_h2_hpack_decode(self.h, blocks_ptr, blocks_cap, fields_ptr, fields_cap, strings_ptr, strings_cap, out)
+        _results(out, [self])
+        return check(n), self.last_result
+
+    def table(self):
+        """the live dynamic table -> ([(name, value), ...] newest first, (entries, table bytes, the size limit in force))"""
+        out = (u64 * 4)()
+        rc = self.lib.grdma_h2_hpack_table(self.h, None, 0, out)
+        if rc and not out[1]:
+            check(rc)
+        buf = C.create_string_buffer(max(1, int(out[1])))
+        check(self.lib.grdma_h2_hpack_table(self.h, buf, int(out[1]), out))
+        raw, pos, entries = buf.raw, 0, []
+        for _ in range(int(out[0])):
+            nl, vl = int.from_bytes(raw[pos:pos + 4], "little"), int.from_bytes(raw[pos + 4:pos + 8], "little")
+            entries.append((raw[pos + 8:pos + 8 + nl], raw[pos + 8 + nl:pos + 8 + nl + vl]))
+            pos += 8 + nl + vl
+        return entries, (int(out[0]), int(out[2]), int(out[3]))
+
+    def stats(self):
+        """dict of STATS; `flags`: the sticky word (FAILED | LOST, error << 8, stream << 32)"""
+        out = (u64 * 8)()
+        check(self.lib.grdma_h2_hpack_stats(self.h, out))
+        r = dict(zip(HeaderDecoder.STATS, [int(x) for x in out]))
+        r["kernel_us"] /= 1e3  # (the ABI word is nanoseconds)
+        return r
+
+    def close(self):
+        if self.h:
+            self.lib.grdma_h2_hpack_destroy(self.h)
             self.h = None
 
 

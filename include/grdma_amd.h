@@ -618,7 +618,8 @@ typedef struct grdma_h2_parser grdma_h2_parser;
  * (grpc_chttp2_mark_stream_closed, chttp2_transport.cc:2194-2244) -- the caller reports the write
  * side with grdma_h2_parser_close_writes.  HPACK, SETTINGS, PING, GOAWAY and WINDOW_UPDATE payloads
  * are control plane and are skipped here.  The deframer skips INCOMING WINDOW_UPDATE and SETTINGS payloads too; the send
- * windows (grdma_h2_sw below) read them from the arena by the deframer's events.  Our own WINDOW_UPDATE frames -- the
+ * windows (grdma_h2_sw below) read them from the arena by the deframer's events, as the header decoder (grdma_h2_hpack
+ * below) reads the HPACK blocks.  Our own WINDOW_UPDATE frames -- the
  * credit for the DATA bytes received -- are produced on the device by the window ledger (grdma_h2_fc below).
  * grdma_h2_parser_create(prefix, max) = create_ex(prefix ? SERVER | FIRST_FRAME : 0, max, 0xffffffff, 0).
  * table_slots: power of two >= 16 (0 = 4096); at most table_slots / 2 streams are live at once. */
@@ -976,7 +977,7 @@ int grdma_h2_fc_account_batch(const grdma_h2_fc_item* items, uint32_t n, uint64_
  * max_frame 0 or >= 2^24, null, zero or misaligned (16 bytes) targets.
  * Not here: intake of a pipe's or group pipe's steps and the windowed framer as a pipe's framing stage (a job's graph
  * carries a fixed slice count per step; a window-cut step has another shape), the
- * other settings, HPACK (the reply framer under these windows: grdma_h2_reply_frame_windowed below) (SETTINGS ACK: grdma_h2_ctl below).  (The many-link batch forms: grdma_h2_sw_intake_batch / _frame_batch below.) */
+ * other settings, the HPACK encoder (the decoder: grdma_h2_hpack below) (the reply framer under these windows: grdma_h2_reply_frame_windowed below) (SETTINGS ACK: grdma_h2_ctl below).  (The many-link batch forms: grdma_h2_sw_intake_batch / _frame_batch below.) */
 enum grdma_h2_sw_violation { GRDMA_H2_SW_BAD_INCREMENT = 1, GRDMA_H2_SW_WINDOW_OVERFLOW = 2, GRDMA_H2_SW_BAD_SETTINGS = 4,
                              GRDMA_H2_SW_LOST = 8 };
 typedef struct grdma_h2_sw grdma_h2_sw;
@@ -1143,7 +1144,8 @@ int grdma_h2_reply_frame_windowed_batch(grdma_h2_wr_item* items, uint32_t n);
  * max_replies outside 1 .. 2^24, no call yet or a call taken in already, a parser that is gone (destroy still works),
  * null, zero or misaligned (16 bytes) targets; in the batch n outside 1 .. GRDMA_H2_BATCH_MAX, a NULL item, the same
  * writer twice.
- * Not here: replies to a pipe's or group pipe's steps, the other settings, HPACK. */
+ * Not here: replies to a pipe's or group pipe's steps, the other settings, the HPACK encoder (the decoder: grdma_h2_hpack
+ * below). */
 enum grdma_h2_ctl_flag { GRDMA_H2_CTL_LOST = 1, GRDMA_H2_CTL_GOAWAY = 2 /* a GOAWAY completed in this call */ };
 typedef struct grdma_h2_ctl grdma_h2_ctl;
 grdma_h2_ctl* grdma_h2_ctl_create(grdma_h2_parser* parser, uint32_t max_replies);  /* 1 .. 2^24; one per parser */
@@ -1167,6 +1169,72 @@ typedef struct grdma_h2_ctl_item {
 } grdma_h2_ctl_item;
 int grdma_h2_ctl_reply_batch(const grdma_h2_ctl_item* items, uint32_t n, uint64_t* out);
 
+/* ---- Header blocks: HPACK on the device (csrc/grdma_h2_hpack.h) ----
+ * The header blocks of a deframing's HEADERS and CONTINUATION frames, decoded (RFC 7541) into device memory: a block
+ * table, a field table and a string arena.  One header decoder per parser, a sibling of the control-reply writer:
+ * independent of the ledger, the send windows and the writer -- any of them may consume the same deframing in any order
+ * -- with its own count of the calls it has taken.  The sequential reference is tests/h2_hpack_model.py.
+ * 1. BLOCK.  grdma_h2_hpack_decode takes in the LAST standalone deframing of the parser (events, slice table, receive
+ *    arena, which must still hold the call's bytes) and is ordered behind it on the device.  A block is the payload of
+ *    a HEADERS frame and of the CONTINUATION frames behind it up to the frame with END_HEADERS (0x4); the HEADERS
+ *    payload loses the pad-length byte (PADDED, 0x8), then 5 priority bytes (PRIORITY, 0x20), and the padding at its
+ *    end.  ERR_PADDING: a padded or prioritised frame shorter than those bytes, a pad length >= what is left.  A block
+ *    is decoded in the call that completes its last frame.  PUSH_PROMISE is no block.  A block on a stream the deframer
+ *    refused is decoded and delivered like any other (the table must stay in step); the status byte of its FRAME event
+ *    rides in the block's flags.
+ * 2. CARRY.  A block the call's end cuts keeps its fragment bytes in the decoder's device buffer (max_block_bytes), the
+ *    open frame's type, flags and size, the payload bytes seen and the pad length if it is in; PAYLOAD events in front
+ *    of the call's first FRAME event continue it.  A block above max_block_bytes: ERR_BLOCK_TOO_LARGE.
+ * 3. HPACK.  Integers need not be minimal; more than five continuation bytes or a value above 2^32 - 1: ERR_INTEGER.
+ *    Huffman padding is at most 7 one-bits and EOS inside a string is an error: ERR_HUFFMAN; a length or an integer that
+ *    runs past the block: ERR_TRUNCATED.  Index 0 or one beyond the live table: ERR_INDEX (1..61 static, 62 the newest
+ *    dynamic entry).  A size update stands in front of the block's first field, may come more than once and is <= our
+ *    setting, else ERR_SIZE_UPDATE; a lowered setting takes effect at once and need not be acknowledged by one.  Entry
+ *    size 32 + name + value; an insertion evicts from the oldest until the entry fits; an entry larger than the table
+ *    empties it and is not inserted; a name reference to an entry the same insertion evicts is valid (4.4).  A block
+ *    with several faults reports the first in wire order among integers, lengths, Huffman strings and size updates, and
+ *    ERR_INDEX only where there is none of those.
+ * 4. OUTPUT.  Blocks in completion order, a block's fields contiguous in wire order, the string arena byte-contiguous:
+ *    name then value, field after field, no terminators; indexed fields copy their bytes too.  Nothing is written
+ *    behind the three totals.  Result block: {blocks, fields, string bytes, entries inserted, entries evicted, table
+ *    bytes after the call, flags (grdma_h2_hpack_flag) | error << 8 | failing stream << 32, overflow}.
+ * 5. ERRORS.  An error in block k of a call delivers and commits blocks 0..k-1 and sets FAILED with the error and the
+ *    stream; it is sticky: every later call is taken, writes nothing and returns 0 with the word.  The same end state,
+ *    with its own flag or code: a call that ended with a connection error of the deframer (FAILED, ERR_DEFRAMER), an
+ *    overflowed event list (LOST, -GRDMA_ERR_CAPACITY, overflow word 2), a deframing never taken in (LOST).
+ * 6. CAPS.  More blocks, fields or string bytes than the caps: overflow word 1, -GRDMA_ERR_CAPACITY, the result block
+ *    holds the totals, NOTHING is written and NOTHING is committed (table, carry, counters), the call is NOT taken and
+ *    may be repeated with larger targets while the deframing's buffers stand.
+ * -GRDMA_ERR_INVALID or NULL (grdma_last_error says why; nothing runs, nothing changes): a second decoder on a parser,
+ * max_table_size above 65536, max_block_bytes outside 64 .. 2^20, no call yet or a call taken in already, a parser that
+ * is gone (destroy still works), null, zero or misaligned (16 bytes) targets.
+ * Not here: the HPACK encoder, the decoder over a table of links or inside a pipe, gRPC's metadata validation,
+ * SETTINGS_MAX_HEADER_LIST_SIZE, PUSH_PROMISE. */
+enum grdma_h2_hpack_flag { GRDMA_H2_HPACK_FAILED = 1, GRDMA_H2_HPACK_LOST = 2, GRDMA_H2_HPACK_OPEN = 4 /* a block is cut by the call's end */ };
+enum grdma_h2_hpack_error {
+  GRDMA_H2_HPACK_ERR_PADDING = 1, GRDMA_H2_HPACK_ERR_BLOCK_TOO_LARGE = 2, GRDMA_H2_HPACK_ERR_INTEGER = 3, GRDMA_H2_HPACK_ERR_TRUNCATED = 4,
+  GRDMA_H2_HPACK_ERR_HUFFMAN = 5, GRDMA_H2_HPACK_ERR_INDEX = 6, GRDMA_H2_HPACK_ERR_SIZE_UPDATE = 7, GRDMA_H2_HPACK_ERR_DEFRAMER = 8
+};
+typedef struct grdma_h2_header_field { uint32_t name_off, value_off, name_len, value_len; } grdma_h2_header_field;
+    /* offsets into the string arena; name_len bits 24..31: representation 0 indexed, 1 incremental, 2 without, 3 never indexed */
+typedef struct grdma_h2_header_block { uint32_t stream, first_field, nfields, flags; } grdma_h2_header_block;
+    /* flags: 1 END_STREAM of the HEADERS frame, 2 it carried PRIORITY, bits 8..15 the status byte of its FRAME event */
+typedef struct grdma_h2_hpack grdma_h2_hpack;
+grdma_h2_hpack* grdma_h2_hpack_create(grdma_h2_parser* parser, uint32_t max_table_size /* our SETTINGS_HEADER_TABLE_SIZE, 0 .. 65536 */,
+                                      uint32_t max_block_bytes /* 64 .. 2^20 */);
+void grdma_h2_hpack_destroy(grdma_h2_hpack* hpack);
+int grdma_h2_hpack_set_max_table_size(grdma_h2_hpack* hpack, uint32_t max_table_size);  /* the bound for the peer's later size updates */
+int64_t grdma_h2_hpack_decode(grdma_h2_hpack* hpack, grdma_h2_header_block* d_blocks, uint64_t blocks_cap,
+                              grdma_h2_header_field* d_fields, uint64_t fields_cap, void* d_strings, uint64_t strings_cap,
+                              uint64_t out[8]);  /* returns the block count */
+/* the live dynamic table, newest first, into host memory: per entry two 32-bit lengths (name, value), then the name's and
+ * the value's bytes.  out: {entries, bytes of the dump, table bytes (RFC 7541 4.1), the size limit in force}; a buffer too
+ * small (NULL with cap 0 asks for the figures): -GRDMA_ERR_CAPACITY with out filled in */
+int grdma_h2_hpack_table(grdma_h2_hpack* hpack, void* host_buf, uint64_t cap, uint64_t out[4]);
+/* {calls taken, blocks, fields, string bytes, inserts, evictions, the sticky flags word, kernel time of the last call in
+ * NANOseconds (HIP events)} */
+int grdma_h2_hpack_stats(grdma_h2_hpack* hpack, uint64_t out[8]);
+
 /* ---- HTTP/2 on several links of ONE job (the group pipe) ----
  * grdma_h2_pipe serves one link, and a job carries one set of kernels in front of and behind its rounds: a second
  * grdma_h2_pipe on another link of the same job replaces the first one's.  The group pipe is the pipe of n links of a
@@ -1181,7 +1249,8 @@ int grdma_h2_ctl_reply_batch(const grdma_h2_ctl_item* items, uint32_t n, uint64_
  * grdma_h2_group_pipe_sync's "slices parsed" word is that count.  (grdma_h2_pipe parses the recorded count.)
  * Create returns NULL (grdma_last_error says why) for: n == 0, a link index out of range or listed twice, a parser
  * listed twice, nmsgs 0 or above 4096, max_frame 0 or >= 2^24, a job that already carries such kernels (another pipe).
- * Not here (yet): the chunked deframer inside the batch (every transport is parsed sequentially) and HPACK.  A parser
+ * Not here (yet): the chunked deframer inside the batch (every transport is parsed sequentially), the HPACK encoder and the
+ * header decoder over a table of links (one transport's: grdma_h2_hpack above).  A parser
  * that has a window ledger at create time is refused: ledgers come later, grdma_h2_group_pipe_attach_flow_control. */
 typedef struct grdma_h2_link_spec {
   uint32_t link;                 /* index into the job's links; distinct */
