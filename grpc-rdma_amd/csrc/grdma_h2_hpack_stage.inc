@@ -191,7 +191,7 @@
   __shared__ h2hp_rec s_rec[H2HP_CHUNK];
   __shared__ uint64_t s_wave[H2HP_THREADS / 64];
   __shared__ uint16_t s_stlen[128];
-  __shared__ uint32_t s_bad, s_m, s_count, s_q, s_cnt, s_ins, s_add, s_isfield, s_fail, s_commit;
+  __shared__ uint32_t s_bad, s_m, s_count, s_q, s_cnt, s_ins, s_add, s_isfield, s_fail, s_fail1, s_commit;
   const uint32_t tid = threadIdx.x;
   const uint32_t mask = H2HP_RING - 1u;
   const uint64_t sticky = F->sticky;
@@ -235,7 +235,7 @@
       inserted = evicted = 0;
       s_cnt = cnt;
       s_ins = ins;
-      s_fail = H2HP_NONE;
+      s_fail = s_fail1 = H2HP_NONE;
     }
     nfields = run = 0;
     __syncthreads();
@@ -317,7 +317,7 @@
             } else {
               uint32_t nsrc = 0, nlen = 0, vsrc = 0, vlen = 0;
               if (!h2hp_resolve(r, s_ring, s_stlen, cnt, ins, nsrc, nlen, vsrc, vlen)) {
-                s_fail = r.rsv;
+                s_fail1 = r.rsv;  // (a word of its own: a thread may still be reading s_fail in front of this step)
               } else {  // (the name was resolved before this evicts: RFC 7541 4.4)
                 const uint64_t need = 32ull + nlen + vlen;
                 H2HP_EVICT(s_ring, need, cur_max);
@@ -338,7 +338,7 @@
             s_ins = ins;
           }
           __syncthreads();
-          if (s_fail != H2HP_NONE) break;  // (uniform)
+          if (s_fail1 != H2HP_NONE) break;  // (uniform)
           o += s_isfield;
           run += s_add;
         }
@@ -346,7 +346,7 @@
       }
       nfields += o;
       __syncthreads();
-      if (s_fail != H2HP_NONE) break;  // (uniform)
+      if (s_fail != H2HP_NONE || s_fail1 != H2HP_NONE) break;  // (uniform)
       // the resolved fields go out, behind those of the steps in front (thread 0 holds the count: through LDS)
       if (tid == 0) s_wave[0] = out0;
       if (m && tid == m - 1u) s_wave[1] = (x >> 32) + B.nfields;  // the fields of the m blocks
@@ -368,8 +368,9 @@
       }
       __syncthreads();
     }
-    if (s_fail == H2HP_NONE) break;
-    bad = s_fail;  // (in front of every block that failed the split: those were not walked)
+    const uint32_t fail = s_fail < s_fail1 ? s_fail : s_fail1;  // (the runs' threads, or thread 0 at an insertion)
+    if (fail == H2HP_NONE) break;
+    bad = fail;  // (in front of every block that failed the split: those were not walked)
     bad_err = H2HP_E_INDEX;
     limit = bad;
     __syncthreads();

@@ -156,7 +156,84 @@ class HpackTable:
         return self.apply(split(data, self.setting))
 
 
+# ---- what the decoder's stages see of a call, from the model alone (the witnesses of tests/h2_hpack_sweep_lib.py) ------
+THREADS, CHUNK, RING, BYTES = 256, 512, 2048, 65536  # H2HP_THREADS, H2HP_CHUNK, H2HP_RING, H2HP_BYTES of csrc/grdma_h2_hpack.h
+
+
+def block_facts(data, setting):
+    """-> (records, fields, size updates) of a block the split takes, None of one it refuses"""
+    try:
+        fs = split(data, setting)
+    except HpackError:
+        return None
+    su = sum(1 for f in fs if f[0] == "size")
+    return len(fs), len(fs) - su, su
+
+
+def walk_steps(nrecs):
+    """the records per block of the blocks a call delivers -> the walk's steps [(first block, blocks taken whole,
+    first record, records)]: as many whole blocks (one a thread: THREADS at most) as sum to <= CHUNK records, else
+    CHUNK records of one block (blocks taken whole: 0)"""
+    out, k = [], 0
+    while k < len(nrecs):
+        m = tot = 0
+        while k + m < len(nrecs) and m < THREADS and tot + nrecs[k + m] <= CHUNK:
+            tot, m = tot + nrecs[k + m], m + 1
+        if m:
+            out.append((k, m, 0, tot))
+            k += m
+        else:
+            out += [(k, 0, f0, min(CHUNK, nrecs[k] - f0)) for f0 in range(0, nrecs[k], CHUNK)]
+            k += 1
+    return out
+
+
+def gather_steps(nevents):
+    """items per step of the gather: item 0 is the carried frame and block, item t event t - 1"""
+    return [min(THREADS, nevents + 1 - c0) for c0 in range(0, nevents + 1, THREADS)]
+
+
+def header_items(events, carried):
+    """the item numbers of a call's header frames (the carried block's is 0)"""
+    return ([0] if carried else []) + [t + 1 for t, e in enumerate(events) if e[0] == EV_FRAME and e[1] in (HEADERS, CONTINUATION)]
+
+
+class RingLayout:
+    """Where the device keeps the strings of the dynamic table: per committed call the byte ring's head advances by the
+    string bytes of the entries inserted in that call that are alive at its end, oldest first, mod BYTES; descriptor i
+    (the i-th insertion since creation) stands in slot i mod RING."""
+
+    def __init__(self):
+        self.head = 0
+        self.where = []  # newest first, beside HpackTable.entries: (offset, name length, value length)
+
+    def commit(self, table, inserted):
+        """behind a committed call that made `inserted` insertions (or a resize: 0)"""
+        fresh = min(inserted, len(table.entries))
+        new = []
+        for name, value in reversed(table.entries[:fresh]):
+            new.insert(0, (self.head, len(name), len(value)))
+            self.head = (self.head + len(name) + len(value)) % BYTES
+        self.where = new + self.where[:len(table.entries) - fresh]
+
+    def straddles(self):
+        """which live strings lie across offset BYTES: [(index from 62, "name" | "value" | "between")]; between: the name
+        ends and the value begins there"""
+        out = []
+        for i, (a, nl, vl) in enumerate(self.where):
+            b, c = a + nl, a + nl + vl
+            if a < BYTES < b:
+                out.append((62 + i, "name"))
+            if nl and vl and b == BYTES:
+                out.append((62 + i, "between"))
+            if b < BYTES < c:
+                out.append((62 + i, "value"))
+        return out
+
+
 class HpackModel:
+    closed = ()  # the blocks the last call completed, delivered or not: their bytes
+
     def __init__(self, setting=4096, max_block=65536):
         self.table = HpackTable(setting)
         self.max_block = max_block
@@ -175,6 +252,7 @@ class HpackModel:
         self.frame = self.block = None
         self.stats["calls"] += 1
         self.stats["flags"] = self.word
+        self.closed = []
         return [], [], b"", (0, 0, 0, 0, 0, self.table.size, self.word, overflow), rc
 
     def decode(self, events, slices, err, caps, skipped=False, lost=False):
@@ -189,6 +267,7 @@ class HpackModel:
             return self._dead(LOST, 0, False)
         if err:
             return self._dead(FAILED | ERR_DEFRAMER << 8, 0, False)
+        self.closed = closed = []
         m = copy.deepcopy(self)  # (nothing is committed when a cap overflows)
         blocks, fields, strings, failure = [], [], bytearray(), 0
         ins0, ev0 = m.table.inserted, m.table.evicted
@@ -208,6 +287,7 @@ class HpackModel:
                     if c:
                         m.frame = None
                         if f["type"] in (HEADERS, CONTINUATION) and f["flags"] & END_HEADERS and m.block is not None:
+                            closed.append(bytes(m.block["frag"]))
                             good = copy.deepcopy(m.table)
                             try:
                                 decoded = m.table.decode_block(bytes(m.block["frag"]))

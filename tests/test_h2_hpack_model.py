@@ -124,3 +124,54 @@ def test_the_golden_vectors():
     for case in VECTORS["malformed"]:
         assert case["blocks"][-1]["fields"] is None and all(b["fields"] is not None for b in case["blocks"][:-1]), case["what"]
         _replay(case["blocks"])
+
+
+# ---- the sweep of tests/test_zz_gpu_h2_hpack_sweep.py: its witnesses, and its block sequences through nghttp2 --------------
+PER_FAMILY = {"01": 20, "02": 22, "03": 16, "04": 10, "05": 6, "06": 60, "07": 39, "08": 61, "09": 10, "10": 6}
+
+
+def test_every_case_of_the_hpack_sweep_shows_its_witness():
+    import collections
+    from tests import h2_hpack_sweep_lib as S
+    cs = S.check_cases()
+    assert collections.Counter(c["fam"] for c in cs) == PER_FAMILY and len(cs) == sum(PER_FAMILY.values()) == 250
+    assert set(PER_FAMILY) == set(S.FAMILIES) and all(c["edge"] and c["key"] for c in cs)
+    subset = S.emu_subset()
+    assert {S.by_id(cid)["fam"] for cid in subset} == set(S.FAMILIES) and all(cid in subset for cid in S.CAUGHT_ALONE)
+    # what the subset always holds: the chunk path, the ring's wrap at 2048, a byte-ring straddle, 2^32 - 1, an index >= 2^24
+    sims = {cid: S.simulate(S.by_id(cid)) for cid in subset}
+    assert any(st[1] == 0 for sim in sims.values() for s in sim for st in s.get("steps", ()))
+    assert any(s.get("ins0", 0) < S.RING < s.get("ins1", 0) for sim in sims.values() for s in sim)
+    assert any(s.get("straddles") for sim in sims.values() for s in sim)
+    assert any(cid.endswith("_2p32m1") for cid in subset) and any(S.by_id(cid)["key"].startswith("big_") for cid in subset)
+    assert not any(cid[:2] in ("04", "05", "07") for cid in S.NGHTTP2_DIFFERS) and set(S.NGHTTP2_DIFFERS) <= set(S._BY_ID)
+
+
+@needs_nghttp2
+@pytest.mark.parametrize("fam", ["01", "02", "04", "05", "06", "07", "09"])
+def test_the_sweeps_block_sequences_through_nghttp2(fam):
+    """accept or reject, the fields with their never-indexed flag and the dynamic table; error codes are not compared"""
+    import copy
+    from tests import h2_hpack_sweep_lib as S
+    assert fam in S.PINNED
+    n = 0
+    for c in (c for c in S.CASES if c["fam"] == fam):
+        table, inf = HpackTable(c["setting"]), L.Inflater(c["setting"])
+        for kind, x in S.pin_sequence(c):
+            if kind == "resize":
+                table.set_setting(x)
+                inf.change_table_size(x)
+                assert (table.entries, table.size) == inf.table(), c["id"]
+                continue
+            good = copy.deepcopy(table)
+            got, theirs = decode(table, x), inf.inflate(x)
+            if theirs is None and got is not None and c["id"] in S.NGHTTP2_DIFFERS:
+                break
+            assert (got is None) == (theirs is None), (c["id"], x[:64].hex())
+            if got is None:
+                table = good
+                break  # (the decoder is dead behind a failed block)
+            assert got == theirs, (c["id"], x[:64].hex())
+            assert (table.entries, table.size) == inf.table(), (c["id"], x[:64].hex())
+            n += 1
+    assert n > 0
