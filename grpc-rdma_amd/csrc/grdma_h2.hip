@@ -313,6 +313,18 @@ static h2_stage h2_stage_hpack_decode(h2hp_dev* d, const h2hp_call* d_call) {
           h2_rec(k_h2_hpack_commit, H2HP_GRID, H2HP_THREADS, d, d_call)};
 }
 static h2_stage h2_stage_hpack_resize(h2hp_dev* d) { return {h2_rec(k_h2_hpack_resize, 1, 64, d)}; }
+// ... of n links in the same six launches: the gathers and the walks side by side, every link a share of the grid stages
+static_assert(H2HP_LINKS_MAX == GRDMA_H2_BATCH_MAX, "the header decoder's link table is the batch's");
+static h2_stage h2_stage_hpack_links_gather(const h2hp_link* d_tab, uint32_t n) {
+  return {h2_rec(k_h2_links_hpack_gather, n, H2HP_THREADS, d_tab, n)};
+}
+static h2_stage h2_stage_hpack_links_decode(const h2hp_link* d_tab, uint32_t n) {
+  return {h2_rec(k_h2_links_hpack_copy, n * H2HP_LINK_GRID, H2HP_THREADS, d_tab, n),
+          h2_rec(k_h2_links_hpack_split, n * H2HP_LINK_GRID, H2HP_THREADS, d_tab, n),
+          h2_rec(k_h2_links_hpack_walk, n, H2HP_THREADS, d_tab, n),
+          h2_rec(k_h2_links_hpack_emit, n * H2HP_LINK_GRID, H2HP_THREADS, d_tab, n),
+          h2_rec(k_h2_links_hpack_commit, n * H2HP_LINK_GRID, H2HP_THREADS, d_tab, n)};
+}
 
 // st goes behind the parser's last deframing by a pipe (the parser state is handed from one deframing to the next),
 // unless that one was enqueued on st itself.  (Only pipe steps leave last_deframed, on a job's or a deframe stream: for

@@ -360,7 +360,7 @@ bool h2_batch_reserve(uint64_t total, hipStream_t st) {
 }  // namespace
 
 // The scaffold of a batch call whose block is [table | one block per item] (the ledgers', the send windows', the
-// writers', the windowed replies' and the replies'): begin, item for each item, open, the facility's per-item steps
+// writers', the header decoders', the windowed replies' and the replies'): begin, item for each item, open, the facility's per-item steps
 // (which fill the image and add each item's own uploads, downloads and parsers to wait for), run.
 struct h2_batch {
   const char* who;   // "h2 ... batch": leads every refusal
@@ -414,6 +414,13 @@ struct h2_batch {
     c.refused = launch_refused;
     c.timed = std::move(timed);
     return h2_call_run(hc, &c);
+  }
+  // a further run of the same call over the block as it stands on the device (the header decoders' second step): the
+  // transfers and the waits of the run before are done with
+  void next() {
+    c.up.clear();
+    c.down.clear();
+    behind.clear();
   }
 };
 
@@ -1713,26 +1720,59 @@ int grdma_h2_hpack_set_max_table_size(grdma_h2_hpack* w, uint32_t max_table_size
   return h2_call_run(hc, &c);
 }
 
+// what a call of an item (the single call's arguments are one) is refused for
+static const char* h2_hpack_refusal(const grdma_h2_hpack_item& it) {
+  if (!it.hpack) return "a call without decoder";
+  if (const char* why = h2_follow_refusal(*it.hpack, "this call is taken in already", true)) return why;
+  if (!it.d_blocks || !it.blocks_cap || !it.d_fields || !it.fields_cap || !it.d_strings || !it.strings_cap || ((uintptr_t)it.d_blocks & 15) ||
+      ((uintptr_t)it.d_fields & 15) || ((uintptr_t)it.d_strings & 15))
+    return "a null, zero or misaligned block table, field table or string arena";
+  return nullptr;
+}
+// where an item's call writes: the leading words of its decoder's device block
+static h2hp_target h2_hpack_target(const grdma_h2_hpack_item& it) {
+  return {reinterpret_cast<h2hp_block_out*>(it.d_blocks), it.blocks_cap, reinterpret_cast<h2hp_field_out*>(it.d_fields), it.fields_cap,
+          static_cast<uint8_t*>(it.d_strings), it.strings_cap};
+}
+// the scratch words of w's device block as the host's tables stand
+static h2hp_scratch h2_hpack_scratch(const grdma_h2_hpack* w) {
+  return {w->d_stage, w->stage_cap, w->d_recs, w->recs_cap, w->d_outs, w->outs_cap, w->d_items, w->d_blks, std::min(w->items_cap, w->blks_cap)};
+}
+// in front of the gather: an item per event and the carried one; as many blocks at most
+static bool h2_hpack_grow_items(grdma_h2_hpack* w) {
+  const uint64_t nitems = w->parser->standalone_ev_cap + 2;
+  return h2_grow(&w->d_items, &w->items_cap, nitems) && h2_grow(&w->d_blks, &w->blks_cap, nitems);
+}
+// what the gather of a call says: more header bytes than a call may hold (the gather commits nothing)
+static bool h2_hpack_too_many(const uint64_t* pre) { return pre[0] > (1ull << 30); }
+// behind the gather: the staging buffer and the record tables by the call's fragment bytes (not by the call's bytes,
+// which are mostly DATA)
+static bool h2_hpack_grow_scratch(grdma_h2_hpack* w, const uint64_t* pre, uint64_t fields_cap) {
+  const uint64_t nouts = std::min<uint64_t>(fields_cap, pre[0]) + 1;
+  return h2_grow(&w->d_stage, &w->stage_cap, pre[0] + 16) && h2_grow(&w->d_recs, &w->recs_cap, pre[0] + 1) &&
+         h2_grow(&w->d_outs, &w->outs_cap, nouts);
+}
+// behind a call of w that ran, res its result words -> whether its blocks stand
+static bool h2_hpack_ran(grdma_h2_hpack* w, float ms, const uint64_t* res) {
+  // (a cap overflow, 1: nothing was written or committed, the call is not taken and may be repeated)
+  h2_follow_ran(w, ms, res[H2HP_OVERFLOW] != 1);
+  return res[H2HP_OVERFLOW] == 0;
+}
+
 int64_t grdma_h2_hpack_decode(grdma_h2_hpack* w, grdma_h2_header_block* d_blocks, uint64_t blocks_cap, grdma_h2_header_field* d_fields,
                               uint64_t fields_cap, void* d_strings, uint64_t strings_cap, uint64_t out[8]) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
   if (!out) return h2_invalid("h2 header decoder", "no result array");
-  if (!w) return h2_invalid("h2 header decoder", "a call without decoder");
-  if (const char* why = h2_follow_refusal(*w, "this call is taken in already", true)) return h2_invalid("h2 header decoder", why);
-  if (!d_blocks || !blocks_cap || !d_fields || !fields_cap || !d_strings || !strings_cap || ((uintptr_t)d_blocks & 15) ||
-      ((uintptr_t)d_fields & 15) || ((uintptr_t)d_strings & 15))
-    return h2_invalid("h2 header decoder", "a null, zero or misaligned block table, field table or string arena");
+  const grdma_h2_hpack_item it{w, d_blocks, blocks_cap, d_fields, fields_cap, d_strings, strings_cap};
+  if (const char* why = h2_hpack_refusal(it)) return h2_invalid("h2 header decoder", why);
   h2_host_ctx* hc = h2_ctx();
   if (!hc) return -GRDMA_ERR_HIP;
   // the stream of the standalone deframings: the call is ordered behind the one it reads
   if (!h2_wait_parser(hc->stream, w->parser)) return -GRDMA_ERR_HIP;
-  const uint64_t nitems = w->parser->standalone_ev_cap + 2;  // (an item per event and the carried one; as many blocks at most)
-  if (!h2_grow(&w->d_items, &w->items_cap, nitems) || !h2_grow(&w->d_blks, &w->blks_cap, nitems)) return -GRDMA_ERR_HIP;
+  if (!h2_hpack_grow_items(w)) return -GRDMA_ERR_HIP;
   const h2hp_call call = h2_follow_deframed(*w);
-  const h2hp_target target = {reinterpret_cast<h2hp_block_out*>(d_blocks), blocks_cap, reinterpret_cast<h2hp_field_out*>(d_fields), fields_cap,
-                              static_cast<uint8_t*>(d_strings), strings_cap};
-  h2hp_scratch scratch = {w->d_stage, w->stage_cap, w->d_recs, w->recs_cap, w->d_outs, w->outs_cap, w->d_items, w->d_blks,
-                          std::min(w->items_cap, w->blks_cap)};
+  const h2hp_target target = h2_hpack_target(it);
+  h2hp_scratch scratch = h2_hpack_scratch(w);
   uint8_t* const d = reinterpret_cast<uint8_t*>(w->d);
   uint64_t pre[4] = {0, 0, 0, 0};
   const h2_stage gather = h2_stage_hpack_gather(w->d, w->d_call);
@@ -1740,22 +1780,71 @@ int64_t grdma_h2_hpack_decode(grdma_h2_hpack* w, grdma_h2_header_block* d_blocks
              {{w->d_call, &call, sizeof(call)}, {d, &target, sizeof(target)}, {d + offsetof(h2hp_dev, stage), &scratch, sizeof(scratch)}}, {},
              {h2_all(gather)}, {h2_result(pre, w->d, offsetof(h2hp_dev, pre), 4)}};
   if (int rc = h2_call_run(hc, &c1)) return rc;
-  if (pre[0] > (1ull << 30)) return h2_invalid("h2 header decoder", "more than 2^30 bytes of header blocks in one call");
-  const uint64_t nouts = std::min<uint64_t>(fields_cap, pre[0]) + 1;
-  if (!h2_grow(&w->d_stage, &w->stage_cap, pre[0] + 16) || !h2_grow(&w->d_recs, &w->recs_cap, pre[0] + 1) ||
-      !h2_grow(&w->d_outs, &w->outs_cap, nouts))
-    return -GRDMA_ERR_HIP;
-  scratch = {w->d_stage, w->stage_cap, w->d_recs, w->recs_cap, w->d_outs, w->outs_cap, w->d_items, w->d_blks, std::min(w->items_cap, w->blks_cap)};
+  if (h2_hpack_too_many(pre)) return h2_invalid("h2 header decoder", "more than 2^30 bytes of header blocks in one call");
+  if (!h2_hpack_grow_scratch(w, pre, fields_cap)) return -GRDMA_ERR_HIP;
+  scratch = h2_hpack_scratch(w);
   const h2_stage stage = h2_stage_hpack_decode(w->d, w->d_call);
   h2_call c2{"grdma_h2_hpack_decode: a launch was rejected", {{d + offsetof(h2hp_dev, stage), &scratch, sizeof(scratch)}}, {}, {h2_all(stage)},
              {h2_result(out, w->d, offsetof(h2hp_dev, res))}};
   if (int rc = h2_call_run(hc, &c2)) return rc;
-  // (a cap overflow, 1: nothing was written or committed, the call is not taken and may be repeated)
-  h2_follow_ran(w, c1.ms[0] + c2.ms[0], out[H2HP_OVERFLOW] != 1);
-  if (out[H2HP_OVERFLOW] == 0) return (int64_t)out[H2HP_BLOCKS];
+  if (h2_hpack_ran(w, c1.ms[0] + c2.ms[0], out)) return (int64_t)out[H2HP_BLOCKS];
   if (out[H2HP_OVERFLOW] == 1)
     return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 header decoder: more blocks, fields or string bytes than the targets hold");
   return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 header decoder: the call's event list overflowed, its header blocks are lost");
+}
+
+// The decoders of many transports in the same six launches (h2_stage_hpack_links_gather, h2_stage_hpack_links_decode).
+// The batch block of the process holds [table | one call block per item] (the writer batch's shape) and goes up in one
+// copy; an item's targets and scratch words are the leading words of its decoder's own device block, its gather's
+// figures and its result words come down from there.  Two runs, as the single call's two steps: the gathers, then --
+// every decoder's scratch sized by its own figure, its scratch words sent again only where that grew something -- the other
+// stages.  One call at a time, as the other batch calls.
+int grdma_h2_hpack_decode_batch(const grdma_h2_hpack_item* items, uint32_t n_items, uint64_t* out) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  h2_batch b{"h2 header decoder batch", "decoder", "h2 header decoder batch: a launch was rejected"};
+  if (int rc = b.begin(items && out, n_items)) return rc;
+  for (uint32_t i = 0; i < n_items; i++)
+    if (int rc = b.item(items[i].hpack, h2_hpack_refusal(items[i]))) return rc;
+  if (int rc = b.open(sizeof(h2hp_link), sizeof(h2hp_call), n_items)) return rc;
+  auto* tab = reinterpret_cast<h2hp_link*>(b.up.data());
+  auto* calls = reinterpret_cast<h2hp_call*>(b.up.data() + b.blocks);
+  struct head { h2hp_target target; h2hp_scratch scratch; };  // (side by side in the device block: one copy)
+  static_assert(sizeof(head) == offsetof(h2hp_dev, carry_buf) && offsetof(head, scratch) == offsetof(h2hp_dev, stage), "layout");
+  std::vector<head> heads(n_items);
+  std::vector<uint64_t> pre(4 * (size_t)n_items, 0);
+  for (uint32_t i = 0; i < n_items; i++) {
+    grdma_h2_hpack* w = items[i].hpack;
+    if (!h2_hpack_grow_items(w)) return -GRDMA_ERR_HIP;
+    calls[i] = h2_follow_deframed(*w);
+    tab[i] = {w->d, reinterpret_cast<const h2hp_call*>(b.d + b.blocks) + i};
+    heads[i] = {h2_hpack_target(items[i]), h2_hpack_scratch(w)};
+    b.c.up.push_back({w->d, &heads[i], sizeof(head)});
+    b.c.down.push_back(h2_result(&pre[4 * (size_t)i], w->d, offsetof(h2hp_dev, pre), 4));
+    b.behind.push_back(w->parser);
+  }
+  const h2hp_link* d_tab = reinterpret_cast<const h2hp_link*>(b.d);
+  const h2_stage gather = h2_stage_hpack_links_gather(d_tab, n_items);
+  if (int rc = b.run({h2_all(gather)})) return rc;
+  const float gather_ms = b.c.ms[0];
+  for (uint32_t i = 0; i < n_items; i++)
+    if (h2_hpack_too_many(&pre[4 * (size_t)i])) return h2_invalid(b.who, "more than 2^30 bytes of header blocks in one item's call");
+  b.next();
+  for (uint32_t i = 0; i < n_items; i++) {
+    grdma_h2_hpack* w = items[i].hpack;
+    if (!h2_hpack_grow_scratch(w, &pre[4 * (size_t)i], items[i].fields_cap)) return -GRDMA_ERR_HIP;
+    const h2hp_scratch grown = h2_hpack_scratch(w);
+    if (memcmp(&grown, &heads[i].scratch, sizeof(grown)) != 0) {  // (a decoder that has served such a call has room already)
+      heads[i].scratch = grown;
+      b.c.up.push_back({reinterpret_cast<uint8_t*>(w->d) + offsetof(h2hp_dev, stage), &heads[i].scratch, sizeof(h2hp_scratch)});
+    }
+    b.c.down.push_back(h2_result(out + 8 * (size_t)i, w->d, offsetof(h2hp_dev, res)));
+  }
+  const h2_stage stage = h2_stage_hpack_links_decode(d_tab, n_items);
+  if (int rc = b.run({h2_all(stage)})) return rc;
+  int ok = 0;
+  for (uint32_t i = 0; i < n_items; i++)
+    ok += h2_hpack_ran(items[i].hpack, gather_ms + b.c.ms[0], out + 8 * (size_t)i);  // (the time: the batch's, repeated)
+  return ok;
 }
 
 int grdma_h2_hpack_table(grdma_h2_hpack* w, void* host_buf, uint64_t cap, uint64_t out[4]) {

@@ -36,7 +36,7 @@
 // and k_h2_hpack_resize, one thread, for grdma_h2_hpack_set_max_table_size.
 // No global atomic: order comes from prefix sums and from the one thread of the walk.  Kernel boundaries are the only
 // agent-scope hand-over.  The stages' bodies are source text (csrc/grdma_h2_hpack_stage.inc), laid out as the control-
-// reply writer's, so that a family over a table of links can include the same text.
+// reply writer's; the k_h2_links_hpack_* kernels at the end of the file include the same text over a table of links.
 #ifndef GRDMA_H2_HPACK_H
 #define GRDMA_H2_HPACK_H
 #include "grdma_h2_kernels.h"
@@ -306,6 +306,86 @@ __global__ __launch_bounds__(H2HP_THREADS) void k_h2_hpack_commit(h2hp_dev* F, c
 }
 __global__ __launch_bounds__(64) void k_h2_hpack_resize(h2hp_dev* F) {
 #define H2HP_STAGE 7
+#include "grdma_h2_hpack_stage.inc"
+#undef H2HP_STAGE
+}
+#undef H2HP_BLK
+#undef H2HP_NBLK
+
+// ---- the six stages over a table of L <= H2HP_LINKS_MAX links: six launches however many links.  Nothing is shared
+// between the links: every entry has its own h2hp_dev (targets, scratch, carry, ring, counters, result block) and its own
+// call block, so a sticky error, a lost call, a deframer error, a cap overflow or an empty event list stay with their
+// link, and each link commits or refuses as its single call would.  The gather and the walk run one workgroup per link
+// (the walk's LDS lets two links share a compute unit); in the grid stages link l owns the workgroups
+// [l * H2HP_LINK_GRID, (l + 1) * H2HP_LINK_GRID).  There is no resize over links.
+#define H2HP_LINKS_MAX 256  // (= GRDMA_H2_BATCH_MAX, include/grdma_amd.h)
+#ifdef GRDMA_WAVE_EMU
+#define H2HP_LINK_GRID 2
+#else
+#define H2HP_LINK_GRID 4    // (256 links: 1024 workgroups, four to a compute unit)
+#endif
+struct h2hp_link {
+  h2hp_dev* F;
+  const h2hp_call* call;
+};
+// (the table is written by the host in front of the launch and only read on the device: constant memory, as H2CTL_ENTRY)
+#ifdef GRDMA_WAVE_EMU
+#define H2HP_ENTRY(tab, l) ((tab)[l])
+#else
+#define H2HP_ENTRY(tab, l) (((const __attribute__((address_space(4))) h2hp_link*)(tab))[l])
+#endif
+
+#define H2HP_BLK (blockIdx.x % H2HP_LINK_GRID)
+#define H2HP_NBLK H2HP_LINK_GRID
+__global__ __launch_bounds__(H2HP_THREADS) void k_h2_links_hpack_gather(const h2hp_link* __restrict__ tab, uint32_t nlinks) {
+  if (blockIdx.x >= nlinks) return;
+  h2hp_dev* const F = H2HP_ENTRY(tab, blockIdx.x).F;
+  const h2hp_call* const call = H2HP_ENTRY(tab, blockIdx.x).call;
+#define H2HP_STAGE 1
+#include "grdma_h2_hpack_stage.inc"
+#undef H2HP_STAGE
+}
+__global__ __launch_bounds__(H2HP_THREADS) void k_h2_links_hpack_copy(const h2hp_link* __restrict__ tab, uint32_t nlinks) {
+  const uint32_t l = blockIdx.x / H2HP_LINK_GRID;
+  if (l >= nlinks) return;
+  h2hp_dev* const F = H2HP_ENTRY(tab, l).F;
+  const h2hp_call* const call = H2HP_ENTRY(tab, l).call;
+#define H2HP_STAGE 2
+#include "grdma_h2_hpack_stage.inc"
+#undef H2HP_STAGE
+}
+__global__ __launch_bounds__(H2HP_THREADS) void k_h2_links_hpack_split(const h2hp_link* __restrict__ tab, uint32_t nlinks) {
+  const uint32_t l = blockIdx.x / H2HP_LINK_GRID;
+  if (l >= nlinks) return;
+  h2hp_dev* const F = H2HP_ENTRY(tab, l).F;
+  const h2hp_call* const call = H2HP_ENTRY(tab, l).call;
+#define H2HP_STAGE 3
+#include "grdma_h2_hpack_stage.inc"
+#undef H2HP_STAGE
+}
+__global__ __launch_bounds__(H2HP_THREADS) void k_h2_links_hpack_walk(const h2hp_link* __restrict__ tab, uint32_t nlinks) {
+  if (blockIdx.x >= nlinks) return;
+  h2hp_dev* const F = H2HP_ENTRY(tab, blockIdx.x).F;
+  const h2hp_call* const call = H2HP_ENTRY(tab, blockIdx.x).call;
+#define H2HP_STAGE 4
+#include "grdma_h2_hpack_stage.inc"
+#undef H2HP_STAGE
+}
+__global__ __launch_bounds__(H2HP_THREADS) void k_h2_links_hpack_emit(const h2hp_link* __restrict__ tab, uint32_t nlinks) {
+  const uint32_t l = blockIdx.x / H2HP_LINK_GRID;
+  if (l >= nlinks) return;
+  h2hp_dev* const F = H2HP_ENTRY(tab, l).F;
+  const h2hp_call* const call = H2HP_ENTRY(tab, l).call;
+#define H2HP_STAGE 5
+#include "grdma_h2_hpack_stage.inc"
+#undef H2HP_STAGE
+}
+__global__ __launch_bounds__(H2HP_THREADS) void k_h2_links_hpack_commit(const h2hp_link* __restrict__ tab, uint32_t nlinks) {
+  const uint32_t l = blockIdx.x / H2HP_LINK_GRID;
+  if (l >= nlinks) return;
+  h2hp_dev* const F = H2HP_ENTRY(tab, l).F;
+  const h2hp_call* const call = H2HP_ENTRY(tab, l).call;
+#define H2HP_STAGE 6
 #include "grdma_h2_hpack_stage.inc"
 #undef H2HP_STAGE
 }

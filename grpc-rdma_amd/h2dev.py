@@ -71,6 +71,11 @@ class H2CtlItem(C.Structure):
                 ("hdr_cap", u64)]
 
 
+class H2HpackItem(C.Structure):
+    _fields_ = [("hpack", C.c_void_p), ("d_blocks", C.c_void_p), ("blocks_cap", u64), ("d_fields", C.c_void_p),
+                ("fields_cap", u64), ("d_strings", C.c_void_p), ("strings_cap", u64)]
+
+
 MSG_OK, MSG_TOO_LARGE, MSG_NO_SPACE, MSG_TRUNCATED = 0, 1, 2, 3
 SYNC_KEYS = ("framed", "frame_overflow", "events", "deframe_overflow", "parsed", "h2_error", "frame_us", "deframe_us",
              "bulk_steps", "bulk_frames", "t_wait", "t_bulk", "t_total", "t_serial")
@@ -302,6 +307,8 @@ def _bind():
         lib.grdma_h2_hpack_table.argtypes = [C.c_void_p, C.c_void_p, u64, C.POINTER(u64)]
         lib.grdma_h2_hpack_stats.restype = C.c_int
         lib.grdma_h2_hpack_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
+        lib.grdma_h2_hpack_decode_batch.restype = C.c_int
+        lib.grdma_h2_hpack_decode_batch.argtypes = [C.POINTER(H2HpackItem), C.c_uint32, C.POINTER(u64)]
         lib.grdma_job_hook_counts.restype = C.c_int   # (not in include/grdma_amd.h: the job's side of the pipes)
         lib.grdma_job_hook_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         _bound = True
@@ -983,6 +990,28 @@ class HeaderDecoder:
         if self.h:
             self.lib.grdma_h2_hpack_destroy(self.h)
             self.h = None
+
+
+def decode_batch(items):
+    """HeaderDecoder.decode for many transports in six launches (grdma_h2_hpack_decode_batch).  items: [(HeaderDecoder,
+    blocks device ptr, blocks cap, fields device ptr, fields cap, strings device ptr, strings cap), ...] with distinct
+    decoders; each decodes the last standalone deframing of its own parser into its own targets.  -> (the number of items
+    without overflow, [result tuple (HeaderDecoder.RESULT) per item]); an item whose call was lost or overflowed a cap
+    reports for itself in its tuple (overflow word 2 / 1: after 1 nothing of it was written or committed and it may be
+    repeated, alone or in a later batch).  The result tuples also land in each decoder's .last_result.  Raises
+    GrdmaError only on a refusal."""
+    lib = _bind()
+    n = len(items)
+    arr = (H2HpackItem * max(1, n))()
+    for i, item in enumerate(items):
+        if item is None:
+            continue
+        dec, *target = item
+        arr[i].hpack = dec.h if dec is not None else None
+        (arr[i].d_blocks, arr[i].blocks_cap, arr[i].d_fields, arr[i].fields_cap, arr[i].d_strings, arr[i].strings_cap) = target
+    out = (u64 * (8 * max(1, n)))()
+    count = check(lib.grdma_h2_hpack_decode_batch(arr, n, out))
+    return count, _results(out, [item[0] for item in items])
 
 
 def control_batch(items):

@@ -1207,9 +1207,19 @@ int grdma_h2_ctl_reply_batch(const grdma_h2_ctl_item* items, uint32_t n, uint64_
  *    may be repeated with larger targets while the deframing's buffers stand.
  * -GRDMA_ERR_INVALID or NULL (grdma_last_error says why; nothing runs, nothing changes): a second decoder on a parser,
  * max_table_size above 65536, max_block_bytes outside 64 .. 2^20, no call yet or a call taken in already, a parser that
- * is gone (destroy still works), null, zero or misaligned (16 bytes) targets.
- * Not here: the HPACK encoder, the decoder over a table of links or inside a pipe, gRPC's metadata validation,
- * SETTINGS_MAX_HEADER_LIST_SIZE, PUSH_PROMISE. */
+ * is gone (destroy still works), null, zero or misaligned (16 bytes) targets; in the batch n outside 1 ..
+ * GRDMA_H2_BATCH_MAX, a NULL item array, result array or decoder, the same decoder twice.
+ * MANY LINKS.  grdma_h2_hpack_decode_batch is grdma_h2_hpack_decode for n decoders (1 .. GRDMA_H2_BATCH_MAX) in six
+ * launches however many (k_h2_links_hpack_*): the gather of every link, one host step that sizes each decoder's own
+ * scratch by its own figure, the five other stages of every link.  Every item decodes the last standalone deframing of
+ * its OWN parser into its own targets against its own table, by rules 1 to 6 exactly as the single call does; the call
+ * is ordered behind every listed parser.  out: 8 result words per item, in item order.  A sticky error, a lost call, a
+ * deframer error or an overflow (word 1: not taken, may be repeated alone or in a later batch; word 2: lost) stay with
+ * the item, the other items are exact; the return value is the number of items whose overflow word is 0, or a negative
+ * error.  An item whose deframing holds more than 2^30 header bytes refuses the whole call (-GRDMA_ERR_INVALID) behind
+ * the gather, which commits nothing: nothing is taken.  set_max_table_size stays per decoder.
+ * Not here: the HPACK encoder, the decoder inside a pipe, gRPC's metadata validation, SETTINGS_MAX_HEADER_LIST_SIZE,
+ * PUSH_PROMISE. */
 enum grdma_h2_hpack_flag { GRDMA_H2_HPACK_FAILED = 1, GRDMA_H2_HPACK_LOST = 2, GRDMA_H2_HPACK_OPEN = 4 /* a block is cut by the call's end */ };
 enum grdma_h2_hpack_error {
   GRDMA_H2_HPACK_ERR_PADDING = 1, GRDMA_H2_HPACK_ERR_BLOCK_TOO_LARGE = 2, GRDMA_H2_HPACK_ERR_INTEGER = 3, GRDMA_H2_HPACK_ERR_TRUNCATED = 4,
@@ -1234,6 +1244,16 @@ int grdma_h2_hpack_table(grdma_h2_hpack* hpack, void* host_buf, uint64_t cap, ui
 /* {calls taken, blocks, fields, string bytes, inserts, evictions, the sticky flags word, kernel time of the last call in
  * NANOseconds (HIP events)} */
 int grdma_h2_hpack_stats(grdma_h2_hpack* hpack, uint64_t out[8]);
+typedef struct grdma_h2_hpack_item {
+  grdma_h2_hpack* hpack;            /* distinct */
+  grdma_h2_header_block* d_blocks;  /* the item's device targets, as grdma_h2_hpack_decode's */
+  uint64_t blocks_cap;
+  grdma_h2_header_field* d_fields;
+  uint64_t fields_cap;
+  void* d_strings;
+  uint64_t strings_cap;
+} grdma_h2_hpack_item;
+int grdma_h2_hpack_decode_batch(const grdma_h2_hpack_item* items, uint32_t n_items, uint64_t* out /* 8 words per item */);
 
 /* ---- HTTP/2 on several links of ONE job (the group pipe) ----
  * grdma_h2_pipe serves one link, and a job carries one set of kernels in front of and behind its rounds: a second
@@ -1250,7 +1270,7 @@ int grdma_h2_hpack_stats(grdma_h2_hpack* hpack, uint64_t out[8]);
  * Create returns NULL (grdma_last_error says why) for: n == 0, a link index out of range or listed twice, a parser
  * listed twice, nmsgs 0 or above 4096, max_frame 0 or >= 2^24, a job that already carries such kernels (another pipe).
  * Not here (yet): the chunked deframer inside the batch (every transport is parsed sequentially), the HPACK encoder and the
- * header decoder over a table of links (one transport's: grdma_h2_hpack above).  A parser
+ * header decoder inside the group pipe (standalone, one transport's or many links': grdma_h2_hpack above).  A parser
  * that has a window ledger at create time is refused: ledgers come later, grdma_h2_group_pipe_attach_flow_control. */
 typedef struct grdma_h2_link_spec {
   uint32_t link;                 /* index into the job's links; distinct */
