@@ -36,6 +36,7 @@
 #include "grdma_h2_wr.h"
 #include "grdma_h2_ctl.h"
 #include "grdma_h2_hpack.h"
+#include "grdma_h2_hpenc.h"
 #include "grdma_h2_block.h"
 
 // --------------------------------------------------------------------- host API
@@ -324,6 +325,13 @@ static h2_stage h2_stage_hpack_links_decode(const h2hp_link* d_tab, uint32_t n) 
           h2_rec(k_h2_links_hpack_walk, n, H2HP_THREADS, d_tab, n),
           h2_rec(k_h2_links_hpack_emit, n * H2HP_LINK_GRID, H2HP_THREADS, d_tab, n),
           h2_rec(k_h2_links_hpack_commit, n * H2HP_LINK_GRID, H2HP_THREADS, d_tab, n)};
+}
+
+// The header encoder (csrc/grdma_h2_hpenc.h): it belongs to no parser.  Three sections, timed apart: scan, walk, emit and
+// commit.
+static h2_stage h2_stage_hpenc(h2he_dev* d) {
+  return {h2_rec(k_h2_hpenc_scan, H2HE_GRID, H2HE_THREADS, d), h2_rec(k_h2_hpenc_walk, 1, H2HE_THREADS, d),
+          h2_rec(k_h2_hpenc_emit, H2HE_GRID, H2HE_THREADS, d), h2_rec(k_h2_hpenc_commit, H2HE_GRID, H2HE_THREADS, d)};
 }
 
 // st goes behind the parser's last deframing by a pipe (the parser state is handed from one deframing to the next),

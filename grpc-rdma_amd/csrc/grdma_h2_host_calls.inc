@@ -1891,6 +1891,186 @@ int grdma_h2_hpack_stats(grdma_h2_hpack* w, uint64_t out[8]) {
   return 0;
 }
 
+// ---- header blocks, sending: the HPACK encoder on the device (csrc/grdma_h2_hpenc.h) ----------------------------------------
+// The encoder follows no parser: its input is three device tables of the caller.  The peer's settings live on the host
+// until a call that sends a block takes them in (a refused call leaves them pending); a call is one run of the stage,
+// repeated once where the occurrence table was too small (blocks may share fields: only the device can count them).
+struct grdma_h2_hpenc {
+  h2he_dev* d = nullptr;
+  h2he_rec* d_recs = nullptr;
+  uint64_t recs_cap = 0;
+  h2he_occ* d_occs = nullptr;
+  uint64_t occs_cap = 0;
+  h2he_blk* d_blks = nullptr;
+  uint64_t blks_cap = 0;
+  uint32_t cur = 0, want = 0, low = 0;  // the limit the peer's decoder is at; what the peer asked for; the lowest since the last block
+  uint32_t max_frame = 0;
+  float ms[3] = {0, 0, 0};  // of the last call: scan, walk, emit and commit
+};
+static_assert(sizeof(h2he_wire_out) == sizeof(grdma_h2_header_wire) && H2HE_F_BAD_INPUT == GRDMA_H2_HPENC_BAD_INPUT &&
+              H2HE_E_FIELD_RANGE == GRDMA_H2_HPENC_ERR_FIELD_RANGE && H2HE_E_BLOCK_TOO_LARGE == GRDMA_H2_HPENC_ERR_BLOCK_TOO_LARGE, "layout");
+static_assert(offsetof(h2he_dev, c) == 0 && sizeof(h2he_huff_code) == sizeof(((h2he_dev*)0)->huff_code) &&
+              sizeof(h2he_huff_bits) == sizeof(((h2he_dev*)0)->huff_bits) && sizeof(h2he_static_name_hash) == sizeof(((h2he_dev*)0)->st_hn) &&
+              sizeof(h2he_static_full_hash) == sizeof(((h2he_dev*)0)->st_hf) && sizeof(h2hp_static_off) == sizeof(((h2he_dev*)0)->st_off) &&
+              sizeof(h2hp_static_bytes) == sizeof(((h2he_dev*)0)->st_bytes), "the call's words lead the block; the tables as they are uploaded");
+
+static const char* h2_hpenc_bad_peer(uint32_t peer_table_size, uint32_t peer_max_frame) {
+  if (peer_table_size > H2HP_MAX_TABLE) return "peer_table_size above 65536";
+  if (peer_max_frame < 16384u || peer_max_frame > 0xffffffu) return "peer_max_frame outside 16384 .. 2^24 - 1";
+  return nullptr;
+}
+
+grdma_h2_hpenc* grdma_h2_hpenc_create(uint32_t peer_table_size, uint32_t peer_max_frame) {
+  if (grdma_device_count() <= 0) return nullptr;
+  if (const char* why = h2_hpenc_bad_peer(peer_table_size, peer_max_frame)) {
+    h2_invalid("h2 header encoder", why);
+    return nullptr;
+  }
+  grdma_h2_hpenc* w = new grdma_h2_hpenc();
+  // (RFC 7541 4.2: both sides begin at 4096 or at the peer's setting where that is less; more is announced in the first block)
+  w->cur = w->low = peer_table_size < 4096u ? peer_table_size : 4096u;
+  w->want = peer_table_size;
+  w->max_frame = peer_max_frame;
+  bool ok = hipMalloc((void**)&w->d, sizeof(h2he_dev)) == hipSuccess && hipMemset(w->d, 0, sizeof(h2he_dev)) == hipSuccess;
+  if (ok) {
+    uint8_t* d = reinterpret_cast<uint8_t*>(w->d);
+    ok = hipMemcpy(d + offsetof(h2he_dev, cur_max), &w->cur, sizeof(w->cur), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + offsetof(h2he_dev, huff_code), h2he_huff_code, sizeof(h2he_huff_code), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + offsetof(h2he_dev, huff_bits), h2he_huff_bits, sizeof(h2he_huff_bits), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + offsetof(h2he_dev, st_hn), h2he_static_name_hash, sizeof(h2he_static_name_hash), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + offsetof(h2he_dev, st_hf), h2he_static_full_hash, sizeof(h2he_static_full_hash), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + offsetof(h2he_dev, st_off), h2hp_static_off, sizeof(h2hp_static_off), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + offsetof(h2he_dev, st_bytes), h2hp_static_bytes, sizeof(h2hp_static_bytes), hipMemcpyHostToDevice) == hipSuccess;
+  }
+  if (!ok) {
+    (void)hipGetLastError();
+    grdma_h2_hpenc_destroy(w);
+    grdma_fail_msg(GRDMA_ERR_HIP, "h2 header encoder: device allocation failed");
+    return nullptr;
+  }
+  return w;
+}
+
+void grdma_h2_hpenc_destroy(grdma_h2_hpenc* w) {
+  if (!w) return;
+  h2_host_ctx* hc = h2_ctx();
+  if (hc) hipStreamSynchronize(hc->stream);  // (standalone calls)
+  hipFree(w->d_blks);
+  hipFree(w->d_occs);
+  hipFree(w->d_recs);
+  hipFree(w->d);
+  delete w;
+}
+
+int grdma_h2_hpenc_set_peer(grdma_h2_hpenc* w, uint32_t peer_table_size, uint32_t peer_max_frame) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!w) return h2_invalid("h2 header encoder", "no encoder");
+  if (const char* why = h2_hpenc_bad_peer(peer_table_size, peer_max_frame)) return h2_invalid("h2 header encoder", why);
+  w->want = peer_table_size;
+  w->low = std::min(w->low, peer_table_size);
+  w->max_frame = peer_max_frame;
+  return 0;
+}
+
+int64_t grdma_h2_hpenc_encode(grdma_h2_hpenc* w, const grdma_h2_header_block* d_blocks, uint64_t nblocks, const grdma_h2_header_field* d_fields,
+                              uint64_t nfields, const void* d_strings, uint64_t strings_bytes, void* d_wire, uint64_t wire_cap,
+                              grdma_h2_header_wire* d_block_wire, uint64_t block_wire_cap, uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  const char* who = "h2 header encoder";
+  if (!w) return h2_invalid(who, "no encoder");
+  if (!out) return h2_invalid(who, "no result array");
+  if (!d_wire || !wire_cap || !d_block_wire || !block_wire_cap || ((uintptr_t)d_wire & 15) || ((uintptr_t)d_block_wire & 15))
+    return h2_invalid(who, "a null, zero or misaligned wire arena or block-wire table");
+  if ((nblocks && !d_blocks) || (nfields && !d_fields) || (strings_bytes && !d_strings) || ((uintptr_t)d_blocks & 15) || ((uintptr_t)d_fields & 15))
+    return h2_invalid(who, "a null or misaligned block table, field table or string arena");
+  if (nblocks >= 0xffffffffull || nfields > 0xffffffffull || strings_bytes > (1ull << 32))
+    return h2_invalid(who, "more than 2^32 - 1 blocks or fields, or a string arena above 2^32 bytes");
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  if (!h2_grow(&w->d_recs, &w->recs_cap, nfields + 1) || !h2_grow(&w->d_blks, &w->blks_cap, nblocks + 2) ||
+      !h2_grow(&w->d_occs, &w->occs_cap, nfields + 64))
+    return -GRDMA_ERR_HIP;
+  uint64_t down[9];  // the result block and the occurrence count behind it
+  static_assert(offsetof(h2he_dev, nocc) == offsetof(h2he_dev, res) + 8 * sizeof(uint64_t), "one download");
+  const h2_stage stage = h2_stage_hpenc(w->d);
+  for (int attempt = 0;; attempt++) {
+    h2he_call call = {reinterpret_cast<const h2hp_block_out*>(d_blocks), nblocks, reinterpret_cast<const h2hp_field_out*>(d_fields), nfields,
+                      static_cast<const uint8_t*>(d_strings), strings_bytes, static_cast<uint8_t*>(d_wire), wire_cap,
+                      reinterpret_cast<h2he_wire_out*>(d_block_wire), block_wire_cap, w->d_recs, w->recs_cap, w->d_occs, w->occs_cap,
+                      w->d_blks, w->blks_cap, w->max_frame, 0, {0, 0}};
+    if (w->low < w->want && w->low < w->cur) {  // lowered, then raised: the smallest since the last block, then the final one (4.2)
+      call.nupd = 2;
+      call.upd[0] = w->low;
+      call.upd[1] = w->want;
+    } else if (w->want != w->cur) {
+      call.nupd = 1;
+      call.upd[0] = w->want;
+    }
+    h2_call c{"grdma_h2_hpenc_encode: a launch was rejected", {{w->d, &call, sizeof(call)}}, {},
+              {{stage.data(), 1}, {stage.data() + 1, 1}, {stage.data() + 2, 2}}, {h2_result(down, w->d, offsetof(h2he_dev, res), 9)}};
+    if (int rc = h2_call_run(hc, &c)) return rc;
+    for (int k = 0; k < 3; k++) w->ms[k] = c.ms[k];
+    if (down[H2HE_OVERFLOW] != H2HE_OVER_SCRATCH) break;
+    if (attempt || down[8] >= 0xffffffffull) return h2_invalid(who, "more than 2^32 - 1 fields in the call's blocks");
+    if (!h2_grow(&w->d_occs, &w->occs_cap, down[8] + 64)) return -GRDMA_ERR_HIP;
+  }
+  for (int k = 0; k < 8; k++) out[k] = down[k];
+  if (out[H2HE_FLAGS] & H2HE_F_BAD_INPUT) return h2_invalid(who, "bad input: a block's fields, a string, a stream id or a length (the result block says which block)");
+  if (out[H2HE_OVERFLOW])
+    return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 header encoder: more wire bytes or blocks than the targets hold");
+  if (nblocks) w->cur = w->low = w->want;  // (the block that said so is out)
+  return (int64_t)out[H2HE_FRAMES];
+}
+
+int grdma_h2_hpenc_table(grdma_h2_hpenc* w, void* host_buf, uint64_t cap, uint64_t out[4]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!w || !out || (!host_buf && cap)) return -GRDMA_ERR_INVALID;
+  uint32_t st[4];  // size limit, bytes, entries, insertions
+  std::vector<uint32_t> nl(H2HP_RING), vl(H2HP_RING), src(H2HP_RING);
+  std::vector<uint8_t> bytes(H2HP_BYTES);
+  const uint8_t* d = reinterpret_cast<const uint8_t*>(w->d);
+  if (!h2_read(st, d + offsetof(h2he_dev, cur_max), sizeof(st)) || !h2_read(nl.data(), d + offsetof(h2he_dev, r_nl), 4 * H2HP_RING) ||
+      !h2_read(vl.data(), d + offsetof(h2he_dev, r_vl), 4 * H2HP_RING) || !h2_read(src.data(), d + offsetof(h2he_dev, r_src), 4 * H2HP_RING) ||
+      !h2_read(bytes.data(), d + offsetof(h2he_dev, bytes), H2HP_BYTES))
+    return -GRDMA_ERR_HIP;
+  const uint32_t cnt = st[2] < H2HP_RING ? st[2] : H2HP_RING;
+  uint64_t need = 0;
+  for (uint32_t q = 0; q < cnt; q++) {
+    const uint32_t slot = (st[3] - 1u - q) & (H2HP_RING - 1u);
+    need += 8ull + nl[slot] + vl[slot];
+  }
+  out[0] = cnt;
+  out[1] = need;
+  out[2] = st[1];
+  out[3] = st[0];
+  if (need > cap) return -GRDMA_ERR_CAPACITY;
+  uint8_t* o = static_cast<uint8_t*>(host_buf);
+  for (uint32_t q = 0; q < cnt; q++) {  // newest first: name length, value length, name, value (grdma_h2_hpack_table's format)
+    const uint32_t slot = (st[3] - 1u - q) & (H2HP_RING - 1u);
+    memcpy(o, &nl[slot], 4);
+    memcpy(o + 4, &vl[slot], 4);
+    o += 8;
+    for (uint32_t k = 0; k < nl[slot] + vl[slot]; k++) *o++ = bytes[(src[slot] + k) & (H2HP_BYTES - 1u)];
+  }
+  return 0;
+}
+
+int grdma_h2_hpenc_stats(grdma_h2_hpenc* w, uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!w || !out) return -GRDMA_ERR_INVALID;
+  // calls, blocks, fields, header-list bytes in, wire bytes out, inserts, evictions
+  if (!h2_read(out, reinterpret_cast<const uint8_t*>(w->d) + offsetof(h2he_dev, st_calls), 7 * sizeof(uint64_t))) return -GRDMA_ERR_HIP;
+  out[7] = (uint64_t)((w->ms[0] + w->ms[1] + w->ms[2]) * 1e6f);
+  return 0;
+}
+
+int grdma_h2_hpenc_last_stages(grdma_h2_hpenc* w, uint64_t out[4]) {
+  if (!w || !out) return -GRDMA_ERR_INVALID;
+  for (int k = 0; k < 3; k++) out[k] = (uint64_t)(w->ms[k] * 1e6f);
+  out[3] = out[0] + out[1] + out[2];
+  return 0;
+}
+
 // ---- the message assembler on many links (h2_stage_asm_links, csrc/grdma_h2_asm.h) ---------------------------------
 namespace {
 // the pinned table of grdma_h2_asm_release_batch with the event of its last upload (the table is reused: the next call

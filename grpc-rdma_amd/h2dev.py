@@ -309,6 +309,20 @@ def _bind():
         lib.grdma_h2_hpack_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
         lib.grdma_h2_hpack_decode_batch.restype = C.c_int
         lib.grdma_h2_hpack_decode_batch.argtypes = [C.POINTER(H2HpackItem), C.c_uint32, C.POINTER(u64)]
+        lib.grdma_h2_hpenc_create.restype = C.c_void_p
+        lib.grdma_h2_hpenc_create.argtypes = [C.c_uint32, C.c_uint32]
+        lib.grdma_h2_hpenc_destroy.argtypes = [C.c_void_p]
+        lib.grdma_h2_hpenc_set_peer.restype = C.c_int
+        lib.grdma_h2_hpenc_set_peer.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        lib.grdma_h2_hpenc_encode.restype = C.c_int64
+        lib.grdma_h2_hpenc_encode.argtypes = [C.c_void_p, C.c_void_p, u64, C.c_void_p, u64, C.c_void_p, u64, C.c_void_p, u64, C.c_void_p, u64,
+                                              C.POINTER(u64)]
+        lib.grdma_h2_hpenc_table.restype = C.c_int
+        lib.grdma_h2_hpenc_table.argtypes = [C.c_void_p, C.c_void_p, u64, C.POINTER(u64)]
+        lib.grdma_h2_hpenc_stats.restype = C.c_int
+        lib.grdma_h2_hpenc_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
+        lib.grdma_h2_hpenc_last_stages.restype = C.c_int
+        lib.grdma_h2_hpenc_last_stages.argtypes = [C.c_void_p, C.POINTER(u64)]
         lib.grdma_job_hook_counts.restype = C.c_int   # (not in include/grdma_amd.h: the job's side of the pipes)
         lib.grdma_job_hook_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         _bound = True
@@ -965,18 +979,7 @@ class HeaderDecoder:
 
     def table(self):
         """the live dynamic table -> ([(name, value), ...] newest first, (entries, table bytes, the size limit in force))"""
-        out = (u64 * 4)()
-        rc = self.lib.grdma_h2_hpack_table(self.h, None, 0, out)
-        if rc and not out[1]:
-            check(rc)
-        buf = C.create_string_buffer(max(1, int(out[1])))
-        check(self.lib.grdma_h2_hpack_table(self.h, buf, int(out[1]), out))
-        raw, pos, entries = buf.raw, 0, []
-        for _ in range(int(out[0])):
-            nl, vl = int.from_bytes(raw[pos:pos + 4], "little"), int.from_bytes(raw[pos + 4:pos + 8], "little")
-            entries.append((raw[pos + 8:pos + 8 + nl], raw[pos + 8 + nl:pos + 8 + nl + vl]))
-            pos += 8 + nl + vl
-        return entries, (int(out[0]), int(out[2]), int(out[3]))
+        return _table_dump(self.lib.grdma_h2_hpack_table, self.h)
 
     def stats(self):
         """dict of STATS; `flags`: the sticky word (FAILED | LOST, error << 8, stream << 32)"""
@@ -989,6 +992,79 @@ class HeaderDecoder:
     def close(self):
         if self.h:
             self.lib.grdma_h2_hpack_destroy(self.h)
+            self.h = None
+
+
+def _table_dump(call, h):
+    """a dynamic table through grdma_h2_hpack_table / grdma_h2_hpenc_table -> ([(name, value)] newest first, (entries,
+    table bytes, the size limit in force))"""
+    out = (u64 * 4)()
+    rc = call(h, None, 0, out)
+    if rc and not out[1]:
+        check(rc)
+    buf = C.create_string_buffer(max(1, int(out[1])))
+    check(call(h, buf, int(out[1]), out))
+    raw, pos, entries = buf.raw, 0, []
+    for _ in range(int(out[0])):
+        nl, vl = int.from_bytes(raw[pos:pos + 4], "little"), int.from_bytes(raw[pos + 4:pos + 8], "little")
+        entries.append((raw[pos + 8:pos + 8 + nl], raw[pos + 8 + nl:pos + 8 + nl + vl]))
+        pos += 8 + nl + vl
+    return entries, (int(out[0]), int(out[2]), int(out[3]))
+
+
+class HeaderEncoder:
+    """Header lists encoded on the device (grdma_h2_hpenc): a block table, a field table and a string arena in device
+    memory -- the layout HeaderDecoder writes -- into the wire bytes of HEADERS and CONTINUATION frames, against the
+    peer's dynamic table.  One per connection; it follows no parser."""
+
+    RESULT = ("blocks", "frames", "wire_bytes", "inserted", "evicted", "table_bytes", "flags", "overflow")
+    STATS = ("calls", "blocks", "fields", "list_bytes", "wire_bytes", "inserted", "evicted", "kernel_us")
+    BAD_INPUT = 1
+    ERRORS = (None, "field range", "stream", "length", "string", "block too large")
+
+    def __init__(self, peer_table_size=4096, peer_max_frame=16384):
+        self.lib = _bind()
+        self.h = self.lib.grdma_h2_hpenc_create(peer_table_size, peer_max_frame)
+        if not self.h:
+            raise GrdmaError("h2 header encoder: " + (self.lib.grdma_last_error() or b"creation failed").decode())
+        self.last_result = None
+
+    def set_peer(self, peer_table_size, peer_max_frame):
+        """the peer's SETTINGS_HEADER_TABLE_SIZE and SETTINGS_MAX_FRAME_SIZE from now on; the next call that sends a block
+        opens it with the size update(s)"""
+        check(self.lib.grdma_h2_hpenc_set_peer(self.h, peer_table_size, peer_max_frame))
+
+    def encode(self, blocks_ptr, nblocks, fields_ptr, nfields, strings_ptr, strings_bytes, wire_ptr, wire_cap, block_wire_ptr, block_wire_cap):
+        """-> (frame count, result tuple (RESULT)); raises GrdmaError on a refusal, on bad input (flags: BAD_INPUT | error
+        << 8 | block << 32) and on a capacity overflow (overflow word 1: nothing was written or committed, the call may
+        be repeated with larger targets) -- the result of the failed call stays in .last_result"""
+        out = (u64 * 8)()
+        self.last_result = None
+        n = self.lib.grdma_h2_hpenc_encode(self.h, blocks_ptr, nblocks, fields_ptr, nfields, strings_ptr, strings_bytes, wire_ptr, wire_cap,
+                                           block_wire_ptr, block_wire_cap, out)
+        self.last_result = tuple(int(x) for x in out)
+        return check(n), self.last_result
+
+    def table(self):
+        """the encoder's view of the peer's dynamic table, as HeaderDecoder.table"""
+        return _table_dump(self.lib.grdma_h2_hpenc_table, self.h)
+
+    def stats(self):
+        out = (u64 * 8)()
+        check(self.lib.grdma_h2_hpenc_stats(self.h, out))
+        r = dict(zip(HeaderEncoder.STATS, [int(x) for x in out]))
+        r["kernel_us"] /= 1e3  # (the ABI word is nanoseconds)
+        return r
+
+    def last_stages(self):
+        """the last call's kernel time by stage, microseconds: (scan, walk, emit and commit, total)"""
+        out = (u64 * 4)()
+        check(self.lib.grdma_h2_hpenc_last_stages(self.h, out))
+        return tuple(int(x) / 1e3 for x in out)
+
+    def close(self):
+        if self.h:
+            self.lib.grdma_h2_hpenc_destroy(self.h)
             self.h = None
 
 

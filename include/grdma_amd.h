@@ -1144,7 +1144,7 @@ int grdma_h2_reply_frame_windowed_batch(grdma_h2_wr_item* items, uint32_t n);
  * max_replies outside 1 .. 2^24, no call yet or a call taken in already, a parser that is gone (destroy still works),
  * null, zero or misaligned (16 bytes) targets; in the batch n outside 1 .. GRDMA_H2_BATCH_MAX, a NULL item, the same
  * writer twice.
- * Not here: replies to a pipe's or group pipe's steps, the other settings, the HPACK encoder (the decoder: grdma_h2_hpack
+ * Not here: replies to a pipe's or group pipe's steps, the other settings (HPACK: grdma_h2_hpack and grdma_h2_hpenc
  * below). */
 enum grdma_h2_ctl_flag { GRDMA_H2_CTL_LOST = 1, GRDMA_H2_CTL_GOAWAY = 2 /* a GOAWAY completed in this call */ };
 typedef struct grdma_h2_ctl grdma_h2_ctl;
@@ -1218,8 +1218,8 @@ int grdma_h2_ctl_reply_batch(const grdma_h2_ctl_item* items, uint32_t n, uint64_
  * the item, the other items are exact; the return value is the number of items whose overflow word is 0, or a negative
  * error.  An item whose deframing holds more than 2^30 header bytes refuses the whole call (-GRDMA_ERR_INVALID) behind
  * the gather, which commits nothing: nothing is taken.  set_max_table_size stays per decoder.
- * Not here: the HPACK encoder, the decoder inside a pipe, gRPC's metadata validation, SETTINGS_MAX_HEADER_LIST_SIZE,
- * PUSH_PROMISE. */
+ * Not here: the decoder inside a pipe, gRPC's metadata validation, SETTINGS_MAX_HEADER_LIST_SIZE, PUSH_PROMISE.  (The
+ * HPACK encoder: "Header blocks, sending" below.) */
 enum grdma_h2_hpack_flag { GRDMA_H2_HPACK_FAILED = 1, GRDMA_H2_HPACK_LOST = 2, GRDMA_H2_HPACK_OPEN = 4 /* a block is cut by the call's end */ };
 enum grdma_h2_hpack_error {
   GRDMA_H2_HPACK_ERR_PADDING = 1, GRDMA_H2_HPACK_ERR_BLOCK_TOO_LARGE = 2, GRDMA_H2_HPACK_ERR_INTEGER = 3, GRDMA_H2_HPACK_ERR_TRUNCATED = 4,
@@ -1255,6 +1255,81 @@ typedef struct grdma_h2_hpack_item {
 } grdma_h2_hpack_item;
 int grdma_h2_hpack_decode_batch(const grdma_h2_hpack_item* items, uint32_t n_items, uint64_t* out /* 8 words per item */);
 
+/* ---- Header blocks, sending: the HPACK encoder on the device (csrc/grdma_h2_hpenc.h) ----
+ * Header lists in device memory encoded (RFC 7541) into the wire bytes of HEADERS and CONTINUATION frames: the response
+ * headers and the trailers around a reply's DATA, or a proxy's re-encoding of what it has just decoded against the next
+ * hop's dynamic table.  One header encoder per connection, resident in device memory; it belongs to no parser (it is the
+ * sending side).  The call is ordered on the stream of the standalone HTTP/2 calls: a grdma_h2_hpack_decode immediately
+ * in front of it needs no host synchronisation.  The sequential reference, which defines the exact bytes, is
+ * tests/h2_hpenc_model.py.
+ * 1. INPUT, all in device memory: nblocks grdma_h2_header_block, nfields grdma_h2_header_field and a string arena of
+ *    strings_bytes bytes -- exactly the decoder's OUTPUT layout.  Of a block: stream, first_field / nfields (blocks may
+ *    share fields), flags bit 0 END_STREAM, its other bits are ignored.  Of a field: name_len bits 24..31 are the
+ *    caller's HINT, of which the low two bits are read: 0 or 1 (indexable) -- indexed if a full match is live, else a
+ *    literal WITH incremental indexing, which is inserted; 2 -- indexed if a full match is live, else a literal without
+ *    indexing; 3 -- always a literal never-indexed, even when a full match is live (a sensitive value must not turn into
+ *    an index).  Decoder output therefore forwards unchanged.
+ * 2. MATCHING runs against the table as it stands in front of the field: the static table and the dynamic entries live
+ *    at that moment, those inserted by earlier fields of this call included.  Full match (name and value equal): the
+ *    lowest static index if there is one, else the NEWEST dynamic entry.  Name reference of a literal: the lowest static
+ *    index whose name is equal, else the newest dynamic entry whose name is equal, else index 0 with a literal name; it
+ *    is resolved in front of the evictions of the field's own insertion (RFC 7541 4.4).  Equality is of bytes; the hash
+ *    (FNV-1a) finds candidates and never decides.
+ * 3. STRINGS AND INTEGERS.  A string is Huffman-coded where that is NOT LONGER than its raw bytes -- names and values
+ *    alike; RFC 7541 Appendix C.6.2 codes "307" in three bytes -- and the empty string goes raw; padding is one-bits;
+ *    integers are minimal.
+ * 4. TABLE.  RFC 7541 4: entry size 32 + name + value; an insertion evicts from the oldest until the entry fits; an
+ *    entry larger than the table empties it, is not inserted and is still sent as a literal with incremental indexing
+ *    (the peer's table empties too).  The limit is the peer's SETTINGS_HEADER_TABLE_SIZE, at most 65536 bytes and 2048
+ *    live entries as the decoder has it.  Both sides begin at 4096, or at peer_table_size where that is less (no size
+ *    update is sent for it: Appendix C.6); grdma_h2_hpenc_set_peer changes the limit between calls, on the host alone:
+ *    the next call that sends a block opens its FIRST block with one size update when the size differs from what the
+ *    peer's decoder is at -- a create above 4096 counts -- or with two, the smallest since the last block and then the
+ *    final one, when it was lowered and then raised (4.2).  The evictions happen first, in front of the block's fields.
+ * 5. FRAMES.  Per block one HEADERS frame -- 9-byte header, END_STREAM from the block's flags, no padding, no priority
+ *    -- then CONTINUATION frames, each full frame of the peer's max frame size; END_HEADERS on the last.  An empty block
+ *    is a HEADERS frame without payload.  Blocks are contiguous in the wire arena, in input order; the block-wire table
+ *    says per block where its frames begin, how many bytes they are and how many frames, so that the caller can put them
+ *    in front of or behind its DATA slices.  Result block: {blocks, frames, wire bytes, entries inserted, entries
+ *    evicted, table bytes after the call, flags (grdma_h2_hpenc_flag) | error << 8 | offending block << 32, overflow}.
+ * 6. CAPS.  A wire arena or a block-wire table too small: overflow word 1, -GRDMA_ERR_CAPACITY, the result block holds
+ *    the totals, NOTHING is written and NOTHING is committed (table, counters, pending size updates); the same call
+ *    with larger targets gives exactly what a never-refused call gives.
+ * 7. BAD INPUT is found on the device, where the input lives: a block whose field range leaves the field table
+ *    (ERR_FIELD_RANGE), a stream id of 0 or above 2^31 - 1 (ERR_STREAM), a value length above 2^24 - 1 (ERR_LENGTH), a
+ *    string that leaves the arena (ERR_STRING) -- the first block with a fault; in it the range, then the stream, then
+ *    its first faulty field, the length first -- and a block whose frames pass 2^32 - 1 bytes (ERR_BLOCK_TOO_LARGE).
+ *    The flag is BAD_INPUT with the code and the block's number, the other result words are 0 but the table bytes;
+ *    nothing is written, nothing is committed, the call returns -GRDMA_ERR_INVALID.  Not sticky: the encoder's state is
+ *    untouched.
+ * -GRDMA_ERR_INVALID or NULL (grdma_last_error says why; nothing runs, nothing changes): null, zero or misaligned (16
+ * bytes) wire arena or block-wire table, a null input table with a count above 0, a misaligned block or field table, a
+ * table size above 65536, a max frame size outside 16384 .. 2^24 - 1, 2^32 - 1 blocks or more.
+ * Not here: the encoder over many links (a batched twin), the encoder as a stage of a reply pipe, gRPC's per-key
+ * metadata policy (which keys are indexable is the caller's hint). */
+enum grdma_h2_hpenc_flag { GRDMA_H2_HPENC_BAD_INPUT = 1 };
+enum grdma_h2_hpenc_error {
+  GRDMA_H2_HPENC_ERR_FIELD_RANGE = 1, GRDMA_H2_HPENC_ERR_STREAM = 2, GRDMA_H2_HPENC_ERR_LENGTH = 3, GRDMA_H2_HPENC_ERR_STRING = 4,
+  GRDMA_H2_HPENC_ERR_BLOCK_TOO_LARGE = 5
+};
+typedef struct grdma_h2_hpenc grdma_h2_hpenc;
+typedef struct grdma_h2_header_wire { uint64_t off; uint32_t len, nframes; } grdma_h2_header_wire;
+    /* a block's frames: offset in the wire arena, bytes (frame headers included), frames */
+grdma_h2_hpenc* grdma_h2_hpenc_create(uint32_t peer_table_size /* 0 .. 65536 */, uint32_t peer_max_frame /* 16384 .. 2^24 - 1 */);
+void grdma_h2_hpenc_destroy(grdma_h2_hpenc* enc);
+int grdma_h2_hpenc_set_peer(grdma_h2_hpenc* enc, uint32_t peer_table_size, uint32_t peer_max_frame);
+int64_t grdma_h2_hpenc_encode(grdma_h2_hpenc* enc, const grdma_h2_header_block* d_blocks, uint64_t nblocks,
+                              const grdma_h2_header_field* d_fields, uint64_t nfields, const void* d_strings, uint64_t strings_bytes,
+                              void* d_wire, uint64_t wire_cap, grdma_h2_header_wire* d_block_wire, uint64_t block_wire_cap,
+                              uint64_t out[8]);  /* returns the frame count */
+/* the encoder's view of the peer's dynamic table, in the dump format of grdma_h2_hpack_table */
+int grdma_h2_hpenc_table(grdma_h2_hpenc* enc, void* host_buf, uint64_t cap, uint64_t out[4]);
+/* {calls, blocks, fields, header-list bytes in, wire bytes out, inserts, evictions, kernel time of the last call in
+ * NANOseconds (HIP events)} */
+int grdma_h2_hpenc_stats(grdma_h2_hpenc* enc, uint64_t out[8]);
+/* the last call's kernel time by stage, NANOseconds: {scan, walk, emit and commit, total} */
+int grdma_h2_hpenc_last_stages(grdma_h2_hpenc* enc, uint64_t out[4]);
+
 /* ---- HTTP/2 on several links of ONE job (the group pipe) ----
  * grdma_h2_pipe serves one link, and a job carries one set of kernels in front of and behind its rounds: a second
  * grdma_h2_pipe on another link of the same job replaces the first one's.  The group pipe is the pipe of n links of a
@@ -1269,8 +1344,8 @@ int grdma_h2_hpack_decode_batch(const grdma_h2_hpack_item* items, uint32_t n_ite
  * grdma_h2_group_pipe_sync's "slices parsed" word is that count.  (grdma_h2_pipe parses the recorded count.)
  * Create returns NULL (grdma_last_error says why) for: n == 0, a link index out of range or listed twice, a parser
  * listed twice, nmsgs 0 or above 4096, max_frame 0 or >= 2^24, a job that already carries such kernels (another pipe).
- * Not here (yet): the chunked deframer inside the batch (every transport is parsed sequentially), the HPACK encoder and the
- * header decoder inside the group pipe (standalone, one transport's or many links': grdma_h2_hpack above).  A parser
+ * Not here (yet): the chunked deframer inside the batch (every transport is parsed sequentially), the header encoder and the
+ * header decoder inside the group pipe (standalone: grdma_h2_hpenc, and grdma_h2_hpack for one transport or many links, above).  A parser
  * that has a window ledger at create time is refused: ledgers come later, grdma_h2_group_pipe_attach_flow_control. */
 typedef struct grdma_h2_link_spec {
   uint32_t link;                 /* index into the job's links; distinct */
