@@ -333,6 +333,15 @@ static h2_stage h2_stage_hpenc(h2he_dev* d) {
   return {h2_rec(k_h2_hpenc_scan, H2HE_GRID, H2HE_THREADS, d), h2_rec(k_h2_hpenc_walk, 1, H2HE_THREADS, d),
           h2_rec(k_h2_hpenc_emit, H2HE_GRID, H2HE_THREADS, d), h2_rec(k_h2_hpenc_commit, H2HE_GRID, H2HE_THREADS, d)};
 }
+// ... of n links in the same four launches and the same three sections: the walks side by side, every link a share of
+// the grid stages
+static_assert(H2HE_LINKS_MAX == GRDMA_H2_BATCH_MAX, "the header encoder's link table is the batch's");
+static h2_stage h2_stage_hpenc_links(const h2he_link* d_tab, uint32_t n) {
+  return {h2_rec(k_h2_links_hpenc_scan, n * H2HE_LINK_GRID, H2HE_THREADS, d_tab, n),
+          h2_rec(k_h2_links_hpenc_walk, n, H2HE_THREADS, d_tab, n),
+          h2_rec(k_h2_links_hpenc_emit, n * H2HE_LINK_GRID, H2HE_THREADS, d_tab, n),
+          h2_rec(k_h2_links_hpenc_commit, n * H2HE_LINK_GRID, H2HE_THREADS, d_tab, n)};
+}
 
 // st goes behind the parser's last deframing by a pipe (the parser state is handed from one deframing to the next),
 // unless that one was enqueued on st itself.  (Only pipe steps leave last_deframed, on a job's or a deframe stream: for

@@ -39,6 +39,14 @@ inline h2_fc_block h2_fc_block_layout(uint64_t link, uint64_t call, uint64_t n_i
   return {b.add(link * n_items), b.add(call * n_items), b.end, b.total()};
 }
 
+// grdma_h2_hpenc_encode_batch: [table | one call block per item | nine result words per item]; [0, results) goes up in
+// one copy, the result words come down in one copy.  (Nothing of a call lies in the encoders' own device blocks.)
+struct h2_hpenc_block { uint64_t tab, calls, results, total; };
+inline h2_hpenc_block h2_hpenc_block_layout(uint64_t link, uint64_t call, uint64_t n_items) {
+  h2_block b;
+  return {b.add(link * n_items), b.add(call * n_items), b.add(9 * sizeof(uint64_t) * n_items), b.total()};
+}
+
 // grdma_h2_reply_frame_batch: [table | one h2r_dev per item]; all of it goes up, the h2r_dev blocks come down.
 struct h2_reply_block { uint64_t tab, devs, end, total; };
 inline h2_reply_block h2_reply_block_layout(uint64_t link, uint64_t dev, uint64_t n_items) {

@@ -1972,55 +1972,147 @@ int grdma_h2_hpenc_set_peer(grdma_h2_hpenc* w, uint32_t peer_table_size, uint32_
   return 0;
 }
 
+// what a call of an item (the single call's arguments are one) is refused for
+static const char* h2_hpenc_refusal(const grdma_h2_hpenc_item& it) {
+  if (!it.enc) return "no encoder";
+  if (!it.d_wire || !it.wire_cap || !it.d_block_wire || !it.block_wire_cap || ((uintptr_t)it.d_wire & 15) || ((uintptr_t)it.d_block_wire & 15))
+    return "a null, zero or misaligned wire arena or block-wire table";
+  if ((it.nblocks && !it.d_blocks) || (it.nfields && !it.d_fields) || (it.strings_bytes && !it.d_strings) || ((uintptr_t)it.d_blocks & 15) ||
+      ((uintptr_t)it.d_fields & 15))
+    return "a null or misaligned block table, field table or string arena";
+  if (it.nblocks >= 0xffffffffull || it.nfields > 0xffffffffull || it.strings_bytes > (1ull << 32))
+    return "more than 2^32 - 1 blocks or fields, or a string arena above 2^32 bytes";
+  return nullptr;
+}
+// in front of a call: a record per field, a row per block and one behind, an occurrence per field and some (blocks that
+// share fields hold more: only the device can count them)
+static bool h2_hpenc_grow(const grdma_h2_hpenc_item& it) {
+  grdma_h2_hpenc* w = it.enc;
+  return h2_grow(&w->d_recs, &w->recs_cap, it.nfields + 1) && h2_grow(&w->d_blks, &w->blks_cap, it.nblocks + 2) &&
+         h2_grow(&w->d_occs, &w->occs_cap, it.nfields + 64);
+}
+// the call's words as the encoder's tables and the peer's pending settings stand
+static h2he_call h2_hpenc_call(const grdma_h2_hpenc_item& it) {
+  const grdma_h2_hpenc* w = it.enc;
+  h2he_call call = {reinterpret_cast<const h2hp_block_out*>(it.d_blocks), it.nblocks, reinterpret_cast<const h2hp_field_out*>(it.d_fields), it.nfields,
+                    static_cast<const uint8_t*>(it.d_strings), it.strings_bytes, static_cast<uint8_t*>(it.d_wire), it.wire_cap,
+                    reinterpret_cast<h2he_wire_out*>(it.d_block_wire), it.block_wire_cap, w->d_recs, w->recs_cap, w->d_occs, w->occs_cap,
+                    w->d_blks, w->blks_cap, w->max_frame, 0, {0, 0}};
+  if (w->low < w->want && w->low < w->cur) {  // lowered, then raised: the smallest since the last block, then the final one (4.2)
+    call.nupd = 2;
+    call.upd[0] = w->low;
+    call.upd[1] = w->want;
+  } else if (w->want != w->cur) {
+    call.nupd = 1;
+    call.upd[0] = w->want;
+  }
+  return call;
+}
+// down: a run's nine words (the result block, the occurrence count).  Whether the run said the occurrence table is too
+// small: then the table is grown for one more run (*rc 0), or the call is refused (*rc: what it returns)
+static bool h2_hpenc_again(grdma_h2_hpenc* w, const char* who, const uint64_t* down, int attempt, int* rc) {
+  if (down[H2HE_OVERFLOW] != H2HE_OVER_SCRATCH) return false;
+  if (attempt || down[8] >= 0xffffffffull) *rc = h2_invalid(who, "more than 2^32 - 1 fields in the call's blocks");
+  else *rc = h2_grow(&w->d_occs, &w->occs_cap, down[8] + 64) ? 0 : -GRDMA_ERR_HIP;
+  return true;
+}
+// behind a call of an item that ran, res its result words, ms the call's three sections -> whether its blocks are on the wire
+static bool h2_hpenc_ran(const grdma_h2_hpenc_item& it, const uint64_t* res, const float* ms) {
+  grdma_h2_hpenc* w = it.enc;
+  for (int k = 0; k < 3; k++) w->ms[k] = ms[k];
+  if ((res[H2HE_FLAGS] & H2HE_F_BAD_INPUT) || res[H2HE_OVERFLOW]) return false;
+  if (it.nblocks) w->cur = w->low = w->want;  // (the block that said so is out)
+  return true;
+}
+
 int64_t grdma_h2_hpenc_encode(grdma_h2_hpenc* w, const grdma_h2_header_block* d_blocks, uint64_t nblocks, const grdma_h2_header_field* d_fields,
                               uint64_t nfields, const void* d_strings, uint64_t strings_bytes, void* d_wire, uint64_t wire_cap,
                               grdma_h2_header_wire* d_block_wire, uint64_t block_wire_cap, uint64_t out[8]) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
   const char* who = "h2 header encoder";
-  if (!w) return h2_invalid(who, "no encoder");
-  if (!out) return h2_invalid(who, "no result array");
-  if (!d_wire || !wire_cap || !d_block_wire || !block_wire_cap || ((uintptr_t)d_wire & 15) || ((uintptr_t)d_block_wire & 15))
-    return h2_invalid(who, "a null, zero or misaligned wire arena or block-wire table");
-  if ((nblocks && !d_blocks) || (nfields && !d_fields) || (strings_bytes && !d_strings) || ((uintptr_t)d_blocks & 15) || ((uintptr_t)d_fields & 15))
-    return h2_invalid(who, "a null or misaligned block table, field table or string arena");
-  if (nblocks >= 0xffffffffull || nfields > 0xffffffffull || strings_bytes > (1ull << 32))
-    return h2_invalid(who, "more than 2^32 - 1 blocks or fields, or a string arena above 2^32 bytes");
+  const grdma_h2_hpenc_item it{w, d_blocks, nblocks, d_fields, nfields, d_strings, strings_bytes, d_wire, wire_cap, d_block_wire, block_wire_cap};
+  if (w && !out) return h2_invalid(who, "no result array");
+  if (const char* why = h2_hpenc_refusal(it)) return h2_invalid(who, why);
   h2_host_ctx* hc = h2_ctx();
   if (!hc) return -GRDMA_ERR_HIP;
-  if (!h2_grow(&w->d_recs, &w->recs_cap, nfields + 1) || !h2_grow(&w->d_blks, &w->blks_cap, nblocks + 2) ||
-      !h2_grow(&w->d_occs, &w->occs_cap, nfields + 64))
-    return -GRDMA_ERR_HIP;
+  if (!h2_hpenc_grow(it)) return -GRDMA_ERR_HIP;
   uint64_t down[9];  // the result block and the occurrence count behind it
   static_assert(offsetof(h2he_dev, nocc) == offsetof(h2he_dev, res) + 8 * sizeof(uint64_t), "one download");
+  float ms[3] = {0, 0, 0};
   const h2_stage stage = h2_stage_hpenc(w->d);
   for (int attempt = 0;; attempt++) {
-    h2he_call call = {reinterpret_cast<const h2hp_block_out*>(d_blocks), nblocks, reinterpret_cast<const h2hp_field_out*>(d_fields), nfields,
-                      static_cast<const uint8_t*>(d_strings), strings_bytes, static_cast<uint8_t*>(d_wire), wire_cap,
-                      reinterpret_cast<h2he_wire_out*>(d_block_wire), block_wire_cap, w->d_recs, w->recs_cap, w->d_occs, w->occs_cap,
-                      w->d_blks, w->blks_cap, w->max_frame, 0, {0, 0}};
-    if (w->low < w->want && w->low < w->cur) {  // lowered, then raised: the smallest since the last block, then the final one (4.2)
-      call.nupd = 2;
-      call.upd[0] = w->low;
-      call.upd[1] = w->want;
-    } else if (w->want != w->cur) {
-      call.nupd = 1;
-      call.upd[0] = w->want;
-    }
+    const h2he_call call = h2_hpenc_call(it);
     h2_call c{"grdma_h2_hpenc_encode: a launch was rejected", {{w->d, &call, sizeof(call)}}, {},
               {{stage.data(), 1}, {stage.data() + 1, 1}, {stage.data() + 2, 2}}, {h2_result(down, w->d, offsetof(h2he_dev, res), 9)}};
     if (int rc = h2_call_run(hc, &c)) return rc;
-    for (int k = 0; k < 3; k++) w->ms[k] = c.ms[k];
-    if (down[H2HE_OVERFLOW] != H2HE_OVER_SCRATCH) break;
-    if (attempt || down[8] >= 0xffffffffull) return h2_invalid(who, "more than 2^32 - 1 fields in the call's blocks");
-    if (!h2_grow(&w->d_occs, &w->occs_cap, down[8] + 64)) return -GRDMA_ERR_HIP;
+    for (int k = 0; k < 3; k++) w->ms[k] = ms[k] = c.ms[k];
+    int rc = 0;
+    if (!h2_hpenc_again(w, who, down, attempt, &rc)) break;
+    if (rc) return rc;
   }
   for (int k = 0; k < 8; k++) out[k] = down[k];
+  if (h2_hpenc_ran(it, down, ms)) return (int64_t)out[H2HE_FRAMES];
   if (out[H2HE_FLAGS] & H2HE_F_BAD_INPUT) return h2_invalid(who, "bad input: a block's fields, a string, a stream id or a length (the result block says which block)");
-  if (out[H2HE_OVERFLOW])
-    return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 header encoder: more wire bytes or blocks than the targets hold");
-  if (nblocks) w->cur = w->low = w->want;  // (the block that said so is out)
-  return (int64_t)out[H2HE_FRAMES];
+  return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 header encoder: more wire bytes or blocks than the targets hold");
 }
+
+// The encoders of many connections in the same four launches (h2_stage_hpenc_links).  The batch block of the process
+// holds [table | one h2he_call per item | nine result words per item]: the table and the call words go up in ONE copy,
+// the result words come down in ONE copy, whatever the number of items -- nothing of a call passes through the encoders'
+// own device blocks, whose words stay the single call's.  Items whose occurrence table was too small (blocks that share
+// fields) get it grown and run once more, in a second run of the four launches over a table of those items only: the
+// walk commits, so an item that stood in the first run is never run twice.  One call at a time, as the other batch calls.
+int grdma_h2_hpenc_encode_batch(const grdma_h2_hpenc_item* items, uint32_t n_items, uint64_t* out) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  h2_batch b{"h2 header encoder batch", "encoder", "h2 header encoder batch: a launch was rejected"};
+  if (int rc = b.begin(items && out, n_items)) return rc;
+  for (uint32_t i = 0; i < n_items; i++)
+    if (int rc = b.item(items[i].enc, h2_hpenc_refusal(items[i]))) return rc;
+  for (uint32_t i = 0; i < n_items; i++)
+    if (!h2_hpenc_grow(items[i])) return -GRDMA_ERR_HIP;
+  std::vector<uint32_t> todo(n_items);  // the items of the run
+  for (uint32_t i = 0; i < n_items; i++) todo[i] = i;
+  std::vector<uint64_t> res(9 * (size_t)n_items, 0), down;
+  float ms[3] = {0, 0, 0};
+  int refused = 0;  // what the call returns for an item whose occurrence table cannot be made to hold its blocks
+  for (int attempt = 0; !todo.empty(); attempt++) {
+    const uint32_t n = (uint32_t)todo.size();
+    const h2_hpenc_block L = h2_hpenc_block_layout(sizeof(h2he_link), sizeof(h2he_call), n);
+    if (attempt) b.next();
+    if (int rc = b.reserve(L.results, L.total)) return rc;
+    auto* tab = reinterpret_cast<h2he_link*>(b.up.data() + L.tab);
+    auto* calls = reinterpret_cast<h2he_call*>(b.up.data() + L.calls);
+    for (uint32_t k = 0; k < n; k++) {
+      calls[k] = h2_hpenc_call(items[todo[k]]);
+      tab[k] = {items[todo[k]].enc->d, reinterpret_cast<const h2he_call*>(b.d + L.calls) + k, reinterpret_cast<uint64_t*>(b.d + L.results) + 9 * (size_t)k};
+    }
+    down.assign(9 * (size_t)n, 0);
+    b.c.down.push_back(h2_result(down.data(), b.d, L.results, 9 * (size_t)n));
+    const h2_stage stage = h2_stage_hpenc_links(reinterpret_cast<const h2he_link*>(b.d + L.tab), n);
+    if (int rc = b.run({{stage.data(), 1}, {stage.data() + 1, 1}, {stage.data() + 2, 2}})) return rc;
+    for (int k = 0; k < 3; k++) ms[k] += b.c.ms[k];
+    std::vector<uint32_t> again;
+    for (uint32_t k = 0; k < n; k++) {
+      const uint32_t i = todo[k];
+      memcpy(&res[9 * (size_t)i], &down[9 * (size_t)k], 9 * sizeof(uint64_t));
+      int rc = 0;
+      if (!h2_hpenc_again(items[i].enc, b.who, &down[9 * (size_t)k], attempt, &rc)) continue;
+      if (rc && !refused) refused = rc;
+      again.push_back(i);
+    }
+    todo.swap(again);
+    if (refused) break;
+  }
+  // (after a refusal the items that stood stay committed on the device: the host takes their results in all the same)
+  int ok = 0;
+  for (uint32_t i = 0; i < n_items; i++) {
+    if (res[9 * (size_t)i + H2HE_OVERFLOW] == H2HE_OVER_SCRATCH) continue;
+    memcpy(out + 8 * (size_t)i, &res[9 * (size_t)i], 8 * sizeof(uint64_t));
+    ok += h2_hpenc_ran(items[i], &res[9 * (size_t)i], ms);  // (the times: the batch's, repeated)
+  }
+  return todo.empty() ? ok : refused;
+}
+
 
 int grdma_h2_hpenc_table(grdma_h2_hpenc* w, void* host_buf, uint64_t cap, uint64_t out[4]) {
   if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;

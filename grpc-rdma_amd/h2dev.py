@@ -76,6 +76,12 @@ class H2HpackItem(C.Structure):
                 ("fields_cap", u64), ("d_strings", C.c_void_p), ("strings_cap", u64)]
 
 
+class H2HpencItem(C.Structure):
+    _fields_ = [("enc", C.c_void_p), ("d_blocks", C.c_void_p), ("nblocks", u64), ("d_fields", C.c_void_p), ("nfields", u64),
+                ("d_strings", C.c_void_p), ("strings_bytes", u64), ("d_wire", C.c_void_p), ("wire_cap", u64),
+                ("d_block_wire", C.c_void_p), ("block_wire_cap", u64)]
+
+
 MSG_OK, MSG_TOO_LARGE, MSG_NO_SPACE, MSG_TRUNCATED = 0, 1, 2, 3
 SYNC_KEYS = ("framed", "frame_overflow", "events", "deframe_overflow", "parsed", "h2_error", "frame_us", "deframe_us",
              "bulk_steps", "bulk_frames", "t_wait", "t_bulk", "t_total", "t_serial")
@@ -323,6 +329,8 @@ def _bind():
         lib.grdma_h2_hpenc_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
         lib.grdma_h2_hpenc_last_stages.restype = C.c_int
         lib.grdma_h2_hpenc_last_stages.argtypes = [C.c_void_p, C.POINTER(u64)]
+        lib.grdma_h2_hpenc_encode_batch.restype = C.c_int
+        lib.grdma_h2_hpenc_encode_batch.argtypes = [C.POINTER(H2HpencItem), C.c_uint32, C.POINTER(u64)]
         lib.grdma_job_hook_counts.restype = C.c_int   # (not in include/grdma_amd.h: the job's side of the pipes)
         lib.grdma_job_hook_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         _bound = True
@@ -1087,6 +1095,30 @@ def decode_batch(items):
         (arr[i].d_blocks, arr[i].blocks_cap, arr[i].d_fields, arr[i].fields_cap, arr[i].d_strings, arr[i].strings_cap) = target
     out = (u64 * (8 * max(1, n)))()
     count = check(lib.grdma_h2_hpack_decode_batch(arr, n, out))
+    return count, _results(out, [item[0] for item in items])
+
+
+def encode_batch(items):
+    """HeaderEncoder.encode for many connections in four launches (grdma_h2_hpenc_encode_batch).  items: [(HeaderEncoder,
+    blocks device ptr, nblocks, fields device ptr, nfields, strings device ptr, strings bytes, wire device ptr, wire cap,
+    block-wire device ptr, block-wire cap), ...] with distinct encoders; each encodes its own input (input tables may be
+    shared between items) against its own peer table into its own targets.  -> (the number of items whose blocks are on
+    the wire, [result tuple (HeaderEncoder.RESULT) per item]); an item with bad input or a cap overflow reports for itself
+    in its tuple (flags: BAD_INPUT | error << 8 | block << 32; overflow word 1: nothing of it was written or committed
+    and it may be repeated, alone or in a later batch).  The result tuples also land in each encoder's .last_result.
+    Raises GrdmaError only on a refusal of the whole call."""
+    lib = _bind()
+    n = len(items)
+    arr = (H2HpencItem * max(1, n))()
+    for i, item in enumerate(items):
+        if item is None:
+            continue
+        enc, *rest = item
+        arr[i].enc = enc.h if enc is not None else None
+        (arr[i].d_blocks, arr[i].nblocks, arr[i].d_fields, arr[i].nfields, arr[i].d_strings, arr[i].strings_bytes, arr[i].d_wire,
+         arr[i].wire_cap, arr[i].d_block_wire, arr[i].block_wire_cap) = rest
+    out = (u64 * (8 * max(1, n)))()
+    count = check(lib.grdma_h2_hpenc_encode_batch(arr, n, out))
     return count, _results(out, [item[0] for item in items])
 
 

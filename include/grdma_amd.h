@@ -1304,9 +1304,28 @@ int grdma_h2_hpack_decode_batch(const grdma_h2_hpack_item* items, uint32_t n_ite
  *    untouched.
  * -GRDMA_ERR_INVALID or NULL (grdma_last_error says why; nothing runs, nothing changes): null, zero or misaligned (16
  * bytes) wire arena or block-wire table, a null input table with a count above 0, a misaligned block or field table, a
- * table size above 65536, a max frame size outside 16384 .. 2^24 - 1, 2^32 - 1 blocks or more.
- * Not here: the encoder over many links (a batched twin), the encoder as a stage of a reply pipe, gRPC's per-key
- * metadata policy (which keys are indexable is the caller's hint). */
+ * table size above 65536, a max frame size outside 16384 .. 2^24 - 1, 2^32 - 1 blocks or more; in the batch n outside
+ * 1 .. GRDMA_H2_BATCH_MAX, a NULL item array, result array or encoder, the same encoder twice, any item the single
+ * call's argument checks refuse.
+ * MANY LINKS.  grdma_h2_hpenc_encode_batch is grdma_h2_hpenc_encode for n encoders (1 .. GRDMA_H2_BATCH_MAX) in four
+ * launches however many (k_h2_links_hpenc_*), ordered on the same stream: a grdma_h2_hpack_decode_batch immediately in
+ * front of it needs no host synchronisation.  Every item encodes its own input into its own wire arena and block-wire
+ * table against its own peer table, with its own pending size updates and its own max frame size, by rules 1 to 7
+ * exactly as the single call does.  Input tables may be shared between items (a proxy fans one header list out to
+ * many links); overlapping wire arenas are the caller's error and are not checked.  out: 8 result words per item, in
+ * item order.  Bad input (the BAD_INPUT flag, the code and the block in the item's words) and a cap overflow (overflow
+ * word 1: nothing of the item is written or committed, its size updates stay pending, it may be repeated alone or in a
+ * later batch and then gives what a never-refused call gives) stay with the item, the other items are exact.  The
+ * return value is the number of items whose blocks are on the wire (overflow word 0 and no BAD_INPUT; an item without
+ * blocks counts, and commits no peer settings), or a negative error.  The call's words go up and the result words come
+ * down in ONE copy each, whatever n.  Items whose blocks share fields so that their occurrences pass nfields + 64 get
+ * their occurrence table grown and run once more, in a second run of the four launches over those items only; an item
+ * that then still asks for more, or that holds 2^32 - 1 occurrences or more, refuses the call (-GRDMA_ERR_INVALID):
+ * that item and the ones waiting with it are untouched, but THE ITEMS THAT STOOD IN THE FIRST RUN STAY COMMITTED --
+ * their bytes are on the wire, their tables and counters moved, and their result words are in out.
+ * grdma_h2_hpenc_stats word 7 and grdma_h2_hpenc_last_stages report the batch's sections, repeated for every item.
+ * Not here: the encoder as a stage of a reply pipe or of the group pipe, gRPC's per-key metadata policy (which keys
+ * are indexable is the caller's hint). */
 enum grdma_h2_hpenc_flag { GRDMA_H2_HPENC_BAD_INPUT = 1 };
 enum grdma_h2_hpenc_error {
   GRDMA_H2_HPENC_ERR_FIELD_RANGE = 1, GRDMA_H2_HPENC_ERR_STREAM = 2, GRDMA_H2_HPENC_ERR_LENGTH = 3, GRDMA_H2_HPENC_ERR_STRING = 4,
@@ -1329,6 +1348,20 @@ int grdma_h2_hpenc_table(grdma_h2_hpenc* enc, void* host_buf, uint64_t cap, uint
 int grdma_h2_hpenc_stats(grdma_h2_hpenc* enc, uint64_t out[8]);
 /* the last call's kernel time by stage, NANOseconds: {scan, walk, emit and commit, total} */
 int grdma_h2_hpenc_last_stages(grdma_h2_hpenc* enc, uint64_t out[4]);
+typedef struct grdma_h2_hpenc_item {
+  grdma_h2_hpenc* enc;                    /* distinct */
+  const grdma_h2_header_block* d_blocks;  /* the item's device input and targets, as grdma_h2_hpenc_encode's */
+  uint64_t nblocks;
+  const grdma_h2_header_field* d_fields;
+  uint64_t nfields;
+  const void* d_strings;
+  uint64_t strings_bytes;
+  void* d_wire;
+  uint64_t wire_cap;
+  grdma_h2_header_wire* d_block_wire;
+  uint64_t block_wire_cap;
+} grdma_h2_hpenc_item;
+int grdma_h2_hpenc_encode_batch(const grdma_h2_hpenc_item* items, uint32_t n_items, uint64_t* out /* 8 words per item */);
 
 /* ---- HTTP/2 on several links of ONE job (the group pipe) ----
  * grdma_h2_pipe serves one link, and a job carries one set of kernels in front of and behind its rounds: a second
