@@ -1,86 +1,13 @@
 """Device-side HTTP/2 DATA framing / deframing (grdma_h2_*), thin ctypes wrappers."""
 import ctypes as C
 
-from ._lib import GrdmaError, ReadSlice, Slice, check, load
+from ._abi import (H2CtlItem, H2DeframeItem, H2Event, H2FcItem, H2HpackItem, H2HpencItem, H2LinkSpec,  # noqa: F401
+                   H2MessagesItem, H2Msg, H2ReplyItem, H2ReplyLinkSpec, H2Route, H2RxMsg, H2SwFrameItem, H2WrItem, ReadSlice,
+                   Slice)
+from ._lib import GrdmaError, check, load
 
 u64 = C.c_uint64
-
-
-class H2Msg(C.Structure):
-    _fields_ = [("payload", C.c_void_p), ("len", u64), ("stream_id", C.c_uint32),
-                ("flags", C.c_uint32)]
-
-
-class H2Event(C.Structure):
-    _fields_ = [(n, C.c_uint32) for n in ("kind", "a", "b", "c", "d", "slice")]
-
-
-class H2RxMsg(C.Structure):
-    _fields_ = [("offset", u64), ("length", u64), ("seq", u64), ("stream_id", C.c_uint32), ("status", C.c_uint32),
-                ("flags", C.c_uint32), ("pad", C.c_uint32)]
-
-
-class H2Route(C.Structure):
-    _fields_ = [("from_stream", C.c_uint32), ("to_stream", C.c_uint32)]
-
-
-class H2DeframeItem(C.Structure):
-    _fields_ = [("parser", C.c_void_p), ("d_arena", C.c_void_p), ("slices", C.POINTER(ReadSlice)), ("n", u64),
-                ("events_out", C.POINTER(H2Event)), ("cap", u64), ("n_events", C.c_int64), ("h2_error", C.c_int)]
-
-
-class H2MessagesItem(C.Structure):
-    _fields_ = H2DeframeItem._fields_ + [("assembler", C.c_void_p), ("msgs_out", C.POINTER(H2RxMsg)), ("msgs_cap", u64),
-                                         ("n_msgs", C.c_int64)]
-
-
-class H2LinkSpec(C.Structure):
-    _fields_ = [("link", C.c_uint32), ("msgs", C.POINTER(H2Msg)), ("nmsgs", u64), ("parser", C.c_void_p),
-                ("delivered_slices", u64), ("events_cap", u64)]
-
-
-class H2ReplyItem(C.Structure):
-    _fields_ = [("reply", C.c_void_p), ("d_slices_out", C.c_void_p), ("slices_cap", u64), ("d_hdr_arena", C.c_void_p),
-                ("hdr_cap", u64), ("out", u64 * 8), ("n_slices", C.c_int64)]
-
-
-class H2ReplyLinkSpec(C.Structure):
-    _fields_ = [("link", C.c_uint32), ("reply", C.c_void_p), ("parser_back", C.c_void_p), ("delivered_slices", u64),
-                ("events_cap", u64), ("recorded_wire_bytes", u64)]
-
-
-class H2FcItem(C.Structure):
-    _fields_ = [("fc", C.c_void_p), ("d_slices_out", C.c_void_p), ("slices_cap", u64), ("d_hdr_arena", C.c_void_p),
-                ("hdr_cap", u64)]
-
-
-class H2SwFrameItem(C.Structure):
-    _fields_ = [("sw", C.c_void_p), ("msgs", C.POINTER(H2Msg)), ("progress", C.POINTER(u64)), ("nmsgs", u64),
-                ("max_frame", C.c_uint32), ("pad", C.c_uint32), ("d_slices_out", C.c_void_p), ("slices_cap", u64),
-                ("d_hdr_arena", C.c_void_p), ("hdr_cap", u64)]
-
-
-class H2WrItem(C.Structure):
-    _fields_ = [("reply", C.c_void_p), ("flags", C.c_uint32), ("pad", C.c_uint32), ("d_slices_out", C.c_void_p),
-                ("slices_cap", u64), ("d_hdr_arena", C.c_void_p), ("hdr_cap", u64), ("n_slices", C.c_int64),
-                ("out", u64 * 16)]
-
-
-class H2CtlItem(C.Structure):
-    _fields_ = [("ctl", C.c_void_p), ("d_slices_out", C.c_void_p), ("slices_cap", u64), ("d_hdr_arena", C.c_void_p),
-                ("hdr_cap", u64)]
-
-
-class H2HpackItem(C.Structure):
-    _fields_ = [("hpack", C.c_void_p), ("d_blocks", C.c_void_p), ("blocks_cap", u64), ("d_fields", C.c_void_p),
-                ("fields_cap", u64), ("d_strings", C.c_void_p), ("strings_cap", u64)]
-
-
-class H2HpencItem(C.Structure):
-    _fields_ = [("enc", C.c_void_p), ("d_blocks", C.c_void_p), ("nblocks", u64), ("d_fields", C.c_void_p), ("nfields", u64),
-                ("d_strings", C.c_void_p), ("strings_bytes", u64), ("d_wire", C.c_void_p), ("wire_cap", u64),
-                ("d_block_wire", C.c_void_p), ("block_wire_cap", u64)]
-
+_bind = load  # (h2dev._bind() is load(): the library with every prototype of _abi.SIGNATURES set; it binds nothing itself)
 
 MSG_OK, MSG_TOO_LARGE, MSG_NO_SPACE, MSG_TRUNCATED = 0, 1, 2, 3
 SYNC_KEYS = ("framed", "frame_overflow", "events", "deframe_overflow", "parsed", "h2_error", "frame_us", "deframe_us",
@@ -148,11 +75,6 @@ def _read_wire(lib, slices):
     return wire
 
 
-def _set_target(item, target):
-    """the target fields of a batch item from (slices device ptr, slices cap, header arena device ptr, header cap)"""
-    item.d_slices_out, item.slices_cap, item.d_hdr_arena, item.hdr_cap = target
-
-
 def _results(out, objs, words=8):
     """the result words `out` of a call cut into one tuple per object, each also left in its object's .last_result"""
     res = [tuple(int(x) for x in out[words * i:words * i + words]) for i in range(len(objs))]
@@ -161,185 +83,72 @@ def _results(out, objs, words=8):
     return res
 
 
-_bound = False
+def _items(cls, items):
+    """the items [(object, value, ...), ...] of a batch call as an array of the ABI struct `cls` (never of length 0): the
+    first field takes the object's handle (None for no object), the fields that follow it the values, in the struct's
+    order; an item that is None stays zero"""
+    first, *rest = [n for n, _ in cls._fields_]
+    arr = (cls * max(1, len(items)))()
+    for a, item in zip(arr, items):
+        if item is not None:
+            setattr(a, first, item[0].h if item[0] is not None else None)
+            for name, v in zip(rest, item[1:]):
+                setattr(a, name, v)
+    return arr
 
 
-def _bind():
-    global _bound
-    lib = load()
-    if not _bound:
-        lib.grdma_h2_frame_messages.restype = C.c_int64
-        lib.grdma_h2_frame_messages.argtypes = [C.POINTER(H2Msg), u64, C.c_uint32, C.c_void_p, u64,
-                                                C.c_void_p, u64, C.POINTER(u64)]
-        lib.grdma_h2_parser_create.restype = C.c_void_p
-        lib.grdma_h2_parser_create.argtypes = [C.c_int, C.c_uint32]
-        lib.grdma_h2_parser_destroy.argtypes = [C.c_void_p]
-        lib.grdma_h2_parser_create_ex.restype = C.c_void_p
-        lib.grdma_h2_parser_create_ex.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32]
-        for fn in (lib.grdma_h2_parser_open_streams, lib.grdma_h2_parser_close_writes):
-            fn.restype = C.c_int
-            fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]
-        lib.grdma_h2_parser_live_streams.restype = C.c_int64
-        lib.grdma_h2_parser_live_streams.argtypes = [C.c_void_p]
-        lib.grdma_h2_last_boundary_steps.restype = C.c_uint64
-        lib.grdma_h2_last_boundary_steps.argtypes = []
-        lib.grdma_h2_last_deframe_stats.restype = None
-        lib.grdma_h2_last_deframe_stats.argtypes = [C.POINTER(u64)]
-        lib.grdma_h2_parser_chunk_stats.restype = C.c_int
-        lib.grdma_h2_parser_chunk_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
-        lib.grdma_h2_parser_chunk_dbg.restype = C.c_int
-        lib.grdma_h2_parser_chunk_dbg.argtypes = [C.c_void_p, C.POINTER(u64), u64]
-        lib.grdma_h2_deframe.restype = C.c_int64
-        lib.grdma_h2_deframe.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ReadSlice), u64,
-                                         C.POINTER(H2Event), u64, C.POINTER(C.c_int)]
-        lib.grdma_h2_asm_create.restype = C.c_void_p
-        lib.grdma_h2_asm_create.argtypes = [C.c_void_p, C.c_void_p, u64, u64, C.c_uint32]
-        lib.grdma_h2_asm_destroy.argtypes = [C.c_void_p]
-        lib.grdma_h2_deframe_messages.restype = C.c_int64
-        lib.grdma_h2_deframe_messages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ReadSlice), u64,
-                                                  C.POINTER(H2Event), u64, C.POINTER(H2RxMsg), u64, C.POINTER(C.c_int)]
-        lib.grdma_h2_asm_release.restype = C.c_int
-        lib.grdma_h2_asm_release.argtypes = [C.c_void_p, u64]
-        lib.grdma_h2_asm_stats.restype = C.c_int
-        lib.grdma_h2_asm_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
-        lib.grdma_h2_pipe_create.restype = C.c_void_p
-        lib.grdma_h2_pipe_create.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(H2Msg), u64, C.c_uint32, C.c_void_p, u64, u64]
-        lib.grdma_h2_pipe_enqueue.argtypes = [C.c_void_p, C.c_int]
-        lib.grdma_h2_pipe_sync.argtypes = [C.c_void_p, C.POINTER(u64), C.POINTER(H2Event), u64]
-        lib.grdma_h2_pipe_destroy.argtypes = [C.c_void_p]
-        lib.grdma_h2_pipe_boundary_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
-        lib.grdma_h2_pipe_attach_assembler.restype = C.c_int
-        lib.grdma_h2_pipe_attach_assembler.argtypes = [C.c_void_p, C.c_void_p]
-        lib.grdma_h2_pipe_messages.restype = C.c_int64
-        lib.grdma_h2_pipe_messages.argtypes = [C.c_void_p, C.POINTER(H2RxMsg), u64]
-        lib.grdma_h2_reply_create.restype = C.c_void_p
-        lib.grdma_h2_reply_create.argtypes = [C.c_void_p, C.POINTER(H2Route), C.c_uint32, C.c_uint32, u64]
-        lib.grdma_h2_reply_destroy.argtypes = [C.c_void_p]
-        lib.grdma_h2_reply_frame.restype = C.c_int64
-        lib.grdma_h2_reply_frame.argtypes = [C.c_void_p, C.c_void_p, u64, C.c_void_p, u64, C.POINTER(u64)]
-        lib.grdma_h2_pipe_create_reply.restype = C.c_void_p
-        lib.grdma_h2_pipe_create_reply.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, u64, u64, u64]
-        lib.grdma_h2_pipe_slice_table.restype = C.c_int64
-        lib.grdma_h2_pipe_slice_table.argtypes = [C.c_void_p, C.POINTER(Slice), u64]
-        lib.grdma_h2_deframe_batch.restype = C.c_int
-        lib.grdma_h2_deframe_batch.argtypes = [C.POINTER(H2DeframeItem), C.c_uint32]
-        lib.grdma_h2_group_pipe_create.restype = C.c_void_p
-        lib.grdma_h2_group_pipe_create.argtypes = [C.c_void_p, C.POINTER(H2LinkSpec), C.c_uint32, C.c_uint32]
-        lib.grdma_h2_group_pipe_enqueue.restype = C.c_int
-        lib.grdma_h2_group_pipe_enqueue.argtypes = [C.c_void_p]
-        lib.grdma_h2_group_pipe_sync.restype = C.c_int
-        lib.grdma_h2_group_pipe_sync.argtypes = [C.c_void_p, C.POINTER(u64), u64]
-        lib.grdma_h2_group_pipe_events.restype = C.c_int64
-        lib.grdma_h2_group_pipe_events.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(H2Event), u64]
-        lib.grdma_h2_group_pipe_slice_table.restype = C.c_int64
-        lib.grdma_h2_group_pipe_slice_table.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Slice), u64]
-        lib.grdma_h2_group_pipe_destroy.argtypes = [C.c_void_p]
-        lib.grdma_h2_deframe_messages_batch.restype = C.c_int
-        lib.grdma_h2_deframe_messages_batch.argtypes = [C.POINTER(H2MessagesItem), C.c_uint32]
-        lib.grdma_h2_asm_release_batch.restype = C.c_int
-        lib.grdma_h2_asm_release_batch.argtypes = [C.POINTER(C.c_void_p), C.POINTER(u64), C.c_uint32]
-        lib.grdma_h2_group_pipe_attach_assemblers.restype = C.c_int
-        lib.grdma_h2_group_pipe_attach_assemblers.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32]
-        lib.grdma_h2_group_pipe_messages.restype = C.c_int64
-        lib.grdma_h2_group_pipe_messages.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(H2RxMsg), u64]
-        lib.grdma_h2_reply_frame_batch.restype = C.c_int
-        lib.grdma_h2_reply_frame_batch.argtypes = [C.POINTER(H2ReplyItem), C.c_uint32]
-        lib.grdma_h2_group_pipe_create_reply.restype = C.c_void_p
-        lib.grdma_h2_group_pipe_create_reply.argtypes = [C.c_void_p, C.POINTER(H2ReplyLinkSpec), C.c_uint32]
-        lib.grdma_h2_fc_create.restype = C.c_void_p
-        lib.grdma_h2_fc_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
-        lib.grdma_h2_fc_destroy.argtypes = [C.c_void_p]
-        lib.grdma_h2_fc_account.restype = C.c_int64
-        lib.grdma_h2_fc_account.argtypes = [C.c_void_p, C.c_void_p, u64, C.c_void_p, u64, C.POINTER(u64)]
-        lib.grdma_h2_fc_stats.restype = C.c_int
-        lib.grdma_h2_fc_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
-        lib.grdma_h2_pipe_attach_flow_control.restype = C.c_int
-        lib.grdma_h2_pipe_attach_flow_control.argtypes = [C.c_void_p, C.c_void_p]
-        lib.grdma_h2_pipe_window_updates.restype = C.c_int64
-        lib.grdma_h2_pipe_window_updates.argtypes = [C.c_void_p, C.POINTER(Slice), u64, C.POINTER(u64)]
-        lib.grdma_h2_pipe_window_update_bytes.restype = C.c_int64
-        lib.grdma_h2_pipe_window_update_bytes.argtypes = [C.c_void_p, C.c_void_p, u64]
-        lib.grdma_h2_fc_account_batch.restype = C.c_int
-        lib.grdma_h2_fc_account_batch.argtypes = [C.POINTER(H2FcItem), C.c_uint32, C.POINTER(u64)]
-        lib.grdma_h2_group_pipe_attach_flow_control.restype = C.c_int
-        lib.grdma_h2_group_pipe_attach_flow_control.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32]
-        lib.grdma_h2_group_pipe_window_updates.restype = C.c_int64
-        lib.grdma_h2_group_pipe_window_updates.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Slice), u64, C.POINTER(u64)]
-        lib.grdma_h2_group_pipe_window_update_bytes.restype = C.c_int64
-        lib.grdma_h2_group_pipe_window_update_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, u64]
-        lib.grdma_h2_sw_create.restype = C.c_void_p
-        lib.grdma_h2_sw_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
-        lib.grdma_h2_sw_destroy.argtypes = [C.c_void_p]
-        lib.grdma_h2_sw_intake.restype = C.c_int64
-        lib.grdma_h2_sw_intake.argtypes = [C.c_void_p, C.POINTER(u64)]
-        lib.grdma_h2_sw_frame.restype = C.c_int64
-        lib.grdma_h2_sw_frame.argtypes = [C.c_void_p, C.POINTER(H2Msg), C.POINTER(u64), u64, C.c_uint32, C.c_void_p, u64,
-                                          C.c_void_p, u64, C.POINTER(u64)]
-        lib.grdma_h2_sw_windows.restype = C.c_int
-        lib.grdma_h2_sw_windows.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_int64)]
-        lib.grdma_h2_sw_stats.restype = C.c_int
-        lib.grdma_h2_sw_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
-        lib.grdma_h2_sw_intake_batch.restype = C.c_int
-        lib.grdma_h2_sw_intake_batch.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(u64)]
-        lib.grdma_h2_sw_frame_batch.restype = C.c_int
-        lib.grdma_h2_sw_frame_batch.argtypes = [C.POINTER(H2SwFrameItem), C.c_uint32, C.POINTER(u64)]
-        lib.grdma_h2_reply_attach_windows.restype = C.c_int
-        lib.grdma_h2_reply_attach_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
-        lib.grdma_h2_reply_frame_windowed.restype = C.c_int64
-        lib.grdma_h2_reply_frame_windowed.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, u64, C.c_void_p, u64, C.POINTER(u64)]
-        lib.grdma_h2_reply_pending.restype = C.c_int64
-        lib.grdma_h2_reply_pending.argtypes = [C.c_void_p, C.POINTER(u64), u64]
-        lib.grdma_h2_reply_frame_windowed_batch.restype = C.c_int
-        lib.grdma_h2_reply_frame_windowed_batch.argtypes = [C.POINTER(H2WrItem), C.c_uint32]
-        lib.grdma_h2_ctl_create.restype = C.c_void_p
-        lib.grdma_h2_ctl_create.argtypes = [C.c_void_p, C.c_uint32]
-        lib.grdma_h2_ctl_destroy.argtypes = [C.c_void_p]
-        lib.grdma_h2_ctl_reply.restype = C.c_int64
-        lib.grdma_h2_ctl_reply.argtypes = [C.c_void_p, C.c_void_p, u64, C.c_void_p, u64, C.POINTER(u64)]
-        lib.grdma_h2_ctl_peer.restype = C.c_int
-        lib.grdma_h2_ctl_peer.argtypes = [C.c_void_p, C.POINTER(u64)]
-        lib.grdma_h2_ctl_stats.restype = C.c_int
-        lib.grdma_h2_ctl_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
-        lib.grdma_h2_ctl_reply_batch.restype = C.c_int
-        lib.grdma_h2_ctl_reply_batch.argtypes = [C.POINTER(H2CtlItem), C.c_uint32, C.POINTER(u64)]
-        lib.grdma_h2_hpack_create.restype = C.c_void_p
-        lib.grdma_h2_hpack_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
-        lib.grdma_h2_hpack_destroy.argtypes = [C.c_void_p]
-        lib.grdma_h2_hpack_set_max_table_size.restype = C.c_int
-        lib.grdma_h2_hpack_set_max_table_size.argtypes = [C.c_void_p, C.c_uint32]
-        lib.grdma_h2_hpack_decode.restype = C.c_int64
-        lib.grdma_h2_hpack_decode.argtypes = [C.c_void_p, C.c_void_p, u64, C.c_void_p, u64, C.c_void_p, u64, C.POINTER(u64)]
-        lib.grdma_h2_hpack_table.restype = C.c_int
-        lib.grdma_h2_hpack_table.argtypes = [C.c_void_p, C.c_void_p, u64, C.POINTER(u64)]
-        lib.grdma_h2_hpack_stats.restype = C.c_int
-        lib.grdma_h2_hpack_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
-        lib.grdma_h2_hpack_decode_batch.restype = C.c_int
-        lib.grdma_h2_hpack_decode_batch.argtypes = [C.POINTER(H2HpackItem), C.c_uint32, C.POINTER(u64)]
-        lib.grdma_h2_hpenc_create.restype = C.c_void_p
-        lib.grdma_h2_hpenc_create.argtypes = [C.c_uint32, C.c_uint32]
-        lib.grdma_h2_hpenc_destroy.argtypes = [C.c_void_p]
-        lib.grdma_h2_hpenc_set_peer.restype = C.c_int
-        lib.grdma_h2_hpenc_set_peer.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
-        lib.grdma_h2_hpenc_encode.restype = C.c_int64
-        lib.grdma_h2_hpenc_encode.argtypes = [C.c_void_p, C.c_void_p, u64, C.c_void_p, u64, C.c_void_p, u64, C.c_void_p, u64, C.c_void_p, u64,
-                                              C.POINTER(u64)]
-        lib.grdma_h2_hpenc_table.restype = C.c_int
-        lib.grdma_h2_hpenc_table.argtypes = [C.c_void_p, C.c_void_p, u64, C.POINTER(u64)]
-        lib.grdma_h2_hpenc_stats.restype = C.c_int
-        lib.grdma_h2_hpenc_stats.argtypes = [C.c_void_p, C.POINTER(u64)]
-        lib.grdma_h2_hpenc_last_stages.restype = C.c_int
-        lib.grdma_h2_hpenc_last_stages.argtypes = [C.c_void_p, C.POINTER(u64)]
-        lib.grdma_h2_hpenc_encode_batch.restype = C.c_int
-        lib.grdma_h2_hpenc_encode_batch.argtypes = [C.POINTER(H2HpencItem), C.c_uint32, C.POINTER(u64)]
-        lib.grdma_job_hook_counts.restype = C.c_int   # (not in include/grdma_amd.h: the job's side of the pipes)
-        lib.grdma_job_hook_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-        _bound = True
-    return lib
+def _batch(call, arr, items):
+    """a batch call that writes eight result words per item -> (what it returned, [result tuple per item]); the tuples
+    also land in the .last_result of each item's object"""
+    out = (u64 * (8 * max(1, len(items))))()
+    rc = check(call(arr, len(items), out))
+    return rc, _results(out, [item[0] for item in items])
+
+
+class _Handle:
+    """One grdma_h2_<KIND>_* object of the library (.lib, .h) and what all kinds do alike."""
+
+    KIND = WHAT = None
+    last_result = None
+
+    def _fn(self, name):
+        return getattr(self.lib, "grdma_h2_%s_%s" % (self.KIND, name))
+
+    def _create(self, *args, error=None):
+        """grdma_h2_<KIND>_create(*args) -> .h; a refusal raises with `error` or, without one, in the library's words"""
+        self.lib = load()
+        self.h = self._fn("create")(*args)
+        if not self.h:
+            raise GrdmaError(error or "%s: %s" % (self.WHAT, (self.lib.grdma_last_error() or b"creation failed").decode()))
+
+    def _call(self, name, *args):
+        """grdma_h2_<KIND>_<name>(handle, *args, eight result words) -> what it returned; the words are in .last_result
+        before a failure raises"""
+        out = (u64 * 8)()
+        n = self._fn(name)(self.h, *args, out)
+        _results(out, [self])
+        return check(n)
+
+    def _words(self, name, keys):
+        """the words grdma_h2_<KIND>_<name> reports (at most eight) as a dict"""
+        out = (u64 * 8)()
+        check(self._fn(name)(self.h, out))
+        return dict(zip(keys, [int(x) for x in out]))
+
+    def _stats(self):
+        r = self._words("stats", self.STATS)
+        r["kernel_us"] /= 1e3  # (the ABI word is nanoseconds)
+        return r
+
+    def close(self):
+        if self.h:
+            self._fn("destroy")(self.h)
+            self.h = None
 
 
 def frame_messages(msgs, max_frame, slices_dev_ptr, slices_cap, hdr_dev_ptr, hdr_cap):
     """msgs: list of (payload device ptr, len, stream_id, flags). -> (nslices, wire_bytes)."""
-    lib = _bind()
+    lib = load()
     wire = u64(0)
     n = check(lib.grdma_h2_frame_messages(_msg_array(msgs), len(msgs), max_frame, slices_dev_ptr, slices_cap,
                                           hdr_dev_ptr, hdr_cap, C.byref(wire)))
@@ -350,14 +159,16 @@ H2_SERVER, H2_FIRST_FRAME, H2_BOUNDARY_STEP, H2_NO_BOUNDARY_STEP, H2_BULK_PAIRS,
 H2_NO_CHUNKS = 128
 
 
-class Parser:
+class Parser(_Handle):
     """Deframe state + stream map of one transport in device memory (grdma_h2_parser).
     expect_client_prefix=True: a fresh server connection (streams accepted from HEADERS);
     False: a client / mid-connection parser whose streams the caller opens."""
 
+    KIND = "parser"  # grdma_h2_parser_destroy
+
     def __init__(self, expect_client_prefix=False, max_frame_size=16384, flags=None,
                  max_concurrent_streams=0xFFFFFFFF, table_slots=0, boundary_step=None, bulk_pairs=None, ticks=False, chunks=None):
-        self.lib = _bind()
+        self.lib = load()
         if flags is None:
             flags = (H2_SERVER | H2_FIRST_FRAME) if expect_client_prefix else 0
         if boundary_step is not None:  # None: GRDMA_H2_BOUNDARY_STEP in the environment decides
@@ -432,18 +243,13 @@ class Parser:
             return err.value, msgs
         return err.value, msgs, [e for e in _events(ev, ev_cap) if e[0]]
 
-    def close(self):
-        if self.h:
-            self.lib.grdma_h2_parser_destroy(self.h)
-            self.h = None
-
 
 def deframe_batch(items, caps=None):
     """The delivered slices of many transports in ONE launch (grdma_h2_deframe_batch).  items: [(Parser, arena device
     ptr, [(offset, len), ...]), ...] with distinct parsers; caps: event capacity per item (default: what
     Parser.deframe takes).  -> [(h2 error, events), ...] per item; every item reports for itself: where the events did
     not fit the item's capacity, `events` is the integer -GRDMA_ERR_CAPACITY (-5) instead of a list."""
-    lib = _bind()
+    lib = load()
     n = len(items)
     arr = (H2DeframeItem * max(1, n))()
     keep = []
@@ -468,7 +274,7 @@ def deframe_messages_batch(items, want_events=False, ev_caps=None, msgs_caps=Non
     per item (default: what Parser.deframe_messages takes).  -> per item (h2 error, [Msg...]) or, with want_events,
     (h2 error, [Msg...], events); every item reports for itself: where its events or descriptors did not fit, the
     list is the integer -GRDMA_ERR_CAPACITY (-5) instead."""
-    lib = _bind()
+    lib = load()
     n = len(items)
     arr = (H2MessagesItem * max(1, n))()
     keep = []
@@ -495,7 +301,7 @@ def deframe_messages_batch(items, want_events=False, ev_caps=None, msgs_caps=Non
 
 def release_batch(pairs):
     """Assembler.release for many assemblers in one launch (grdma_h2_asm_release_batch): [(Assembler, n), ...]"""
-    lib = _bind()
+    lib = load()
     n = len(pairs)
     hs = (C.c_void_p * max(1, n))(*[a.h for a, _ in pairs])
     cs = (u64 * max(1, n))(*[c for _, c in pairs])
@@ -508,15 +314,10 @@ def reply_frame_batch(items):
     assemblers.  -> per item (slice count, dict of Reply.REPLY_STATS); every item reports for itself: where its caps
     overflowed, the count is the integer -GRDMA_ERR_CAPACITY (-5) and nothing of that item was written.  frame_us is
     the batch's, repeated.  The stats also land in each Reply's .last_stats."""
-    lib = _bind()
-    n = len(items)
-    arr = (H2ReplyItem * max(1, n))()
-    for i, (reply, *target) in enumerate(items):
-        arr[i].reply = reply.h if reply is not None else None
-        _set_target(arr[i], target)
-    check(lib.grdma_h2_reply_frame_batch(arr, n))
+    arr = _items(H2ReplyItem, items)
+    check(load().grdma_h2_reply_frame_batch(arr, len(items)))
     res = []
-    for i in range(n):
+    for i in range(len(items)):
         st = dict(zip(Reply.REPLY_STATS, [int(x) for x in arr[i].out]))
         items[i][0].last_stats = st
         res.append((int(arr[i].n_slices), st))
@@ -537,7 +338,7 @@ class GroupPipe:
         link whose step has another shape than the job's recorded run keeps its table and reports frame_overflow 2; the
         others go on.  Close it before the forward pipes and before the replies."""
         self = cls.__new__(cls)
-        self.lib = _bind()
+        self.lib = load()
         specs = list(specs)
         arr = (H2ReplyLinkSpec * max(1, len(specs)))()
         self._keep = []
@@ -558,7 +359,7 @@ class GroupPipe:
         return self
 
     def __init__(self, job, specs, max_frame=16384):
-        self.lib = _bind()
+        self.lib = load()
         specs = list(specs)
         arr = (H2LinkSpec * max(1, len(specs)))()
         self._keep = []
@@ -660,16 +461,17 @@ class GroupPipe:
 
 def job_hook_counts(job):
     out = (C.c_uint32 * 2)()
-    check(_bind().grdma_job_hook_counts(job.h, out))
+    check(load().grdma_job_hook_counts(job.h, out))
     return int(out[0]), int(out[1])
 
 
-class Assembler:
+class Assembler(_Handle):
     """Received gRPC messages, contiguous in a ring over `arena` (grdma_h2_asm): a DeviceBuffer-like object (.ptr,
     .nbytes) or a torch uint8 tensor on the device.  max_message_bytes = 0: no limit."""
 
+    KIND = "asm"  # grdma_h2_asm_create, grdma_h2_asm_destroy
+
     def __init__(self, parser, arena, max_message_bytes=4 << 20, max_pending=4096):
-        self.lib = _bind()
         self.parser = parser  # (kept alive)
         self.arena = arena
         if hasattr(arena, "data_ptr"):
@@ -677,19 +479,15 @@ class Assembler:
         else:
             ptr, size = arena.ptr, arena.nbytes
         self.ptr, self.size = ptr, size
-        self.h = self.lib.grdma_h2_asm_create(parser.h, ptr, size, max_message_bytes, max_pending)
-        if not self.h:
-            raise GrdmaError("h2 assembler creation failed")
+        self._create(parser.h, ptr, size, max_message_bytes, max_pending, error="h2 assembler creation failed")
 
     def release(self, n):
         check(self.lib.grdma_h2_asm_release(self.h, n))
 
     def stats(self):
         """dict(reported, ok_bytes, too_large, no_space, truncated, bytes_in_use, plan_us, copy_us)"""
-        out = (u64 * 8)()
-        check(self.lib.grdma_h2_asm_stats(self.h, out))
-        return dict(zip(("reported", "ok_bytes", "too_large", "no_space", "truncated", "bytes_in_use", "plan_us",
-                         "copy_us"), [int(x) for x in out]))
+        return self._words("stats", ("reported", "ok_bytes", "too_large", "no_space", "truncated", "bytes_in_use", "plan_us",
+                                     "copy_us"))  # grdma_h2_asm_stats
 
     def view(self, msg):
         """the bytes of an OK message: a slice of the arena tensor, or bytes read back from the device"""
@@ -701,30 +499,24 @@ class Assembler:
         check(self.lib.grdma_copy_to_host(dst, self.ptr + msg.offset, msg.length))
         return dst.raw[:msg.length]
 
-    def close(self):
-        if self.h:
-            self.lib.grdma_h2_asm_destroy(self.h)
-            self.h = None
 
-
-class Reply:
+class Reply(_Handle):
     """Replies framed on the device from the descriptors of `assembler`'s last call (grdma_h2_reply): every OK message
     back on its own stream (routes=None), or the messages of the streams in routes = [(from_stream, to_stream), ...]
     on their to_stream and the others dropped.  Slices point into the assembler's arena: release behind the send."""
 
+    KIND = "reply"  # grdma_h2_reply_create, grdma_h2_reply_destroy
     REPLY_STATS = ("kept", "dropped_status", "unrouted", "slices", "hdr_bytes", "wire_bytes", "overflow", "frame_us")
 
     def __init__(self, assembler, routes=None, max_frame=16384, max_messages=4096):
-        self.lib = _bind()
         self.assembler = assembler  # (kept alive)
         routes = list(routes or [])
         arr = (H2Route * max(1, len(routes)))()
         for i, (a, b) in enumerate(routes):
             arr[i].from_stream, arr[i].to_stream = a, b
-        self.h = self.lib.grdma_h2_reply_create(assembler.h, arr if routes else None, len(routes), max_frame, max_messages)
-        if not self.h:
-            raise GrdmaError("h2 reply creation failed (a duplicate or zero stream id in the routes, more than 4096 of "
-                             "them, max_frame or max_messages out of range)")
+        self._create(assembler.h, arr if routes else None, len(routes), max_frame, max_messages,
+                     error="h2 reply creation failed (a duplicate or zero stream id in the routes, more than 4096 of them, "
+                           "max_frame or max_messages out of range)")
         self.last_stats = None
 
     def frame(self, slices_ptr, cap, hdr_ptr, hdr_cap):
@@ -766,11 +558,6 @@ class Reply:
         n = check(self.lib.grdma_h2_reply_pending(self.h, out, n))
         return [(int(out[3 * i]), int(out[3 * i + 1]), int(out[3 * i + 2])) for i in range(n)]
 
-    def close(self):
-        if self.h:
-            self.lib.grdma_h2_reply_destroy(self.h)
-            self.h = None
-
 
 def reply_frame_windowed_batch(items):
     """Reply.frame_windowed for many transports in four launches (grdma_h2_reply_frame_windowed_batch).  items: [(Reply,
@@ -778,16 +565,12 @@ def reply_frame_windowed_batch(items):
     distinct source assemblers, each attached to its own SendWindows.  -> per item (slice list, or the integer
     -GRDMA_ERR_CAPACITY (-5) where that item overflowed and nothing of it was written; dict of Reply.WINDOWED).  frame_us
     is the batch's, repeated.  The results also land in each Reply's .last_windowed."""
-    lib = _bind()
-    n = len(items)
-    arr = (H2WrItem * max(1, n))()
-    for i, (reply, *target, pending_only) in enumerate(items):
-        arr[i].reply = reply.h if reply is not None else None
-        arr[i].flags = Reply.PENDING_ONLY if pending_only else 0
-        _set_target(arr[i], target)
-    check(lib.grdma_h2_reply_frame_windowed_batch(arr, n))
+    lib = load()
+    # (H2WrItem's fields in their order: reply, flags, pad, the four target fields)
+    arr = _items(H2WrItem, [(reply, Reply.PENDING_ONLY if pending_only else 0, 0, *target) for reply, *target, pending_only in items])
+    check(lib.grdma_h2_reply_frame_windowed_batch(arr, len(items)))
     res = []
-    for i in range(n):
+    for i in range(len(items)):
         st = dict(zip(Reply.WINDOWED, [int(x) for x in arr[i].out]))
         items[i][0].last_windowed = st
         k = int(arr[i].n_slices)
@@ -798,37 +581,28 @@ def reply_frame_windowed_batch(items):
 FC_CONN_OVERFLOW, FC_STREAM_OVERFLOW, FC_LOST = 1, 2, 4
 
 
-class FlowControl:
+class FlowControl(_Handle):
     """Receive flow control of one transport on the device (grdma_h2_fc): the DATA bytes of a deframing counted
     against stream_window / conn_window, and the WINDOW_UPDATE frames that return them.  One per parser."""
 
+    KIND, WHAT = "fc", "h2 flow control"  # grdma_h2_fc_create, grdma_h2_fc_destroy
     RESULT = ("frames", "slices", "wire_bytes", "conn_bytes", "stream_bytes", "violations", "first_violator", "overflow")
     STATS = ("calls", "conn_bytes", "stream_bytes", "frames", "conn_overflows", "stream_overflows", "announced", "kernel_us")
 
     def __init__(self, parser, stream_window=65535, conn_window=65535, conn_threshold=0, max_updates=4096):
-        self.lib = _bind()
         self.parser = parser  # (kept alive)
         self.max_updates = max_updates
-        self.h = self.lib.grdma_h2_fc_create(parser.h, stream_window, conn_window, conn_threshold, max_updates)
-        if not self.h:
-            raise GrdmaError("h2 flow control: " + (self.lib.grdma_last_error() or b"creation failed").decode())
-        self.last_result = None
+        self._create(parser.h, stream_window, conn_window, conn_threshold, max_updates)
 
     def account(self, slices_ptr, cap, hdr_ptr, hdr_cap):
         """accounts the parser's last standalone deframing -> ([(ptr, len), ...], result tuple (RESULT), wire bytes);
         raises GrdmaError on a refusal or a capacity overflow -- the result of the failed call stays in .last_result"""
-        out = (u64 * 8)()
-        n = self.lib.grdma_h2_fc_account(self.h, slices_ptr, cap, hdr_ptr, hdr_cap, out)
-        _results(out, [self])
-        sl = _read_slice_table(self.lib, slices_ptr, check(n))
+        sl = _read_slice_table(self.lib, slices_ptr, self._call("account", slices_ptr, cap, hdr_ptr, hdr_cap))  # grdma_h2_fc_account
         return sl, self.last_result, _read_wire(self.lib, sl)
 
     def stats(self):
         """dict of STATS; `lost`: the sticky flag; announced: the connection window the peer knows (may be negative)"""
-        out = (u64 * 8)()
-        check(self.lib.grdma_h2_fc_stats(self.h, out))
-        r = dict(zip(FlowControl.STATS, [int(x) for x in out]))
-        r["kernel_us"] /= 1e3  # (the ABI word is nanoseconds)
+        r = self._stats()  # grdma_h2_fc_stats
         r["lost"] = bool(r["stream_overflows"] >> 63)
         r["stream_overflows"] &= (1 << 63) - 1
         r["announced"] = r["announced"] - (1 << 64) if r["announced"] >> 63 else r["announced"]
@@ -841,10 +615,11 @@ class FlowControl:
             self.h = None
 
 
-class SendWindows:
+class SendWindows(_Handle):
     """Send flow control of one transport on the device (grdma_h2_sw): the peer's windows, fed from the parser's
     deframings (intake), and grdma_h2_frame_messages under them (frame).  One per parser."""
 
+    KIND, WHAT = "sw", "h2 send windows"  # grdma_h2_sw_create, grdma_h2_sw_destroy
     INTAKE = ("window_updates", "conn_credit", "stream_credit", "settings", "violations", "first_offender", "live_entries",
               "overflow")
     FRAME = ("completed", "held", "slices", "hdr_bytes", "wire_bytes", "granted", "stall", "overflow")
@@ -852,20 +627,13 @@ class SendWindows:
     BAD_INCREMENT, WINDOW_OVERFLOW, BAD_SETTINGS, LOST = 1, 2, 4, 8
 
     def __init__(self, parser, initial_window=65535, conn_window=65535, peer_max_frame=16384):
-        self.lib = _bind()
         self.parser = parser  # (kept alive)
-        self.h = self.lib.grdma_h2_sw_create(parser.h, initial_window, conn_window, peer_max_frame)
-        if not self.h:
-            raise GrdmaError("h2 send windows: " + (self.lib.grdma_last_error() or b"creation failed").decode())
-        self.last_result = None
+        self._create(parser.h, initial_window, conn_window, peer_max_frame)
 
     def intake(self):
         """takes in the parser's last standalone deframing -> result tuple (INTAKE); raises GrdmaError on a refusal or a
         lost call -- the result of the failed call stays in .last_result"""
-        out = (u64 * 8)()
-        n = self.lib.grdma_h2_sw_intake(self.h, out)
-        _results(out, [self])
-        check(n)
+        self._call("intake")  # grdma_h2_sw_intake
         return self.last_result
 
     def frame(self, msgs, progress, max_frame, slices_ptr, cap, hdr_ptr, hdr_cap):
@@ -874,10 +642,8 @@ class SendWindows:
         a capacity overflow -- the result of the failed call stays in .last_result, nothing was sent"""
         n = len(msgs)
         prog = (u64 * max(1, n))(*progress)
-        out = (u64 * 8)()
-        k = self.lib.grdma_h2_sw_frame(self.h, _msg_array(msgs), prog, n, max_frame, slices_ptr, cap, hdr_ptr, hdr_cap, out)
-        _results(out, [self])
-        return _read_slice_table(self.lib, slices_ptr, check(k)), self.last_result, [int(x) for x in prog[:n]]
+        k = self._call("frame", _msg_array(msgs), prog, n, max_frame, slices_ptr, cap, hdr_ptr, hdr_cap)  # grdma_h2_sw_frame
+        return _read_slice_table(self.lib, slices_ptr, k), self.last_result, [int(x) for x in prog[:n]]
 
     def windows(self, ids):
         """the windows as they are: id 0 is the connection's, another id its stream's (may be negative)"""
@@ -889,87 +655,61 @@ class SendWindows:
 
     def stats(self):
         """dict of STATS plus `lost` (the sticky flag), `initial_window` and `max_frame` (the peer's settings)"""
-        out = (u64 * 8)()
-        check(self.lib.grdma_h2_sw_stats(self.h, out))
-        r = dict(zip(SendWindows.STATS, [int(x) for x in out]))
-        r["kernel_us"] /= 1e3  # (the ABI word is nanoseconds)
+        r = self._stats()  # grdma_h2_sw_stats
         r["lost"] = bool(r["violations"] >> 63)
         r["violations"] &= (1 << 63) - 1
         r["initial_window"], r["max_frame"] = r["peer_settings"] & 0xffffffff, r.pop("peer_settings") >> 32
         return r
 
-    def close(self):
-        if self.h:
-            self.lib.grdma_h2_sw_destroy(self.h)
-            self.h = None
 
-
-class ControlReplies:
+class ControlReplies(_Handle):
     """The control replies of one transport on the device (grdma_h2_ctl): SETTINGS ACK, PING ACK and RST_STREAM written
     from the parser's deframings, and the record of what the peer said.  One per parser; independent of FlowControl and
     SendWindows, which may consume the same deframing."""
 
+    KIND, WHAT = "ctl", "h2 control replies"  # grdma_h2_ctl_create, grdma_h2_ctl_destroy
     RESULT = ("frames", "slices", "wire_bytes", "settings_acks", "ping_acks", "rst_streams", "flags", "overflow")
     PEER = ("settings_acks", "ping_acks", "last_ping_opaque", "goaways", "goaway_last_stream", "goaway_error", "goaway_call")
     STATS = ("calls", "settings_acks", "ping_acks", "rst_streams", "wire_bytes", "reserved", "lost", "kernel_us")
     LOST, GOAWAY = 1, 2
 
     def __init__(self, parser, max_replies=4096):
-        self.lib = _bind()
         self.parser = parser  # (kept alive)
-        self.h = self.lib.grdma_h2_ctl_create(parser.h, max_replies)
-        if not self.h:
-            raise GrdmaError("h2 control replies: " + (self.lib.grdma_last_error() or b"creation failed").decode())
-        self.last_result = None
+        self._create(parser.h, max_replies)
 
     def reply(self, slices_ptr, cap, hdr_ptr, hdr_cap):
         """answers the parser's last standalone deframing -> ([(ptr, len), ...], result tuple (RESULT)); raises
         GrdmaError on a refusal, a lost call or a capacity overflow -- the result of the failed call stays in
         .last_result; after a capacity overflow (overflow word 1) the call may be repeated with larger targets"""
-        out = (u64 * 8)()
-        n = self.lib.grdma_h2_ctl_reply(self.h, slices_ptr, cap, hdr_ptr, hdr_cap, out)
-        _results(out, [self])
-        return _read_slice_table(self.lib, slices_ptr, check(n)), self.last_result
+        n = self._call("reply", slices_ptr, cap, hdr_ptr, hdr_cap)  # grdma_h2_ctl_reply
+        return _read_slice_table(self.lib, slices_ptr, n), self.last_result
 
     def peer(self):
         """dict of PEER: what the peer said so far"""
-        out = (u64 * 8)()
-        check(self.lib.grdma_h2_ctl_peer(self.h, out))
-        return dict(zip(ControlReplies.PEER, [int(x) for x in out]))
+        return self._words("peer", ControlReplies.PEER)  # grdma_h2_ctl_peer
 
     def stats(self):
         """dict of STATS; `lost`: the sticky flag"""
-        out = (u64 * 8)()
-        check(self.lib.grdma_h2_ctl_stats(self.h, out))
-        r = dict(zip(ControlReplies.STATS, [int(x) for x in out]))
+        r = self._stats()  # grdma_h2_ctl_stats
         r.pop("reserved")
-        r["kernel_us"] /= 1e3  # (the ABI word is nanoseconds)
         r["lost"] = bool(r["lost"])
         return r
 
-    def close(self):
-        if self.h:
-            self.lib.grdma_h2_ctl_destroy(self.h)
-            self.h = None
 
-
-class HeaderDecoder:
+class HeaderDecoder(_Handle):
     """The header blocks of one transport decoded on the device (grdma_h2_hpack): the HPACK blocks of the parser's
     deframings as a block table, a field table and a string arena in device memory.  One per parser; independent of
     FlowControl, SendWindows and ControlReplies, which may consume the same deframing."""
 
+    KIND, WHAT = "hpack", "h2 header decoder"  # grdma_h2_hpack_create, grdma_h2_hpack_destroy
     RESULT = ("blocks", "fields", "string_bytes", "inserted", "evicted", "table_bytes", "flags", "overflow")
     STATS = ("calls", "blocks", "fields", "string_bytes", "inserted", "evicted", "flags", "kernel_us")
     FAILED, LOST, OPEN = 1, 2, 4
     ERRORS = (None, "padding", "block too large", "integer", "truncated", "huffman", "index", "size update", "deframer")
 
     def __init__(self, parser, max_table_size=4096, max_block_bytes=65536):
-        self.lib = _bind()
         self.parser = parser  # (kept alive)
-        self.h = self.lib.grdma_h2_hpack_create(parser.h, max_table_size, max_block_bytes)
-        if not self.h:
-            raise GrdmaError("h2 header decoder: " + (self.lib.grdma_last_error() or b"creation failed").decode())
-        self.last_result = None
+        self._create(parser.h, max_table_size, max_block_bytes)
 
     def set_max_table_size(self, n):
         """our SETTINGS_HEADER_TABLE_SIZE from now on: the bound of the peer's size updates; a lowered one evicts at once"""
@@ -980,10 +720,8 @@ class HeaderDecoder:
         count, result tuple (RESULT)); raises GrdmaError on a refusal, a lost call or a capacity overflow -- the result
         of the failed call stays in .last_result; after a capacity overflow (overflow word 1) the call may be repeated
         with larger targets.  flags: FAILED | LOST | OPEN, the error in bits 8..15, the failing stream from bit 32"""
-        out = (u64 * 8)()
-        n = self.lib.grdma_h2_hpack_decode(self.h, blocks_ptr, blocks_cap, fields_ptr, fields_cap, strings_ptr, strings_cap, out)
-        _results(out, [self])
-        return check(n), self.last_result
+        n = self._call("decode", blocks_ptr, blocks_cap, fields_ptr, fields_cap, strings_ptr, strings_cap)  # grdma_h2_hpack_decode
+        return n, self.last_result
 
     def table(self):
         """the live dynamic table -> ([(name, value), ...] newest first, (entries, table bytes, the size limit in force))"""
@@ -991,16 +729,7 @@ class HeaderDecoder:
 
     def stats(self):
         """dict of STATS; `flags`: the sticky word (FAILED | LOST, error << 8, stream << 32)"""
-        out = (u64 * 8)()
-        check(self.lib.grdma_h2_hpack_stats(self.h, out))
-        r = dict(zip(HeaderDecoder.STATS, [int(x) for x in out]))
-        r["kernel_us"] /= 1e3  # (the ABI word is nanoseconds)
-        return r
-
-    def close(self):
-        if self.h:
-            self.lib.grdma_h2_hpack_destroy(self.h)
-            self.h = None
+        return self._stats()  # grdma_h2_hpack_stats
 
 
 def _table_dump(call, h):
@@ -1020,22 +749,19 @@ def _table_dump(call, h):
     return entries, (int(out[0]), int(out[2]), int(out[3]))
 
 
-class HeaderEncoder:
+class HeaderEncoder(_Handle):
     """Header lists encoded on the device (grdma_h2_hpenc): a block table, a field table and a string arena in device
     memory -- the layout HeaderDecoder writes -- into the wire bytes of HEADERS and CONTINUATION frames, against the
     peer's dynamic table.  One per connection; it follows no parser."""
 
+    KIND, WHAT = "hpenc", "h2 header encoder"  # grdma_h2_hpenc_create, grdma_h2_hpenc_destroy
     RESULT = ("blocks", "frames", "wire_bytes", "inserted", "evicted", "table_bytes", "flags", "overflow")
     STATS = ("calls", "blocks", "fields", "list_bytes", "wire_bytes", "inserted", "evicted", "kernel_us")
     BAD_INPUT = 1
     ERRORS = (None, "field range", "stream", "length", "string", "block too large")
 
     def __init__(self, peer_table_size=4096, peer_max_frame=16384):
-        self.lib = _bind()
-        self.h = self.lib.grdma_h2_hpenc_create(peer_table_size, peer_max_frame)
-        if not self.h:
-            raise GrdmaError("h2 header encoder: " + (self.lib.grdma_last_error() or b"creation failed").decode())
-        self.last_result = None
+        self._create(peer_table_size, peer_max_frame)
 
     def set_peer(self, peer_table_size, peer_max_frame):
         """the peer's SETTINGS_HEADER_TABLE_SIZE and SETTINGS_MAX_FRAME_SIZE from now on; the next call that sends a block
@@ -1046,34 +772,23 @@ class HeaderEncoder:
         """-> (frame count, result tuple (RESULT)); raises GrdmaError on a refusal, on bad input (flags: BAD_INPUT | error
         << 8 | block << 32) and on a capacity overflow (overflow word 1: nothing was written or committed, the call may
         be repeated with larger targets) -- the result of the failed call stays in .last_result"""
-        out = (u64 * 8)()
         self.last_result = None
-        n = self.lib.grdma_h2_hpenc_encode(self.h, blocks_ptr, nblocks, fields_ptr, nfields, strings_ptr, strings_bytes, wire_ptr, wire_cap,
-                                           block_wire_ptr, block_wire_cap, out)
-        self.last_result = tuple(int(x) for x in out)
-        return check(n), self.last_result
+        n = self._call("encode", blocks_ptr, nblocks, fields_ptr, nfields, strings_ptr, strings_bytes, wire_ptr, wire_cap, block_wire_ptr,
+                       block_wire_cap)  # grdma_h2_hpenc_encode
+        return n, self.last_result
 
     def table(self):
         """the encoder's view of the peer's dynamic table, as HeaderDecoder.table"""
         return _table_dump(self.lib.grdma_h2_hpenc_table, self.h)
 
     def stats(self):
-        out = (u64 * 8)()
-        check(self.lib.grdma_h2_hpenc_stats(self.h, out))
-        r = dict(zip(HeaderEncoder.STATS, [int(x) for x in out]))
-        r["kernel_us"] /= 1e3  # (the ABI word is nanoseconds)
-        return r
+        return self._stats()  # grdma_h2_hpenc_stats
 
     def last_stages(self):
         """the last call's kernel time by stage, microseconds: (scan, walk, emit and commit, total)"""
         out = (u64 * 4)()
         check(self.lib.grdma_h2_hpenc_last_stages(self.h, out))
         return tuple(int(x) / 1e3 for x in out)
-
-    def close(self):
-        if self.h:
-            self.lib.grdma_h2_hpenc_destroy(self.h)
-            self.h = None
 
 
 def decode_batch(items):
@@ -1084,18 +799,7 @@ def decode_batch(items):
     reports for itself in its tuple (overflow word 2 / 1: after 1 nothing of it was written or committed and it may be
     repeated, alone or in a later batch).  The result tuples also land in each decoder's .last_result.  Raises
     GrdmaError only on a refusal."""
-    lib = _bind()
-    n = len(items)
-    arr = (H2HpackItem * max(1, n))()
-    for i, item in enumerate(items):
-        if item is None:
-            continue
-        dec, *target = item
-        arr[i].hpack = dec.h if dec is not None else None
-        (arr[i].d_blocks, arr[i].blocks_cap, arr[i].d_fields, arr[i].fields_cap, arr[i].d_strings, arr[i].strings_cap) = target
-    out = (u64 * (8 * max(1, n)))()
-    count = check(lib.grdma_h2_hpack_decode_batch(arr, n, out))
-    return count, _results(out, [item[0] for item in items])
+    return _batch(load().grdma_h2_hpack_decode_batch, _items(H2HpackItem, items), items)
 
 
 def encode_batch(items):
@@ -1107,19 +811,7 @@ def encode_batch(items):
     in its tuple (flags: BAD_INPUT | error << 8 | block << 32; overflow word 1: nothing of it was written or committed
     and it may be repeated, alone or in a later batch).  The result tuples also land in each encoder's .last_result.
     Raises GrdmaError only on a refusal of the whole call."""
-    lib = _bind()
-    n = len(items)
-    arr = (H2HpencItem * max(1, n))()
-    for i, item in enumerate(items):
-        if item is None:
-            continue
-        enc, *rest = item
-        arr[i].enc = enc.h if enc is not None else None
-        (arr[i].d_blocks, arr[i].nblocks, arr[i].d_fields, arr[i].nfields, arr[i].d_strings, arr[i].strings_bytes, arr[i].d_wire,
-         arr[i].wire_cap, arr[i].d_block_wire, arr[i].block_wire_cap) = rest
-    out = (u64 * (8 * max(1, n)))()
-    count = check(lib.grdma_h2_hpenc_encode_batch(arr, n, out))
-    return count, _results(out, [item[0] for item in items])
+    return _batch(load().grdma_h2_hpenc_encode_batch, _items(H2HpencItem, items), items)
 
 
 def control_batch(items):
@@ -1128,19 +820,9 @@ def control_batch(items):
     standalone deframing of its own parser.  -> per item ([(ptr, len), ...], result tuple (ControlReplies.RESULT)); an
     item whose call was lost or overflowed a cap reports for itself: its result tuple and None, nothing of it was
     written.  The result tuples also land in each writer's .last_result.  Raises GrdmaError on a refusal."""
-    lib = _bind()
-    n = len(items)
-    arr = (H2CtlItem * max(1, n))()
-    for i, item in enumerate(items):
-        if item is None:
-            continue
-        ctl, *target = item
-        arr[i].ctl = ctl.h if ctl is not None else None
-        _set_target(arr[i], target)
-    out = (u64 * (8 * max(1, n)))()
-    check(lib.grdma_h2_ctl_reply_batch(arr, n, out))
-    return [(r, None) if r[7] else (_read_slice_table(lib, item[1], r[1]), r)
-            for item, r in zip(items, _results(out, [item[0] for item in items]))]
+    lib = load()
+    _, results = _batch(lib.grdma_h2_ctl_reply_batch, _items(H2CtlItem, items), items)
+    return [(r, None) if r[7] else (_read_slice_table(lib, item[1], r[1]), r) for item, r in zip(items, results)]
 
 
 def account_batch(items):
@@ -1149,16 +831,10 @@ def account_batch(items):
     accounts the last standalone deframing of its own parser.  -> per item ([(ptr, len), ...], result tuple
     (FlowControl.RESULT), wire bytes); an item whose call was lost or overflowed a cap reports for itself: its result
     tuple and None, nothing of it was written.  The result tuples also land in each ledger's .last_result."""
-    lib = _bind()
-    n = len(items)
-    arr = (H2FcItem * max(1, n))()
-    for i, (fc, *target) in enumerate(items):
-        arr[i].fc = fc.h if fc is not None else None
-        _set_target(arr[i], target)
-    out = (u64 * (8 * max(1, n)))()
-    check(lib.grdma_h2_fc_account_batch(arr, n, out))
+    lib = load()
+    _, results = _batch(lib.grdma_h2_fc_account_batch, _items(H2FcItem, items), items)
     res = []
-    for item, r in zip(items, _results(out, [item[0] for item in items])):
+    for item, r in zip(items, results):
         if r[7]:
             res.append((r, None))
             continue
@@ -1172,12 +848,8 @@ def intake_batch(sws):
     each takes in the last standalone deframing of its own parser.  -> per item its result tuple (SendWindows.INTAKE);
     an item whose call was lost reports for itself (overflow word 2, the LOST bit): its tuple is in the list, the
     others are exact.  The result tuples also land in each object's .last_result.  Raises GrdmaError on a refusal."""
-    lib = _bind()
-    n = len(sws)
-    arr = (C.c_void_p * max(1, n))(*[s.h if s is not None else None for s in sws])
-    out = (u64 * (8 * max(1, n)))()
-    check(lib.grdma_h2_sw_intake_batch(arr, n, out))
-    return _results(out, sws)
+    arr = (C.c_void_p * max(1, len(sws)))(*[s.h if s is not None else None for s in sws])
+    return _batch(load().grdma_h2_sw_intake_batch, arr, [(s,) for s in sws])[1]
 
 
 def frame_windowed_batch(items):
@@ -1187,24 +859,15 @@ def frame_windowed_batch(items):
     (SendWindows.FRAME), progress after the call); an item whose cap overflowed reports for itself: its result tuple and
     None -- nothing of it was written, no window of it moved.  The result tuples also land in each object's
     .last_result.  Raises GrdmaError on a refusal."""
-    lib = _bind()
-    n = len(items)
-    arr = (H2SwFrameItem * max(1, n))()
-    keep = []  # (the arrays the items point to)
-    for i, (sw, msgs, progress, max_frame, *target) in enumerate(items):
+    lib = load()
+    rows = []  # (per item the struct's fields in their order, arrays for msgs and progress; they also keep the arrays alive)
+    for sw, msgs, progress, max_frame, *target in items:
         marr = _msg_array(msgs) if msgs is not None else None
         prog = (u64 * max(1, len(progress)))(*progress) if progress is not None else None
-        keep.append((marr, prog))
-        arr[i].sw = sw.h if sw is not None else None
-        arr[i].msgs = marr
-        arr[i].progress = prog
-        arr[i].nmsgs = len(msgs) if msgs is not None else 0
-        arr[i].max_frame = max_frame
-        _set_target(arr[i], target)
-    out = (u64 * (8 * max(1, n)))()
-    check(lib.grdma_h2_sw_frame_batch(arr, n, out))
-    return [(r, None) if r[7] else (_read_slice_table(lib, item[4], r[2]), r, [int(x) for x in prog[:len(item[1])]])
-            for item, (_, prog), r in zip(items, keep, _results(out, [item[0] for item in items]))]
+        rows.append((sw, marr, prog, len(msgs) if msgs is not None else 0, max_frame, 0, *target))
+    _, results = _batch(lib.grdma_h2_sw_frame_batch, _items(H2SwFrameItem, rows), items)
+    return [(r, None) if r[7] else (_read_slice_table(lib, item[4], r[2]), r, [int(x) for x in row[2][:len(item[1])]])
+            for item, row, r in zip(items, rows, results)]
 
 
 class Pipe:
@@ -1214,7 +877,7 @@ class Pipe:
     GroupPipe (a second Pipe on another link would replace this one's kernels in the job's graph)."""
 
     def __init__(self, job, msgs, parser, delivered_slices, events_cap, link=0, max_frame=16384):
-        self.lib = _bind()
+        self.lib = load()
         self.events_cap = events_cap
         self.delivered = delivered_slices
         self.parser = parser  # (kept alive)
@@ -1229,7 +892,7 @@ class Pipe:
         forward step reported, sends it through `job` and deframes it with `parser`.  recorded_wire_bytes: what the
         job's recorded run sent.  Close it before the forward pipes and before `reply`."""
         self = cls.__new__(cls)
-        self.lib = _bind()
+        self.lib = load()
         self.events_cap = events_cap
         self.delivered = delivered_slices
         self.parser, self.reply_framer = parser, reply  # (kept alive)

@@ -209,23 +209,18 @@ class Pair:
         return out, bool(wb.value)
 
     def set_latency_mode(self, on=True):
-        self.lib.grdma_pair_set_latency_mode.argtypes = [C.c_void_p, C.c_int]
         check(self.lib.grdma_pair_set_latency_mode(self.h, int(on)))
 
     def arm_read(self, max_reads=64):
         """grdma_pair_arm_read: a standing read order, carried out by a watcher workgroup of the latency engine when
         bytes land in this pair's ring; 0 disarms."""
-        self.lib.grdma_pair_arm_read.argtypes = [C.c_void_p, C.c_uint64]
         check(self.lib.grdma_pair_arm_read(self.h, int(max_reads)))
 
     def watch_hits(self):
         """Completions a watcher workgroup of the engine produced (arrival-triggered drains) that a read has taken."""
-        self.lib.grdma_pair_watch_hits.argtypes = [C.c_void_p]
-        self.lib.grdma_pair_watch_hits.restype = C.c_int64
         return int(self.lib.grdma_pair_watch_hits(self.h))
 
     def armed_ready(self):
-        self.lib.grdma_pair_armed_ready.argtypes = [C.c_void_p]
         return int(self.lib.grdma_pair_armed_ready(self.h))
 
     # -- observability -------------------------------------------------------------
@@ -269,9 +264,6 @@ def pingpong(a, b, req_slices, resp_slices, iters=1000, warmup=100):
     """Unary ping-pong a -> b -> a (grdma_pingpong).  Slices are host bytes.
     -> (list of RTT in ns, [phase ns sums: client write, server read, server write, client read])"""
     lib = load()
-    lib.grdma_pingpong.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Slice), C.c_uint64,
-                                   C.POINTER(Slice), C.c_uint64, C.c_int, C.c_uint64, C.c_uint64,
-                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     ra, ka, _ = Pair._slices(req_slices)
     rb, kb, _ = Pair._slices(resp_slices)
     rtt = (C.c_uint64 * iters)()

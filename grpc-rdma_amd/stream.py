@@ -2,53 +2,21 @@
 list through a connected loop-back link with no host round trips."""
 import ctypes as C
 
-from ._lib import GrdmaError, ReadSlice, Slice, check, load
+from ._abi import ReadSlice, Slice, StreamResult
+from ._lib import GrdmaError, check, load
 
 u64 = C.c_uint64
-
-
-class StreamResult(C.Structure):
-    _fields_ = [(n, u64) for n in ("bytes_sent", "bytes_delivered", "slices_delivered",
-                                   "tx_rounds", "rx_rounds", "tx_records", "rx_records", "done")] + \
-               [("ms_total", C.c_double), ("ms_class", C.c_double * 8),
-                ("launches_class", u64 * 8)]
 
 
 RUN_EAGER, RUN_GRAPH, RUN_INSTRUMENTED, RUN_INSTRUMENTED_SCHEDULE = 0, 1, 2, 4
 # classes 5 and 6 exist in RUN_INSTRUMENTED_SCHEDULE only: the launches two stages of neighbouring rounds share
 CLASS_NAMES = ["tx_plan", "gather", "wire", "rx_plan", "rx_apply", "plan_pair", "scatter_gather"]
 
-_bound = False
-
-
-def _bind():
-    global _bound
-    lib = load()
-    if not _bound:
-        lib.grdma_stream_job_create.restype = C.c_void_p
-        lib.grdma_stream_job_create.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Slice), u64,
-                                                C.c_void_p, u64, u64, u64]
-        lib.grdma_stream_job_destroy.argtypes = [C.c_void_p]
-        lib.grdma_stream_job_run.argtypes = [C.c_void_p, C.c_int, C.POINTER(StreamResult)]
-        lib.grdma_stream_job_slices.argtypes = [C.c_void_p, C.POINTER(ReadSlice), u64]
-        lib.grdma_stream_job_set_rounds.argtypes = [C.c_void_p, u64]
-        lib.grdma_stream_job_set_pipeline.argtypes = [C.c_void_p, C.c_int]
-        lib.grdma_stream_job_launch.argtypes = [C.c_void_p]
-        lib.grdma_stream_job_launch_streams.argtypes = [C.c_void_p]
-        lib.grdma_stream_job_create_multi.restype = C.c_void_p
-        lib.grdma_stream_job_create_multi.argtypes = [C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                                      C.POINTER(Slice), C.POINTER(u64), C.POINTER(C.c_void_p),
-                                                      C.POINTER(u64), C.POINTER(u64), u64]
-        lib.grdma_stream_job_slices_of.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(ReadSlice), u64]
-        lib.grdma_stream_job_sync.argtypes = [C.c_void_p]
-        _bound = True
-    return lib
-
 
 class StreamJob:
     def __init__(self, tx, rx, slices, rx_dst_ptr, rx_dst_cap, slices_cap, max_rounds):
         """slices: list of (device ptr, len)."""
-        self.lib = _bind()
+        self.lib = load()
         arr = (Slice * len(slices))()
         for i, (p, n) in enumerate(slices):
             arr[i].ptr, arr[i].len = p, n
@@ -65,13 +33,11 @@ class StreamJob:
     def set_sends(self, sends):
         """`sends` consecutive Sends per round in one plan (grdma_stream_job_set_sends: rdma_flush's loop while the ring
         has room), paired schedule of a pipelined job."""
-        self.lib.grdma_stream_job_set_sends.argtypes = [C.c_void_p, C.c_uint32]
         check(self.lib.grdma_stream_job_set_sends(self.h, sends))
 
     def set_promised_credit(self, on=True):
         """Paired schedule, staged wire: the Send of round t + 1 priced with the credit the drain of round t will post
         (grdma_stream_job_set_promised_credit)."""
-        self.lib.grdma_stream_job_set_promised_credit.argtypes = [C.c_void_p, C.c_int]
         check(self.lib.grdma_stream_job_set_promised_credit(self.h, 1 if on else 0))
 
     def set_fused_wire(self, on=True):
@@ -85,7 +51,6 @@ class StreamJob:
     def set_rebuild_index(self, on=True):
         """The slice tables are rewritten between steps: the index the Sends are priced from is rebuilt in every step
         (grdma_stream_job_set_rebuild_index)."""
-        self.lib.grdma_stream_job_set_rebuild_index.argtypes = [C.c_void_p, C.c_int]
         check(self.lib.grdma_stream_job_set_rebuild_index(self.h, 1 if on else 0))
 
     def set_pipeline(self, on):
@@ -121,7 +86,7 @@ class MultiStreamJob(StreamJob):
 
     def __init__(self, links, max_rounds):
         """links: list of (tx Pair, rx Pair, slices [(ptr,len)...], dst ptr, dst cap, slices cap)."""
-        self.lib = _bind()
+        self.lib = load()
         n = len(links)
         self._ends = [(l[0], l[1]) for l in links]  # (kept alive: the job's kernels work on the pairs' rings)
         txs = (C.c_void_p * n)(*[l[0].h for l in links])

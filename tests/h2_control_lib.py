@@ -182,5 +182,5 @@ def reply_batch_raw(hs, order, caps=None):
         arr[k].ctl = h.ctl.h
         arr[k].d_slices_out, arr[k].slices_cap, arr[k].d_hdr_arena, arr[k].hdr_cap = h.target.slices.ptr, cap, h.target.hdr.ptr, hdr_cap
     out = (C.c_uint64 * (8 * len(order)))()
-    rc = h2dev._bind().grdma_h2_ctl_reply_batch(arr, len(order), out)
+    rc = h2dev.load().grdma_h2_ctl_reply_batch(arr, len(order), out)
     return rc, [tuple(int(x) for x in out[8 * k:8 * k + 8]) for k in range(len(order))]

@@ -33,7 +33,7 @@ def decode_batch_raw(hs, order, caps=None):
         arr[k].hpack = h.dec.h
         (arr[k].d_blocks, arr[k].blocks_cap, arr[k].d_fields, arr[k].fields_cap, arr[k].d_strings, arr[k].strings_cap) = h.target.args()
     out = (C.c_uint64 * (8 * len(order)))()
-    rc = h2dev._bind().grdma_h2_hpack_decode_batch(arr, len(order), out)
+    rc = h2dev.load().grdma_h2_hpack_decode_batch(arr, len(order), out)
     return rc, [tuple(int(x) for x in out[8 * k:8 * k + 8]) for k in range(len(order))]
 
 

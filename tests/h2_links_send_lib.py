@@ -47,7 +47,7 @@ def intake_batch(hs, order, lost=(), got=None):
 
 def intake_batch_raw(hs, order):
     """grdma_h2_sw_intake_batch itself -> (its return value, the result tuples)"""
-    lib = hs[order[0]].h2dev._bind()
+    lib = hs[order[0]].h2dev.load()
     arr = (C.c_void_p * len(order))(*[hs[i].sw.h for i in order])
     out = (C.c_uint64 * (8 * len(order)))()
     rc = lib.grdma_h2_sw_intake_batch(arr, len(order), out)

@@ -405,9 +405,6 @@ def run_on_device(g, seq, fast, count_exact=True):
     caller has set it (read when the engine starts)."""
     lib = g.load()
     F = seq.final
-    lib.grdma_watch_fast_drains.restype = C.c_uint64
-    lib.grdma_express_drains.restype = C.c_uint64
-    lib.grdma_pair_debug_hist.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     a, b = mk_link(g, seq.ring, MAX_SGE, seq.flags)
     a.set_latency_mode(True)
     b.set_latency_mode(True)

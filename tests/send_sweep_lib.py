@@ -381,24 +381,6 @@ class _States:
         return self.st[side]
 
 
-_DECLARED = False
-
-
-def _declare(lib):
-    global _DECLARED
-    if _DECLARED:
-        return
-    lib.grdma_pair_last_dbg.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    lib.grdma_pair_last_dbg.restype = C.c_int
-    lib.grdma_endpoint_set_async.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
-    lib.grdma_endpoint_set_async.restype = C.c_int
-    lib.grdma_endpoint_write_submit.argtypes = [C.c_void_p]
-    lib.grdma_endpoint_write_submit.restype = C.c_int
-    lib.grdma_endpoint_write_test.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64)]
-    lib.grdma_endpoint_write_test.restype = C.c_int
-    _DECLARED = True
-
-
 def _window_of(lib, pair):
     tx, rx = (C.c_uint64 * 16)(), (C.c_uint64 * 16)()
     assert lib.grdma_pair_last_dbg(pair.h, tx, rx) == 0
@@ -421,7 +403,6 @@ WRITE_DEADLINE = 30.0   # seconds one burst may take before the test fails
 def run_on_device(g, script, wire, tag=""):
     """The finished script on a connected pair a -> b: after every step what the oracle showed after the same step."""
     lib = g.load()
-    _declare(lib)
     flags = WIRES[wire]
     R = script.ring
     a, b = mk_link(g, R, script.max_sge, flags)

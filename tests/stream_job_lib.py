@@ -109,7 +109,6 @@ def _table_cache_stats(g):
     import ctypes as C
     lib = g.load()
     out = (C.c_uint64 * 2)()
-    lib.grdma_rx_table_cache_stats.argtypes = [C.POINTER(C.c_uint64)]
     assert lib.grdma_rx_table_cache_stats(out) == 0
     return [int(x) for x in out]
 
@@ -118,10 +117,8 @@ def _fast_counts(g):
     import ctypes as C
     lib = g.load()
     out = (C.c_uint64 * 6)()
-    lib.grdma_rx_fast_drains.argtypes = [C.POINTER(C.c_uint64)]
     assert lib.grdma_rx_fast_drains(out) == 0
     tx = (C.c_uint64 * 2)()
-    lib.grdma_tx_fast_sends.argtypes = [C.POINTER(C.c_uint64)]
     assert lib.grdma_tx_fast_sends(tx) == 0
     return [int(x) for x in out] + [int(x) for x in tx]
 

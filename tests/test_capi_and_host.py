@@ -28,12 +28,6 @@ def test_library_exports_every_declared_symbol(built):
         assert hasattr(lib, n), "libgrdma_amd.so does not export %s" % n
 
 
-def test_python_binding_table_covers_the_core_abi(built):
-    names = set(declared_functions())
-    assert set(_lib.SIGNATURES) <= names
-    assert g.load().grdma_abi_version() == 2
-
-
 def test_no_device_fails_loudly(built):
     lib = g.load()
     if lib.grdma_device_count() > 0:
@@ -97,14 +91,7 @@ def test_config_defaults_and_env(built, monkeypatch):
 
 
 def test_host_ring_arithmetic_matches_oracle(built):
-    lib = C.CDLL(_lib.LIB_PATH)
-    for f in ("grdma_host_free_size", "grdma_host_writable"):
-        getattr(lib, f).restype = C.c_uint64
-        getattr(lib, f).argtypes = [C.c_uint64] * 3
-    lib.grdma_host_encoded_size.restype = C.c_uint64
-    lib.grdma_host_encoded_size.argtypes = [C.c_uint64]
-    lib.grdma_host_calc_writable.restype = C.c_uint64
-    lib.grdma_host_calc_writable.argtypes = [C.c_uint64]
+    lib = _lib.bind(C.CDLL(_lib.LIB_PATH))
     o = pyorc.lib()
     for v in list(range(0, 100)) + [1000, 4096, (1 << 22) - 3]:
         assert lib.grdma_host_calc_writable(v) == o.orc_calc_writable(v)

@@ -120,7 +120,6 @@ def test_write_queue_limits_are_sixteen_sends_and_a_quarter_of_the_ring(gpu, rin
     p = gpu.Pair(ring_kb * 1024, max_sge, 2)
     lib = gpu.load()
     out = (C.c_uint64 * 2)()
-    lib.grdma_endpoint_write_queue_limits.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     assert lib.grdma_endpoint_write_queue_limits(p.h, out) == 0
     assert (int(out[0]), int(out[1])) == (slices, nbytes)
     p.close()

@@ -337,8 +337,6 @@ def test_express_drain_matches_oracle(gpu, sizes):
     credit and head state -- message after message."""
     g = gpu
     lib = g.load()
-    import ctypes as C
-    lib.grdma_express_drains.restype = C.c_uint64
     before = lib.grdma_express_drains()
     rng = random.Random(77 + len(sizes))
     R = 8192  # small ring: the cap/2 credit rule is crossed many times

@@ -762,7 +762,6 @@ def _verdict_counts(g):
     import ctypes as C
     lib = g.load()
     out = (C.c_uint64 * 2)()
-    lib.grdma_rx_verdict_counts.argtypes = [C.POINTER(C.c_uint64)]
     assert lib.grdma_rx_verdict_counts(out) == 0
     return [int(x) for x in out]
 
@@ -897,7 +896,6 @@ def test_a_promised_credit_wait_that_runs_out_gives_the_promise_up_for_the_whole
             slices.append(wire[off:off + ln])
             off += ln
     lib = g.load()
-    lib.grdma_debug_set_promise_wait.argtypes = [C.c_uint32]
     rng = random.Random(5)
     bufs = [g.DeviceBuffer(data=s, offset=rng.randrange(16)) for s in slices]
     tx, rx = g.Pair(R, max_sge, 0), g.Pair(R, max_sge, 0)

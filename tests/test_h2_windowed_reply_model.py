@@ -20,7 +20,7 @@ BIG = 1 << 40
 def test_the_entry_points_exist(built):
     """(what makes every test of this file fail on a tree without the feature: the model describes calls that are there)"""
     from grpc_rdma_amd import h2dev
-    lib = h2dev._bind()
+    lib = h2dev.load()
     assert all(hasattr(lib, n) for n in ("grdma_h2_reply_attach_windows", "grdma_h2_reply_frame_windowed",
                                          "grdma_h2_reply_frame_windowed_batch", "grdma_h2_reply_pending"))
     assert h2dev.Reply.WINDOWED[12] == "releasable" and len(h2dev.Reply.WINDOWED) == 16

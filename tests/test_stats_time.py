@@ -20,15 +20,6 @@ OPS = ["POLLABLE_EPOLL", "POLLSET_WORK", "TRANSPORT_DO_READ", "TRANSPORT_CONTINU
 def lib(built):
     import grpc_rdma_amd
     L = grpc_rdma_amd.load()
-    L.grdma_stats_time_op_name.restype = C.c_char_p
-    L.grdma_stats_time_op_name.argtypes = [C.c_int]
-    L.grdma_stats_time_add.argtypes = [C.c_int, C.c_int64]
-    L.grdma_stats_time_add_custom.argtypes = [C.c_int, C.c_int64]
-    L.grdma_stats_time_get.restype = C.c_uint64
-    L.grdma_stats_time_get.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double)]
-    L.grdma_stats_time_print.restype = C.c_int64
-    L.grdma_stats_time_print.argtypes = [C.c_char_p, C.c_uint64]
-    L.grdma_stats_time_init.argtypes = [C.c_int]
     L.grdma_stats_time_shutdown()
     yield L
     L.grdma_stats_time_shutdown()

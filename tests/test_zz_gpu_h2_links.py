@@ -188,7 +188,7 @@ def test_refusals(gpu, monkeypatch):
         h2dev.deframe_batch([(p1, buf.ptr, table), (p2, buf.ptr, table), (p1, buf.ptr, table)])   # the same parser twice
     with pytest.raises(GrdmaError):
         h2dev.deframe_batch([(p1, 0, table)])                                                     # no arena
-    lib = h2dev._bind()
+    lib = h2dev.load()
     assert lib.grdma_h2_deframe_batch(None, 1) == -2
     too_many = (h2dev.H2DeframeItem * 257)()
     assert lib.grdma_h2_deframe_batch(too_many, 257) == -2

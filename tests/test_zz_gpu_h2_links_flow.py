@@ -345,7 +345,7 @@ def test_refusals_and_lifetime(gpu, monkeypatch):
     t = g.DeviceBuffer(nbytes=4096)
     data, table = pack_slices([frame(0, 0, 1, b"abc")])
     buf = g.DeviceBuffer(data=data)
-    lib = h2dev._bind()
+    lib = h2dev.load()
 
     # --- the batch call
     def item(fc, k=0):

@@ -219,7 +219,7 @@ def test_refusals(gpu):
             arr, out = (h2dev.H2HpackItem * 1)(), (C.c_uint64 * 8)()
             arr[0].hpack = hs[0].dec.h
             (arr[0].d_blocks, arr[0].blocks_cap, arr[0].d_fields, arr[0].fields_cap, arr[0].d_strings, arr[0].strings_cap) = hs[0].target.args()
-            rc = h2dev._bind().grdma_h2_hpack_decode_batch(*((None, 1, out) if what == "no item array" else (arr, 1, None)))
+            rc = h2dev.load().grdma_h2_hpack_decode_batch(*((None, 1, out) if what == "no item array" else (arr, 1, None)))
             same(rc, INVALID, what)
         else:
             with pytest.raises(gpu.GrdmaError, match=why):

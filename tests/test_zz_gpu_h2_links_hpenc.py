@@ -276,7 +276,7 @@ def test_refusals(gpu):
             arr, out = (h2dev.H2HpencItem * 1)(), (C.c_uint64 * 8)()
             (arr[0].enc, arr[0].d_blocks, arr[0].nblocks, arr[0].d_fields, arr[0].nfields, arr[0].d_strings, arr[0].strings_bytes, arr[0].d_wire,
              arr[0].wire_cap, arr[0].d_block_wire, arr[0].block_wire_cap) = (hs[0].enc.h,) + item(0)[1:]
-            rc = h2dev._bind().grdma_h2_hpenc_encode_batch(*((None, 1, out) if what == "no item array" else (arr, 1, None)))
+            rc = h2dev.load().grdma_h2_hpenc_encode_batch(*((None, 1, out) if what == "no item array" else (arr, 1, None)))
             same(rc, INVALID, what)
         else:
             with pytest.raises(gpu.GrdmaError, match=ERR2) as e:

@@ -252,7 +252,7 @@ def test_refusals(gpu, monkeypatch):
     from grpc_rdma_amd._lib import GrdmaError
     monkeypatch.delenv("GRDMA_H2_PIPE_FUSED", raising=False)
     g = gpu
-    lib = h2dev._bind()
+    lib = h2dev.load()
     wire = frame(0, 0, 1, grpc_msg(b"abc"))
     buf = g.DeviceBuffer(data=wire + bytes(64))
     table = [(0, len(wire))]

@@ -198,7 +198,7 @@ def test_refusals_and_lifetime(gpu, monkeypatch):
     from grpc_rdma_amd._lib import GrdmaError
     monkeypatch.delenv("GRDMA_H2_PIPE_FUSED", raising=False)
     g = gpu
-    lib = h2dev._bind()
+    lib = h2dev.load()
     # --- the batch: nothing runs
     hs = [RHarness(g, 1 << 16, streams=[1]) for _ in range(2)]
     _assemble(hs, [[frame(0, 0, 1, grpc_msg(b"abc"))], [frame(0, 0, 1, grpc_msg(b"defg"))]])

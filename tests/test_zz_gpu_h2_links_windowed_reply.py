@@ -114,7 +114,7 @@ def test_256_links(gpu):
 def test_refusals(gpu):
     g = gpu
     from grpc_rdma_amd import h2dev
-    lib = h2dev._bind()
+    lib = h2dev.load()
     assert lib.grdma_h2_reply_frame_windowed_batch(None, 1) == -2
     assert lib.grdma_h2_reply_frame_windowed_batch((h2dev.H2WrItem * 257)(), 257) == -2
     a, b = WH(g), WH(g)

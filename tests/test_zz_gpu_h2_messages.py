@@ -255,7 +255,7 @@ def test_torch_tensor_arena(gpu):
 def test_bad_arguments(gpu):
     from grpc_rdma_amd import h2dev, _lib
     lib = _lib.load()
-    h2dev._bind()
+    h2dev.load()
     p = h2dev.Parser(False)
     other = h2dev.Parser(False)
     buf = gpu.DeviceBuffer(nbytes=4096)

@@ -79,7 +79,7 @@ def test_routes(gpu):
 def test_route_table_errors(gpu):
     from grpc_rdma_amd import h2dev, _lib
     lib = _lib.load()
-    h2dev._bind()
+    h2dev.load()
     h = RHarness(gpu, 1 << 16, streams=[1])
     for bad in ([(1, 3), (5, 7), (1, 9)], [(0, 3)], [(1, 0)], [(2 * i + 1, 1) for i in range(4097)]):
         with pytest.raises(Exception):
@@ -119,7 +119,7 @@ def test_cut_calls(gpu):
 def test_caps_and_arguments(gpu):
     from grpc_rdma_amd import h2dev, _lib
     lib = _lib.load()
-    h2dev._bind()
+    h2dev.load()
     lens = [100, 0, 70000, 50]  # (no payload piece as short as an inlined slice: those are the slices of <= 23 bytes)
     bodies, wire, slices = _batch(lens, 16384, 3)
     h = RHarness(gpu, 1 << 20, streams=[1])

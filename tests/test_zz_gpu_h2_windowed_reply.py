@@ -330,13 +330,13 @@ def test_refusals_and_lifetime(gpu):
     h.receive(data(1, body(10, 1)))
     with pytest.raises(g.GrdmaError):  # (one message could go out twice)
         h.reply.frame(*ok)
-    assert b"frames under send windows" in h2dev._bind().grdma_last_error()
+    assert b"frames under send windows" in h2dev.load().grdma_last_error()
     for args, why in (((t.ptr + 8, 8, t.ptr + 4096, 128), "misaligned"), ((t.ptr, 0, t.ptr + 4096, 128), "misaligned"),
                       ((t.ptr, 8, 0, 128), "misaligned"), ((t.ptr, 8, t.ptr + 4100, 128), "misaligned")):
         with pytest.raises(g.GrdmaError, match=why):
             h.reply.frame_windowed(*args)
     out = (h2dev.u64 * 16)()
-    assert h2dev._bind().grdma_h2_reply_frame_windowed(h.reply.h, 2, t.ptr, 8, t.ptr + 4096, 128, out) == -2
+    assert h2dev.load().grdma_h2_reply_frame_windowed(h.reply.h, 2, t.ptr, 8, t.ptr + 4096, 128, out) == -2
     sl, st = h.reply.frame_windowed(*ok)  # (the refusals left it working)
     assert st["finished"] == 1 and st["releasable"] == 1 and len(sl) == 2
     # the send windows destroyed first: the reply refuses every call and can still be closed

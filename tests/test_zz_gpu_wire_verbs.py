@@ -47,7 +47,6 @@ VARIANT = os.path.join(ROOT, "oracle", "_build", "libgrdma_amd_fakeverbs.so")
 def wire_here_or_in_the_variant(lib, request):
     """True: this process's library has the NIC wire, go on.  False: the test has just passed in a child pytest that
     loaded the gfx950 build with the wire over the HIP fabric.  Skips only where neither exists."""
-    lib.grdma_verbs_supported.restype = C.c_int
     if lib.grdma_verbs_supported():
         return True
     if os.environ.get("GRDMA_LIB_PATH") or not os.path.exists(VARIANT):
@@ -69,10 +68,6 @@ def pattern(seed, i, n):
 
 def verbs_link(g, lib, R, sge):
     a, b = g.Pair(R, sge, 8), g.Pair(R, sge, 8)          # GRDMA_WIRE_ORDERED: a NIC writes these rings
-    lib.grdma_pair_verbs_open.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int]
-    lib.grdma_pair_verbs_address.argtypes = [C.c_void_p, C.POINTER(VerbsAddress)]
-    lib.grdma_pair_verbs_connect.argtypes = [C.c_void_p, C.POINTER(VerbsAddress)]
-    lib.grdma_pair_verbs_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     for p in (a, b):
         g._lib.check(lib.grdma_pair_verbs_open(p.h, None, 1, 0))
     aa, ab = VerbsAddress(), VerbsAddress()
@@ -148,7 +143,6 @@ def test_verbs_wire_checks(gpu, request):
     lib = g.load()
     if not wire_here_or_in_the_variant(lib, request):
         return
-    lib.grdma_pair_verbs_open.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int]
     plain = g.Pair(1 << 16, 30, 0)
     assert lib.grdma_pair_verbs_open(plain.h, None, 1, 0) < 0 and b"GRDMA_WIRE_ORDERED" in lib.grdma_last_error()
     plain.close()
@@ -165,9 +159,6 @@ def test_verbs_wire_checks(gpu, request):
     assert b"".join(got) == b"".join(msg)
     # what has no way to reach the queue pair is refused, not silently accounted (the engine's commands, asynchronous
     # launch chains and device-resident jobs write through a peer-ring pointer this wire does not have)
-    lib.grdma_pair_set_latency_mode.argtypes = [C.c_void_p, C.c_int]
-    lib.grdma_endpoint_set_async.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
-    lib.grdma_pair_arm_read.argtypes = [C.c_void_p, C.c_uint64]
     assert lib.grdma_pair_set_latency_mode(a.h, 1) < 0 and b"NIC wire" in lib.grdma_last_error()
     assert lib.grdma_endpoint_set_async(a.h, 0, 0) < 0 and b"NIC wire" in lib.grdma_last_error()
     assert lib.grdma_pair_arm_read(b.h, 4) < 0 and b"NIC wire" in lib.grdma_last_error()

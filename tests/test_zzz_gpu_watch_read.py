@@ -110,7 +110,6 @@ def test_watched_reads_on_a_random_sequence(gpu, flags, ring, fast, monkeypatch)
     # (the watcher's own single-wave drain of unary-sized messages, rxw_fast, or every drain through the plan body:
     #  both against the oracle -- read when the engine is launched)
     monkeypatch.setenv("GRDMA_WATCH_FAST", fast)
-    lib.grdma_watch_fast_drains.restype = C.c_uint64
     fd0 = int(lib.grdma_watch_fast_drains())
     rng = random.Random(20260923 + flags + ring)
     big = [1, 5, 9, 14, 66, 100, 200, 256, 257, 600, 1500, 5000]
@@ -139,7 +138,6 @@ def test_watched_reads_on_a_random_sequence(gpu, flags, ring, fast, monkeypatch)
     for p in (a, b):
         h = (C.c_uint32 * 4096)()
         cnt, per = C.c_uint64(), C.c_uint32()
-        lib.grdma_pair_debug_hist.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
         assert lib.grdma_pair_debug_hist(p.h, h, C.byref(cnt), C.byref(per)) == 0
         hist.append(int(cnt.value))
     o = pyorc.OracleLink(ring, 30)

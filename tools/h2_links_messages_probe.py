@@ -18,7 +18,6 @@ per link and step, 16 KiB frames, 4 MiB rings, paired schedule, two rounds of sl
 Run every GPU step under a time limit of its own (timeout -k 10 <s> ...) and chain the steps with &&."""
 import argparse
 import csv
-import ctypes as C
 import json
 import os
 import re
@@ -85,7 +84,6 @@ def main():
     from grpc_rdma_amd import h2dev, stream as gs
     g.init(0)
     lib = g.load()
-    lib.grdma_h2_last_kernel_us.restype = C.c_double
     L, ring = args.links, args.ring_kb * 1024
     assert L % 2 == 0
     wls = [bench.Workload(g, args.msgs, args.payload, stream_id=1) for _ in range(L)]

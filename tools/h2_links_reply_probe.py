@@ -22,7 +22,6 @@ time limit of its own (timeout -k 10 <s> ...), and the driver stops at the first
   python tools/h2_links_reply_probe.py --merge-stats DIR/..._kernel_stats.csv --out profiles/h2_links_reply_probe.json"""
 import argparse
 import csv
-import ctypes as C
 import glob
 import json
 import os
@@ -114,7 +113,6 @@ def main():
     from grpc_rdma_amd import h2dev, stream as gs
     g.init(0)
     lib = g.load()
-    lib.grdma_h2_last_kernel_us.restype = C.c_double
     L, ring = args.links, args.ring_kb * 1024
     assert L % 2 == 0
     wls = [bench.Workload(g, args.msgs, args.payload, stream_id=1) for _ in range(L)]

@@ -114,7 +114,6 @@ def main():
         reply_s = h2dev.Reply(asm_s, None, 16384, 4096)
         cap = len(w.lens) + 64
         sl_buf, hdr_buf = g.DeviceBuffer(nbytes=16 * cap), g.DeviceBuffer(nbytes=32 * cap)
-        lib.grdma_h2_last_kernel_us.restype = __import__("ctypes").c_double
         t_host, t_reply = [], []
         for _ in range(args.frames):
             n, wire = h2dev.frame_messages(msgs, 16384, sl_buf.ptr, cap, hdr_buf.ptr, 32 * cap)

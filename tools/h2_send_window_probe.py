@@ -54,7 +54,6 @@ def main():
     from grpc_rdma_amd import h2dev, stream as gs
     g.init(0)
     lib = g.load()
-    lib.grdma_h2_last_kernel_us.restype = __import__("ctypes").c_double
     w = bench.Workload(g, args.msgs)
     ring = args.ring_kb * 1024
     tx, rx = g.Pair(ring, 4095, 0), g.Pair(ring, 4095, 0)

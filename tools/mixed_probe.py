@@ -28,10 +28,8 @@ def main():
 
     def counts():
         out = (C.c_uint64 * 6)()
-        lib.grdma_rx_fast_drains.argtypes = [C.POINTER(C.c_uint64)]
         lib.grdma_rx_fast_drains(out)
         t = (C.c_uint64 * 2)()
-        lib.grdma_tx_fast_sends.argtypes = [C.POINTER(C.c_uint64)]
         lib.grdma_tx_fast_sends(t)
         return [int(x) for x in out] + [int(x) for x in t]
 

@@ -44,7 +44,6 @@ def main():
     names = gs.CLASS_NAMES
     print("us per launch:", {names[i]: round(1e3 * inst.ms_class[i] / max(1, int(inst.launches_class[i])), 1) for i in range(len(names))})
     lib = g.load()
-    lib.grdma_stream_job_debug.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     for odd in (0, 1):
         if odd:
             os.environ["GRDMA_DBG_ODD"] = "1"

@@ -33,7 +33,6 @@ def main():
         inst = job.run(gs.RUN_INSTRUMENTED)
     lib = g.load()
     td, rd = (C.c_uint64 * 16)(), (C.c_uint64 * 16)()
-    lib.grdma_stream_job_debug.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.grdma_stream_job_debug(job.h, td, rd)
     names = gs.CLASS_NAMES
     us = {names[i]: 1e3 * inst.ms_class[i] / max(1, int(inst.launches_class[i])) for i in range(len(names))}

@@ -31,7 +31,6 @@ def main():
     b.set_latency_mode(True)
     g._lib.check(lib.grdma_engine_start())
     if armed:
-        lib.grdma_pair_arm_read.argtypes = [C.c_void_p, C.c_uint64]
         lib.grdma_pair_arm_read(a.h, 64)
         lib.grdma_pair_arm_read(b.h, 64)
     g.pingpong(a, b, slices, slices, iters=2000, warmup=200)

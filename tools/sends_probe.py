@@ -13,10 +13,8 @@ import bench  # noqa: E402
 def counts(g):
     lib = g.load()
     out = (C.c_uint64 * 6)()
-    lib.grdma_rx_fast_drains.argtypes = [C.POINTER(C.c_uint64)]
     lib.grdma_rx_fast_drains(out)
     tx = (C.c_uint64 * 2)()
-    lib.grdma_tx_fast_sends.argtypes = [C.POINTER(C.c_uint64)]
     lib.grdma_tx_fast_sends(tx)
     return [int(x) for x in out], [int(x) for x in tx]
 
