@@ -326,6 +326,11 @@ SIGNATURES = {
     "grdma_h2_hpenc_stats": (i32, [vp, P(u64)]),
     "grdma_h2_hpenc_last_stages": (i32, [vp, P(u64)]),
     "grdma_h2_hpenc_encode_batch": (i32, [P(H2HpencItem), u32, P(u64)]),
+    "grdma_h2_meta_create": (vp, [vp, u64, u32, u32]),
+    "grdma_h2_meta_destroy": (None, [vp]),
+    "grdma_h2_meta_read": (i64, [vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, u64, P(u64)]),
+    "grdma_h2_meta_reject_tables": (i32, [vp, P(u64)]),
+    "grdma_h2_meta_stats": (i32, [vp, P(u64)]),
     "grdma_h2_group_pipe_create": (vp, [vp, P(H2LinkSpec), u32, u32]),
     "grdma_h2_group_pipe_enqueue": (i32, [vp]),
     "grdma_h2_group_pipe_sync": (i32, [vp, P(u64), u64]),

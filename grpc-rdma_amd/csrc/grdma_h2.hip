@@ -26,6 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "grdma_h2_kernels.h"
@@ -37,6 +38,7 @@
 #include "grdma_h2_ctl.h"
 #include "grdma_h2_hpack.h"
 #include "grdma_h2_hpenc.h"
+#include "grdma_h2_meta.h"
 #include "grdma_h2_block.h"
 
 // --------------------------------------------------------------------- host API
@@ -341,6 +343,12 @@ static h2_stage h2_stage_hpenc_links(const h2he_link* d_tab, uint32_t n) {
           h2_rec(k_h2_links_hpenc_walk, n, H2HE_THREADS, d_tab, n),
           h2_rec(k_h2_links_hpenc_emit, n * H2HE_LINK_GRID, H2HE_THREADS, d_tab, n),
           h2_rec(k_h2_links_hpenc_commit, n * H2HE_LINK_GRID, H2HE_THREADS, d_tab, n)};
+}
+
+// The metadata reader (csrc/grdma_h2_meta.h): it belongs to no parser.  One section.
+static h2_stage h2_stage_meta(h2m_dev* d) {
+  return {h2_rec(k_h2_meta_fields, H2M_GRID, H2M_THREADS, d), h2_rec(k_h2_meta_blocks, H2M_GRID, H2M_BLK_THREADS, d),
+          h2_rec(k_h2_meta_emit, H2M_GRID, H2M_THREADS, d)};
 }
 
 // st goes behind the parser's last deframing by a pipe (the parser state is handed from one deframing to the next),

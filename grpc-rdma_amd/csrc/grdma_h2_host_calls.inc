@@ -2163,6 +2163,175 @@ int grdma_h2_hpenc_last_stages(grdma_h2_hpenc* w, uint64_t out[4]) {
   return 0;
 }
 
+// ---- call metadata: the metadata reader on the device (csrc/grdma_h2_meta.h) ------------------------------------------------
+// The reader follows no parser: its input is three device tables of the caller.  What it owns in device memory is
+// constant after creation -- the method table, the known keys, the field table and the string arena of the rejection
+// lists -- and a call is one run of the stage.
+struct grdma_h2_meta {
+  h2m_dev* d = nullptr;
+  h2m_slot* d_slots = nullptr;
+  uint8_t* d_paths = nullptr;
+  grdma_h2_header_field* d_rej_fields = nullptr;
+  uint8_t* d_rej_strings = nullptr;
+  uint64_t rej_nfields = 0, rej_bytes = 0;
+  h2m_rec* d_recs = nullptr;
+  uint64_t recs_cap = 0;
+  h2m_meta_out* d_mrecs = nullptr;
+  uint64_t mrecs_cap = 0;
+  float ms = 0;  // of the last call
+};
+static_assert(sizeof(h2m_meta_out) == sizeof(grdma_h2_call_meta) && sizeof(grdma_h2_call_meta) == 48 && offsetof(h2m_dev, c) == 0 &&
+              H2M_F_BAD_INPUT == GRDMA_H2_META_BAD_INPUT && H2M_E_STRING == GRDMA_H2_META_ERR_STRING &&
+              H2M_IS_TRAILERS == GRDMA_H2_META_TRAILERS && H2M_BAD_GRPC_STATUS == GRDMA_H2_META_BAD_GRPC_STATUS &&
+              H2M_HAS_MESSAGE == GRDMA_H2_META_HAS_MESSAGE && sizeof(h2m_key_off) <= sizeof(((h2m_dev*)0)->key_off) &&
+              sizeof(h2m_key_bytes) <= sizeof(((h2m_dev*)0)->key_bytes), "layout");
+
+grdma_h2_meta* grdma_h2_meta_create(const void* methods, uint64_t methods_bytes, uint32_t nmethods, uint32_t accept_encodings) {
+  if (grdma_device_count() <= 0) return nullptr;
+  if (nmethods > 4096u) return h2_no("h2 metadata reader: more than 4096 methods");
+  if ((accept_encodings >> 3) || !(accept_encodings & 1u)) return h2_no("h2 metadata reader: accept_encodings has bits above 7 or lacks identity");
+  if (!methods && (nmethods || methods_bytes)) return h2_no("h2 metadata reader: no method list");
+  // the method table: open addressing over a power of two >= 2 n slots, FNV-1a, linear probing
+  uint32_t nslots = 2;
+  while (nslots < 2u * nmethods) nslots *= 2;
+  std::vector<h2m_slot> slots(nslots, h2m_slot{0, 0, 0, 0});
+  std::vector<uint8_t> paths;
+  const uint8_t* p = static_cast<const uint8_t*>(methods);
+  uint64_t pos = 0;
+  for (uint32_t i = 0; i < nmethods; i++) {
+    uint32_t len = 0;
+    if (pos + 4 > methods_bytes) return h2_no("h2 metadata reader: the method list ends inside an entry");
+    memcpy(&len, p + pos, 4);
+    pos += 4;
+    if (len < 1u || len > 1024u) return h2_no("h2 metadata reader: a path outside 1 .. 1024 bytes");
+    if (pos + len > methods_bytes) return h2_no("h2 metadata reader: the method list ends inside an entry");
+    uint32_t h = 0x811c9dc5u;
+    for (uint32_t k = 0; k < len; k++) h = (h ^ p[pos + k]) * 0x01000193u;
+    uint32_t at = h & (nslots - 1u);
+    for (; slots[at].len; at = (at + 1u) & (nslots - 1u))
+      if (slots[at].hash == h && slots[at].len == len && !memcmp(paths.data() + slots[at].off, p + pos, len))
+        return h2_no("h2 metadata reader: a path twice");
+    slots[at] = h2m_slot{h, (uint32_t)paths.size(), len, i};
+    paths.insert(paths.end(), p + pos, p + pos + len);
+    pos += len;
+  }
+  if (pos != methods_bytes) return h2_no("h2 metadata reader: the method list does not end at methods_bytes");
+  // the rejection lists (rule 8): per verdict :status, content-type, grpc-status, grpc-message, all with hint 1
+  std::vector<grdma_h2_header_field> rf;
+  std::vector<uint8_t> rs;
+  std::vector<uint8_t> mirror(sizeof(h2m_dev), 0);
+  h2m_dev* m = reinterpret_cast<h2m_dev*>(mirror.data());
+  auto put = [&](const char* name, const std::string& value) {
+    const uint32_t nl = (uint32_t)strlen(name), off = (uint32_t)rs.size();
+    rf.push_back(grdma_h2_header_field{off, off + nl, nl | 1u << 24, (uint32_t)value.size()});
+    rs.insert(rs.end(), name, name + nl);
+    rs.insert(rs.end(), value.begin(), value.end());
+  };
+  for (const h2m_rejection& r : h2m_rejections) {
+    m->rej_first[r.verdict] = (uint32_t)rf.size();
+    put(":status", r.status);
+    put("content-type", H2M_CONTENT_TYPE);
+    put("grpc-status", r.grpc_status);
+    put("grpc-message", r.message);
+    if (r.verdict == H2M_BAD_ENCODING) {
+      std::string set;
+      for (uint32_t k = 0; k < 3; k++)
+        if ((accept_encodings >> k) & 1u) set += (set.empty() ? "" : ",") + std::string(h2m_encodings[k]);
+      put("grpc-accept-encoding", set);
+    }
+    m->rej_n[r.verdict] = (uint32_t)rf.size() - m->rej_first[r.verdict];
+  }
+  grdma_h2_meta* w = new grdma_h2_meta();
+  w->rej_nfields = rf.size();
+  w->rej_bytes = rs.size();
+  bool ok = hipMalloc((void**)&w->d, sizeof(h2m_dev)) == hipSuccess && hipMalloc((void**)&w->d_slots, sizeof(h2m_slot) * nslots) == hipSuccess &&
+            hipMalloc((void**)&w->d_paths, paths.size() + 16) == hipSuccess &&
+            hipMalloc((void**)&w->d_rej_fields, sizeof(grdma_h2_header_field) * rf.size()) == hipSuccess &&
+            hipMalloc((void**)&w->d_rej_strings, rs.size() + 16) == hipSuccess;
+  if (ok) {
+    m->slots = w->d_slots;
+    m->paths = w->d_paths;
+    m->slot_mask = nslots - 1u;
+    m->accept = accept_encodings;
+    memcpy(m->key_off, h2m_key_off, sizeof(h2m_key_off));
+    memcpy(m->key_bytes, h2m_key_bytes, sizeof(h2m_key_bytes));
+    for (h2m_wg& g : m->wg) g.bad = ~0ull;
+    ok = hipMemcpy(w->d, m, sizeof(h2m_dev), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(w->d_slots, slots.data(), sizeof(h2m_slot) * nslots, hipMemcpyHostToDevice) == hipSuccess &&
+         (paths.empty() || hipMemcpy(w->d_paths, paths.data(), paths.size(), hipMemcpyHostToDevice) == hipSuccess) &&
+         hipMemcpy(w->d_rej_fields, rf.data(), sizeof(grdma_h2_header_field) * rf.size(), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(w->d_rej_strings, rs.data(), rs.size(), hipMemcpyHostToDevice) == hipSuccess;
+  }
+  if (!ok) {
+    (void)hipGetLastError();
+    grdma_h2_meta_destroy(w);
+    grdma_fail_msg(GRDMA_ERR_HIP, "h2 metadata reader: device allocation failed");
+    return nullptr;
+  }
+  return w;
+}
+
+void grdma_h2_meta_destroy(grdma_h2_meta* w) {
+  if (!w) return;
+  h2_host_ctx* hc = h2_ctx();
+  if (hc) hipStreamSynchronize(hc->stream);  // (standalone calls; an encode of the rejection lists reads the constant tables)
+  hipFree(w->d_mrecs);
+  hipFree(w->d_recs);
+  hipFree(w->d_rej_strings);
+  hipFree(w->d_rej_fields);
+  hipFree(w->d_paths);
+  hipFree(w->d_slots);
+  hipFree(w->d);
+  delete w;
+}
+
+int64_t grdma_h2_meta_read(grdma_h2_meta* w, const grdma_h2_header_block* d_blocks, uint64_t nblocks, const grdma_h2_header_field* d_fields,
+                           uint64_t nfields, const void* d_strings, uint64_t strings_bytes, grdma_h2_call_meta* d_meta, uint64_t meta_cap,
+                           grdma_h2_header_block* d_reject, uint64_t reject_cap, uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  const char* who = "h2 metadata reader";
+  if (!w) return h2_invalid(who, "no reader");
+  if (!out) return h2_invalid(who, "no result array");
+  if (!d_meta || !meta_cap || !d_reject || !reject_cap || ((uintptr_t)d_meta & 15) || ((uintptr_t)d_reject & 15))
+    return h2_invalid(who, "a null, zero or misaligned record table or rejection list");
+  if ((nblocks && !d_blocks) || (nfields && !d_fields) || (strings_bytes && !d_strings) || ((uintptr_t)d_blocks & 15) || ((uintptr_t)d_fields & 15))
+    return h2_invalid(who, "a null or misaligned block table, field table or string arena");
+  if (nblocks >= 0xffffffffull || nfields > 0xffffffffull || strings_bytes > (1ull << 32))
+    return h2_invalid(who, "more than 2^32 - 1 blocks or fields, or a string arena above 2^32 bytes");
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  if (!h2_grow(&w->d_recs, &w->recs_cap, nfields + 1) || !h2_grow(&w->d_mrecs, &w->mrecs_cap, nblocks + 1)) return -GRDMA_ERR_HIP;
+  const h2m_call call = {reinterpret_cast<const h2hp_block_out*>(d_blocks), nblocks, reinterpret_cast<const h2hp_field_out*>(d_fields), nfields,
+                         static_cast<const uint8_t*>(d_strings), strings_bytes, reinterpret_cast<h2m_meta_out*>(d_meta), meta_cap,
+                         reinterpret_cast<h2hp_block_out*>(d_reject), reject_cap, w->d_recs, w->recs_cap, w->d_mrecs, w->mrecs_cap};
+  const h2_stage stage = h2_stage_meta(w->d);
+  h2_call c{"grdma_h2_meta_read: a launch was rejected", {{w->d, &call, sizeof(call)}}, {}, {h2_all(stage)},
+            {h2_result(out, w->d, offsetof(h2m_dev, res))}};
+  if (int rc = h2_call_run(hc, &c)) return rc;
+  w->ms = c.ms[0];
+  if (out[H2M_FLAGS] & H2M_F_BAD_INPUT) return h2_invalid(who, "bad input: a block's fields, a stream id or a string (the result block says which block)");
+  if (out[H2M_OVERFLOW]) return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 metadata reader: more blocks or rejections than the targets hold");
+  return (int64_t)out[H2M_REJECTIONS];
+}
+
+int grdma_h2_meta_reject_tables(grdma_h2_meta* w, uint64_t out[4]) {
+  if (!w || !out) return -GRDMA_ERR_INVALID;
+  out[0] = (uint64_t)(uintptr_t)w->d_rej_fields;
+  out[1] = w->rej_nfields;
+  out[2] = (uint64_t)(uintptr_t)w->d_rej_strings;
+  out[3] = w->rej_bytes;
+  return 0;
+}
+
+int grdma_h2_meta_stats(grdma_h2_meta* w, uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!w || !out) return -GRDMA_ERR_INVALID;
+  // calls, blocks, requests, responses, trailers, rejections, malformed
+  if (!h2_read(out, reinterpret_cast<const uint8_t*>(w->d) + offsetof(h2m_dev, st_calls), 7 * sizeof(uint64_t))) return -GRDMA_ERR_HIP;
+  out[7] = (uint64_t)(w->ms * 1e6f);
+  return 0;
+}
+
 // ---- the message assembler on many links (h2_stage_asm_links, csrc/grdma_h2_asm.h) ---------------------------------
 namespace {
 // the pinned table of grdma_h2_asm_release_batch with the event of its last upload (the table is reused: the next call

@@ -791,6 +791,73 @@ class HeaderEncoder(_Handle):
         return tuple(int(x) / 1e3 for x in out)
 
 
+_CALL_META_FIELDS = ("stream", "word", "method", "http_status", "grpc_status", "timeout_lo", "timeout_hi", "path_field",
+                     "authority_field", "message_field", "ncustom", "bad_field")  # grdma_h2_call_meta: twelve 32-bit words
+
+
+def _call_meta_dtype():
+    import numpy as np  # (only the call records need it)
+    return np.dtype([(name, "<u4") for name in _CALL_META_FIELDS])
+
+
+def __getattr__(name):
+    if name == "CALL_META":  # the numpy structured dtype of grdma_h2_call_meta (48 bytes), made on first use
+        return _call_meta_dtype()
+    raise AttributeError(name)
+
+
+class CallMetadata(_Handle):
+    """gRPC's reading of decoded header blocks on the device (grdma_h2_meta): a block table, a field table and a string
+    arena in device memory -- the layout HeaderDecoder writes -- into one call record per block (CALL_META) and a compact
+    list of rejection blocks over the reader's constant tables, which HeaderEncoder.encode takes as they are.  Stateless
+    between calls apart from its counters; it follows no parser."""
+
+    KIND, WHAT = "meta", "h2 metadata reader"  # grdma_h2_meta_create, grdma_h2_meta_destroy
+    RESULT = ("blocks", "requests", "responses", "trailers", "rejections", "malformed", "flags", "overflow")
+    STATS = ("calls", "blocks", "requests", "responses", "trailers", "rejections", "malformed", "kernel_us")
+    NONE = 0xffffffff
+    REQUEST, RESPONSE, TRAILERS = 1, 2, 3  # kind: word bits 0..7
+    (OK, MALFORMED, BAD_METHOD, BAD_CONTENT_TYPE, BAD_TE, BAD_TIMEOUT, UNIMPLEMENTED, BAD_ENCODING, HTTP_STATUS, NO_STATUS,
+     BAD_GRPC_STATUS) = range(11)  # verdict: word bits 8..15
+    HAS_TIMEOUT, END_STREAM, HAS_GRPC_STATUS, HAS_MESSAGE = 1, 2, 4, 8  # flags: word bits 24..31
+    ENCODINGS = ("identity", "gzip", "deflate")  # bit k of accept_encodings; encoding k in word bits 16..23, 255: another
+    BAD_INPUT = 1
+    ERRORS = (None, "field range", "stream", "string")
+
+    def __init__(self, methods=(), accept=("identity",)):
+        methods = [bytes(m) for m in methods]
+        dump = b"".join(len(m).to_bytes(4, "little") + m for m in methods)
+        bits = 0
+        for name in accept:
+            bits |= 1 << self.ENCODINGS.index(name)
+        self._create(dump, len(dump), len(methods), bits)
+
+    def read(self, blocks_ptr, nblocks, fields_ptr, nfields, strings_ptr, strings_bytes, meta_ptr, meta_cap, reject_ptr, reject_cap):
+        """-> (rejection blocks, result tuple (RESULT)); raises GrdmaError on a refusal, on bad input (flags: BAD_INPUT |
+        error << 8 | block << 32) and on a capacity overflow (overflow word 1: nothing was written, no counter moved, the
+        call may be repeated with larger targets) -- the result of the failed call stays in .last_result"""
+        self.last_result = None
+        n = self._call("read", blocks_ptr, nblocks, fields_ptr, nfields, strings_ptr, strings_bytes, meta_ptr, meta_cap, reject_ptr,
+                       reject_cap)  # grdma_h2_meta_read
+        return n, self.last_result
+
+    def reject_tables(self):
+        """the constant tables the rejection blocks point into -> (fields device ptr, fields, strings device ptr, string
+        bytes): the field table and the string arena of a HeaderEncoder.encode of the rejection list"""
+        out = (u64 * 4)()
+        check(self.lib.grdma_h2_meta_reject_tables(self.h, out))
+        return tuple(int(x) for x in out)
+
+    def stats(self):
+        return self._stats()  # grdma_h2_meta_stats
+
+    @staticmethod
+    def records(raw_bytes):
+        """the bytes of a record table as a numpy array of CALL_META (a view: no copy)"""
+        import numpy as np
+        return np.frombuffer(raw_bytes, dtype=_call_meta_dtype())
+
+
 def decode_batch(items):
     """HeaderDecoder.decode for many transports in six launches (grdma_h2_hpack_decode_batch).  items: [(HeaderDecoder,
     blocks device ptr, blocks cap, fields device ptr, fields cap, strings device ptr, strings cap), ...] with distinct

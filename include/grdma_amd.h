@@ -1218,8 +1218,8 @@ int grdma_h2_ctl_reply_batch(const grdma_h2_ctl_item* items, uint32_t n, uint64_
  * the item, the other items are exact; the return value is the number of items whose overflow word is 0, or a negative
  * error.  An item whose deframing holds more than 2^30 header bytes refuses the whole call (-GRDMA_ERR_INVALID) behind
  * the gather, which commits nothing: nothing is taken.  set_max_table_size stays per decoder.
- * Not here: the decoder inside a pipe, gRPC's metadata validation, SETTINGS_MAX_HEADER_LIST_SIZE, PUSH_PROMISE.  (The
- * HPACK encoder: "Header blocks, sending" below.) */
+ * Not here: the decoder inside a pipe, SETTINGS_MAX_HEADER_LIST_SIZE, PUSH_PROMISE.  (The HPACK encoder: "Header
+ * blocks, sending" below; gRPC's metadata validation: "Call metadata" behind it.) */
 enum grdma_h2_hpack_flag { GRDMA_H2_HPACK_FAILED = 1, GRDMA_H2_HPACK_LOST = 2, GRDMA_H2_HPACK_OPEN = 4 /* a block is cut by the call's end */ };
 enum grdma_h2_hpack_error {
   GRDMA_H2_HPACK_ERR_PADDING = 1, GRDMA_H2_HPACK_ERR_BLOCK_TOO_LARGE = 2, GRDMA_H2_HPACK_ERR_INTEGER = 3, GRDMA_H2_HPACK_ERR_TRUNCATED = 4,
@@ -1362,6 +1362,111 @@ typedef struct grdma_h2_hpenc_item {
   uint64_t block_wire_cap;
 } grdma_h2_hpenc_item;
 int grdma_h2_hpenc_encode_batch(const grdma_h2_hpenc_item* items, uint32_t n_items, uint64_t* out /* 8 words per item */);
+
+/* ---- Call metadata: gRPC's reading of decoded header blocks on the device (csrc/grdma_h2_meta.h) ----
+ * The tables the header decoder writes, read where they lie: one fixed-size CALL RECORD per header block -- its kind, a
+ * verdict, the method id from a path list registered at creation, the timeout, the encoding, the HTTP and the gRPC
+ * status, the field indices of the strings a later stage wants -- and a compact REJECTION LIST, one
+ * grdma_h2_header_block per request the server must refuse, each pointing into a constant field table and string arena
+ * the reader owns in device memory, so that grdma_h2_hpenc_encode turns the list into Trailers-Only responses with no
+ * host step and no per-call string work.  The reader is stateless between calls apart from its counters and belongs to
+ * no parser.  The call is ordered on the stream of the standalone HTTP/2 calls: a grdma_h2_hpack_decode in front of it
+ * and a grdma_h2_hpenc_encode behind it need no host synchronisation (the host knows the three counts from the
+ * decoder's result block).  The sequential reference, which defines the exact output, is tests/h2_meta_model.py.
+ * CREATE.  methods is host memory: nmethods entries back to back, each a 32-bit little-endian length and the path's
+ * bytes (the dump style of grdma_h2_hpack_table); a method's id is its position.  nmethods 0 .. 4096, a path 1 .. 1024
+ * bytes.  accept_encodings: bit 0 identity, bit 1 gzip, bit 2 deflate.  NULL (grdma_last_error says why) for a path
+ * twice, a list that does not end at exactly methods_bytes, accept_encodings with bits above 7 or without bit 0.  On
+ * the device the paths live in an open-addressed table of a power of two >= 2 nmethods slots (FNV-1a, linear probing);
+ * the hash finds candidates and bytes decide.
+ * 1. INPUT, all in device memory, by the encoder's input rules: blocks may share fields; of a block only stream,
+ *    first_field, nfields and flags bit 0 (END_STREAM) are read; bits 24..31 of name_len are ignored.  BAD INPUT is
+ *    found on the device: a block whose field range leaves the field table (ERR_FIELD_RANGE), a stream id of 0 or above
+ *    2^31 - 1 (ERR_STREAM), a string that leaves the arena (ERR_STRING) -- the first block with a fault; in it the
+ *    range, then the stream, then the strings.  Result word 6 is BAD_INPUT | code << 8 | block << 32, the other words
+ *    are 0, nothing is written, no counter moves, the call returns -GRDMA_ERR_INVALID.  Not sticky.
+ * 2. FIELDS.  Known keys: :method :scheme :path :authority :status, content-type te grpc-timeout grpc-encoding
+ *    grpc-accept-encoding grpc-status grpc-message, and the connection-specific names connection keep-alive
+ *    proxy-connection transfer-encoding upgrade.  A field is BAD when its name is empty; when its name has a byte
+ *    outside a-z 0-9 - _ . (upper case included; a ':' at position 0 is allowed); when it starts with ':' and is none
+ *    of the five pseudo-headers; when its name does not end in -bin and its value has a byte outside 0x20 .. 0x7e; when
+ *    its name is connection-specific; when it is te with a value other than trailers.
+ * 3. KIND, from content alone (no per-stream state): a block with any of the four request pseudo-headers is a REQUEST;
+ *    else a block with :status is a RESPONSE; else it is TRAILERS (the empty block too).
+ * 4. A block is MALFORMED (the stream error PROTOCOL_ERROR of RFC 7540 8.1.2.6) when it holds a bad field; has a
+ *    pseudo-header (a name that starts with ':') behind a regular field; has a pseudo-header twice; has :status
+ *    together with a request pseudo-header; is a REQUEST without :method, :scheme or :path, with a :scheme other than
+ *    http or https or with an empty :path; is a RESPONSE whose first :status is not exactly three digits.  bad_field
+ *    names the first offending field in block order: the bad field, the pseudo-header that came late, the second
+ *    occurrence, the later of :status and the request pseudo-header beside it, the :scheme or the empty :path, the
+ *    :status; a missing pseudo-header offends nowhere (none).
+ * 5. Known keys: the FIRST occurrence wins (a bad field's too); later ones count in nothing.
+ * 6. VALUES.  grpc-timeout: 1 to 8 digits and one of H M S m u n, in nanoseconds, saturated at 2^63 - 1 (2562047H is
+ *    exact, 2562048H saturates; compared before it is multiplied); anything else is BAD_TIMEOUT.  content-type is good
+ *    when it is application/grpc, alone or followed by '+' or ';' and anything.  grpc-encoding: identity 0, gzip 1,
+ *    deflate 2, any other value 255; 0 without the key.  grpc-status: 1 to 3 digits.  :method is good when it is POST.
+ *    The method id is the lookup of :path.  path_field, authority_field and message_field name the first occurrence,
+ *    as an index into the FIELD TABLE.  http_status is the number of a three-digit :status, grpc_status that of a
+ *    good grpc-status, else none.  ncustom counts the fields whose name is none of the known keys.
+ * 7. VERDICT, the first that applies: MALFORMED (rule 4); BAD_METHOD (REQUEST, :method not POST); BAD_CONTENT_TYPE
+ *    (REQUEST or RESPONSE; missing counts as bad); BAD_TE (REQUEST without te: trailers); BAD_TIMEOUT (rule 6);
+ *    UNIMPLEMENTED (REQUEST, path not registered); BAD_ENCODING (REQUEST, encoding 255 or not in accept_encodings);
+ *    HTTP_STATUS (RESPONSE, :status other than 200); NO_STATUS (a RESPONSE or TRAILERS with END_STREAM and without
+ *    grpc-status); BAD_GRPC_STATUS (grpc-status present and not 1 to 3 digits); else OK.  Flags: HAS_TIMEOUT (a good
+ *    one), END_STREAM, HAS_GRPC_STATUS and HAS_MESSAGE (the key is present).
+ * 8. REJECTIONS.  Every REQUEST whose verdict is neither OK nor MALFORMED gets one block in d_reject, in input order,
+ *    compacted: {the request's stream, first_field / nfields into the reader's constant tables
+ *    (grdma_h2_meta_reject_tables), flags 1}.  The constant lists, every field with hint 1, are a FIXED POLICY, as flow
+ *    control is -- :status / grpc-status: BAD_METHOD 405 / 13, BAD_CONTENT_TYPE 415 / 13, BAD_TE 400 / 13, BAD_TIMEOUT
+ *    400 / 13, UNIMPLEMENTED 200 / 12, BAD_ENCODING 200 / 12 -- with content-type: application/grpc between the two and
+ *    a fixed grpc-message behind them (csrc/grdma_h2_meta_tables.h spells it); BAD_ENCODING adds grpc-accept-encoding
+ *    with the create-time set.  A MALFORMED request gets no block: its RST_STREAM is the control-reply writer's side
+ *    and is not here.
+ * 9. RESULT BLOCK: {blocks, requests, responses, trailers, rejections, malformed, flags (grdma_h2_meta_flag) | error <<
+ *    8 | offending block << 32, overflow}.
+ * 10. CAPS.  meta_cap < nblocks or reject_cap < rejections: overflow word 1, -GRDMA_ERR_CAPACITY, the result block
+ *    holds the totals, NOTHING is written to either target and no counter moves; the same call with larger targets
+ *    gives what a never-refused call gives.  Nothing is written behind the totals in any case.
+ * 11. -GRDMA_ERR_INVALID (grdma_last_error says why; nothing runs, nothing changes): null, zero-cap or misaligned (16
+ *    bytes) targets, a null input table with a count above 0, a misaligned block or field table, 2^32 - 1 blocks or
+ *    more, no reader, no result array.
+ * Not here: the reader over a table of links, the reader inside a pipe, percent-decoding of grpc-message (the record
+ * names the field), base64 of -bin values, SETTINGS_MAX_HEADER_LIST_SIZE, RST_STREAM for malformed blocks. */
+enum grdma_h2_meta_flag { GRDMA_H2_META_BAD_INPUT = 1 };
+enum grdma_h2_meta_error { GRDMA_H2_META_ERR_FIELD_RANGE = 1, GRDMA_H2_META_ERR_STREAM = 2, GRDMA_H2_META_ERR_STRING = 3 };
+enum grdma_h2_meta_kind { GRDMA_H2_META_REQUEST = 1, GRDMA_H2_META_RESPONSE = 2, GRDMA_H2_META_TRAILERS = 3 };
+enum grdma_h2_meta_verdict {
+  GRDMA_H2_META_OK = 0, GRDMA_H2_META_MALFORMED = 1, GRDMA_H2_META_BAD_METHOD = 2, GRDMA_H2_META_BAD_CONTENT_TYPE = 3, GRDMA_H2_META_BAD_TE = 4,
+  GRDMA_H2_META_BAD_TIMEOUT = 5, GRDMA_H2_META_UNIMPLEMENTED = 6, GRDMA_H2_META_BAD_ENCODING = 7, GRDMA_H2_META_HTTP_STATUS = 8,
+  GRDMA_H2_META_NO_STATUS = 9, GRDMA_H2_META_BAD_GRPC_STATUS = 10
+};
+enum grdma_h2_meta_call_flag {
+  GRDMA_H2_META_HAS_TIMEOUT = 1, GRDMA_H2_META_END_STREAM = 2, GRDMA_H2_META_HAS_GRPC_STATUS = 4, GRDMA_H2_META_HAS_MESSAGE = 8
+};
+typedef struct grdma_h2_call_meta {   /* 48 bytes, one per input block, in block order */
+  uint32_t stream;
+  uint32_t word;          /* kind (bits 0..7) | verdict << 8 | encoding << 16 | flags << 24 */
+  uint32_t method;        /* index into the create-time path list, 0xffffffff: none */
+  uint32_t http_status;   /* :status as a number, 0xffffffff: none */
+  uint32_t grpc_status;   /* grpc-status as a number, 0xffffffff: none */
+  uint32_t timeout_lo, timeout_hi;   /* nanoseconds, saturated at 2^63 - 1; 0 without HAS_TIMEOUT */
+  uint32_t path_field, authority_field, message_field;  /* index into the FIELD TABLE, 0xffffffff: none */
+  uint32_t ncustom;       /* fields whose name is none of the known keys */
+  uint32_t bad_field;     /* index into the field table of the first field (block order) that made the block MALFORMED, else none */
+} grdma_h2_call_meta;
+typedef struct grdma_h2_meta grdma_h2_meta;
+grdma_h2_meta* grdma_h2_meta_create(const void* methods, uint64_t methods_bytes, uint32_t nmethods, uint32_t accept_encodings);
+void grdma_h2_meta_destroy(grdma_h2_meta* meta);
+int64_t grdma_h2_meta_read(grdma_h2_meta* meta, const grdma_h2_header_block* d_blocks, uint64_t nblocks,
+                           const grdma_h2_header_field* d_fields, uint64_t nfields, const void* d_strings, uint64_t strings_bytes,
+                           grdma_h2_call_meta* d_meta, uint64_t meta_cap, grdma_h2_header_block* d_reject, uint64_t reject_cap,
+                           uint64_t out[8]);  /* returns the number of rejection blocks */
+/* {device address of the constant field table, its fields, device address of its string arena, its bytes}: valid until
+ * the reader is destroyed */
+int grdma_h2_meta_reject_tables(grdma_h2_meta* meta, uint64_t out[4]);
+/* {calls, blocks, requests, responses, trailers, rejections, malformed, kernel time of the last call in NANOseconds (HIP
+ * events)} */
+int grdma_h2_meta_stats(grdma_h2_meta* meta, uint64_t out[8]);
 
 /* ---- HTTP/2 on several links of ONE job (the group pipe) ----
  * grdma_h2_pipe serves one link, and a job carries one set of kernels in front of and behind its rounds: a second
