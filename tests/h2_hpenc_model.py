@@ -6,6 +6,7 @@ against the decoder's model (tests/h2_hpack_model.py) and against nghttp2 before
 import copy
 
 from tests.h2_hpack_data import HUFFMAN, STATIC
+from tests.h2_hpack_model import RingLayout
 
 BAD_INPUT = 1                                                      # GRDMA_H2_HPENC_BAD_INPUT
 ERR_FIELD_RANGE, ERR_STREAM, ERR_LENGTH, ERR_STRING, ERR_BLOCK_TOO_LARGE = range(1, 6)  # GRDMA_H2_HPENC_ERR_*
@@ -86,10 +87,10 @@ class EncTable:
         i = _STATIC_FULL.get((name, value))
         if i:
             return i
-        for k, e in enumerate(self.entries):
-            if e == (name, value):
-                return 62 + k
-        return 0
+        try:
+            return 62 + self.entries.index((name, value))  # (the newest)
+        except ValueError:
+            return 0
 
     def name(self, name):
         i = _STATIC_NAME.get(name)
@@ -209,6 +210,69 @@ class HpencModel:
         st["inserted"] += res[3]
         st["evicted"] += res[4]
         return bytes(wire), bw, res + (0,), None
+
+
+# ---- what the encoder's stages see of a call, from the model alone (the witnesses of tests/h2_hpenc_sweep_lib.py) ------
+# Nothing here decides a byte: the facts are read off the model's own sequential run (EncTable.field, one occurrence
+# after the other) and off the bytes it gave.
+def first_int(data, nbits):
+    """the prefix integer a field's bytes begin with"""
+    limit = (1 << nbits) - 1
+    v = data[0] & limit
+    if v < limit:
+        return v
+    k = 1
+    while True:
+        v += (data[k] & 0x7f) << (7 * (k - 1))
+        if not data[k] & 0x80:
+            return v
+        k += 1
+
+
+def occurrences(blocks):
+    """a good call's occurrences in wire order -> [(block, field index)]"""
+    return [(k, first + j) for k, (_, first, n, _) in enumerate(blocks) for j in range(n)]
+
+
+def trace(model, blocks, fields, arena):
+    """a call the model takes (no bad input), replayed on a copy of its table -> dict(occ: per occurrence (its step of
+    the walk, its representation, the index its bytes begin with, whether it is taken by the one inserting thread --
+    an entry larger than the table is, and inserts nothing --, the entries it evicted, whether it inserted), steps: per
+    step the inserting occurrences in order [(occurrence, evicted, inserted)], updates: the size updates in front)"""
+    t, occ, steps = copy.deepcopy(model.table), [], {}
+    ups = model.updates() if blocks else []
+    for u in ups:
+        t.resize(u)
+    for i, (_, fi) in enumerate(occurrences(blocks)):
+        no, vo, nl, vl = fields[fi]
+        ins0, ev0 = t.inserted, t.evicted
+        b, rep = t.field(bytes(arena[no:no + (nl & 0xffffff)]), bytes(arena[vo:vo + vl]), nl >> 24)
+        o = (i // CHUNK, rep, first_int(b, (7, 6, 4, 4)[rep]), rep == 1, t.evicted - ev0, t.inserted > ins0)
+        occ.append(o)
+        if o[3]:
+            steps.setdefault(o[0], []).append((i, o[4], o[5]))
+    return dict(occ=occ, steps=steps, updates=ups)
+
+
+def live(table):
+    """-> every live entry's (insertion number since creation, ring slot), newest first"""
+    return [(table.inserted - 1 - k, (table.inserted - 1 - k) % RING) for k in range(len(table.entries))]
+
+
+class ByteRing(RingLayout):
+    """the decoder's RingLayout over an EncTable (the head advances by the string bytes of the entries a call inserted
+    and that survive it, in insertion order, modulo BYTES; straddles(): which live strings lie across BYTES, and in
+    which part), and the bytes the ring then holds"""
+
+    def __init__(self):
+        RingLayout.__init__(self)
+        self.bytes = bytearray(BYTES)
+
+    def commit(self, table, inserted):
+        RingLayout.commit(self, table, inserted)
+        for (off, nl, vl), (name, value) in list(zip(self.where, table.entries))[:min(inserted, len(table.entries))]:
+            for k, b in enumerate(name + value):
+                self.bytes[(off + k) % BYTES] = b
 
 
 def pack(lists, hints=None):

@@ -189,3 +189,68 @@ def test_bad_input_and_caps_commit_nothing():
 def copy_of(m):
     import copy
     return copy.deepcopy(m)
+
+
+# ---- the sweep of tests/test_zz_gpu_h2_hpenc_sweep.py: its witnesses, and its committed calls through both decoders ----------
+PER_FAMILY = {"01": 28, "02": 20, "03": 40, "04": 15, "05": 12, "06": 10, "07": 87, "08": 43, "09": 11, "10": 44, "11": 14}
+
+
+def test_every_case_of_the_hpenc_sweep_shows_its_witness():
+    import collections
+    from tests import h2_hpenc_sweep_lib as S
+    cs = S.check_cases()
+    assert collections.Counter(c["fam"] for c in cs) == PER_FAMILY and len(cs) == sum(PER_FAMILY.values()) == 324
+    assert set(PER_FAMILY) == set(S.FAMILIES) and all(c["edge"] and c["key"] for c in cs)
+    subset = S.emu_subset()
+    assert {S.by_id(cid)["fam"] for cid in subset} == set(S.FAMILIES) and all(cid in subset for cid in S.CAUGHT_ALONE)
+    assert all(S.links_cases(fam) for fam in S.FAMILIES)
+    # the grid stride: calls of more occurrences than the stages have lanes, compared whole as every call is
+    assert max(s["nocc"] for c in S.CASES if c["key"] == "grid" for s in S.simulate(c)) == 32769 > 2 * S.GRID
+    assert max(s["nocc"] for c in S.links_cases("04") for s in S.simulate(c)) == 1025 > S.LINK_GRID
+    # the ring is never full, and the sweep says so
+    assert max(s["entries"] for c in S.CASES for s in S.simulate(c) if "entries" in s) == 1942 < M.RING
+    assert not S.NGHTTP2_DIFFERS
+
+
+def _pin(fam, make, resize, decode, table_of):
+    """every committed call of the family's cases through a decoder that shares no code with the model: the header lists
+    come back, and behind every call the decoder's dynamic table is the model's.  A ("peer", n) step is the decoder's side
+    changing its SETTINGS_HEADER_TABLE_SIZE."""
+    from tests import h2_hpenc_sweep_lib as S
+    calls = 0
+    for c in (c for c in S.CASES if c["fam"] == fam):
+        dec, lead = make(c["table"])
+        for item in S.pin_sequence(c):
+            if item[0] == "peer":
+                resize(dec, item[1])
+                lead = b""
+                continue
+            _, lists, wire, table = item
+            blocks = M.deframe(wire)
+            assert [(s, es) for s, es, _ in blocks] == [(s, es) for s, es, _ in lists], c["id"]
+            for (_, _, hs), (_, _, block) in zip(lists, blocks):
+                got = decode(dec, lead + block)
+                lead = b""
+                assert got is not None, c["id"]
+                assert [(n, v, h == 3) for n, v, h in hs] == [(n, v, r is True or r == 3) for n, v, r in got], c["id"]
+            assert table_of(dec) == table, c["id"]
+            calls += 1
+    assert calls
+
+
+@pytest.mark.parametrize("fam", sorted(PER_FAMILY))
+def test_the_sweeps_calls_through_the_decoders_model(fam):
+    _pin(fam, lambda n: (HpackTable(n), b""), lambda d, n: d.set_setting(n), lambda d, b: d.decode_block(b), lambda d: (d.entries, d.size))
+
+
+@needs_nghttp2
+@pytest.mark.parametrize("fam", sorted(PER_FAMILY))
+def test_the_sweeps_calls_through_nghttp2(fam):
+    """Both sides begin at 4096, or at the peer's table size where that is less, and no size update is sent for that
+    (include/grdma_amd.h, "Header blocks, sending", 4; RFC 7541 Appendix C.6).  nghttp2's inflater can only be made at 4096
+    and wants to be told of a smaller size in the first block it reads: the pin tells it, in front of the encoder's first
+    block, what the encoder was created with.  Nothing else is added or left out; NGHTTP2_DIFFERS stays empty."""
+    def make(n):
+        return (L.Inflater(None if n == 4096 else n), M.enc_int(n, 5, 0x20) if n < 4096 else b"")
+
+    _pin(fam, make, lambda d, n: d.change_table_size(n), lambda d, b: d.inflate(b), lambda d: d.table())

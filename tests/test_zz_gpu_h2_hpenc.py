@@ -13,11 +13,11 @@ import pytest
 from tests.h2_hpenc_lib import ERR2, FULL_COLLISION, HE, NAME_COLLISION, Wire, by_bits, chunk_lists, fill, huffman_bits
 from tests.h2_hpenc_model import (BAD_INPUT, CHUNK, ERR_FIELD_RANGE, ERR_LENGTH, ERR_STREAM, ERR_STRING, HUFFMAN, deframe, enc_int, enc_str,
                                   pack)
+from tests.h2_hpenc_sweep_lib import RAW, sized
 
 pytestmark = pytest.mark.gpu
 
 VECTORS = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "h2_hpenc_vectors.json")))
-RAW = b"\x01"  # a byte whose code has 23 bits: strings of it go raw
 
 
 def block_of(h, fields, stream=1, flags=0):
@@ -268,15 +268,6 @@ def test_a_run_of_empty_blocks_longer_than_a_step(gpu):
 
 
 # ---- frames ---------------------------------------------------------------------------------------------------------------------------
-def sized(target, more=()):
-    """a block whose bytes are `target` long: one raw value, then the fields of `more`"""
-    for n in range(target - 12, target):
-        fs = [(b"x-f", RAW * n, 2)]
-        if len(b"\x00" + enc_str(b"x-f") + enc_str(RAW * n)) == target:
-            return fs + list(more)
-    raise AssertionError(target)
-
-
 @pytest.mark.parametrize("length", [16384, 16385, 2 * 16384 + 1])
 def test_blocks_around_the_max_frame_size(gpu, length):
     h = HE(gpu)
