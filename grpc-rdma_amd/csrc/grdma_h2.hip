@@ -350,6 +350,13 @@ static h2_stage h2_stage_meta(h2m_dev* d) {
   return {h2_rec(k_h2_meta_fields, H2M_GRID, H2M_THREADS, d), h2_rec(k_h2_meta_blocks, H2M_GRID, H2M_BLK_THREADS, d),
           h2_rec(k_h2_meta_emit, H2M_GRID, H2M_THREADS, d)};
 }
+// ... of n links in the same three launches: ONE reader (its constants, its counters), every link a share of the grid
+static_assert(H2M_LINKS_MAX == GRDMA_H2_BATCH_MAX, "the metadata reader's link table is the batch's");
+static h2_stage h2_stage_meta_links(h2m_dev* d, const h2m_link* d_tab, uint32_t n) {
+  return {h2_rec(k_h2_links_meta_fields, n * H2M_LINK_GRID, H2M_THREADS, d, d_tab, n),
+          h2_rec(k_h2_links_meta_blocks, n * H2M_LINK_GRID, H2M_BLK_THREADS, d, d_tab, n),
+          h2_rec(k_h2_links_meta_emit, n * H2M_LINK_GRID, H2M_THREADS, d, d_tab, n)};
+}
 
 // st goes behind the parser's last deframing by a pipe (the parser state is handed from one deframing to the next),
 // unless that one was enqueued on st itself.  (Only pipe steps leave last_deframed, on a job's or a deframe stream: for

@@ -47,6 +47,15 @@ inline h2_hpenc_block h2_hpenc_block_layout(uint64_t link, uint64_t call, uint64
   return {b.add(link * n_items), b.add(call * n_items), b.add(9 * sizeof(uint64_t) * n_items), b.total()};
 }
 
+// grdma_h2_meta_read_batch: [table | one h2m_call per item | link_grid h2m_wg per item, bad = ~0 | eight result words
+// per item]; [0, results) goes up in one copy, the result words -- the emit launch writes all eight of every item --
+// come down in one copy.  (The reader's own device block holds the constants and the counters only.)
+struct h2_meta_block { uint64_t tab, calls, wgs, results, total; };
+inline h2_meta_block h2_meta_block_layout(uint64_t link, uint64_t call, uint64_t wg, uint64_t link_grid, uint64_t n_items) {
+  h2_block b;
+  return {b.add(link * n_items), b.add(call * n_items), b.add(wg * link_grid * n_items), b.add(8 * sizeof(uint64_t) * n_items), b.total()};
+}
+
 // grdma_h2_reply_frame_batch: [table | one h2r_dev per item]; all of it goes up, the h2r_dev blocks come down.
 struct h2_reply_block { uint64_t tab, devs, end, total; };
 inline h2_reply_block h2_reply_block_layout(uint64_t link, uint64_t dev, uint64_t n_items) {

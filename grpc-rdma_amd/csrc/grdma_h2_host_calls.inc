@@ -2285,6 +2285,26 @@ void grdma_h2_meta_destroy(grdma_h2_meta* w) {
   delete w;
 }
 
+// what a call of an item (the single call's arguments are one) is refused for
+static const char* h2_meta_refusal(const grdma_h2_meta_item& it) {
+  if (!it.d_meta || !it.meta_cap || !it.d_reject || !it.reject_cap || ((uintptr_t)it.d_meta & 15) || ((uintptr_t)it.d_reject & 15))
+    return "a null, zero or misaligned record table or rejection list";
+  if ((it.nblocks && !it.d_blocks) || (it.nfields && !it.d_fields) || (it.strings_bytes && !it.d_strings) || ((uintptr_t)it.d_blocks & 15) ||
+      ((uintptr_t)it.d_fields & 15))
+    return "a null or misaligned block table, field table or string arena";
+  if (it.nblocks >= 0xffffffffull || it.nfields > 0xffffffffull || it.strings_bytes > (1ull << 32))
+    return "more than 2^32 - 1 blocks or fields, or a string arena above 2^32 bytes";
+  return nullptr;
+}
+// the call's words of an item over its part of the reader's scratch: a record per field, a call record per block
+static h2m_call h2_meta_call(const grdma_h2_meta_item& it, h2m_rec* recs, uint64_t recs_cap, h2m_meta_out* mrecs, uint64_t mrecs_cap) {
+  return {reinterpret_cast<const h2hp_block_out*>(it.d_blocks), it.nblocks, reinterpret_cast<const h2hp_field_out*>(it.d_fields), it.nfields,
+          static_cast<const uint8_t*>(it.d_strings), it.strings_bytes, reinterpret_cast<h2m_meta_out*>(it.d_meta), it.meta_cap,
+          reinterpret_cast<h2hp_block_out*>(it.d_reject), it.reject_cap, recs, recs_cap, mrecs, mrecs_cap};
+}
+// whether an item's result words say it was read
+static bool h2_meta_was_read(const uint64_t* res) { return !(res[H2M_FLAGS] & H2M_F_BAD_INPUT) && !res[H2M_OVERFLOW]; }
+
 int64_t grdma_h2_meta_read(grdma_h2_meta* w, const grdma_h2_header_block* d_blocks, uint64_t nblocks, const grdma_h2_header_field* d_fields,
                            uint64_t nfields, const void* d_strings, uint64_t strings_bytes, grdma_h2_call_meta* d_meta, uint64_t meta_cap,
                            grdma_h2_header_block* d_reject, uint64_t reject_cap, uint64_t out[8]) {
@@ -2292,18 +2312,12 @@ int64_t grdma_h2_meta_read(grdma_h2_meta* w, const grdma_h2_header_block* d_bloc
   const char* who = "h2 metadata reader";
   if (!w) return h2_invalid(who, "no reader");
   if (!out) return h2_invalid(who, "no result array");
-  if (!d_meta || !meta_cap || !d_reject || !reject_cap || ((uintptr_t)d_meta & 15) || ((uintptr_t)d_reject & 15))
-    return h2_invalid(who, "a null, zero or misaligned record table or rejection list");
-  if ((nblocks && !d_blocks) || (nfields && !d_fields) || (strings_bytes && !d_strings) || ((uintptr_t)d_blocks & 15) || ((uintptr_t)d_fields & 15))
-    return h2_invalid(who, "a null or misaligned block table, field table or string arena");
-  if (nblocks >= 0xffffffffull || nfields > 0xffffffffull || strings_bytes > (1ull << 32))
-    return h2_invalid(who, "more than 2^32 - 1 blocks or fields, or a string arena above 2^32 bytes");
+  const grdma_h2_meta_item it{d_blocks, nblocks, d_fields, nfields, d_strings, strings_bytes, d_meta, meta_cap, d_reject, reject_cap};
+  if (const char* why = h2_meta_refusal(it)) return h2_invalid(who, why);
   h2_host_ctx* hc = h2_ctx();
   if (!hc) return -GRDMA_ERR_HIP;
   if (!h2_grow(&w->d_recs, &w->recs_cap, nfields + 1) || !h2_grow(&w->d_mrecs, &w->mrecs_cap, nblocks + 1)) return -GRDMA_ERR_HIP;
-  const h2m_call call = {reinterpret_cast<const h2hp_block_out*>(d_blocks), nblocks, reinterpret_cast<const h2hp_field_out*>(d_fields), nfields,
-                         static_cast<const uint8_t*>(d_strings), strings_bytes, reinterpret_cast<h2m_meta_out*>(d_meta), meta_cap,
-                         reinterpret_cast<h2hp_block_out*>(d_reject), reject_cap, w->d_recs, w->recs_cap, w->d_mrecs, w->mrecs_cap};
+  const h2m_call call = h2_meta_call(it, w->d_recs, w->recs_cap, w->d_mrecs, w->mrecs_cap);
   const h2_stage stage = h2_stage_meta(w->d);
   h2_call c{"grdma_h2_meta_read: a launch was rejected", {{w->d, &call, sizeof(call)}}, {}, {h2_all(stage)},
             {h2_result(out, w->d, offsetof(h2m_dev, res))}};
@@ -2312,6 +2326,53 @@ int64_t grdma_h2_meta_read(grdma_h2_meta* w, const grdma_h2_header_block* d_bloc
   if (out[H2M_FLAGS] & H2M_F_BAD_INPUT) return h2_invalid(who, "bad input: a block's fields, a stream id or a string (the result block says which block)");
   if (out[H2M_OVERFLOW]) return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 metadata reader: more blocks or rejections than the targets hold");
   return (int64_t)out[H2M_REJECTIONS];
+}
+
+// n items through the ONE reader in the same three launches (h2_stage_meta_links).  The batch block of the process holds
+// [table | one h2m_call per item | the items' workgroup counts | eight result words per item] (csrc/grdma_h2_block.h):
+// the table, the call words and the counts' fill go up in ONE copy, the result words come down in ONE copy, whatever
+// the number of items -- nothing of a call passes through the reader's own device block but the counters, which the
+// emit launch bumps once.  An item's records and call records are its slice of the reader's scratch, grown to the sum
+// over the items and one more each (a slice starts on 16 bytes: both records are multiples of 16 bytes long).  One
+// call at a time, as the other batch calls.
+int grdma_h2_meta_read_batch(grdma_h2_meta* w, const grdma_h2_meta_item* items, uint32_t n_items, uint64_t* out) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  h2_batch b{"h2 metadata reader batch", "item", "grdma_h2_meta_read_batch: a launch was rejected"};
+  if (!w) return h2_invalid(b.who, "no reader");
+  if (!items) return h2_invalid(b.who, "no item array");
+  if (!out) return h2_invalid(b.who, "no result array");
+  if (int rc = b.begin(true, n_items)) return rc;
+  uint64_t nrecs = 0, nmrecs = 0;
+  for (uint32_t i = 0; i < n_items; i++) {
+    if (int rc = b.item(nullptr, h2_meta_refusal(items[i]))) return rc;
+    nrecs += items[i].nfields + 1;
+    nmrecs += items[i].nblocks + 1;
+  }
+  static_assert(sizeof(h2m_rec) % 16 == 0 && sizeof(h2m_meta_out) % 16 == 0, "a slice of the scratch starts on 16 bytes");
+  const h2_meta_block L = h2_meta_block_layout(sizeof(h2m_link), sizeof(h2m_call), sizeof(h2m_wg), H2M_LINK_GRID, n_items);
+  if (int rc = b.reserve(L.results, L.total)) return rc;
+  if (!h2_grow(&w->d_recs, &w->recs_cap, nrecs) || !h2_grow(&w->d_mrecs, &w->mrecs_cap, nmrecs)) return -GRDMA_ERR_HIP;
+  auto* tab = reinterpret_cast<h2m_link*>(b.up.data() + L.tab);
+  auto* calls = reinterpret_cast<h2m_call*>(b.up.data() + L.calls);
+  auto* wgs = reinterpret_cast<h2m_wg*>(b.up.data() + L.wgs);
+  uint64_t rec0 = 0, mrec0 = 0;
+  for (uint32_t i = 0; i < n_items; i++) {
+    calls[i] = h2_meta_call(items[i], w->d_recs + rec0, items[i].nfields + 1, w->d_mrecs + mrec0, items[i].nblocks + 1);
+    rec0 += items[i].nfields + 1;
+    mrec0 += items[i].nblocks + 1;
+    for (uint32_t k = 0; k < H2M_LINK_GRID; k++) wgs[(size_t)i * H2M_LINK_GRID + k].bad = ~0ull;
+    tab[i] = {reinterpret_cast<const h2m_call*>(b.d + L.calls) + i, reinterpret_cast<h2m_wg*>(b.d + L.wgs) + (size_t)i * H2M_LINK_GRID,
+              reinterpret_cast<uint64_t*>(b.d + L.results) + 8 * (size_t)i};
+  }
+  std::vector<uint64_t> down(8 * (size_t)n_items, 0);  // (out is not touched unless the call ran)
+  b.c.down.push_back(h2_result(down.data(), b.d, L.results, down.size()));
+  const h2_stage stage = h2_stage_meta_links(w->d, reinterpret_cast<const h2m_link*>(b.d + L.tab), n_items);
+  if (int rc = b.run({h2_all(stage)})) return rc;
+  w->ms = b.c.ms[0];
+  memcpy(out, down.data(), down.size() * sizeof(uint64_t));
+  int read = 0;
+  for (uint32_t i = 0; i < n_items; i++) read += h2_meta_was_read(out + 8 * (size_t)i);
+  return read;
 }
 
 int grdma_h2_meta_reject_tables(grdma_h2_meta* w, uint64_t out[4]) {

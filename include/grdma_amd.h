@@ -1429,9 +1429,28 @@ int grdma_h2_hpenc_encode_batch(const grdma_h2_hpenc_item* items, uint32_t n_ite
  *    gives what a never-refused call gives.  Nothing is written behind the totals in any case.
  * 11. -GRDMA_ERR_INVALID (grdma_last_error says why; nothing runs, nothing changes): null, zero-cap or misaligned (16
  *    bytes) targets, a null input table with a count above 0, a misaligned block or field table, 2^32 - 1 blocks or
- *    more, no reader, no result array.
- * Not here: the reader over a table of links, the reader inside a pipe, percent-decoding of grpc-message (the record
- * names the field), base64 of -bin values, SETTINGS_MAX_HEADER_LIST_SIZE, RST_STREAM for malformed blocks. */
+ *    more, no reader, no result array; in the batch n outside 1 .. GRDMA_H2_BATCH_MAX, a NULL item array or result
+ *    array, any item the single call's argument checks refuse -- out is not touched.
+ * MANY LINKS.  grdma_h2_meta_read_batch is grdma_h2_meta_read for n items (1 .. GRDMA_H2_BATCH_MAX) in three launches
+ * however many (k_h2_links_meta_*), ordered on the same stream: a grdma_h2_hpack_decode_batch in front of it and a
+ * grdma_h2_hpenc_encode_batch behind it need no host synchronisation.  ONE reader, n items, by design (unlike the
+ * encoder, whose state is per connection): the method table, the accepted encodings and the constant rejection tables
+ * belong to the server and are the same on every link, so an item is one link's decoder output and that link's two
+ * targets.  Every item is read by rules 1 to 10 exactly as the single call reads it: its record table, its rejection
+ * list and its eight result words are byte for byte what grdma_h2_meta_read gives for the same arguments.  Input tables
+ * may be shared between items; overlapping targets are the caller's error and are not checked.  The rejection blocks of
+ * every item point into the reader's one pair of constant tables (grdma_h2_meta_reject_tables): an encode batch passes
+ * that pair as the field table and string arena of every item.  out: 8 result words per item, in item order.  Bad input
+ * (the BAD_INPUT flag, the code and the block in the item's word 6, its other words 0) and a cap overflow (overflow
+ * word 1 and the totals, nothing written to either of its targets; repeated alone or in a later batch it gives what a
+ * never-refused call gives) stay with the item, the other items are exact.  The return value is the number of items
+ * read (overflow word 0 and no BAD_INPUT; an item with 0 blocks counts), or a negative error.  COUNTERS: the call is
+ * ONE call in grdma_h2_meta_stats, which moves by the sums of blocks, requests, responses, trailers, rejections and
+ * malformed over the items that were read and by nothing for the others; a batch in which no item was read moves no
+ * counter, as a refused single call moves none.  Word 7 is the batch's kernel time.  All items' call words go up in
+ * ONE copy and all result words come down in ONE copy, whatever n.
+ * Not here: the reader inside a pipe or a group pipe, a grid per link sized by the link's block count,
+ * percent-decoding of grpc-message (the record names the field), base64 of -bin values, SETTINGS_MAX_HEADER_LIST_SIZE, RST_STREAM for malformed blocks. */
 enum grdma_h2_meta_flag { GRDMA_H2_META_BAD_INPUT = 1 };
 enum grdma_h2_meta_error { GRDMA_H2_META_ERR_FIELD_RANGE = 1, GRDMA_H2_META_ERR_STREAM = 2, GRDMA_H2_META_ERR_STRING = 3 };
 enum grdma_h2_meta_kind { GRDMA_H2_META_REQUEST = 1, GRDMA_H2_META_RESPONSE = 2, GRDMA_H2_META_TRAILERS = 3 };
@@ -1464,6 +1483,14 @@ int64_t grdma_h2_meta_read(grdma_h2_meta* meta, const grdma_h2_header_block* d_b
 /* {device address of the constant field table, its fields, device address of its string arena, its bytes}: valid until
  * the reader is destroyed */
 int grdma_h2_meta_reject_tables(grdma_h2_meta* meta, uint64_t out[4]);
+typedef struct grdma_h2_meta_item {      /* 80 bytes, every member 8 bytes wide: one link's input and targets, as grdma_h2_meta_read's */
+  const grdma_h2_header_block* d_blocks; uint64_t nblocks;
+  const grdma_h2_header_field* d_fields; uint64_t nfields;
+  const void* d_strings;                 uint64_t strings_bytes;
+  grdma_h2_call_meta* d_meta;            uint64_t meta_cap;
+  grdma_h2_header_block* d_reject;       uint64_t reject_cap;
+} grdma_h2_meta_item;
+int grdma_h2_meta_read_batch(grdma_h2_meta* meta, const grdma_h2_meta_item* items, uint32_t n_items, uint64_t* out /* 8 words per item */);
 /* {calls, blocks, requests, responses, trailers, rejections, malformed, kernel time of the last call in NANOseconds (HIP
  * events)} */
 int grdma_h2_meta_stats(grdma_h2_meta* meta, uint64_t out[8]);

@@ -12,6 +12,17 @@ stamps), the whole call on the host's clock, medians of --calls calls after one 
 
   python tools/h2_meta_probe.py --run --out profiles/h2_meta.json
 
+  --links 1,8,64,256 measures the many-link reader instead (CallMetadata.read_batch): the same workload spread evenly
+  over L links, one item a link, for every L of the list
+  batch:       one read_batch of the L items
+  loop:        L single reads of the same items, in the same run, interleaved with the batch
+  chain:       at L = 64, h2dev.decode_batch of every link's request headers, read_batch on the decoders' device tables
+               (the counts from the decoders' result blocks) and h2dev.encode_batch of the L rejection lists over the
+               reader's constant tables; the deframing in front of it is not timed
+  uneven:      one link with 1000 blocks beside 63 links of 4: a link's grid is four workgroups whatever it holds
+
+  python tools/h2_meta_probe.py --run --links 1,8,64,256 --out profiles/h2_meta_links.json
+
 --run is the driver: the measuring step is a child process under a time limit of its own (timeout -k 10 <s> ...), and
 the driver stops at a non-zero status.  Without --run the process measures (it needs the device)."""
 import argparse
@@ -27,6 +38,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def drive(args):
     me = [sys.executable, os.path.abspath(__file__), "--requests", str(args.requests), "--calls", str(args.calls)]
+    me += ["--links", args.links] if args.links else []
     cmd = ["timeout", "-k", "10", "300"] + me + (["--out", args.out] if args.out else [])
     rc = subprocess.call(cmd, cwd=ROOT)
     if rc != 0:
@@ -46,8 +58,119 @@ def workload(n, methods):
     return lists
 
 
+def spread(n, parts):
+    """n requests as evenly as they go over `parts` links -> the number each link takes"""
+    return [n // parts + (1 if k < n % parts else 0) for k in range(parts)]
+
+
+def measure_links(args, g, h2dev):
+    """the batch legs -> the result dict"""
+    from tests.h2_hpenc_lib import Input
+    from tests.h2_hpenc_model import pack
+    from tests.h2_meta_model import MetaModel, record_bytes
+    methods = [b"/probe.Service/Method%d" % i for i in range(64)]
+    lists = workload(args.requests, methods)
+    reader = h2dev.CallMetadata(methods=methods)
+    med = lambda xs: statistics.median(xs)  # noqa: E731
+    res = {"workload": "%d requests of ten fields, every 16th refused, spread evenly over L links; medians of %d after a warm-up" % (args.requests, args.calls)}
+
+    def links_of(parts):
+        """parts: the block counts of the links -> per link (Input, record table, rejection list, what the model says)"""
+        out, at = [], 0
+        for n in parts:
+            tables = pack(lists[at:at + n])
+            at += n
+            recs, rej, want, _ = MetaModel(methods, 1).read(*tables, 1 << 30, 1 << 30)
+            out.append((Input(g, *tables), g.DeviceBuffer(nbytes=48 * (n + 1)), g.DeviceBuffer(nbytes=16 * (len(rej) + 1)), (recs, rej, want)))
+        return out
+
+    def legs(links):
+        """batch and loop, interleaved -> {leg: [(kernels us, wall us)]} without the warm-up"""
+        items = [inp.args() + (meta.ptr, len(want[0]) + 1, reject.ptr, len(want[1]) + 1) for inp, meta, reject, want in links]
+        rows = {"batch": [], "loop": []}
+        for it in range(args.calls + 1):
+            t0 = time.perf_counter()
+            count, got = reader.read_batch(items)
+            wall = 1e6 * (time.perf_counter() - t0)
+            rows["batch"].append((reader.stats()["kernel_us"], wall))
+            if it == 0:  # the batch wrote what the model says, on every link
+                assert count == len(links), count
+                for (inp, meta, reject, (recs, rej, want)), r in zip(links, got):
+                    assert r == want and meta.read(48 * len(recs)) == b"".join(record_bytes(x) for x in recs), (r, want)
+                    assert reject.read(16 * len(rej)) == b"".join(int(w).to_bytes(4, "little") for x in rej for w in x)
+            t0 = time.perf_counter()
+            for item in items:
+                reader.read(*item)
+            wall = 1e6 * (time.perf_counter() - t0)
+            kernels = 0.0  # (a second pass: reading a call's kernel time is a device read of its own, kept off the clock)
+            for item in items:
+                reader.read(*item)
+                kernels += reader.stats()["kernel_us"]
+            rows["loop"].append((kernels, wall))
+        return {k: v[1:] for k, v in rows.items()}
+
+    for L in [int(x) for x in args.links.split(",")]:
+        rows = legs(links_of(spread(args.requests, L)))
+        for leg, r in rows.items():
+            res["L%d_%s_kernels_us" % (L, leg)] = med([x[0] for x in r])
+            res["L%d_%s_wall_us" % (L, leg)] = med([x[1] for x in r])
+            res["L%d_%s_all" % (L, leg)] = [list(x) for x in r]
+    # one link of 1000 blocks beside 63 of 4: the big link has its four workgroups and no more
+    old, args.requests = lists, 1000 + 63 * 4
+    lists = workload(args.requests, methods)
+    rows = legs(links_of([4] * 31 + [1000] + [4] * 32))
+    rows["big_alone"] = legs(links_of([1000]))["batch"]
+    for leg, r in rows.items():
+        res["uneven_%s_kernels_us" % leg] = med([x[0] for x in r])
+        res["uneven_%s_wall_us" % leg] = med([x[1] for x in r])
+        res["uneven_%s_all" % leg] = [list(x) for x in r]
+    lists, args.requests = old, len(old)
+    res.update(measure_chain(args, g, h2dev, reader, lists, 64))
+    reader.close()
+    return res
+
+
+def measure_chain(args, g, h2dev, reader, lists, L):
+    """decode batch -> read batch -> encode batch of the refusals on L links -> the result dict's part"""
+    from tests.h2_hpack_lib import HH, Targets, headers_frames, literal
+    parts, at, per_link = spread(len(lists), L), 0, []
+    for n in parts:
+        per_link.append(lists[at:at + n])
+        at += n
+    fp, nf, sp, ns = reader.reject_tables()
+    hhs = [HH(g) for _ in range(L)]
+    encs = [h2dev.HeaderEncoder() for _ in range(L)]
+    targets = [Targets(g, 64, 1024, 1 << 16) for _ in range(L)]
+    outs = [(g.DeviceBuffer(nbytes=48 * 65), g.DeviceBuffer(nbytes=16 * 65), g.DeviceBuffer(nbytes=1 << 14), g.DeviceBuffer(nbytes=16 * 65)) for _ in range(L)]
+    rows = []
+    for it in range(args.calls + 1):
+        for hh, mine in zip(hhs, per_link):  # (not timed: the deframing of new streams on every link)
+            base = 2 * len(lists) * it
+            hh.deframe([b"".join(headers_frames(base + sid, b"".join(literal(n, v, 2) for n, v in hs), flags=1) for sid, _, hs in mine)], checked=False)
+        t0 = time.perf_counter()
+        _, dres = h2dev.decode_batch([(hh.dec,) + t.args() for hh, t in zip(hhs, targets)])
+        t1 = time.perf_counter()
+        count, mres = reader.read_batch([(t.blocks.ptr, d[0], t.fields.ptr, d[1], t.strings.ptr, d[2], o[0].ptr, 64, o[1].ptr, 64)
+                                         for t, d, o in zip(targets, dres, outs)])
+        t2 = time.perf_counter()
+        ecount, eres = h2dev.encode_batch([(e, o[1].ptr, m[4], fp, nf, sp, ns, o[2].ptr, 1 << 14, o[3].ptr, 64) for e, m, o in zip(encs, mres, outs)])
+        t3 = time.perf_counter()
+        assert count == L and ecount == L, (count, ecount)
+        assert [m[:2] for m in mres] == [(n, n) for n in parts] and sum(m[4] for m in mres) == len(lists) // 16, mres[:3]
+        assert [e[0] for e in eres] == [m[4] for m in mres]
+        rows.append([1e6 * (t1 - t0), 1e6 * (t2 - t1), 1e6 * (t3 - t2), 1e6 * (t3 - t0), reader.stats()["kernel_us"]])
+    for x in hhs + encs:
+        x.close()
+    rows = rows[1:]
+    keys = ("decode_wall_us", "read_wall_us", "encode_wall_us", "wall_us", "read_kernels_us")
+    out = {"chain_L%d_%s" % (L, k): statistics.median(r[i] for r in rows) for i, k in enumerate(keys)}
+    out["chain_L%d_all" % L] = rows
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--links", default=None, help="measure the many-link reader over these link counts, e.g. 1,8,64,256")
     ap.add_argument("--requests", type=int, default=1008)
     ap.add_argument("--calls", type=int, default=7, help="calls per leg (median)")
     ap.add_argument("--run", action="store_true", help="drive the measuring step as a child process under a time limit")
@@ -62,6 +185,12 @@ def main():
     from tests.h2_hpenc_model import HpencModel, pack
     from tests.h2_meta_model import MetaModel, record_bytes
     g.init(0)
+    if args.links:
+        res = measure_links(args, g, h2dev)
+        print(json.dumps(res))
+        if args.out:
+            json.dump(res, open(args.out, "w"), indent=1)
+        return
     methods = [b"/probe.Service/Method%d" % i for i in range(64)]
     blocks, fields, arena = pack(workload(args.requests, methods))
     model = MetaModel(methods, 1)
