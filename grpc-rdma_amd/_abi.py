@@ -332,6 +332,12 @@ SIGNATURES = {
     "grdma_h2_meta_read_batch": (i32, [vp, vp, u32, P(u64)]),  # (the items: a (n, 10) array of 64-bit words, h2dev.META_ITEM)
     "grdma_h2_meta_reject_tables": (i32, [vp, P(u64)]),
     "grdma_h2_meta_stats": (i32, [vp, P(u64)]),
+    "grdma_h2_calls_create": (vp, [u32, u32]),
+    "grdma_h2_calls_destroy": (None, [vp]),
+    "grdma_h2_calls_step": (i64, [vp, vp, vp, u64, vp, u64, vp, u64, u64, vp, u64, vp, vp, u64, P(u64)]),
+    "grdma_h2_calls_dump": (i32, [vp, vp, u64, P(u64)]),
+    "grdma_h2_calls_stats": (i32, [vp, P(u64)]),
+    "grdma_h2_asm_last_call": (i32, [vp, P(u64)]),
     "grdma_h2_group_pipe_create": (vp, [vp, P(H2LinkSpec), u32, u32]),
     "grdma_h2_group_pipe_enqueue": (i32, [vp]),
     "grdma_h2_group_pipe_sync": (i32, [vp, P(u64), u64]),

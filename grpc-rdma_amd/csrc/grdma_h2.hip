@@ -39,6 +39,7 @@
 #include "grdma_h2_hpack.h"
 #include "grdma_h2_hpenc.h"
 #include "grdma_h2_meta.h"
+#include "grdma_h2_calls.h"
 #include "grdma_h2_block.h"
 
 // --------------------------------------------------------------------- host API
@@ -356,6 +357,14 @@ static h2_stage h2_stage_meta_links(h2m_dev* d, const h2m_link* d_tab, uint32_t 
   return {h2_rec(k_h2_links_meta_fields, n * H2M_LINK_GRID, H2M_THREADS, d, d_tab, n),
           h2_rec(k_h2_links_meta_blocks, n * H2M_LINK_GRID, H2M_BLK_THREADS, d, d_tab, n),
           h2_rec(k_h2_links_meta_emit, n * H2M_LINK_GRID, H2M_THREADS, d, d_tab, n)};
+}
+
+// The call table (csrc/grdma_h2_calls.h): it belongs to no parser.  One section, eight launches whatever the counts.
+static h2_stage h2_stage_calls(h2c_dev* d) {
+  return {h2_rec(k_h2_calls_clear, H2C_GRID, H2C_THREADS, d),  h2_rec(k_h2_calls_claim, H2C_GRID, H2C_THREADS, d),
+          h2_rec(k_h2_calls_wins, H2C_GRID, H2C_THREADS, d),   h2_rec(k_h2_calls_insert, H2C_GRID, H2C_THREADS, d),
+          h2_rec(k_h2_calls_msgs, H2C_GRID, H2C_THREADS, d),   h2_rec(k_h2_calls_cols, H2C_GRID, H2C_THREADS, d),
+          h2_rec(k_h2_calls_finish, 1, H2C_THREADS, d),        h2_rec(k_h2_calls_emit, H2C_GRID, H2C_THREADS, d)};
 }
 
 // st goes behind the parser's last deframing by a pipe (the parser state is handed from one deframing to the next),

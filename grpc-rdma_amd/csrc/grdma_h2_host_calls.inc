@@ -513,6 +513,7 @@ struct grdma_h2_asm {
   hipEvent_t last_read = nullptr;  // the gather of the last reply step enqueued: the next release waits for it
   uint64_t calls = 0;              // standalone assembler calls, single and batch (the windowed reply takes each one once)
   float plan_ms = 0, copy_ms = 0;  // of the last standalone call
+  uint64_t last_ndesc = 0, last_nev = 0;  // of the last grdma_h2_deframe_messages (grdma_h2_asm_last_call)
 };
 
 static void h2_asm_free_scratch(h2a_dev* h) {
@@ -645,6 +646,8 @@ int64_t grdma_h2_deframe_messages(grdma_h2_parser* p, grdma_h2_asm* a, const voi
   p->standalone_nsl = n;
   if (h2_error) *h2_error = (int)h_res.error;
   const uint64_t m = h_res.nevents < ev_cap ? h_res.nevents : ev_cap;
+  a->last_nev = h_res.overflow ? 0 : m;
+  a->last_ndesc = (h_res.overflow || h.skip || h.ndesc > h.desc_cap) ? 0 : h.ndesc;
   if (events_out && m && !h2_read(events_out, p->d_ev, sizeof(grdma_h2_event) * m)) return -GRDMA_ERR_HIP;
   if (h_res.overflow) return -GRDMA_ERR_CAPACITY;
   const int64_t nmsgs = h2_asm_descriptors(h, msgs_out, msgs_cap, st);
@@ -661,6 +664,16 @@ int grdma_h2_asm_release(grdma_h2_asm* a, uint64_t count) {
   if (!h2_wait_parser(hc->stream, a->parser)) return -GRDMA_ERR_HIP;
   const grdma_job_hook release = h2_rec(k_h2_asm_release, 1, 64, a->d, count);
   return h2_launch(&release, 1, hc->stream) == hipSuccess ? 0 : h2_refused(hc->stream, "grdma_h2_asm_release: the launch was rejected");
+}
+
+int grdma_h2_asm_last_call(grdma_h2_asm* a, uint64_t out[4]) {
+  if (!a || !out) return -GRDMA_ERR_INVALID;
+  if (a->attached) return h2_invalid("h2 assembler", "last_call on an assembler attached to a pipe");
+  out[0] = (uint64_t)(uintptr_t)a->h.desc;
+  out[1] = a->last_ndesc;
+  out[2] = (uint64_t)(uintptr_t)a->parser->d_ev;
+  out[3] = a->last_nev;
+  return 0;
 }
 
 int grdma_h2_asm_stats(grdma_h2_asm* a, uint64_t out[8]) {
@@ -2389,6 +2402,146 @@ int grdma_h2_meta_stats(grdma_h2_meta* w, uint64_t out[8]) {
   if (!w || !out) return -GRDMA_ERR_INVALID;
   // calls, blocks, requests, responses, trailers, rejections, malformed
   if (!h2_read(out, reinterpret_cast<const uint8_t*>(w->d) + offsetof(h2m_dev, st_calls), 7 * sizeof(uint64_t))) return -GRDMA_ERR_HIP;
+  out[7] = (uint64_t)(w->ms * 1e6f);
+  return 0;
+}
+
+// ---- the call table (csrc/grdma_h2_calls.h) -----------------------------------------------------------------------------------
+// The table follows no parser: a step's input is four device tables of the caller.  What it owns in device memory is the
+// two entry tables, the count rows (sized at creation) and the scratch that grows with a step's records and descriptors.
+struct grdma_h2_calls {
+  h2c_dev* d = nullptr;
+  h2c_dev h;  // the words set at creation
+  uint32_t* d_cls = nullptr;
+  uint64_t cls_cap = 0;
+  h2c_dd* d_dd = nullptr;
+  uint64_t dd_cap = 0;
+  h2c_mrec* d_mrec = nullptr;
+  uint64_t mrec_cap = 0;
+  float ms = 0;  // of the last step
+};
+static_assert(sizeof(h2c_disp) == sizeof(grdma_h2_dispatch) && sizeof(grdma_h2_dispatch) == 48 && sizeof(h2c_done) == sizeof(grdma_h2_call_done) &&
+              sizeof(grdma_h2_call_done) == 32 && sizeof(h2c_entry) == sizeof(grdma_h2_call_entry) && sizeof(grdma_h2_call_entry) == 48 &&
+              sizeof(h2c_msg) == sizeof(grdma_h2_rx_msg) && offsetof(h2c_dev, c) == 0 && H2C_F_BAD_INPUT == GRDMA_H2_CALLS_BAD_INPUT &&
+              H2C_F_LOST == GRDMA_H2_CALLS_LOST && H2C_E_METHOD == GRDMA_H2_CALLS_ERR_METHOD && H2C_COMPRESSED_IDENTITY == GRDMA_H2_ORPHAN_COMPRESSED_IDENTITY &&
+              H2C_DEADLINE == GRDMA_H2_DONE_DEADLINE && H2C_COMPRESSED == GRDMA_H2_DISPATCH_COMPRESSED, "layout");
+
+void grdma_h2_calls_destroy(grdma_h2_calls* w) {
+  if (!w) return;
+  h2_host_ctx* hc = h2_ctx();
+  if (hc) hipStreamSynchronize(hc->stream);
+  hipFree(w->d_mrec);
+  hipFree(w->d_dd);
+  hipFree(w->d_cls);
+  hipFree(w->h.exp_rank);
+  hipFree(w->h.exp_slot);
+  hipFree(w->h.ktot);
+  hipFree(w->h.row_k);
+  hipFree(w->h.row_s);
+  hipFree(w->h.aux);
+  hipFree(w->h.tab[1]);
+  hipFree(w->h.tab[0]);
+  hipFree(w->d);
+  delete w;
+}
+
+grdma_h2_calls* grdma_h2_calls_create(uint32_t table_slots, uint32_t nmethods) {
+  if (grdma_device_count() <= 0) return nullptr;
+  if (!table_slots) table_slots = 4096;
+  if (table_slots < 16u || table_slots > H2C_SLOTS_MAX || (table_slots & (table_slots - 1u)))
+    return h2_no("h2 call table: table_slots is no power of two in 16 .. 65536");
+  if (nmethods > 4096u) return h2_no("h2 call table: more than 4096 methods");
+  grdma_h2_calls* w = new grdma_h2_calls();
+  memset(&w->h, 0, sizeof(w->h));
+  h2c_dev* m = &w->h;
+  const size_t slots = table_slots;
+  bool ok = hipMalloc((void**)&w->d, sizeof(h2c_dev)) == hipSuccess && hipMalloc((void**)&m->tab[0], sizeof(h2c_entry) * slots) == hipSuccess &&
+            hipMalloc((void**)&m->tab[1], sizeof(h2c_entry) * slots) == hipSuccess && hipMalloc((void**)&m->aux, sizeof(h2c_aux) * slots) == hipSuccess &&
+            hipMalloc((void**)&m->row_s, sizeof(uint32_t) * slots * H2C_GRID) == hipSuccess &&
+            hipMalloc((void**)&m->row_k, sizeof(uint32_t) * H2C_KEYS_MAX * H2C_GRID) == hipSuccess &&
+            hipMalloc((void**)&m->ktot, sizeof(uint32_t) * (H2C_KEYS_MAX + 1u)) == hipSuccess &&
+            hipMalloc((void**)&m->exp_slot, sizeof(uint32_t) * slots / 2) == hipSuccess &&
+            hipMalloc((void**)&m->exp_rank, sizeof(uint32_t) * slots / 2) == hipSuccess;
+  if (ok) {
+    m->slots = table_slots;
+    m->nmethods = nmethods;
+    ok = hipMemset(m->tab[0], 0, sizeof(h2c_entry) * slots) == hipSuccess && hipMemset(m->tab[1], 0, sizeof(h2c_entry) * slots) == hipSuccess &&
+         hipMemcpy(w->d, m, sizeof(h2c_dev), hipMemcpyHostToDevice) == hipSuccess;
+  }
+  if (!ok) {
+    (void)hipGetLastError();
+    grdma_h2_calls_destroy(w);
+    grdma_fail_msg(GRDMA_ERR_HIP, "h2 call table: device allocation failed");
+    return nullptr;
+  }
+  return w;
+}
+
+int64_t grdma_h2_calls_step(grdma_h2_calls* w, const grdma_h2_header_block* d_blocks, const grdma_h2_call_meta* d_meta, uint64_t nblocks,
+                            const grdma_h2_rx_msg* d_msgs, uint64_t nmsgs, const grdma_h2_event* d_events, uint64_t nevents, uint64_t now_ns,
+                            grdma_h2_dispatch* d_dispatch, uint64_t dispatch_cap, uint32_t* d_segments, grdma_h2_call_done* d_done,
+                            uint64_t done_cap, uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  const char* who = "h2 call table";
+  if (!w) return h2_invalid(who, "no table");
+  if (!out) return h2_invalid(who, "no result array");
+  if (!d_dispatch || !dispatch_cap || !d_done || !done_cap || !d_segments || ((uintptr_t)d_dispatch & 15) || ((uintptr_t)d_done & 15) ||
+      ((uintptr_t)d_segments & 15))
+    return h2_invalid(who, "a null, zero or misaligned dispatch table, done list or segment table");
+  if ((nblocks && (!d_blocks || !d_meta)) || (nmsgs && !d_msgs) || (nevents && !d_events))
+    return h2_invalid(who, "a null input table with a count above 0");
+  if (nmsgs > H2C_MSGS_MAX) return h2_invalid(who, "more than 2^20 descriptors");
+  if (nblocks >= 0xffffffffull || nevents >= 0xffffffffull) return h2_invalid(who, "2^32 - 1 records or events, or more");
+  h2_host_ctx* hc = h2_ctx();
+  if (!hc) return -GRDMA_ERR_HIP;
+  uint64_t dd = 64;
+  while (dd < 2 * nblocks) dd *= 2;
+  if (!h2_grow(&w->d_cls, &w->cls_cap, nblocks + 1) || !h2_grow(&w->d_dd, &w->dd_cap, dd) || !h2_grow(&w->d_mrec, &w->mrec_cap, nmsgs + 1))
+    return -GRDMA_ERR_HIP;
+  const h2c_call call{reinterpret_cast<const h2hp_block_out*>(d_blocks), reinterpret_cast<const h2m_meta_out*>(d_meta), nblocks,
+                      reinterpret_cast<const h2c_msg*>(d_msgs), nmsgs, d_events, nevents, now_ns, reinterpret_cast<h2c_disp*>(d_dispatch),
+                      dispatch_cap, d_segments, reinterpret_cast<h2c_done*>(d_done), done_cap, w->d_cls, w->d_dd, dd - 1, w->d_mrec};
+  const h2_stage stage = h2_stage_calls(w->d);
+  h2_call c{"grdma_h2_calls_step: a launch was rejected", {{w->d, &call, sizeof(call)}}, {}, {h2_all(stage)},
+            {h2_result(out, w->d, offsetof(h2c_dev, res))}};
+  if (int rc = h2_call_run(hc, &c)) return rc;
+  w->ms = c.ms[0];
+  if (out[H2C_FLAGS] & H2C_F_BAD_INPUT) return h2_invalid(who, "bad input: a request's stream id or method (the result block says which record)");
+  if (out[H2C_OVERFLOW]) return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 call table: more descriptors or done records than the targets hold");
+  return (int64_t)(out[H2C_DISPATCHED] + out[H2C_ORPHANS]);
+}
+
+int grdma_h2_calls_dump(grdma_h2_calls* w, void* host_buf, uint64_t cap, uint64_t out[4]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!w || !out || (!host_buf && cap)) return -GRDMA_ERR_INVALID;
+  h2c_dev h;
+  std::vector<h2c_entry> tab(w->h.slots);
+  if (!h2_read(&h, w->d, sizeof(h)) || !h2_read(tab.data(), w->h.tab[h.cur & 1u], sizeof(h2c_entry) * tab.size())) return -GRDMA_ERR_HIP;
+  std::vector<h2c_entry> live;
+  for (h2c_entry e : tab) {
+    if (e.stream == 0 || (e.fin & H2C_EF_DEAD)) continue;
+    e.word |= e.fin;
+    e.fin = 0;
+    e.pad1 = 0;
+    live.push_back(e);
+  }
+  std::sort(live.begin(), live.end(), [](const h2c_entry& a, const h2c_entry& b) { return a.stream < b.stream; });
+  out[0] = live.size();
+  out[1] = live.size() * sizeof(h2c_entry);
+  out[2] = h.serial;
+  out[3] = w->h.slots;
+  if (out[1] > cap) return -GRDMA_ERR_CAPACITY;
+  if (!live.empty()) memcpy(host_buf, live.data(), out[1]);
+  return 0;
+}
+
+int grdma_h2_calls_stats(grdma_h2_calls* w, uint64_t out[8]) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  if (!w || !out) return -GRDMA_ERR_INVALID;
+  h2c_dev h;
+  if (!h2_read(&h, w->d, sizeof(h))) return -GRDMA_ERR_HIP;
+  out[0] = h.st_steps, out[1] = h.st_opened, out[2] = h.st_msgs, out[3] = h.st_bytes, out[4] = h.st_orphans, out[5] = h.st_done;
+  out[6] = h.lost ? GRDMA_H2_CALLS_LOST : 0;
   out[7] = (uint64_t)(w->ms * 1e6f);
   return 0;
 }

@@ -489,6 +489,14 @@ class Assembler(_Handle):
         return self._words("stats", ("reported", "ok_bytes", "too_large", "no_space", "truncated", "bytes_in_use", "plan_us",
                                      "copy_us"))  # grdma_h2_asm_stats
 
+    def last_call(self):
+        """(descriptors device ptr, their number, events device ptr, their number) of the last deframe_messages through
+        this assembler: what CallTable.step takes with no table copied through the host; valid until the parser's next
+        deframing"""
+        out = (u64 * 4)()
+        check(self.lib.grdma_h2_asm_last_call(self.h, out))
+        return tuple(int(x) for x in out)
+
     def view(self, msg):
         """the bytes of an OK message: a slice of the arena tensor, or bytes read back from the device"""
         if hasattr(self.arena, "data_ptr"):
@@ -804,9 +812,22 @@ def _call_meta_dtype():
     return np.dtype([(name, "<u4") for name in _CALL_META_FIELDS])
 
 
+_CALLS_DTYPES = {
+    # grdma_h2_dispatch (48 bytes), grdma_h2_call_done (32), grdma_h2_call_entry (48)
+    "DISPATCH": [("offset", "<u8"), ("length", "<u8"), ("call", "<u8"), ("stream", "<u4"), ("msg", "<u4"), ("method", "<u4"), ("word", "<u4"),
+                 ("seq", "<u4"), ("pad", "<u4")],
+    "CALL_DONE": [("call", "<u8"), ("bytes", "<u8"), ("stream", "<u4"), ("method", "<u4"), ("messages", "<u4"), ("word", "<u4")],
+    "CALL_ENTRY": [("call", "<u8"), ("deadline_ns", "<u8"), ("bytes", "<u8"), ("stream", "<u4"), ("method", "<u4"), ("messages", "<u4"),
+                   ("word", "<u4"), ("pad0", "<u4"), ("pad1", "<u4")],
+}
+
+
 def __getattr__(name):
     if name == "CALL_META":  # the numpy structured dtype of grdma_h2_call_meta (48 bytes), made on first use
         return _call_meta_dtype()
+    if name in _CALLS_DTYPES:  # the call table's records, as numpy structured dtypes
+        import numpy as np
+        return np.dtype(_CALLS_DTYPES[name])
     raise AttributeError(name)
 
 
@@ -881,6 +902,53 @@ class CallMetadata(_Handle):
         """the bytes of a record table as a numpy array of CALL_META (a view: no copy)"""
         import numpy as np
         return np.frombuffer(raw_bytes, dtype=_call_meta_dtype())
+
+
+class CallTable(_Handle):
+    """Per-call state of one connection on the device, keyed by stream (grdma_h2_calls): a step joins it with the call
+    records of CallMetadata.read, the descriptors of Parser.deframe_messages and the deframer's events, all in device
+    memory, and writes the messages sorted by method (DISPATCH records, nmethods + 2 segment words) and a done list
+    (CALL_DONE).  It follows no parser."""
+
+    KIND, WHAT = "calls", "h2 call table"  # grdma_h2_calls_create, grdma_h2_calls_destroy
+    RESULT = ("opened", "dispatched", "orphans", "done", "expired", "live", "flags", "overflow")
+    STATS = ("steps", "opened", "messages", "bytes", "orphans", "done", "lost", "kernel_us")
+    NONE = 0xffffffff
+    BAD_INPUT, LOST = 1, 2
+    ERRORS = (None, "stream", "method")
+    FIRST, LAST, COMPRESSED = 1, 2, 4  # a dispatch record's flags: word bits 0..7
+    NO_CALL, EXPIRED, BAD_STATUS, COMPRESSED_IDENTITY = 1, 2, 3, 4  # an orphan's reason: word bits 8..15
+    READS_CLOSED, LEFT, DEADLINE = 1, 2, 3  # a done record's reason: word bits 0..7
+    WAS_READS_CLOSED = 1
+
+    def __init__(self, table_slots=0, nmethods=0):
+        self.nmethods = nmethods
+        self._create(table_slots, nmethods)
+
+    def step(self, blocks_ptr, meta_ptr, nblocks, msgs_ptr, nmsgs, events_ptr, nevents, now_ns, dispatch_ptr, dispatch_cap, segments_ptr,
+             done_ptr, done_cap):
+        """-> (dispatch records, result tuple (RESULT)); raises GrdmaError on a refusal, on bad input (flags: BAD_INPUT |
+        error << 8 | record << 32) and on a capacity overflow (overflow word 1: nothing was written or committed, the
+        step may be repeated with larger targets) -- the result of the failed step stays in .last_result"""
+        self.last_result = None
+        n = self._call("step", blocks_ptr, meta_ptr, nblocks, msgs_ptr, nmsgs, events_ptr, nevents, now_ns, dispatch_ptr, dispatch_cap,
+                       segments_ptr, done_ptr, done_cap)  # grdma_h2_calls_step
+        return n, self.last_result
+
+    def dump(self):
+        """-> (the live entries sorted by stream as a numpy array of CALL_ENTRY, (entries, the serial counter,
+        table_slots))"""
+        import numpy as np
+        out = (u64 * 4)()
+        rc = self.lib.grdma_h2_calls_dump(self.h, None, 0, out)
+        if rc and not out[1]:
+            check(rc)
+        buf = C.create_string_buffer(max(1, int(out[1])))
+        check(self.lib.grdma_h2_calls_dump(self.h, buf, int(out[1]), out))
+        return np.frombuffer(buf.raw[:int(out[1])], dtype=np.dtype(_CALLS_DTYPES["CALL_ENTRY"])), (int(out[0]), int(out[2]), int(out[3]))
+
+    def stats(self):
+        return self._stats()  # grdma_h2_calls_stats
 
 
 def decode_batch(items):

@@ -1495,6 +1495,113 @@ int grdma_h2_meta_read_batch(grdma_h2_meta* meta, const grdma_h2_meta_item* item
  * events)} */
 int grdma_h2_meta_stats(grdma_h2_meta* meta, uint64_t out[8]);
 
+/* ---- Call table: per-call state on the device, messages routed by method (csrc/grdma_h2_calls.h) ----
+ * One table per connection, resident in HBM, keyed by stream.  A STEP joins it with three device tables the earlier
+ * stages wrote -- the call records of grdma_h2_meta_read (record k belongs to block k of the decoder's block table), the
+ * received-message descriptors of grdma_h2_deframe_messages and the deframer's events -- and writes the DISPATCH TABLE,
+ * the messages sorted by registered method so that a handler kernel for method m takes d_segments[m] ..
+ * d_segments[m + 1] and nothing else, and the DONE LIST (deadlines that passed, streams that closed).  The table
+ * belongs to no parser; every input and output is passed by address.  A step is ordered on the stream of the standalone
+ * HTTP/2 calls: a grdma_h2_deframe_messages, grdma_h2_hpack_decode and grdma_h2_meta_read in front of it need no host
+ * synchronisation beyond the counts the host already has (grdma_h2_asm_last_call names the assembler's tables).  The
+ * sequential reference, which defines the exact output, is tests/h2_calls_model.py.
+ * CREATE.  table_slots: a power of two in 16 .. 65536, 0 = 4096; at most half may be live.  nmethods: 0 .. 4096, the
+ * reader's.  Keys hash as everywhere: (id >> 1) & mask, linear probing.
+ * A step runs rules 1 to 4 in this order -- the wire's own: on one stream HEADERS precede DATA, which precedes the
+ * close, and HTTP/2 never reuses an id.
+ * 1. OPEN.  A record opens a call when its kind is REQUEST, its verdict OK, the status byte of its block (flags bits
+ *    8..15) 0 and its stream has no entry.  The entry: {serial = the next of a 64-bit counter that starts at 0, given in
+ *    record order; method; encoding; deadline = now_ns + timeout saturated at 2^64 - 1, or 2^64 - 1 without HAS_TIMEOUT;
+ *    0 messages; 0 bytes}.  Ignored: a REQUEST with another verdict or a non-zero status byte (refused); a stream that
+ *    has an entry or comes a second time in the step, where the first wins whether it opened or was lost (duplicate);
+ *    any other kind (RESPONSE and TRAILERS: the client side is not here).  An opening that would make more than
+ *    table_slots / 2 entries live does not happen: the call is lost, the sticky flag GRDMA_H2_CALLS_LOST is set, the
+ *    records in front of it are unaffected.
+ * 2. EXPIRE.  A live entry not yet EXPIRED whose deadline is <= now_ns becomes EXPIRED, stays in the table and gets one
+ *    DEADLINE record; one opened in this step with timeout 0 is included.
+ * 3. MESSAGES, in descriptor order.  A descriptor is an ORPHAN, in this order of checks, when its status is not
+ *    GRDMA_H2_MSG_OK (BAD_STATUS), its stream has no entry (NO_CALL), the entry is EXPIRED (EXPIRED), the compressed bit
+ *    is set on encoding 0 (COMPRESSED_IDENTITY).  Every other descriptor is DISPATCHED to its entry's method: seq
+ *    continues the entry's message count, the entry's messages and bytes grow.  A dispatch record: offset and length
+ *    are the descriptor's, msg its index in d_msgs; word = flags | reason << 8 | encoding << 16.  Flags: FIRST (a
+ *    dispatched record whose seq is 0), LAST (the last DISPATCHED message of its stream in this step, when the step
+ *    holds a STREAM_CLOSED event of the stream with a of 0 or 1), COMPRESSED (bit 0 of the descriptor's flags).  An
+ *    orphan has method 0xffffffff, seq 0, neither FIRST nor LAST; call and encoding are its entry's where the entry was
+ *    looked at (EXPIRED, COMPRESSED_IDENTITY) and 0 otherwise.
+ * 4. CLOSE, in event order, over the events of kind STREAM_CLOSED (7) whose stream (word c) has an entry.  a == 0: the
+ *    entry becomes READS_CLOSED, one READS_CLOSED record.  a == 1: one LEFT record, the entry is removed (a later event
+ *    of the stream finds no entry).  No other event is read, nor a STREAM_CLOSED with another a.  A done record's word is
+ *    reason | flags << 8, the flag WAS_READS_CLOSED on a LEFT or DEADLINE record of an entry that was READS_CLOSED;
+ *    messages and bytes are the call's dispatched messages since it opened, this step's included.
+ * 5. THE DONE LIST holds the DEADLINE records first, in ascending stream order, then the close records in event order.
+ * 6. THE DISPATCH TABLE is sorted by method, stable in descriptor order, the orphans behind the last method.
+ *    d_segments has nmethods + 2 words: [m] .. [m + 1] is method m's list, index nmethods the orphans', [nmethods + 1]
+ *    the total.
+ * 7. BAD INPUT is found on the device: a record that meets the first three conditions of rule 1 with a stream of 0 or
+ *    above 2^31 - 1 (ERR_STREAM) or a method >= nmethods (ERR_METHOD); the first such record in record order, in it
+ *    the stream first.  Result word 6 is BAD_INPUT | code << 8 | record << 32, the other words are 0, nothing is
+ *    written, nothing is committed, the call returns -GRDMA_ERR_INVALID.  Not sticky.
+ * 8. CAPS.  dispatch_cap < nmsgs or done_cap < the done records: overflow word 1, -GRDMA_ERR_CAPACITY, the result block
+ *    holds the totals, NOTHING is written to any target (d_segments included) and NOTHING is committed: not the table,
+ *    the serial counter, the counters or the LOST flag.  The same step with larger targets gives what a never-refused
+ *    step gives.  Nothing is written behind the totals in any case; d_segments is written whole.
+ * 9. RESULT BLOCK: {opened, dispatched, orphans, done records, expired in this step, live entries after the step, flags
+ *    (grdma_h2_calls_flag) | error << 8 | record << 32, overflow}.  grdma_h2_calls_step returns the number of dispatch
+ *    records (= nmsgs).  STATS: {steps, opened, dispatched messages, dispatched bytes, orphans, done records, the LOST
+ *    flag, kernel time of the last step in NANOseconds}.  DUMP: the live entries, sorted by stream, 48 bytes each
+ *    (grdma_h2_call_entry); out = {entries, bytes, the serial counter, table_slots}; -GRDMA_ERR_CAPACITY with out filled
+ *    in when cap is too small.
+ * 10. -GRDMA_ERR_INVALID (grdma_last_error says why; nothing runs, nothing changes): null, zero-cap or misaligned (16
+ *    bytes) targets, a null input table with a count above 0, nmsgs above 2^20, 2^32 - 1 records or events or more, no
+ *    table, no result array.
+ * A step is eight launches whatever the counts; its call words go up in one copy, its result words come down in one.
+ * Not here: the table over many links, the table inside a pipe or group pipe, the client side (RESPONSE and TRAILERS
+ * records are ignored), RST_STREAM for malformed or expired calls, reporting finished replies to
+ * grdma_h2_parser_close_writes, decompression. */
+enum grdma_h2_calls_flag { GRDMA_H2_CALLS_BAD_INPUT = 1, GRDMA_H2_CALLS_LOST = 2 };
+enum grdma_h2_calls_error { GRDMA_H2_CALLS_ERR_STREAM = 1, GRDMA_H2_CALLS_ERR_METHOD = 2 };
+enum grdma_h2_dispatch_flag { GRDMA_H2_DISPATCH_FIRST = 1, GRDMA_H2_DISPATCH_LAST = 2, GRDMA_H2_DISPATCH_COMPRESSED = 4 };
+enum grdma_h2_orphan_reason {
+  GRDMA_H2_ORPHAN_NO_CALL = 1, GRDMA_H2_ORPHAN_EXPIRED = 2, GRDMA_H2_ORPHAN_BAD_STATUS = 3, GRDMA_H2_ORPHAN_COMPRESSED_IDENTITY = 4
+};
+enum grdma_h2_done_reason { GRDMA_H2_DONE_READS_CLOSED = 1, GRDMA_H2_DONE_LEFT = 2, GRDMA_H2_DONE_DEADLINE = 3 };
+enum grdma_h2_done_flag { GRDMA_H2_DONE_WAS_READS_CLOSED = 1 };
+enum grdma_h2_call_entry_flag { GRDMA_H2_CALL_READS_CLOSED = 1, GRDMA_H2_CALL_EXPIRED = 2 };
+typedef struct grdma_h2_dispatch {    /* 48 bytes */
+  uint64_t offset, length;            /* the descriptor's */
+  uint64_t call;                      /* the call's serial */
+  uint32_t stream;
+  uint32_t msg;                       /* index of the descriptor in d_msgs */
+  uint32_t method;                    /* 0xffffffff in the orphan segment */
+  uint32_t word;                      /* flags | reason << 8 | encoding << 16 */
+  uint32_t seq;                       /* number of this message within its call, from 0 */
+  uint32_t pad;
+} grdma_h2_dispatch;
+typedef struct grdma_h2_call_done {   /* 32 bytes */
+  uint64_t call, bytes;
+  uint32_t stream, method, messages;
+  uint32_t word;                      /* reason | flags << 8 */
+} grdma_h2_call_done;
+typedef struct grdma_h2_call_entry {  /* 48 bytes: a dumped entry */
+  uint64_t call, deadline_ns, bytes;
+  uint32_t stream, method, messages;
+  uint32_t word;                      /* encoding | flags << 8 (grdma_h2_call_entry_flag) */
+  uint32_t pad[2];
+} grdma_h2_call_entry;
+typedef struct grdma_h2_calls grdma_h2_calls;
+grdma_h2_calls* grdma_h2_calls_create(uint32_t table_slots, uint32_t nmethods);
+void grdma_h2_calls_destroy(grdma_h2_calls* calls);
+int64_t grdma_h2_calls_step(grdma_h2_calls* calls, const grdma_h2_header_block* d_blocks, const grdma_h2_call_meta* d_meta, uint64_t nblocks,
+                            const grdma_h2_rx_msg* d_msgs, uint64_t nmsgs, const grdma_h2_event* d_events, uint64_t nevents,
+                            uint64_t now_ns, grdma_h2_dispatch* d_dispatch, uint64_t dispatch_cap, uint32_t* d_segments,
+                            grdma_h2_call_done* d_done, uint64_t done_cap, uint64_t out[8]);
+int grdma_h2_calls_dump(grdma_h2_calls* calls, void* host_buf, uint64_t cap, uint64_t out[4]);
+int grdma_h2_calls_stats(grdma_h2_calls* calls, uint64_t out[8]);
+/* {device address of the descriptors of the assembler's last grdma_h2_deframe_messages, their number, device address of
+ * its parser's event list, its number of events}: valid until that parser's next deframing (both numbers are 0 behind a
+ * call whose events or descriptors overflowed).  -GRDMA_ERR_INVALID on an assembler attached to a pipe. */
+int grdma_h2_asm_last_call(grdma_h2_asm* a, uint64_t out[4]);
+
 /* ---- HTTP/2 on several links of ONE job (the group pipe) ----
  * grdma_h2_pipe serves one link, and a job carries one set of kernels in front of and behind its rounds: a second
  * grdma_h2_pipe on another link of the same job replaces the first one's.  The group pipe is the pipe of n links of a
