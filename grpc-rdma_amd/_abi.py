@@ -335,6 +335,7 @@ SIGNATURES = {
     "grdma_h2_calls_create": (vp, [u32, u32]),
     "grdma_h2_calls_destroy": (None, [vp]),
     "grdma_h2_calls_step": (i64, [vp, vp, vp, u64, vp, u64, vp, u64, u64, vp, u64, vp, vp, u64, P(u64)]),
+    "grdma_h2_calls_step_batch": (i32, [vp, u32, P(u64)]),  # (the items: a (n, 14) array of 64-bit words, h2dev.CALLS_ITEM)
     "grdma_h2_calls_dump": (i32, [vp, vp, u64, P(u64)]),
     "grdma_h2_calls_stats": (i32, [vp, P(u64)]),
     "grdma_h2_asm_last_call": (i32, [vp, P(u64)]),

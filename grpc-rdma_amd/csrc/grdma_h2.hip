@@ -366,6 +366,15 @@ static h2_stage h2_stage_calls(h2c_dev* d) {
           h2_rec(k_h2_calls_msgs, H2C_GRID, H2C_THREADS, d),   h2_rec(k_h2_calls_cols, H2C_GRID, H2C_THREADS, d),
           h2_rec(k_h2_calls_finish, 1, H2C_THREADS, d),        h2_rec(k_h2_calls_emit, H2C_GRID, H2C_THREADS, d)};
 }
+// ... of n links' tables in the same eight launches: every link a share of the grid stages, the finishes side by side
+static_assert(H2C_LINKS_MAX == GRDMA_H2_BATCH_MAX, "the call table's link table is the batch's");
+static h2_stage h2_stage_calls_links(const h2c_link* d_tab, uint32_t n) {
+  const uint32_t grid = n * H2C_LINK_GRID;
+  return {h2_rec(k_h2_links_calls_clear, grid, H2C_THREADS, d_tab, n),  h2_rec(k_h2_links_calls_claim, grid, H2C_THREADS, d_tab, n),
+          h2_rec(k_h2_links_calls_wins, grid, H2C_THREADS, d_tab, n),   h2_rec(k_h2_links_calls_insert, grid, H2C_THREADS, d_tab, n),
+          h2_rec(k_h2_links_calls_msgs, grid, H2C_THREADS, d_tab, n),   h2_rec(k_h2_links_calls_cols, grid, H2C_THREADS, d_tab, n),
+          h2_rec(k_h2_links_calls_finish, n, H2C_THREADS, d_tab, n),    h2_rec(k_h2_links_calls_emit, grid, H2C_THREADS, d_tab, n)};
+}
 
 // st goes behind the parser's last deframing by a pipe (the parser state is handed from one deframing to the next),
 // unless that one was enqueued on st itself.  (Only pipe steps leave last_deframed, on a job's or a deframe stream: for

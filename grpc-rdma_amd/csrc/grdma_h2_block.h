@@ -56,6 +56,15 @@ inline h2_meta_block h2_meta_block_layout(uint64_t link, uint64_t call, uint64_t
   return {b.add(link * n_items), b.add(call * n_items), b.add(wg * link_grid * n_items), b.add(8 * sizeof(uint64_t) * n_items), b.total()};
 }
 
+// grdma_h2_calls_step_batch: [table | one h2c_call per item | eight result words per item]; [0, results) goes up in one
+// copy, the result words -- the finish launch writes all eight of every item -- come down in one copy.  (Nothing of a
+// step lies in the tables' own device blocks but their state and counters.)
+struct h2_calls_block { uint64_t tab, calls, results, total; };
+inline h2_calls_block h2_calls_block_layout(uint64_t link, uint64_t call, uint64_t n_items) {
+  h2_block b;
+  return {b.add(link * n_items), b.add(call * n_items), b.add(8 * sizeof(uint64_t) * n_items), b.total()};
+}
+
 // grdma_h2_reply_frame_batch: [table | one h2r_dev per item]; all of it goes up, the h2r_dev blocks come down.
 struct h2_reply_block { uint64_t tab, devs, end, total; };
 inline h2_reply_block h2_reply_block_layout(uint64_t link, uint64_t dev, uint64_t n_items) {

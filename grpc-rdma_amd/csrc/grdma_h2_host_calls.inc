@@ -2477,6 +2477,38 @@ grdma_h2_calls* grdma_h2_calls_create(uint32_t table_slots, uint32_t nmethods) {
   return w;
 }
 
+// The single step and the batch share these three: the single call's arguments are one item.
+// what a step of an item is refused for
+static const char* h2_calls_refusal(const grdma_h2_calls_item& it) {
+  if (!it.calls) return "no table";
+  if (!it.d_dispatch || !it.dispatch_cap || !it.d_done || !it.done_cap || !it.d_segments || ((uintptr_t)it.d_dispatch & 15) ||
+      ((uintptr_t)it.d_done & 15) || ((uintptr_t)it.d_segments & 15))
+    return "a null, zero or misaligned dispatch table, done list or segment table";
+  if ((it.nblocks && (!it.d_blocks || !it.d_meta)) || (it.nmsgs && !it.d_msgs) || (it.nevents && !it.d_events))
+    return "a null input table with a count above 0";
+  if (it.nmsgs > H2C_MSGS_MAX) return "more than 2^20 descriptors";
+  if (it.nblocks >= 0xffffffffull || it.nevents >= 0xffffffffull) return "2^32 - 1 records or events, or more";
+  return nullptr;
+}
+// the step's words of an item over its table's per-step scratch, grown to the step: a word per record, the dedup table (a
+// power of two >= 2 nblocks), a record per descriptor.  false: no device memory
+static bool h2_calls_call(const grdma_h2_calls_item& it, h2c_call* call) {
+  grdma_h2_calls* w = it.calls;
+  uint64_t dd = 64;
+  while (dd < 2 * it.nblocks) dd *= 2;
+  if (!h2_grow(&w->d_cls, &w->cls_cap, it.nblocks + 1) || !h2_grow(&w->d_dd, &w->dd_cap, dd) || !h2_grow(&w->d_mrec, &w->mrec_cap, it.nmsgs + 1))
+    return false;
+  *call = {reinterpret_cast<const h2hp_block_out*>(it.d_blocks), reinterpret_cast<const h2m_meta_out*>(it.d_meta), it.nblocks,
+           reinterpret_cast<const h2c_msg*>(it.d_msgs), it.nmsgs, it.d_events, it.nevents, it.now_ns, reinterpret_cast<h2c_disp*>(it.d_dispatch),
+           it.dispatch_cap, it.d_segments, reinterpret_cast<h2c_done*>(it.d_done), it.done_cap, w->d_cls, w->d_dd, dd - 1, w->d_mrec};
+  return true;
+}
+// an item's outcome from its result words: whether its table committed; ms: what the launches took
+static bool h2_calls_committed(grdma_h2_calls* w, const uint64_t* res, float ms) {
+  w->ms = ms;
+  return !(res[H2C_FLAGS] & H2C_F_BAD_INPUT) && !res[H2C_OVERFLOW];
+}
+
 int64_t grdma_h2_calls_step(grdma_h2_calls* w, const grdma_h2_header_block* d_blocks, const grdma_h2_call_meta* d_meta, uint64_t nblocks,
                             const grdma_h2_rx_msg* d_msgs, uint64_t nmsgs, const grdma_h2_event* d_events, uint64_t nevents, uint64_t now_ns,
                             grdma_h2_dispatch* d_dispatch, uint64_t dispatch_cap, uint32_t* d_segments, grdma_h2_call_done* d_done,
@@ -2485,30 +2517,51 @@ int64_t grdma_h2_calls_step(grdma_h2_calls* w, const grdma_h2_header_block* d_bl
   const char* who = "h2 call table";
   if (!w) return h2_invalid(who, "no table");
   if (!out) return h2_invalid(who, "no result array");
-  if (!d_dispatch || !dispatch_cap || !d_done || !done_cap || !d_segments || ((uintptr_t)d_dispatch & 15) || ((uintptr_t)d_done & 15) ||
-      ((uintptr_t)d_segments & 15))
-    return h2_invalid(who, "a null, zero or misaligned dispatch table, done list or segment table");
-  if ((nblocks && (!d_blocks || !d_meta)) || (nmsgs && !d_msgs) || (nevents && !d_events))
-    return h2_invalid(who, "a null input table with a count above 0");
-  if (nmsgs > H2C_MSGS_MAX) return h2_invalid(who, "more than 2^20 descriptors");
-  if (nblocks >= 0xffffffffull || nevents >= 0xffffffffull) return h2_invalid(who, "2^32 - 1 records or events, or more");
+  const grdma_h2_calls_item it{w, d_blocks, d_meta, nblocks, d_msgs, nmsgs, d_events, nevents, now_ns, d_dispatch, dispatch_cap, d_segments, d_done, done_cap};
+  if (const char* why = h2_calls_refusal(it)) return h2_invalid(who, why);
   h2_host_ctx* hc = h2_ctx();
   if (!hc) return -GRDMA_ERR_HIP;
-  uint64_t dd = 64;
-  while (dd < 2 * nblocks) dd *= 2;
-  if (!h2_grow(&w->d_cls, &w->cls_cap, nblocks + 1) || !h2_grow(&w->d_dd, &w->dd_cap, dd) || !h2_grow(&w->d_mrec, &w->mrec_cap, nmsgs + 1))
-    return -GRDMA_ERR_HIP;
-  const h2c_call call{reinterpret_cast<const h2hp_block_out*>(d_blocks), reinterpret_cast<const h2m_meta_out*>(d_meta), nblocks,
-                      reinterpret_cast<const h2c_msg*>(d_msgs), nmsgs, d_events, nevents, now_ns, reinterpret_cast<h2c_disp*>(d_dispatch),
-                      dispatch_cap, d_segments, reinterpret_cast<h2c_done*>(d_done), done_cap, w->d_cls, w->d_dd, dd - 1, w->d_mrec};
+  h2c_call call;
+  if (!h2_calls_call(it, &call)) return -GRDMA_ERR_HIP;
   const h2_stage stage = h2_stage_calls(w->d);
   h2_call c{"grdma_h2_calls_step: a launch was rejected", {{w->d, &call, sizeof(call)}}, {}, {h2_all(stage)},
             {h2_result(out, w->d, offsetof(h2c_dev, res))}};
   if (int rc = h2_call_run(hc, &c)) return rc;
-  w->ms = c.ms[0];
+  if (h2_calls_committed(w, out, c.ms[0])) return (int64_t)(out[H2C_DISPATCHED] + out[H2C_ORPHANS]);
   if (out[H2C_FLAGS] & H2C_F_BAD_INPUT) return h2_invalid(who, "bad input: a request's stream id or method (the result block says which record)");
-  if (out[H2C_OVERFLOW]) return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 call table: more descriptors or done records than the targets hold");
-  return (int64_t)(out[H2C_DISPATCHED] + out[H2C_ORPHANS]);
+  return grdma_fail_msg(GRDMA_ERR_CAPACITY, "h2 call table: more descriptors or done records than the targets hold");
+}
+
+// The tables of many connections in the same eight launches (h2_stage_calls_links).  The batch block of the process holds
+// [table | one h2c_call per item | eight result words per item] (csrc/grdma_h2_block.h): the table and the call words go
+// up in ONE copy, the result words come down in ONE copy, whatever the number of items -- nothing of a step passes through
+// the tables' own device blocks (F->c stays the last single step's), whose state and counters the finish launch moves
+// per table as the single step does.  Every table brings its own per-step scratch.  The table follows no parser: nothing
+// to wait for.  One call at a time, as the other batch calls.
+int grdma_h2_calls_step_batch(const grdma_h2_calls_item* items, uint32_t n_items, uint64_t* out) {
+  if (grdma_device_count() <= 0) return -GRDMA_ERR_NO_DEVICE;
+  h2_batch b{"h2 call table batch", "table", "grdma_h2_calls_step_batch: a launch was rejected"};
+  if (!items) return h2_invalid(b.who, "no item array");
+  if (!out) return h2_invalid(b.who, "no result array");
+  if (int rc = b.begin(true, n_items)) return rc;
+  for (uint32_t i = 0; i < n_items; i++)
+    if (int rc = b.item(items[i].calls, h2_calls_refusal(items[i]))) return rc;
+  const h2_calls_block L = h2_calls_block_layout(sizeof(h2c_link), sizeof(h2c_call), n_items);
+  if (int rc = b.reserve(L.results, L.total)) return rc;
+  auto* tab = reinterpret_cast<h2c_link*>(b.up.data() + L.tab);
+  auto* calls = reinterpret_cast<h2c_call*>(b.up.data() + L.calls);
+  for (uint32_t i = 0; i < n_items; i++) {
+    if (!h2_calls_call(items[i], &calls[i])) return -GRDMA_ERR_HIP;
+    tab[i] = {items[i].calls->d, reinterpret_cast<const h2c_call*>(b.d + L.calls) + i, reinterpret_cast<uint64_t*>(b.d + L.results) + 8 * (size_t)i};
+  }
+  std::vector<uint64_t> down(8 * (size_t)n_items, 0);  // (out is not touched unless the call ran)
+  b.c.down.push_back(h2_result(down.data(), b.d, L.results, down.size()));
+  const h2_stage stage = h2_stage_calls_links(reinterpret_cast<const h2c_link*>(b.d + L.tab), n_items);
+  if (int rc = b.run({h2_all(stage)})) return rc;
+  memcpy(out, down.data(), down.size() * sizeof(uint64_t));
+  int committed = 0;
+  for (uint32_t i = 0; i < n_items; i++) committed += h2_calls_committed(items[i].calls, out + 8 * (size_t)i, b.c.ms[0]);  // (the time: the batch's, repeated)
+  return committed;
 }
 
 int grdma_h2_calls_dump(grdma_h2_calls* w, void* host_buf, uint64_t cap, uint64_t out[4]) {

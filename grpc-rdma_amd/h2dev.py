@@ -951,6 +951,35 @@ class CallTable(_Handle):
         return self._stats()  # grdma_h2_calls_stats
 
 
+# grdma_h2_calls_item: fourteen 64-bit words, the table and the arguments of CallTable.step in order
+CALLS_ITEM = ("calls", "d_blocks", "d_meta", "nblocks", "d_msgs", "nmsgs", "d_events", "nevents", "now_ns", "d_dispatch", "dispatch_cap",
+              "d_segments", "d_done", "done_cap")
+
+
+def calls_step_batch(items):
+    """CallTable.step for the tables of many connections in eight launches (grdma_h2_calls_step_batch).  items:
+    [(CallTable, blocks device ptr, record-table device ptr, nblocks, descriptors device ptr, nmsgs, events device ptr,
+    nevents, now_ns, dispatch device ptr, dispatch cap, segments device ptr, done-list device ptr, done cap), ...] with
+    distinct tables (CALLS_ITEM names the columns); input tables may be shared between items, targets may not.  -> (the
+    number of items that committed, [result tuple (CallTable.RESULT) per item]); an item with bad input or a cap overflow
+    reports for itself in its tuple (flags: BAD_INPUT | error << 8 | record << 32, the other words 0; overflow word 1 and
+    the totals: nothing of it was written or committed and it may be repeated, alone or in a later batch).  The result
+    tuples also land in each table's .last_result, before a failure raises.  Raises GrdmaError only on a refusal of the
+    whole call (the library leaves the result words alone: all 0)."""
+    import numpy as np
+    arr = np.zeros((max(1, len(items)), len(CALLS_ITEM)), dtype="<u8")  # grdma_h2_calls_item: fourteen 64-bit words
+    for row, item in zip(arr, items):
+        row[0] = int(item[0].h or 0) if item[0] is not None else 0
+        row[1:] = [int(v or 0) for v in item[1:]]
+    out = (u64 * (8 * max(1, len(items))))()
+    rc = load().grdma_h2_calls_step_batch(arr.ctypes.data_as(C.c_void_p), len(items), out)
+    results = [tuple(int(x) for x in out[8 * i:8 * i + 8]) for i in range(len(items))]
+    for item, r in zip(items, results):
+        if item[0] is not None:  # (an item without table: the whole call is refused below)
+            item[0].last_result = r
+    return check(rc), results
+
+
 def decode_batch(items):
     """HeaderDecoder.decode for many transports in six launches (grdma_h2_hpack_decode_batch).  items: [(HeaderDecoder,
     blocks device ptr, blocks cap, fields device ptr, fields cap, strings device ptr, strings cap), ...] with distinct

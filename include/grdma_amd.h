@@ -1555,8 +1555,35 @@ int grdma_h2_meta_stats(grdma_h2_meta* meta, uint64_t out[8]);
  *    bytes) targets, a null input table with a count above 0, nmsgs above 2^20, 2^32 - 1 records or events or more, no
  *    table, no result array.
  * A step is eight launches whatever the counts; its call words go up in one copy, its result words come down in one.
- * Not here: the table over many links, the table inside a pipe or group pipe, the client side (RESPONSE and TRAILERS
- * records are ignored), RST_STREAM for malformed or expired calls, reporting finished replies to
+ * MANY LINKS.  grdma_h2_calls_step_batch is grdma_h2_calls_step for n items (1 .. GRDMA_H2_BATCH_MAX) in eight launches
+ * however many (k_h2_links_calls_*), ordered on the same stream: a grdma_h2_hpack_decode_batch and a
+ * grdma_h2_meta_read_batch in front of it need no host synchronisation beyond the counts the host already has.  n tables,
+ * one item each, by design (unlike the metadata reader, which is one object for all links): a table's state is per
+ * connection, as the header encoder's, so an item is a table and the thirteen arguments of the single step behind it.
+ *  1. Every item is stepped by rules 1 to 9 exactly as the single call steps it: its dispatch table, its segment words,
+ *     its done list, its eight result words, its table (the dump) and its counters are byte for byte what
+ *     grdma_h2_calls_step gives that table for the same arguments.
+ *  2. Single and batch steps may alternate on one table.
+ *  3. now_ns is per item.
+ *  4. Input tables may be shared between items; overlapping targets are the caller's error and are not checked.
+ *  5. Trouble stays with its item, the other items are exact.  Bad input (rule 7): the flag, the code and the record in
+ *     the item's word 6, its other words 0, nothing is written or committed for that table.  A cap overflow (rule 8):
+ *     overflow word 1 and the totals, nothing is written or committed.  Repeated alone or in a later batch with larger
+ *     targets the item gives what a never-refused step gives.  The sticky LOST flag behaves per table as in the single
+ *     call.
+ *  6. An item with no records, messages or events is still a step: it commits, `steps` moves, EXPIRE runs against its
+ *     now_ns.
+ *  7. The return value is the number of items that committed (overflow word 0 and no BAD_INPUT), or a negative error.
+ *     out: 8 result words per item, in item order.
+ *  8. -GRDMA_ERR_INVALID (grdma_last_error says why; nothing runs, nothing changes, out is not touched): n outside 1 ..
+ *     GRDMA_H2_BATCH_MAX, a NULL item array or result array, an item without table, the same table twice, any item the
+ *     single call's argument checks (rule 10) refuse.
+ *  9. COUNTERS are per table: a committed item moves its table's grdma_h2_calls_stats as one single step would, an item
+ *     that did not commit moves nothing.  Word 7 of every table in the batch is the batch's kernel time.
+ * All items' call words go up in ONE copy and all result words come down in ONE copy, whatever n; no table needs device
+ * memory for the batch beyond what its single steps use.
+ * Not here: the table inside a pipe or group pipe, a grid per link sized by the link's counts, the client side
+ * (RESPONSE and TRAILERS records are ignored), RST_STREAM for malformed or expired calls, reporting finished replies to
  * grdma_h2_parser_close_writes, decompression. */
 enum grdma_h2_calls_flag { GRDMA_H2_CALLS_BAD_INPUT = 1, GRDMA_H2_CALLS_LOST = 2 };
 enum grdma_h2_calls_error { GRDMA_H2_CALLS_ERR_STREAM = 1, GRDMA_H2_CALLS_ERR_METHOD = 2 };
@@ -1595,6 +1622,17 @@ int64_t grdma_h2_calls_step(grdma_h2_calls* calls, const grdma_h2_header_block* 
                             const grdma_h2_rx_msg* d_msgs, uint64_t nmsgs, const grdma_h2_event* d_events, uint64_t nevents,
                             uint64_t now_ns, grdma_h2_dispatch* d_dispatch, uint64_t dispatch_cap, uint32_t* d_segments,
                             grdma_h2_call_done* d_done, uint64_t done_cap, uint64_t out[8]);
+typedef struct grdma_h2_calls_item {     /* 112 bytes, every member 8 bytes wide: a table and its step's arguments, as grdma_h2_calls_step's */
+  grdma_h2_calls* calls;
+  const grdma_h2_header_block* d_blocks; const grdma_h2_call_meta* d_meta; uint64_t nblocks;
+  const grdma_h2_rx_msg* d_msgs;         uint64_t nmsgs;
+  const grdma_h2_event* d_events;        uint64_t nevents;
+  uint64_t now_ns;
+  grdma_h2_dispatch* d_dispatch;         uint64_t dispatch_cap;
+  uint32_t* d_segments;
+  grdma_h2_call_done* d_done;            uint64_t done_cap;
+} grdma_h2_calls_item;
+int grdma_h2_calls_step_batch(const grdma_h2_calls_item* items, uint32_t n_items, uint64_t* out /* 8 words per item */);
 int grdma_h2_calls_dump(grdma_h2_calls* calls, void* host_buf, uint64_t cap, uint64_t out[4]);
 int grdma_h2_calls_stats(grdma_h2_calls* calls, uint64_t out[8]);
 /* {device address of the descriptors of the assembler's last grdma_h2_deframe_messages, their number, device address of
